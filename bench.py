@@ -11,6 +11,21 @@ checksums (sum of the output = sum_x rowsum(m)_x * rowsum(f)_x) and an exact
 spot check of 512 random output entries against the same arithmetic in torch
 (fp32 products, sums in the reference's order).
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) does what the headline
+figure needs and nothing else: it sets the bucket up, warms up, times the K
+steps and prints the line (value, ms_per_step, the roofline of those same
+steps).  Everything else described here -- the checksum and spot check, the CPU
+baseline, "fp64_bucket", "mar", "mar_f64", the secondary instance, the sliced
+leg -- runs only with --full, where --no-cpu / --no-mar / --no-mar-f64 /
+--no-fp64 still drop single legs; the exit status reports a failed check only
+there.  --dump-outputs DIR writes, right after the timed steps, what the last
+step left in the bucket's output message as DIR/bucket_out.npy
+(DIR/bucket_out_rank<r>.npy for N > 1) in the compute dtype: the whole
+message when it has at most DUMP_MAX_ENTRIES entries, else its entries at a
+fixed, seeded set of DUMP_MAX_ENTRIES positions (dump_positions), so two
+builds run with the same arguments write arrays that compare entry by entry
+(the inputs are seeded: identical from run to run).
+
 A "step" = one fused bucket (one kernel launch) through the C ABI
 (bnpp_bucket_eliminate) on torch's current stream.  Roofline: algorithmic bytes
 = 4 B x (|m| + |f| + |out|) per launch over the kernel's average duration (HIP
@@ -65,6 +80,8 @@ sys.path.insert(0, os.path.join(REPO, "bn-pp_amd", "python"))
 
 METRIC = "factor-entries/sec on fused product+sum-out; MAR wall-clock on 32x32 grid UAI"
 HBM_PEAK = 8.0e12          # B/s, MI355X_MICROARCH.md chip table (spec)
+DUMP_MAX_ENTRIES = 1 << 22 # --dump-outputs: 16 MB in fp32, 32 MB in fp64
+DUMP_SEED = 20240607
 
 
 def host_cpu():
@@ -317,6 +334,27 @@ def merge_sliced(line, sl, world):
     line["mar_segment"] = seg
 
 
+def check_bucket(m_t, f_t, out, k, S, is_f32, dev, rank):
+    """The timed bucket's output against its inputs: (both checks ok, spot
+    check exact)."""
+    import torch
+    # sanity: checksum of checksums (sum_out = sum_x rowsum(m)_x * rowsum(f)_x)
+    want = (m_t.double().reshape(k, S).sum(1) * f_t.double().reshape(k, k).sum(1)).sum().item()
+    got = out.double().sum().item()
+    ok = abs(got - want) <= (1e-4 if is_f32 else 1e-9) * want
+    # exact spot check: out[s*k + y] = ((0 + m[0,s] f[0,y]) + m[1,s] f[1,y]) + ... in the
+    # compute dtype, products and sums rounded one at a time like factor.cpp:131-143, 199-205
+    gs = torch.Generator(device=dev).manual_seed(99 + rank)
+    idx = torch.randint(0, S * k, (512,), generator=gs, device=dev)
+    s_i, y_i = idx // k, idx % k
+    M, F = m_t.reshape(k, S), f_t.reshape(k, k)
+    acc = torch.zeros(512, device=dev, dtype=m_t.dtype)
+    for x in range(k):
+        acc = acc + M[x, s_i] * F[x, y_i]
+    spot_ok = bool(torch.equal(out[idx], acc))
+    return ok and spot_ok, spot_ok
+
+
 def fp64_bucket(ctx, dev, stream, rank, k=4, w=14, steps=10):
     """The bench bucket in fp64 (the reference's arithmetic; bit-exact against
     it): m(x, S_1..S_w) * f(x, y) -> sum_x, timed with HIP events on the
@@ -367,6 +405,35 @@ def fp64_bucket(ctx, dev, stream, rank, k=4, w=14, steps=10):
             "frac": alg / (kern_ms * 1e-3) / HBM_PEAK, "spot_check_exact": bool(torch.equal(out[idx], acc))}
 
 
+def dump_positions(n_entries: int):
+    """The positions of the output message that --dump-outputs writes: all of
+    them, in order, up to DUMP_MAX_ENTRIES entries; past that DUMP_MAX_ENTRIES
+    positions drawn (with repetition) by a seeded numpy PCG64 stream, which
+    numpy keeps stable across versions.  They depend on the message's size
+    alone, so every run and every build of one shape samples the same entries."""
+    import numpy as np
+    if n_entries <= DUMP_MAX_ENTRIES:
+        return np.arange(n_entries, dtype=np.int64)
+    return np.random.Generator(np.random.PCG64(DUMP_SEED)).integers(0, n_entries, DUMP_MAX_ENTRIES, dtype=np.int64)
+
+
+def dump_outputs(dirname: str, name: str, out):
+    """Write the 1-D tensor `out` (the output message, on any device; float32
+    or float64) at dump_positions as dirname/name.npy, dtype kept."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    pos = dump_positions(out.numel())
+    if len(pos) == out.numel():
+        arr = out.detach().cpu().numpy()
+    else:
+        arr = out[torch.from_numpy(pos).to(out.device)].cpu().numpy()
+    assert arr.dtype in (np.float32, np.float64), arr.dtype
+    path = os.path.join(dirname, name + ".npy")
+    np.save(path, arr)
+    return path
+
+
 def launcher_cmd(n: int, port: int, argv):
     """The command that starts `n` ranks of this script on one node (the
     driver's own launch line for N > 1)."""
@@ -405,6 +472,12 @@ def parse_args(argv=None):
     ap.add_argument("--k", type=int, default=4)
     ap.add_argument("--w", type=int, default=14)
     ap.add_argument("--dtype", choices=["f32", "f64"], default="f32")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and every other leg (CPU baseline, fp64 bucket, MAR f32/f64, secondary, "
+                         "sliced); a plain run times the bucket only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output message of the last timed step (a fixed sample of it when large) as "
+                         "DIR/<name>.npy")
     ap.add_argument("--cpu-w", type=int, default=10, help="bucket width of the bounded CPU-baseline sample")
     ap.add_argument("--cpu-reps", type=int, default=5)
     ap.add_argument("--no-cpu", action="store_true")
@@ -415,14 +488,17 @@ def parse_args(argv=None):
     ap.add_argument("--mar-cols", type=int, default=32)
     ap.add_argument("--secondary", default="ising12x12.uai",
                     help="reference-runnable MAR instance timed beside the reference's own BN::marginals")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:                                       # a plain run: the timed bucket alone
+        args.no_cpu = args.no_mar = args.no_mar_f64 = args.no_fp64 = True
+    return args
 
 
-def main():
-    args = parse_args()
+def main(argv=None):
+    args = parse_args(argv)
     # N > 1 without a launcher: start the N ranks ourselves (children)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and os.environ.get("BNPP_BENCH_CHILD") != "1":
-        sys.exit(self_launch(args.gpus, sys.argv[1:]))
+        sys.exit(self_launch(args.gpus, sys.argv[1:] if argv is None else list(argv)))
 
     import torch
     import torch.distributed as dist
@@ -516,31 +592,23 @@ def main():
     alg_bytes = eb * (k * S + k * k + S * k)       # |m| + |f| + |out|
     achieved = alg_bytes / (kern_ms * 1e-3)
 
-    # sanity: checksum of checksums (sum_out = sum_x rowsum(m)_x * rowsum(f)_x)
-    want = (m_t.double().reshape(k, S).sum(1) * f_t.double().reshape(k, k).sum(1)).sum().item()
-    got = out.double().sum().item()
-    ok = abs(got - want) <= (1e-4 if dt == bnpp.F32 else 1e-9) * want
-    # exact spot check: out[s*k + y] = ((0 + m[0,s] f[0,y]) + m[1,s] f[1,y]) + ... in the
-    # compute dtype, products and sums rounded one at a time like factor.cpp:131-143, 199-205
-    gs = torch.Generator(device=dev).manual_seed(99 + rank)
-    idx = torch.randint(0, S * k, (512,), generator=gs, device=dev)
-    s_i, y_i = idx // k, idx % k
-    M, F = m_t.reshape(k, S), f_t.reshape(k, k)
-    acc = torch.zeros(512, device=dev, dtype=tdt)
-    for x in range(k):
-        acc = acc + M[x, s_i] * F[x, y_i]
-    spot_ok = bool(torch.equal(out[idx], acc))
-    ok = ok and spot_ok
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "bucket_out" if world == 1 else "bucket_out_rank%d" % rank, out)
+
+    ok, spot_ok = True, None
+    if args.full:
+        ok, spot_ok = check_bucket(m_t, f_t, out, k, S, dt == bnpp.F32, dev, rank)
 
     fp64 = None
     if not args.no_fp64:
         fp64 = fp64_bucket(ctx, dev, stream, rank)
-    del m_t, f_t, out, M, F, acc, idx, s_i, y_i
+    del m_t, f_t, out
     torch.cuda.synchronize(dev)
     torch.cuda.empty_cache()
 
     traffic = None
-    # newest profiles/traffic_rNN.json (tools/profile_bench.sh) for this kernel
+    # newest profiles/traffic_rNN.json (tools/profile_bench.sh) for this kernel:
+    # a recorded figure read from the tree, no run of its own
     for tpath in sorted(glob.glob(os.path.join(REPO, "profiles", "traffic_r*.json")), reverse=True):
         tj = json.load(open(tpath))
         if tj.get("k") == k and tj.get("w") == w and tj.get("dtype") == args.dtype:
@@ -623,9 +691,13 @@ def main():
             "mar": mar,
             "mar_f64": mar_f64,
             "fp64_bucket": fp64,
-            "checksum_ok": ok,
-            "spot_check_exact": spot_ok,
+            "full": args.full,
         }
+        if args.full:
+            line.update({"checksum_ok": ok, "spot_check_exact": spot_ok})
+        if args.dump_outputs:
+            line["dump_outputs"] = {"entries": min(int(S * k), DUMP_MAX_ENTRIES), "of": int(S * k),
+                                    "sampled": S * k > DUMP_MAX_ENTRIES}
     # exactly one JSON line, whichever thread gets there first
     import threading
     print_lock = threading.Lock()

@@ -108,3 +108,47 @@ def test_secondary_default_is_the_12x12_grid():
     import bench
     assert bench.parse_args([]).secondary == "ising12x12.uai"
     assert os.path.exists(os.path.join(REPO, "tests", "golden", "models", "ising12x12.uai"))
+
+
+def test_plain_run_drops_every_side_leg_and_full_restores_them():
+    """A plain run times the bucket alone; --full runs the other legs, each
+    still droppable by its own --no-* option."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "4", "--warmup", "1"])
+    assert not a.full and a.dump_outputs is None
+    assert a.no_cpu and a.no_mar and a.no_mar_f64 and a.no_fp64
+    a = bench.parse_args(["--full"])
+    assert a.full and not (a.no_cpu or a.no_mar or a.no_mar_f64 or a.no_fp64)
+    a = bench.parse_args(["--full", "--no-mar-f64", "--dump-outputs", "d"])
+    assert a.full and a.no_mar_f64 and not a.no_mar and a.dump_outputs == "d"
+
+
+def test_dump_positions_are_fixed_and_bounded():
+    import numpy as np
+    import bench
+    cap = bench.DUMP_MAX_ENTRIES
+    assert cap * 8 <= 64 << 20                              # fp64, the widest dtype dumped
+    assert np.array_equal(bench.dump_positions(1000), np.arange(1000))
+    assert np.array_equal(bench.dump_positions(cap), np.arange(cap))
+    n = 4 ** 15                                             # the default bucket's output message
+    p, q = bench.dump_positions(n), bench.dump_positions(n)
+    assert p.dtype == np.int64 and len(p) == cap and np.array_equal(p, q)
+    assert 0 <= p.min() and p.max() < n
+    assert (int(p[0]), int(p[1]), int(p[-1])) == (int(q[0]), int(q[1]), int(q[-1]))
+    assert len(np.unique(p // (n // 64))) == 64             # spread over the whole message
+
+
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+def test_dump_outputs_writes_the_message_or_its_sample(tmp_path, monkeypatch, dtype):
+    import numpy as np
+    import torch
+    import bench
+    t = torch.arange(5000, dtype=getattr(torch, dtype)) * 0.25
+    path = bench.dump_outputs(str(tmp_path / "new" / "dir"), "bucket_out", t)
+    got = np.load(path)
+    assert path.endswith("bucket_out.npy") and got.dtype == np.dtype(dtype)
+    assert np.array_equal(got, t.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_ENTRIES", 512)     # past the cap: the seeded sample
+    got = np.load(bench.dump_outputs(str(tmp_path), "sampled", t))
+    assert got.dtype == np.dtype(dtype) and got.shape == (512,)
+    assert np.array_equal(got, t.numpy()[bench.dump_positions(5000)])

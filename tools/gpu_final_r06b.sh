@@ -13,7 +13,7 @@ timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/mar64 -o mar64 --outp
 cd $R
 grep -o '"wall_ms": [0-9.]*' $OUT/mar32.log | tr '\n' ' '; echo
 grep -o '"wall_ms": [0-9.]*' $OUT/mar64.log | tr '\n' ' '; echo
-BNPP_BENCH_REHEARSE=1 timeout -k 10 500 python3 -u bench.py --gpus 2 --no-mar-f64 --mar-rows 16 --mar-cols 16 > $OUT/rehearse2.json 2> $OUT/rehearse2.err || { tail -20 $OUT/rehearse2.err; exit 1; }
+BNPP_BENCH_REHEARSE=1 timeout -k 10 500 python3 -u bench.py --full --gpus 2 --no-mar-f64 --mar-rows 16 --mar-cols 16 > $OUT/rehearse2.json 2> $OUT/rehearse2.err || { tail -20 $OUT/rehearse2.err; exit 1; }
 head -4 $(find $OUT/mar32 -name "*kernel_stats.csv") | cut -c1-160
 head -4 $(find $OUT/mar64 -name "*kernel_stats.csv") | cut -c1-160
 python3 -c "

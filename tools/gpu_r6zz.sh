@@ -16,7 +16,7 @@ for l in open('$O/sliced.jsonl'):
     d = json.loads(l)
     print('ranks', d['ranks'], 'nocopy', [round(x, 1) for x in d['nocopy_walls_ms']], 'model_64', [round(x, 1) for x in d['model_64_walls_ms']])"
 FINAL_OUT=r6zz_final bash tools/gpu_final_r06a.sh || exit 1
-BNPP_BENCH_REHEARSE=1 timeout -k 10 500 python3 -u bench.py --gpus 2 --no-mar-f64 --mar-rows 16 --mar-cols 16 > $O/rehearse2.json 2> $O/rehearse2.err || { tail -20 $O/rehearse2.err; exit 1; }
+BNPP_BENCH_REHEARSE=1 timeout -k 10 500 python3 -u bench.py --full --gpus 2 --no-mar-f64 --mar-rows 16 --mar-cols 16 > $O/rehearse2.json 2> $O/rehearse2.err || { tail -20 $O/rehearse2.err; exit 1; }
 python3 -c "
 import json
 d = json.loads(open('$O/rehearse2.json').read().strip().splitlines()[-1])

@@ -14,4 +14,4 @@ timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -d $OUT/write -o run --output-forma
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/mar32 -o mar32 --output-format csv -- python3 $R/tools/mar_grid.py --rows 32 --cols 32 --check 3 --reps 2 > $OUT/mar32.log 2>&1
 cd $R
 python3 tools/pmc_traffic.py $(find $OUT/fetch -name "*counter_collection.csv") $(find $OUT/write -name "*counter_collection.csv") > $OUT/traffic.json
-timeout -k 10 600 python3 bench.py > $OUT/bench.log 2>&1
+timeout -k 10 600 python3 bench.py --full > $OUT/bench.log 2>&1
