@@ -429,6 +429,63 @@ def test_plan_tree_sliced_exchange_steps(capfd):
         assert steps["2"] + late == n, (R, n, steps, late)             # one data pass per exchange
 
 
+def test_plan_tree_sliced_shapes_the_world_tests_rely_on(capfd):
+    """The exchange shapes behind tests/test_gpu_sliced_world.py: which xchg.hip
+    branch a world case runs is decided by the planner, so the shapes are
+    pinned here -- should the planner stop producing them, this test says so
+    and the GPU cases do not go quietly blind.
+      * every world plans exchanges;
+      * the binary grids transpose in the pack (kind=2 mode=1), at R = 16 with
+        blocks=16 steps (the runtime-R kernels, 4096 entries);
+      * the card-3 grids with binary slice rows below pack in the same order
+        (kind=2 mode=0) with entries % 4 != 0 -- the fp32 vector tail -- and
+        unpack (kind=4) with an inner size that is no multiple of 4;
+      * binary rows above the card-3 rows give a transposing pack whose inner
+        size is no multiple of 4 (the scalar branch of the mode-1 pack).
+    Unreached by the planner on any column-sweep grid searched (rows 10-12,
+    cards 2/3/5 in any rows, 11-14 columns, R = 2/4/8): a kind=4 mode=1 unpack
+    (xchg_unpack_kernel with x_t < 0) -- every unpack is mode 2."""
+    import sliced_world as sw
+
+    def steps(model, rows, cols, R):
+        m = bnpp.Model.from_dict(model)
+        os.environ["BNPP_DUMP_PLAN"] = "1"
+        capfd.readouterr()
+        try:
+            _, st = bnpp.plan_tree_sliced(m, 0, R, order=sw.column_order(rows, cols))
+        finally:
+            del os.environ["BNPP_DUMP_PLAN"]
+        err = capfd.readouterr().err
+        found = [tuple(int(x) for x in s) for s in
+                 re.findall(r"xchg kind=(\d) mode=(\d) blocks=(\d+) tables:\S+ entries=(\d+)", err)]
+        assert int(st[8]) > 0 and sum(1 for s in found if s[0] == 3) == int(st[8]), (rows, cols, R, st[8])
+        assert all(b == R for _, _, b, _ in found), (rows, cols, R)
+        assert not [s for s in found if s[0] == 4 and s[1] != 2], (rows, cols, R)
+        return found
+
+    for rows, cols, R in sw.ISING_WORLDS:
+        found = steps(synth.ising_grid(rows, cols, seed=5), rows, cols, R)
+        assert [s for s in found if s[:2] == (2, 1)], (rows, cols, R)
+        if R == 16:
+            assert (2, 1, 16, 4096) in found and (4, 2, 16, 4096) in found, found
+    # inner sizes down to 4 and 1 on the two smallest (the oracle-checked) worlds
+    assert (4, 2, 2, 4) in steps(synth.ising_grid(10, 10, seed=5), 10, 10, 2)
+    assert (2, 0, 4, 1) in steps(synth.ising_grid(11, 11, seed=5), 11, 11, 4)
+    tails = 0
+    for rc, cols, R in sw.MIXED_WORLDS:
+        found = steps(sw.mixed_grid(rc, cols), len(rc), cols, R)
+        tails += len([s for s in found if s[:2] == (2, 0) and s[3] % 4 != 0])
+        assert [s for s in found if s[0] == 4 and (s[3] // s[2]) % 4 != 0], (rc, cols, R)
+    assert tails > 0
+    assert (2, 0, 2, 13122) in steps(sw.mixed_grid([3] * 8 + [2] * 2, 12), 10, 12, 2)
+    assert (4, 2, 4, 17496) in steps(sw.mixed_grid([3] * 7 + [2] * 3, 12), 10, 12, 4)
+    wide = steps(sw.mixed_grid([3] * 6 + [2] * 6, 14), 12, 14, 8)
+    assert (4, 2, 8, 46656) in wide and (4, 2, 8, 11664) in wide, wide
+    for rc, cols, R in sw.FAST_SLICE_WORLDS:
+        found = steps(sw.mixed_grid(rc, cols), len(rc), cols, R)
+        assert [s for s in found if s[:2] == (2, 1) and (s[3] // s[2]) % 4 != 0], (rc, cols, R, found)
+
+
 def test_checkpoint_search_picks_a_fitting_slot_count():
     """The checkpoint-slot search (k-ary, probes planned in parallel): under
     budgets below the full tree's arena it returns exactly the plan of one
