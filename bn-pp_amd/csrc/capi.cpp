@@ -126,11 +126,11 @@ bool valid_scope(int ndims, const int *vars, const int *cards, int n_cards) {
 
 int max_vec_for(int dtype) { return dtype == BNPP_F32 ? 4 : 2; }
 
-// Launch one bucket with the descriptor in the kernel-argument segment.
-int run_single(bnpp_ctx *ctx, void *stream, int dtype, const std::vector<int> &cards, const BucketSpec &b,
-               const std::vector<const void *> &in_ptrs, void *out) {
+// Plan one single-op call: the descriptor, its dims pool and the entries each
+// view can reach, all a launch needs but the table addresses.  run_single
+// launches what this fills and bnpp_plan_single reports it.
+int plan_single(int dtype, const std::vector<int> &cards, const BucketSpec &b, SingleArgs &a) {
     if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "dtype must be BNPP_F64 or BNPP_F32");
-    SingleArgs a;
     std::memset(&a, 0, sizeof a);
     std::vector<int64_t> pool;
     std::string msg;
@@ -139,14 +139,20 @@ int run_single(bnpp_ctx *ctx, void *stream, int dtype, const std::vector<int> &c
         return set_err(BNPP_ERR_UNSUPPORTED, "too many non-mergeable output dims for a single-op call");
     std::copy(pool.begin(), pool.end(), a.pool);
     a.d.dim_off = 0;
-    for (size_t i = 0; i < in_ptrs.size(); ++i) {
-        a.meta[i].ptr = const_cast<void *>(in_ptrs[i]);
-        // entries the view can reach (the launcher picks 32-bit offsets by it)
-        a.meta[i].size = view_span(b.in[i], cards);
-    }
+    // entries the view can reach (the launcher picks 32-bit offsets by it)
+    for (size_t i = 0; i < b.in.size(); ++i) a.meta[i].size = view_span(b.in[i], cards);
     // BNPP_NO_O32=1 (tests): claim a span that rules out the 32-bit-offset kernels
     if (const char *no32 = std::getenv("BNPP_NO_O32"); no32 && *no32 == '1')
-        for (size_t i = 0; i < in_ptrs.size(); ++i) a.meta[i].size = (int64_t)1 << 40;
+        for (size_t i = 0; i < b.in.size(); ++i) a.meta[i].size = (int64_t)1 << 40;
+    return BNPP_OK;
+}
+
+// Launch one bucket with the descriptor in the kernel-argument segment.
+int run_single(bnpp_ctx *ctx, void *stream, int dtype, const std::vector<int> &cards, const BucketSpec &b,
+               const std::vector<const void *> &in_ptrs, void *out) {
+    SingleArgs a;
+    if (int rc = plan_single(dtype, cards, b, a)) return rc;
+    for (size_t i = 0; i < in_ptrs.size(); ++i) a.meta[i].ptr = const_cast<void *>(in_ptrs[i]);
     a.meta[in_ptrs.size()].ptr = out;
     if (a.d.big >= 0) {
         const int eb = dtype == BNPP_F32 ? 4 : 8;
@@ -1471,7 +1477,7 @@ int bnpp_plan_stats(const bnpp_model *m, int kind, int n_ev, const int *ev_vars,
                     const int *order, int n_order, int dtype, double *stats, int n_stats) {
     BNPP_GUARD_BEGIN
     if (!m || !stats) return set_err(BNPP_ERR_INVALID, "null argument");
-    if (kind != 0 && kind != 1 && kind != 3) return set_err(BNPP_ERR_INVALID, "kind must be 0, 1 or 3");
+    if (kind < 0 || kind > 3) return set_err(BNPP_ERR_INVALID, "kind must be 0, 1, 2 or 3");
     std::vector<int> ev, targets;
     std::string msg;
     if (!evidence_array(m->d, n_ev, ev_vars, ev_vals, ev, msg)) return set_err(BNPP_ERR_INVALID, msg);
@@ -1482,6 +1488,71 @@ int bnpp_plan_stats(const bnpp_model *m, int kind, int n_ev, const int *ev_vars,
     int rc = plan_schedules(m->d, ev, kind, heuristic, order, n_order, targets, dtype, memory_budget(nullptr), batches, st);
     if (rc) return rc;
     for (int i = 0; i < n_stats && i < 8; ++i) stats[i] = st[i];
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+int bnpp_plan_single(int dtype, int n_cards, const int *cards, int n_in, const int *in_ndims, const int *const *in_vars,
+                     int elim_var, int out_ndims, const int *out_vars, int divide, int n_ev, const int *ev_vars,
+                     const int *ev_vals, int64_t *info, int n_info) {
+    BNPP_GUARD_BEGIN
+    if (!cards || n_in < 1 || !in_ndims || !in_vars || !info || (n_ev > 0 && (!ev_vars || !ev_vals)))
+        return set_err(BNPP_ERR_INVALID, "null argument");
+    if (n_in > kMaxIn) return set_err(BNPP_ERR_UNSUPPORTED, "at most 8 inputs per fused call");
+    if (n_cards < 0 || elim_var >= n_cards || (out_ndims > 0 && !out_vars) || n_ev < 0)
+        return set_err(BNPP_ERR_INVALID, "variable id outside cards[0, n_cards)");
+    for (int i = 0; i < n_in; ++i)
+        if (!valid_scope(in_ndims[i], in_vars[i], cards, n_cards)) return set_err(BNPP_ERR_INVALID, "bad input scope");
+    if (!valid_scope(out_ndims, out_vars, cards, n_cards)) return set_err(BNPP_ERR_INVALID, "bad output scope");
+    if (divide && (n_in != 2 || elim_var >= 0)) return set_err(BNPP_ERR_INVALID, "divide takes two inputs and sums nothing");
+    std::vector<int> cv(cards, cards + n_cards);
+    // the conditioning view (bnpp_condition): evidence on a variable outside a scope does not touch it
+    std::vector<int> ev(n_cards, -1);
+    for (int i = 0; i < n_ev; ++i) {
+        const int v = ev_vars[i];
+        if (v < 0) return set_err(BNPP_ERR_INVALID, "bad evidence variable");
+        if (v >= n_cards) continue;
+        if (ev_vals[i] < 0 || ev_vals[i] >= cv[v]) return set_err(BNPP_ERR_INVALID, "evidence value out of range");
+        ev[v] = ev_vals[i];
+    }
+    BucketSpec b;
+    for (int i = 0; i < n_in; ++i) {
+        std::vector<int> s(in_vars[i], in_vars[i] + in_ndims[i]);
+        b.in.push_back(n_ev > 0 ? conditioned_view(i, s, cv, ev) : natural_view(i, s, cv));
+    }
+    b.elim_var = elim_var;
+    std::vector<int> u = chain_scope(b.in);
+    if (elim_var >= 0) u = remove_var(u, elim_var);
+    std::vector<int> ov(out_vars, out_vars + out_ndims), us = u, os = ov;
+    std::sort(us.begin(), us.end());
+    std::sort(os.begin(), os.end());
+    if (us != os) return set_err(BNPP_ERR_INVALID, "output scope must be the union of the inputs minus elim_var");
+    b.out_vars = ov;
+    b.out_table = n_in;
+    b.divide = divide != 0;
+    SingleArgs a;
+    if (int rc = plan_single(dtype, cv, b, a)) return rc;
+    const SingleKey sk = single_key(dtype == BNPP_F32, a);
+    std::vector<int> keys;
+    kernel_keys(dtype == BNPP_F32, 0, sk.family, keys);
+    const bool o32 = sk.family == kFamGeneric && (sk.key & kGenericO32);
+    const int64_t v[12] = {sk.family, sk.key, a.d.n_in, a.d.k, a.d.v1, a.d.v2, a.d.big >= 0 ? a.d.bcls : 0, o32 ? 1 : 0,
+                           a.d.n_tiles, a.d.lanes, a.d.slab_y2,
+                           std::find(keys.begin(), keys.end(), sk.key) != keys.end() ? 1 : 0};
+    for (int i = 0; i < n_info && i < 12; ++i) info[i] = v[i];
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+int bnpp_kernel_keys(int dtype, int launch, int family, int *keys, int cap, int *n) {
+    BNPP_GUARD_BEGIN
+    if (!n || (cap > 0 && !keys)) return set_err(BNPP_ERR_INVALID, "null argument");
+    if ((dtype != BNPP_F32 && dtype != BNPP_F64) || (launch != 0 && launch != 1) || family < kFamGeneric || family > kFamSlab)
+        return set_err(BNPP_ERR_INVALID, "bad dtype, launch or family");
+    std::vector<int> k;
+    kernel_keys(dtype == BNPP_F32, launch, family, k);
+    *n = (int)k.size();
+    for (int i = 0; i < *n && i < cap; ++i) keys[i] = k[i];
     return BNPP_OK;
     BNPP_GUARD_END
 }

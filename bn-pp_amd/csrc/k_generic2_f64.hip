@@ -5,6 +5,8 @@
 // slot is selected at run time, and the whole tile then lives in scratch
 // memory (80-272 B per lane, each load waited for at once).  The one-dim
 // tiles measured slower without the sinking and keep the default.
+#include <vector>
+
 #include "kernels.cuh"
 
 namespace bnpp {
@@ -16,5 +18,9 @@ hipError_t dispatch_level_f64_2d(int key, const LevelArgs &a, int max_grid, hipS
 hipError_t dispatch_single_f64_2d(int key, const SingleArgs &a, int max_grid, hipStream_t stream) {
     switch (key) { BNPP_ALL(BNPP_CASE_SINGLE, BNPP_TILES_F64_2D, double) default: break; }
     return hipErrorInvalidValue;
+}
+void keys_generic_f64_2d(std::vector<int> &keys) {
+    static const int k[] = {BNPP_ALL(BNPP_LIST_GENERIC, BNPP_TILES_F64_2D, double)};
+    keys.insert(keys.end(), k, k + sizeof k / sizeof *k);
 }
 }  // namespace bnpp

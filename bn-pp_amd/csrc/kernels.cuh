@@ -1022,10 +1022,16 @@ static hipError_t go_stream_single(const SingleArgs &a, int max_grid, hipStream_
     BNPP_STREAM_BC(X, T, 2, 8)
 #define BNPP_STREAM_F64(X, T) BNPP_STREAM_INTER(X, T) BNPP_STREAM_BC(X, T, 1, 1) BNPP_STREAM_BC(X, T, 2, 1) BNPP_STREAM_BC(X, T, 4, 1) \
     BNPP_STREAM_BC(X, T, 2, 2) BNPP_STREAM_BC(X, T, 2, 4) BNPP_STREAM_BC(X, T, 4, 2)
+// one key expression per family, shared by the dispatch cases and the key
+// lists (BNPP_LIST_*: bnpp_kernel_keys), so a list is its switch's cases
+#define BNPP_KEY_STREAM(V1, V2, BC) (4096 + BC * 256 + V1 * 16 + V2)
+#define BNPP_KEY_STREAM8(V1, V2, BC) (4096 + kStream8In + BC * 256 + V1 * 16 + V2)
+#define BNPP_LIST_STREAM(T, V1, V2, BC) BNPP_KEY_STREAM(V1, V2, BC),
+#define BNPP_LIST_STREAM8(T, V1, V2, BC) BNPP_KEY_STREAM8(V1, V2, BC),
 #define BNPP_CASE_SLEVEL(T, V1, V2, BC) \
-    case 4096 + BC * 256 + V1 * 16 + V2: return go_stream_level<T, V1, V2, BC>(a, small_elems, max_grid, stream);
+    case BNPP_KEY_STREAM(V1, V2, BC): return go_stream_level<T, V1, V2, BC>(a, small_elems, max_grid, stream);
 #define BNPP_CASE_SSINGLE(T, V1, V2, BC) \
-    case 4096 + BC * 256 + V1 * 16 + V2: return go_stream_single<T, V1, V2, BC>(a, max_grid, stream);
+    case BNPP_KEY_STREAM(V1, V2, BC): return go_stream_single<T, V1, V2, BC>(a, max_grid, stream);
 // 5-8 inputs (kStream8In): the direct big classes over the plain tiles, no interleaved forms
 #define BNPP_STREAM8_BC(X, T, V1, V2) X(T, V1, V2, 1) X(T, V1, V2, 2) X(T, V1, V2, 3) X(T, V1, V2, 4) X(T, V1, V2, 5)
 #define BNPP_STREAM8_F32(X, T) BNPP_STREAM8_BC(X, T, 1, 1) BNPP_STREAM8_BC(X, T, 2, 1) BNPP_STREAM8_BC(X, T, 4, 1) \
@@ -1033,9 +1039,9 @@ static hipError_t go_stream_single(const SingleArgs &a, int max_grid, hipStream_
 #define BNPP_STREAM8_F64(X, T) BNPP_STREAM8_BC(X, T, 1, 1) BNPP_STREAM8_BC(X, T, 2, 1) BNPP_STREAM8_BC(X, T, 4, 1) \
     BNPP_STREAM8_BC(X, T, 2, 2) BNPP_STREAM8_BC(X, T, 2, 4) BNPP_STREAM8_BC(X, T, 4, 2)
 #define BNPP_CASE_SLEVEL8(T, V1, V2, BC) \
-    case 4096 + kStream8In + BC * 256 + V1 * 16 + V2: return go_stream_level<T, V1, V2, BC, 8>(a, small_elems, max_grid, stream);
+    case BNPP_KEY_STREAM8(V1, V2, BC): return go_stream_level<T, V1, V2, BC, 8>(a, small_elems, max_grid, stream);
 #define BNPP_CASE_SSINGLE8(T, V1, V2, BC) \
-    case 4096 + kStream8In + BC * 256 + V1 * 16 + V2: return go_stream_single<T, V1, V2, BC, 8>(a, max_grid, stream);
+    case BNPP_KEY_STREAM8(V1, V2, BC): return go_stream_single<T, V1, V2, BC, 8>(a, max_grid, stream);
 
 // (3, 1) (5, 1) (6, 1) (7, 1): a whole fastest dim of that card per thread
 #define BNPP_TILES_ODD(X, T, NIN) X(T, NIN, 3, 1) X(T, NIN, 5, 1) X(T, NIN, 6, 1) X(T, NIN, 7, 1)
@@ -1046,12 +1052,14 @@ static hipError_t go_stream_single(const SingleArgs &a, int max_grid, hipStream_
 #define BNPP_TILES_F64_2D(X, T, NIN) X(T, NIN, 2, 2) X(T, NIN, 2, 4) X(T, NIN, 4, 2)
 #define BNPP_ALL(X, TILES, T) TILES(X, T, 1) TILES(X, T, 2) TILES(X, T, 4) TILES(X, T, 8)
 
+#define BNPP_KEY_GENERIC(NIN, V1, V2) (NIN * 64 + V1 * 8 + V2)
+#define BNPP_LIST_GENERIC(T, NIN, V1, V2) BNPP_KEY_GENERIC(NIN, V1, V2), kGenericO32 + BNPP_KEY_GENERIC(NIN, V1, V2),
 #define BNPP_CASE_LEVEL(T, NIN, V1, V2) \
-    case NIN * 64 + V1 * 8 + V2: return go_level<T, NIN, V1, V2, false>(a, max_grid, stream); \
-    case kGenericO32 + NIN * 64 + V1 * 8 + V2: return go_level<T, NIN, V1, V2, true>(a, max_grid, stream);
+    case BNPP_KEY_GENERIC(NIN, V1, V2): return go_level<T, NIN, V1, V2, false>(a, max_grid, stream); \
+    case kGenericO32 + BNPP_KEY_GENERIC(NIN, V1, V2): return go_level<T, NIN, V1, V2, true>(a, max_grid, stream);
 #define BNPP_CASE_SINGLE(T, NIN, V1, V2) \
-    case NIN * 64 + V1 * 8 + V2: return go_single<T, NIN, V1, V2, false>(a, max_grid, stream); \
-    case kGenericO32 + NIN * 64 + V1 * 8 + V2: return go_single<T, NIN, V1, V2, true>(a, max_grid, stream);
+    case BNPP_KEY_GENERIC(NIN, V1, V2): return go_single<T, NIN, V1, V2, false>(a, max_grid, stream); \
+    case kGenericO32 + BNPP_KEY_GENERIC(NIN, V1, V2): return go_single<T, NIN, V1, V2, true>(a, max_grid, stream);
 
 
 }  // namespace bnpp

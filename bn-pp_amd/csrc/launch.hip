@@ -27,6 +27,15 @@ hipError_t dispatch_slab_single_f64(int key, const SingleArgs &a, hipStream_t st
 hipError_t dispatch_slab_level_f32(int key, const LevelArgs &a, hipStream_t stream);
 hipError_t dispatch_slab_level_f64(int key, const LevelArgs &a, hipStream_t stream);
 
+// the keys of each dispatch switch above (the generic and stream switches hold
+// the same keys for single-op and level launches)
+void keys_generic_f32(std::vector<int> &keys);
+void keys_generic_f64(std::vector<int> &keys);
+void keys_stream_f32(std::vector<int> &keys);
+void keys_stream_f64(std::vector<int> &keys);
+void keys_slab_f32(int level, std::vector<int> &keys);
+void keys_slab_f64(int level, std::vector<int> &keys);
+
 // Result tables out of the arena: blockIdx.x picks the table, the
 // kCopyParts workgroups along y share it grid-stride (a multi-GB
 // variable_elimination result would crawl through one workgroup); 16-B moves
@@ -56,20 +65,19 @@ hipError_t launch_copies(const CopyItem *items, int n, int64_t max_bytes, hipStr
 
 hipError_t launch_single(int is_f32, const SingleArgs &a, int max_grid, hipStream_t stream) {
     if (a.d.n_tiles <= 0) return hipSuccess;
-    if (a.d.big >= 0 && a.d.bcls == kBigSlab) {
-        const int key = slab_key(a.d.k, a.d.v1, a.d.v2, a.d.lanes, 1, a.d.slab_y2 ? 8 : a.d.n_in);
-        return is_f32 ? dispatch_slab_single_f32(key, a, stream) : dispatch_slab_single_f64(key, a, stream);
-    }
-    if (a.d.big >= 0) {
-        const int key = stream_key(a.d.bcls, a.d.v1, a.d.v2, a.d.n_in);
-        return is_f32 ? dispatch_stream_single_f32(key, a, max_grid, stream)
-                      : dispatch_stream_single_f64(key, a, max_grid, stream);
-    }
-    int64_t in_bytes = 0;
-    for (int i = 0; i < a.d.n_in && i < kMaxIn; ++i)
-        in_bytes = std::max<int64_t>(in_bytes, a.meta[i].size * (is_f32 ? 4 : 8));
-    const int key = variant_key(a.d.n_in, a.d.v1, a.d.v2) + (generic_o32(in_bytes) ? kGenericO32 : 0);   // plan.hpp generic_variant
-    return is_f32 ? dispatch_single_f32(key, a, max_grid, stream) : dispatch_single_f64(key, a, max_grid, stream);
+    const SingleKey sk = single_key(is_f32, a);
+    if (sk.family == kFamSlab)
+        return is_f32 ? dispatch_slab_single_f32(sk.key, a, stream) : dispatch_slab_single_f64(sk.key, a, stream);
+    if (sk.family == kFamStream)
+        return is_f32 ? dispatch_stream_single_f32(sk.key, a, max_grid, stream)
+                      : dispatch_stream_single_f64(sk.key, a, max_grid, stream);
+    return is_f32 ? dispatch_single_f32(sk.key, a, max_grid, stream) : dispatch_single_f64(sk.key, a, max_grid, stream);
+}
+
+void kernel_keys(int is_f32, int level, int family, std::vector<int> &keys) {
+    if (family == kFamGeneric) is_f32 ? keys_generic_f32(keys) : keys_generic_f64(keys);
+    else if (family == kFamStream) is_f32 ? keys_stream_f32(keys) : keys_stream_f64(keys);
+    else if (family == kFamSlab) is_f32 ? keys_slab_f32(level, keys) : keys_slab_f64(level, keys);
 }
 
 hipError_t launch_level(int is_f32, int variant, const BucketDesc *descs, int n_desc, const int64_t *pool,

@@ -1047,19 +1047,36 @@ struct PlanBuilder {
     // a bucket over `in` (any length) summing out `x` (-1: none); inputs past
     // kMaxIn are folded into materialised products left to right, like the
     // reference's chain
+    // a message's scope in the reference's order (the chain's union minus the
+    // summed variable, factor.cpp): messages are laid out canon()-ically, but
+    // the final result is delivered in the reference's order, which its
+    // message inputs carry here
+    std::map<int, std::vector<int>> ref_vars;
+    std::vector<int> ref_scope(const std::vector<View> &in) const {
+        std::vector<int> u;
+        for (const View &v : in) {
+            auto it = ref_vars.find(v.table);
+            u = union_scope(u, it != ref_vars.end() && it->second.size() == v.vars.size() ? it->second : v.vars);
+        }
+        return u;
+    }
     int emit(std::vector<View> in, int x, bool final_result) {
         while ((int)in.size() > kMaxIn) {
             std::vector<View> head(in.begin(), in.begin() + kMaxIn);
+            const std::vector<int> hr = ref_scope(head);
             int t = push_bucket(head, -1, canon(chain_scope(head)));
+            ref_vars[t] = hr;
             std::vector<View> rest;
             rest.push_back(view(t));
             rest.insert(rest.end(), in.begin() + kMaxIn, in.end());
             in.swap(rest);
         }
         std::vector<int> u = chain_scope(in);
+        const std::vector<int> ru = x >= 0 ? remove_var(ref_scope(in), x) : ref_scope(in);
         std::vector<int> ov = x >= 0 ? remove_var(u, x) : u;
-        if (!final_result) ov = canon(ov);
+        ov = final_result ? ru : canon(ov);
         int t = push_bucket(in, x, ov);
+        ref_vars[t] = ru;
         p.width = std::max(p.width, (int)ov.size());
         return t;
     }
@@ -2814,6 +2831,7 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
                 std::fprintf(stderr, "->%d", d.out_table);
                 if (d.outer_n > 0) std::fprintf(stderr, " outer=%d", d.outer_n);
                 if (d.slab_r > 1) std::fprintf(stderr, " passes=%d", d.slab_r);
+                std::fprintf(stderr, " key=%d", g.variant);
                 std::fprintf(stderr, "\n");
             }
         }

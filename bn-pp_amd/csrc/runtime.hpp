@@ -31,6 +31,26 @@ struct SingleArgs {
     int64_t pool[kMaxPool];
 };
 hipError_t launch_single(int is_f32, const SingleArgs &a, int max_grid, hipStream_t stream);
+// the kernel a single-op launch runs: family (0 generic, 1 stream, 2 slab) and
+// the key its dispatcher switches on.  launch_single dispatches by it and
+// bnpp_plan_single reports it, so the report is what launches
+enum KernelFamily : int { kFamGeneric = 0, kFamStream = 1, kFamSlab = 2 };
+struct SingleKey {
+    int family, key;
+};
+inline SingleKey single_key(int is_f32, const SingleArgs &a) {
+    if (a.d.big >= 0 && a.d.bcls == kBigSlab)
+        return {kFamSlab, slab_key(a.d.k, a.d.v1, a.d.v2, a.d.lanes, 1, a.d.slab_y2 ? 8 : a.d.n_in)};
+    if (a.d.big >= 0) return {kFamStream, stream_key(a.d.bcls, a.d.v1, a.d.v2, a.d.n_in)};
+    int64_t in_bytes = 0;
+    for (int i = 0; i < a.d.n_in && i < kMaxIn; ++i)
+        in_bytes = in_bytes > a.meta[i].size * (is_f32 ? 4 : 8) ? in_bytes : a.meta[i].size * (is_f32 ? 4 : 8);
+    return {kFamGeneric, variant_key(a.d.n_in, a.d.v1, a.d.v2) + (generic_o32(in_bytes) ? kGenericO32 : 0)};   // plan.hpp generic_variant
+}
+// the keys a family's dispatch switch holds (single-op or level launches),
+// appended to `keys`: generated from the X-macro lists of the switches
+// themselves (kernels.cuh, slab.cuh), so the two cannot diverge
+void kernel_keys(int is_f32, int level, int family, std::vector<int> &keys);
 // the reference's running sum of a single-op call (seqsum.hip): the terms
 // prod_n in[n][pos_n(i, val)] (or in[0] / in[1]) for i over the output dims
 // (reference scope order, last fastest) and val < k inner, added in order

@@ -273,6 +273,11 @@ static hipError_t go_slab_level(const LevelArgs &a, hipStream_t stream) {
     BNPP_SLAB_K(X, T, 2, 2, 1) BNPP_SLAB_K(X, T, 4, 1, 1) BNPP_SLAB_K(X, T, 4, 2, 1) BNPP_SLAB_K(X, T, 4, 2, 2)
 #define BNPP_SLAB_F64(X, T) BNPP_SLAB_K(X, T, 1, 1, 1) BNPP_SLAB_K(X, T, 1, 2, 1) BNPP_SLAB_K(X, T, 2, 1, 1) \
     BNPP_SLAB_K(X, T, 4, 1, 1) BNPP_SLAB_K(X, T, 2, 2, 1) BNPP_SLAB_K(X, T, 2, 2, 2) BNPP_SLAB_K(X, T, 4, 1, 2)
+// key lists of the dispatch cases below (bnpp_kernel_keys): the slab_key() calls of the cases
+#define BNPP_LIST_SLAB(T, K, C0, V, H) slab_key(K, C0, V, H),
+#define BNPP_LIST_SLAB_R2(T, K, C0, V, H) slab_key(K, C0, V, H, 2),
+#define BNPP_LIST_SLAB8_SINGLE(T, K, C0, V, H) slab_key(K, C0, V, H, 1, 8),
+#define BNPP_LIST_SLAB8_LEVEL(T, K, C0, V, H) slab_key(K, C0, V, H, 1, 8), slab_key(K, C0, V, H, 2, 8), slab_key(K, C0, V, H, 4, 8),
 #define BNPP_CASE_SLAB_SINGLE(T, K, C0, V, H) \
     case slab_key(K, C0, V, H): return go_slab_single<T, K, C0, V, H>(a, stream);
 #define BNPP_CASE_SLAB_LEVEL(T, K, C0, V, H) \

@@ -87,6 +87,8 @@ _SIGS = {
     "bnpp_variable_elimination": (_I, [_P, _P, _I, _IP, _I, _I, _I, _IP, _IP, C.c_int64, C.POINTER(C.c_int64), _DP,
                                        C.POINTER(C.c_int64)]),
     "bnpp_plan_stats": (_I, [_P, _I, _I, _IP, _IP, _I, _IP, _I, _I, _DP, _I]),
+    "bnpp_plan_single": (_I, [_I, _I, _IP, _I, _IP, C.POINTER(_IP), _I, _I, _IP, _I, _I, _IP, _IP, _LP, _I]),
+    "bnpp_kernel_keys": (_I, [_I, _I, _I, _IP, _I, _IP]),
     "bnpp_job_create": (_I, [_P, _P, _I, _I, _IP, _IP, _I, _IP, _I, _I, _IP, _I, C.POINTER(_P)]),
     "bnpp_job_stats": (_I, [_P, _DP, _I]),
     "bnpp_job_launch": (_I, [_P, _P]),
@@ -102,7 +104,7 @@ EXPORTED = sorted(_SIGS)
 
 # The signature table above is for this ABI version (include/bnpp.h
 # BNPP_VERSION); a library of another version would take shifted arguments.
-ABI_VERSION = 202
+ABI_VERSION = 203
 if _lib.bnpp_version() != ABI_VERSION:
     raise ImportError("libbnpp.so ABI version %d, this binding expects %d (%s)"
                       % (_lib.bnpp_version(), ABI_VERSION, LIB_PATH))
@@ -290,6 +292,37 @@ def plan_stats(model: Model, kind: int = 0, evidence=None, heuristic: str = "mf"
     _check(_lib.bnpp_plan_stats(model.handle, kind, n, ev_v, ev_x, h, oa, len(order) if order is not None else 0,
                                 dtype, st, 8), "bnpp_plan_stats")
     return list(st)
+
+
+PLAN_SINGLE_FIELDS = ("family", "key", "n_in", "k", "v1", "v2", "bcls", "o32", "n_tiles", "lanes", "slab_y2",
+                      "instantiated")
+FAMILIES = ("generic", "stream", "slab")
+
+
+def plan_single(dtype: int, cards: Sequence[int], scopes: Sequence[Sequence[int]], elim: int,
+                out_vars: Sequence[int], divide: bool = False, evidence: Optional[Dict[int, int]] = None
+                ) -> Dict[str, int]:
+    """Planning introspection for tests (bnpp_plan_single, host only): the
+    kernel bucket_eliminate / divide / condition would launch for these
+    arguments, as a dict of PLAN_SINGLE_FIELDS."""
+    arrs = [_ints(s) for s in scopes]
+    ptrs = (_IP * max(len(arrs), 1))(*[C.cast(a, _IP) for a in arrs])
+    n, ev_v, ev_x = _ev(evidence)
+    info = (C.c_int64 * len(PLAN_SINGLE_FIELDS))()
+    _check(_lib.bnpp_plan_single(dtype, len(cards), _ints(cards), len(scopes), _ints([len(s) for s in scopes]), ptrs,
+                                 elim, len(out_vars), _ints(out_vars), 1 if divide else 0, n, ev_v, ev_x, info,
+                                 len(PLAN_SINGLE_FIELDS)), "bnpp_plan_single")
+    return dict(zip(PLAN_SINGLE_FIELDS, list(info)))
+
+
+def kernel_keys(dtype: int, family: int, level: bool = False) -> List[int]:
+    """The dispatch keys instantiated for `dtype` in a family (index into
+    FAMILIES), for single-op or level launches (bnpp_kernel_keys)."""
+    n = C.c_int()
+    _check(_lib.bnpp_kernel_keys(dtype, 1 if level else 0, family, None, 0, C.byref(n)), "bnpp_kernel_keys")
+    out = (C.c_int * max(n.value, 1))()
+    _check(_lib.bnpp_kernel_keys(dtype, 1 if level else 0, family, out, n.value, C.byref(n)), "bnpp_kernel_keys")
+    return list(out[: n.value])
 
 
 def partition(ctx: Context, model: Model, evidence=None, heuristic: str = "mf", dtype: int = F64,

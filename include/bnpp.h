@@ -37,8 +37,9 @@
 extern "C" {
 #endif
 
-#define BNPP_VERSION 202   /* 200: single ops take n_cards (the length of cards); 201: sliced bucket-tree marginals;
-                              202: single ops return the reference's partition sum (out_sum) */
+#define BNPP_VERSION 203   /* 200: single ops take n_cards (the length of cards); 201: sliced bucket-tree marginals;
+                              202: single ops return the reference's partition sum (out_sum);
+                              203: planning introspection for tests (bnpp_plan_single, bnpp_kernel_keys) */
 
 enum bnpp_status {
     BNPP_OK = 0,
@@ -282,10 +283,29 @@ int bnpp_variable_elimination(bnpp_ctx *ctx, const bnpp_model *m, int n_vars, co
 
 /* Host-only planning statistics (no device needed): kind 0 partition (explicit
  * order if `order` is non-NULL), 1 marginals of all variables (one VE each),
- * 3 bucket-tree marginals of all variables.  stats as
- * bnpp_job_stats. */
+ * 2 bnpp_variable_elimination of the variables in `order`, 3 bucket-tree
+ * marginals of all variables.  stats as bnpp_job_stats. */
 int bnpp_plan_stats(const bnpp_model *m, int kind, int n_ev, const int *ev_vars, const int *ev_vals, int heuristic,
                     const int *order, int n_order, int dtype, double *stats, int n_stats);
+
+/* Planning introspection for tests (host only, no device): which kernel a
+ * single-op call launches.  The arguments of bnpp_bucket_eliminate without
+ * tables or stream; divide != 0 plans bnpp_divide (two inputs, elim_var -1);
+ * n_ev > 0 plans the inputs as bnpp_condition's views of that evidence
+ * (out_vars then holds the variables left).  It fails exactly where the call
+ * would.  info[0 .. n_info), n_info <= 12:
+ * [0] family (0 generic, 1 stream, 2 slab)  [1] dispatch key  [2] n_in
+ * [3] k (card of the summed variable, 1: none)  [4] v1  [5] v2 (register tile)
+ * [6] big class (0: generic)  [7] 32-bit offsets  [8] n_tiles  [9] lanes
+ * [10] slab_y2  [11] 1 when the key is instantiated for the dtype */
+int bnpp_plan_single(int dtype, int n_cards, const int *cards, int n_in, const int *in_ndims, const int *const *in_vars,
+                     int elim_var, int out_ndims, const int *out_vars, int divide, int n_ev, const int *ev_vars,
+                     const int *ev_vals, int64_t *info, int n_info);
+
+/* Planning introspection for tests: the dispatch keys instantiated for a dtype
+ * in the generic (0), stream (1) or slab (2) family, for single-op (launch 0)
+ * or level (launch 1) launches: *n keys, the first min(*n, cap) in keys. */
+int bnpp_kernel_keys(int dtype, int launch, int family, int *keys, int cap, int *n);
 
 /* Host-only planning of one part of bnpp_marginals_tree_part (all variables
  * as targets): owned[v] = 1 when this part computes v's marginal; stats as

@@ -48,11 +48,16 @@ def _cards_list(cards: dict):
     return [cards.get(v, 1) for v in range(n)]
 
 
-def run_bucket(ctx, dtype, cards, inputs, elim, out_vars=None, with_sum=False):
-    """inputs: [(scope, values)] -> (out_scope, values list[, partition sum])"""
+def run_bucket(ctx, dtype, cards, inputs, elim, out_vars=None, with_sum=False, expect=None):
+    """inputs: [(scope, values)] -> (out_scope, values list[, partition sum]).
+    expect: fields of bnpp.plan_single (the kernel this call launches) that
+    must hold, checked before the launch."""
     scopes = [s for s, _ in inputs]
     if out_vars is None:
         out_vars = bnpp.out_scope(scopes, elim)
+    if expect:
+        info = bnpp.plan_single(dtype, _cards_list(cards), scopes, elim, out_vars)
+        assert {f: info[f] for f in expect} == expect, (info, scopes, out_vars)
     size = 1
     for v in out_vars:
         size *= cards[v]
@@ -179,7 +184,9 @@ def test_random_buckets_bit_exact_vs_oracle(ctx):
 def test_interleaved_stream_buckets(ctx, k, n_other):
     """Stream form with the summed variable as the big input's FASTEST dim and
     the output's dim 0 right above it (the backward messages of a column-sweep
-    bucket tree): bit-exact against the oracle in fp64, 1e-6 in fp32."""
+    bucket tree): bit-exact against the oracle in fp64, 1e-6 in fp32.  That these shapes reach that kernel is
+    asserted by the planner's own report (bnpp.plan_single); test_variant_census.py
+    covers every instantiated key the same way."""
     rng = random.Random(k * 100 + n_other)
     y = 0
     others = list(range(1, n_other + 2))
@@ -187,6 +194,10 @@ def test_interleaved_stream_buckets(ctx, k, n_other):
     for v in others:
         cards[v] = rng.choice([2, 3, 4])
     cards[others[-1]] = 4                     # output dim 0: a multiple of the tile width
+    for v in others[:-1]:                     # the stream form starts at 1024 tiles (plan.cpp build_desc):
+        if math.prod(cards[w] for w in others) >= 1 << 15:
+            break
+        cards[v] = 8                          # widen the slowest dims up to 2^15 output entries
     big_scope = others + [y]
     size = 1
     for v in big_scope:
@@ -197,11 +208,16 @@ def test_interleaved_stream_buckets(ctx, k, n_other):
     for ins in ([big, pair], [pair, big, unary], [unary, big]):
         fs = [refcpu.Factor.new(sc, cards, v) for sc, v in ins]
         ref = refcpu.bucket(fs, y, cards[y])
-        scope, vals = run_bucket(ctx, bnpp.F64, cards, ins, y)
-        assert scope == ref.scope
-        assert vals == ref.values
-        scope, vals = run_bucket(ctx, bnpp.F32, cards, ins, y)
-        assert max(abs(a - b) / abs(b) for a, b in zip(vals, ref.values)) < 1e-6
+        # the output in the big input's order (the reference's chain order puts
+        # the pair's variable first when the pair leads: another layout, Direct loads)
+        t = torch.tensor(ref.values, dtype=torch.float64).reshape([cards[v] for v in ref.scope])
+        want = t.permute([ref.scope.index(v) for v in others]).reshape(-1).tolist()
+        inter = {"family": 1, "bcls": 6 if k == 2 else 7}      # stream, kBigInter2 / kBigInter4
+        scope, vals = run_bucket(ctx, bnpp.F64, cards, ins, y, out_vars=others, expect=inter)
+        assert scope == others
+        assert vals == want
+        scope, vals = run_bucket(ctx, bnpp.F32, cards, ins, y, out_vars=others, expect=inter)
+        assert max(abs(a - b) / abs(b) for a, b in zip(vals, want)) < 1e-6
 
 
 @pytest.mark.parametrize("k,kq,n_other", [(2, 2, 12), (2, 4, 8), (4, 2, 6), (4, 4, 5)])
@@ -209,7 +225,9 @@ def test_interleaved_broadcast_rows(ctx, k, kq, n_other):
     """The tree's backward message: the parent variable xq is absent from the
     big input and is the output's SLOWEST dim; the tile spans xq so one load of
     the big values serves every row (output rows at xq's stride).  Compared
-    with the oracle's table (reference order) transposed to the planned layout."""
+    with the oracle's table (reference order) transposed to the planned layout.  That these shapes reach that kernel is
+    asserted by the planner's own report (bnpp.plan_single); test_variant_census.py
+    covers every instantiated key the same way."""
     rng = random.Random(k * 1000 + kq * 100 + n_other)
     xq, y = 0, 1
     others = list(range(2, n_other + 2))
@@ -217,6 +235,10 @@ def test_interleaved_broadcast_rows(ctx, k, kq, n_other):
     for v in others:
         cards[v] = rng.choice([2, 4])
     cards[others[-1]] = 4
+    for v in others[:-1]:                     # the stream form starts at 1024 tiles (plan.cpp build_desc):
+        if math.prod(cards[w] for w in others) >= 1 << 15:
+            break
+        cards[v] = 8                          # widen the slowest dims up to 2^15 entries per row
     size = k
     for v in others:
         size *= cards[v]
@@ -230,21 +252,24 @@ def test_interleaved_broadcast_rows(ctx, k, kq, n_other):
     planned = [xq] + others
     t = torch.tensor(ref.values, dtype=torch.float64).reshape([cards[v] for v in ref.scope])
     want = t.permute([ref.scope.index(v) for v in planned]).reshape(-1).tolist()
-    scope, vals = run_bucket(ctx, bnpp.F64, cards, ins, y, out_vars=planned)
+    rows = {"family": 1, "bcls": 6 if k == 2 else 7, "v2": kq}   # interleaved, the tile spans xq
+    scope, vals = run_bucket(ctx, bnpp.F64, cards, ins, y, out_vars=planned, expect=rows)
     assert scope == planned
     assert vals == want
-    scope, vals = run_bucket(ctx, bnpp.F32, cards, ins, y, out_vars=planned)
+    scope, vals = run_bucket(ctx, bnpp.F32, cards, ins, y, out_vars=planned, expect=rows)
     assert max(abs(a - b) / abs(b) for a, b in zip(vals, want)) < 1e-6
 
 
 @pytest.mark.parametrize("k,c0,scards", [(4, 4, [4] * 6), (2, 2, [2] * 13), (2, 4, [2] * 12), (3, 1, [3] * 8),
-                                         (1, 2, [2] * 13), (2, 2, [3] * 8), (4, 1, [2] * 12), (3, 4, [3, 2] * 4)])
+                                         (1, 2, [2] * 13), (2, 2, [3] * 8), (4, 1, [2] * 12), (3, 4, [3, 2] * 5)])
 def test_slab_form_buckets(ctx, k, c0, scards):
     """Slab form (slab.cuh, flat grid): the big input holds the summed variable
     x as its slowest dim (k slabs contiguous along the output's slow index S),
     small inputs depend on (x, y) only, the output is (S..., y).  Every chain
     position of the big input; odd S cards force the one-entry-per-lane tile.
-    fp64 bit-exact against the oracle, fp32 1e-6 relative."""
+    fp64 bit-exact against the oracle, fp32 1e-6 relative.  That these shapes reach that kernel is
+    asserted by the planner's own report (bnpp.plan_single); test_variant_census.py
+    covers every instantiated key the same way."""
     rng = random.Random(k * 1000 + c0 * 100 + len(scards))
     x, y = 0, 1
     S = list(range(2, 2 + len(scards)))
@@ -271,9 +296,10 @@ def test_slab_form_buckets(ctx, k, c0, scards):
         planned = S + ys + ([x] if elim < 0 else [])
         t = torch.tensor(ref.values, dtype=torch.float64).reshape([cards[v] for v in ref.scope])
         want = t.permute([ref.scope.index(v) for v in planned]).reshape(-1).tolist()
-        scope, vals = run_bucket(ctx, bnpp.F64, cards, ins, elim, out_vars=planned)
+        slab = {"family": 2, "bcls": 8, "k": k}
+        scope, vals = run_bucket(ctx, bnpp.F64, cards, ins, elim, out_vars=planned, expect=slab)
         assert vals == want, [s for s, _ in ins]
-        scope, vals = run_bucket(ctx, bnpp.F32, cards, ins, elim, out_vars=planned)
+        scope, vals = run_bucket(ctx, bnpp.F32, cards, ins, elim, out_vars=planned, expect=slab)
         assert max(abs(a - b) / abs(b) for a, b in zip(vals, want)) < 1e-6
 
 
@@ -283,7 +309,9 @@ def test_stream_buckets_five_to_eight_inputs(ctx, n_small, big_at):
     small ones from LDS) -- the conditioned 32x32 PR's 5-input bucket over an
     8-GiB message.  Small inputs over the output's fastest dims, the summed
     variable and a slow dim; the big one at every chain position.  fp64
-    bit-exact against the oracle (and its partition sum), fp32 1e-6."""
+    bit-exact against the oracle (and its partition sum), fp32 1e-6.  That these shapes reach that kernel is
+    asserted by the planner's own report (bnpp.plan_single); test_variant_census.py
+    covers every instantiated key the same way."""
     rng = random.Random(n_small * 10 + big_at)
     x, a, b, z = 0, 1, 2, 3                       # summed var; fastest output dims a, b; slow dim z
     mid = list(range(4, 15))                      # the big input's middle dims (>= 2^13 entries)
@@ -309,9 +337,10 @@ def test_stream_buckets_five_to_eight_inputs(ctx, n_small, big_at):
     planned = [z] + mid + [b, a]
     t = torch.tensor(ref.values, dtype=torch.float64).reshape([cards[v] for v in ref.scope])
     want = t.permute([ref.scope.index(v) for v in planned]).reshape(-1).tolist()
-    scope, vals = run_bucket(ctx, bnpp.F64, cards, ins, x, out_vars=planned)
+    stream8 = {"family": 1, "n_in": n_small + 1}               # n_in > 4: the kStream8In instantiations
+    scope, vals = run_bucket(ctx, bnpp.F64, cards, ins, x, out_vars=planned, expect=stream8)
     assert vals == want
-    scope, vals = run_bucket(ctx, bnpp.F32, cards, ins, x, out_vars=planned)
+    scope, vals = run_bucket(ctx, bnpp.F32, cards, ins, x, out_vars=planned, expect=stream8)
     assert max(abs(p - q) / abs(q) for p, q in zip(vals, want)) < 1e-6
     # the whole-table partition sum in the reference's (entry, value) order
     scope, vals, psum2 = run_bucket(ctx, bnpp.F64, cards, ins, x, with_sum=True)
@@ -324,7 +353,9 @@ def test_slab_rows_over_two_dims(ctx, n_small, big_at):
     which the big input does not vary along (slab_y2), with 2-8 inputs
     (kSlab8In from 5): the big input holds x as slabs contiguous along the
     output's slow index, the small inputs depend on (x, a, b).  fp64
-    bit-exact against the oracle, fp32 1e-6."""
+    bit-exact against the oracle, fp32 1e-6.  That these shapes reach that kernel is
+    asserted by the planner's own report (bnpp.plan_single); test_variant_census.py
+    covers every instantiated key the same way."""
     rng = random.Random(700 + n_small * 10 + big_at)
     x, a, b = 0, 1, 2
     mid = list(range(3, 15))
@@ -350,9 +381,10 @@ def test_slab_rows_over_two_dims(ctx, n_small, big_at):
     planned = mid + [b, a]
     t = torch.tensor(ref.values, dtype=torch.float64).reshape([cards[v] for v in ref.scope])
     want = t.permute([ref.scope.index(v) for v in planned]).reshape(-1).tolist()
-    scope, vals = run_bucket(ctx, bnpp.F64, cards, ins, x, out_vars=planned)
+    rows2 = {"family": 2, "bcls": 8, "slab_y2": 2, "v1": 4}    # slab, the row over dims 0 and 1
+    scope, vals = run_bucket(ctx, bnpp.F64, cards, ins, x, out_vars=planned, expect=rows2)
     assert vals == want
-    scope, vals = run_bucket(ctx, bnpp.F32, cards, ins, x, out_vars=planned)
+    scope, vals = run_bucket(ctx, bnpp.F32, cards, ins, x, out_vars=planned, expect=rows2)
     assert max(abs(p - q) / abs(q) for p, q in zip(vals, want)) < 1e-6
 
 
