@@ -319,7 +319,10 @@ int build_plans(const ModelData &d, const std::vector<int> &ev, int kind, int he
         for (int v : vars)
             if (v < 0 || v >= nv) return set_err(BNPP_ERR_INVALID, "bad variable");
         max_width = elimination_order(nv, d.cards, scopes, vars, (Heuristic)heuristic, ord);
-        plans.push_back(plan_ve(d.cards, views, ord, true));
+        // BNPP_VE_CHAIN=1 (tests): fused runs as in kind 0, so that a run's message is
+        // seen entry by entry; the result keeps the reference's scope order either way
+        const char *vc = std::getenv("BNPP_VE_CHAIN");
+        plans.push_back(plan_ve(d.cards, views, ord, true, vc && *vc == '1' ? chain_eb : 0));
     } else if (kind == 0) {
         std::vector<int> vars, ord;
         if (order) {
@@ -1064,6 +1067,7 @@ int bnpp_ctx_create(int device, bnpp_ctx **out) {
     if (const char *g = tuning_knob("BNPP_GRID_PER_CU")) per_cu = std::max(0, std::min(64, std::atoi(g)));
     // 0: flat grid, one virtual block per workgroup (no grid-stride)
     ctx->c.max_grid = per_cu == 0 ? INT32_MAX : prop.multiProcessorCount * per_cu;
+    ctx->c.default_max_grid = ctx->c.max_grid;
     if ((e = hipStreamCreateWithFlags(&ctx->c.stream, hipStreamNonBlocking)) != hipSuccess)
         return set_err(BNPP_ERR_HIP, hipGetErrorString(e));
     {
@@ -1096,6 +1100,16 @@ int bnpp_ctx_destroy(bnpp_ctx *ctx) {
     drop_arena_cache(ctx->c);
     drop_buffer_cache(ctx->c);
     delete ctx;
+    return BNPP_OK;
+}
+
+int bnpp_ctx_set_max_grid(bnpp_ctx *ctx, int n) {
+    if (!ctx) return set_err(BNPP_ERR_INVALID, "null context");
+    if (n < 0) return set_err(BNPP_ERR_INVALID, "negative grid cap");
+    // launches read both at enqueue time; plans and cached jobs do not depend on them
+    std::lock_guard<std::mutex> lk(ctx->cache_mu);
+    ctx->c.grid_cap = n;
+    ctx->c.max_grid = n > 0 ? std::min(ctx->c.default_max_grid, n) : ctx->c.default_max_grid;
     return BNPP_OK;
 }
 
@@ -1492,6 +1506,39 @@ int bnpp_plan_stats(const bnpp_model *m, int kind, int n_ev, const int *ev_vars,
     BNPP_GUARD_END
 }
 
+int bnpp_plan_groups(const bnpp_model *m, int kind, int n_ev, const int *ev_vars, const int *ev_vals, int heuristic,
+                     const int *order, int n_order, int dtype, int part, int n_parts, int64_t *rows, int cap_rows,
+                     int *n_rows) {
+    BNPP_GUARD_BEGIN
+    if (!m || !n_rows || (cap_rows > 0 && !rows)) return set_err(BNPP_ERR_INVALID, "null argument");
+    if (kind < 0 || kind > 3) return set_err(BNPP_ERR_INVALID, "kind must be 0, 1, 2 or 3");
+    if (n_parts < 1 || part < 0 || part >= n_parts || (n_parts > 1 && kind != 3))
+        return set_err(BNPP_ERR_INVALID, "bad part / n_parts");
+    std::vector<int> ev, targets;
+    std::string msg;
+    if (!evidence_array(m->d, n_ev, ev_vars, ev_vals, ev, msg)) return set_err(BNPP_ERR_INVALID, msg);
+    if (kind == 1 || kind == 3)
+        for (int v = 0; v < (int)m->d.cards.size(); ++v) targets.push_back(v);
+    std::vector<Schedule> batches;
+    double st[10] = {0};
+    int rc = plan_schedules(m->d, ev, kind, heuristic, order, n_order, targets, dtype, memory_budget(nullptr), batches, st,
+                            part, n_parts);
+    if (rc) return rc;
+    int64_t n = 0;
+    for (size_t b = 0; b < batches.size(); ++b)
+        for (const Schedule::Group &g : batches[b].groups) {
+            if (n < cap_rows) {
+                const int64_t v[BNPP_PLAN_GROUP_FIELDS] = {(int64_t)b, g.level, g.variant, g.end - g.begin, g.vblocks, g.lane};
+                std::copy(v, v + BNPP_PLAN_GROUP_FIELDS, rows + n * BNPP_PLAN_GROUP_FIELDS);
+            }
+            ++n;
+        }
+    if (n > INT32_MAX) return set_err(BNPP_ERR_UNSUPPORTED, "more launch groups than the count can hold");
+    *n_rows = (int)n;
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
 int bnpp_plan_single(int dtype, int n_cards, const int *cards, int n_in, const int *in_ndims, const int *const *in_vars,
                      int elim_var, int out_ndims, const int *out_vars, int divide, int n_ev, const int *ev_vars,
                      const int *ev_vals, int64_t *info, int n_info) {
@@ -1547,7 +1594,7 @@ int bnpp_plan_single(int dtype, int n_cards, const int *cards, int n_in, const i
 int bnpp_kernel_keys(int dtype, int launch, int family, int *keys, int cap, int *n) {
     BNPP_GUARD_BEGIN
     if (!n || (cap > 0 && !keys)) return set_err(BNPP_ERR_INVALID, "null argument");
-    if ((dtype != BNPP_F32 && dtype != BNPP_F64) || (launch != 0 && launch != 1) || family < kFamGeneric || family > kFamSlab)
+    if ((dtype != BNPP_F32 && dtype != BNPP_F64) || (launch != 0 && launch != 1) || family < kFamGeneric || family > kFamChain)
         return set_err(BNPP_ERR_INVALID, "bad dtype, launch or family");
     std::vector<int> k;
     kernel_keys(dtype == BNPP_F32, launch, family, k);
@@ -1555,6 +1602,12 @@ int bnpp_kernel_keys(int dtype, int launch, int family, int *keys, int cap, int 
     for (int i = 0; i < *n && i < cap; ++i) keys[i] = k[i];
     return BNPP_OK;
     BNPP_GUARD_END
+}
+
+int bnpp_chain_key_supported(int dtype, int key, int *supported) {
+    if (!supported || (dtype != BNPP_F32 && dtype != BNPP_F64)) return set_err(BNPP_ERR_INVALID, "bad dtype or null output");
+    *supported = chain_supported(dtype == BNPP_F32 ? 4 : 8, key) ? 1 : 0;
+    return BNPP_OK;
 }
 
 int bnpp_plan_tree_part(const bnpp_model *m, int n_ev, const int *ev_vars, const int *ev_vals, int heuristic,

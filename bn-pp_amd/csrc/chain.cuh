@@ -457,6 +457,8 @@ static hipError_t go_chain_level(const LevelArgs &a, int small_elems, int max_gr
 #define BNPP_CASE_CHAIN(T, K, F, FORM, DEP) \
     case 8192 + DEP * 2048 + FORM * 256 + K * 16 + F: return go_chain_level<T, K, F, FORM, DEP>(a, small_elems, max_grid, stream);
 #define BNPP_CASE_CHAIN_OK(T, K, F, FORM, DEP) case 8192 + DEP * 2048 + FORM * 256 + K * 16 + F: return true;
+// key list of the dispatch cases (bnpp_kernel_keys family 3): the same X-macro lists, so a list is its switch's cases
+#define BNPP_LIST_CHAIN(T, K, F, FORM, DEP) 8192 + DEP * 2048 + FORM * 256 + K * 16 + F,
 // instantiated shapes: forward rows <= 256 B (V-wide forward for runs of
 // 4..16 entries), backward tables <= 64 entries
 // (V = 1 there); dep "any" only for tables <= 16 entries

@@ -894,7 +894,7 @@ void chain_split_kernel(const BucketDesc *__restrict__ descs, int n_desc, const 
 #define BNPP_SPLIT_WAVES_PER_CU 16     // resident waves per CU the persistent grid is sized for
 #endif
 template <typename T, int F, int FORM, int DEP, bool DENSE, bool BEL>
-static hipError_t go_chain_split(const LevelArgs &a, int small_elems, hipStream_t stream) {
+static hipError_t go_chain_split(const LevelArgs &a, int small_elems, int grid_cap, hipStream_t stream) {
     constexpr int EB = sizeof(T);
     constexpr int MODE1 = BEL ? 1 : 0;                    // one-run kernel of this key
     const bool one = a.n_desc == 1;
@@ -933,7 +933,8 @@ static hipError_t go_chain_split(const LevelArgs &a, int small_elems, hipStream_
     // (an fp64 run of 7 buckets holds 130.5 KiB: one workgroup, 8 waves)
     int per_cu = BNPP_SPLIT_WAVES_PER_CU / split_waves(F) > 0 ? BNPP_SPLIT_WAVES_PER_CU / split_waves(F) : 1;
     per_cu = std::max(1, std::min<int>(per_cu, (int)((size_t)kSplitLdsBytes / shm)));
-    const int64_t grid = a.vblocks < (int64_t)cus * per_cu ? a.vblocks : (int64_t)cus * per_cu;
+    int64_t grid = a.vblocks < (int64_t)cus * per_cu ? a.vblocks : (int64_t)cus * per_cu;
+    if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;   // bnpp_ctx_set_max_grid (0: the grid above)
     if (one)
         hipLaunchKernelGGL((chain_split_kernel<T, F, FORM, DEP, DENSE, MODE1>), dim3((unsigned)grid),
                            dim3(64 * split_waves(F)), shm, stream, a.descs, a.n_desc, a.pool, a.meta, a.vblocks);
@@ -949,9 +950,11 @@ static hipError_t go_chain_split(const LevelArgs &a, int small_elems, hipStream_
 // (chain_key + kChainBelKey)
 #define BNPP_CASE_CHAIN_SPLIT(T, F, FORM, KFORM, DEP, DENSE, BEL) \
     case 8192 + DEP * 2048 + FORM * 256 + 2 * 16 + F + (BEL ? kChainBelKey : 0): \
-        return go_chain_split<T, F, KFORM, DEP, DENSE, BEL>(a, small_elems, stream);
+        return go_chain_split<T, F, KFORM, DEP, DENSE, BEL>(a, small_elems, grid_cap, stream);
 #define BNPP_CASE_CHAIN_SPLIT_OK(T, F, FORM, KFORM, DEP, DENSE, BEL) \
     case 8192 + DEP * 2048 + FORM * 256 + 2 * 16 + F + (BEL ? kChainBelKey : 0): return true;
+#define BNPP_LIST_CHAIN_SPLIT(T, F, FORM, KFORM, DEP, DENSE, BEL) \
+    8192 + DEP * 2048 + FORM * 256 + 2 * 16 + F + (BEL ? kChainBelKey : 0),
 #define BNPP_CHAIN_SPLIT_FD(X, T, F) X(T, F, 5, kChainFwd, 0, false, false) X(T, F, 5, kChainFwd, 1, false, false) \
     X(T, F, 6, kChainBwd, 0, false, false) X(T, F, 6, kChainBwd, 1, false, false) \
     X(T, F, 7, kChainFwd, 0, true, false) X(T, F, 7, kChainFwd, 1, true, false) \

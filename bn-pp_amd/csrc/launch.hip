@@ -19,8 +19,10 @@ hipError_t dispatch_stream_single_f32(int key, const SingleArgs &a, int max_grid
 hipError_t dispatch_stream_level_f64(int key, const LevelArgs &a, int small_elems, int max_grid, hipStream_t stream);
 hipError_t dispatch_stream_single_f64(int key, const SingleArgs &a, int max_grid, hipStream_t stream);
 
-hipError_t dispatch_chain_level_f32(int key, const LevelArgs &a, int small_elems, int max_grid, hipStream_t stream);
-hipError_t dispatch_chain_level_f64(int key, const LevelArgs &a, int small_elems, int max_grid, hipStream_t stream);
+hipError_t dispatch_chain_level_f32(int key, const LevelArgs &a, int small_elems, int max_grid, int grid_cap,
+                                    hipStream_t stream);
+hipError_t dispatch_chain_level_f64(int key, const LevelArgs &a, int small_elems, int max_grid, int grid_cap,
+                                    hipStream_t stream);
 
 hipError_t dispatch_slab_single_f32(int key, const SingleArgs &a, hipStream_t stream);
 hipError_t dispatch_slab_single_f64(int key, const SingleArgs &a, hipStream_t stream);
@@ -35,6 +37,8 @@ void keys_stream_f32(std::vector<int> &keys);
 void keys_stream_f64(std::vector<int> &keys);
 void keys_slab_f32(int level, std::vector<int> &keys);
 void keys_slab_f64(int level, std::vector<int> &keys);
+void keys_chain_f32(std::vector<int> &keys);
+void keys_chain_f64(std::vector<int> &keys);
 
 // Result tables out of the arena: blockIdx.x picks the table, the
 // kCopyParts workgroups along y share it grid-stride (a multi-GB
@@ -78,17 +82,19 @@ void kernel_keys(int is_f32, int level, int family, std::vector<int> &keys) {
     if (family == kFamGeneric) is_f32 ? keys_generic_f32(keys) : keys_generic_f64(keys);
     else if (family == kFamStream) is_f32 ? keys_stream_f32(keys) : keys_stream_f64(keys);
     else if (family == kFamSlab) is_f32 ? keys_slab_f32(level, keys) : keys_slab_f64(level, keys);
+    else if (family == kFamChain && level) is_f32 ? keys_chain_f32(keys) : keys_chain_f64(keys);   // runs are level launches only
 }
 
 hipError_t launch_level(int is_f32, int variant, const BucketDesc *descs, int n_desc, const int64_t *pool,
-                        TableMeta *meta, int64_t total_vblocks, int small_elems, int max_grid, hipStream_t stream) {
+                        TableMeta *meta, int64_t total_vblocks, int small_elems, int max_grid, int grid_cap,
+                        hipStream_t stream) {
     if (n_desc <= 0 || total_vblocks <= 0) return hipSuccess;
     LevelArgs a{descs, n_desc, pool, meta, total_vblocks};
     if (variant >= 16384)                               // slab form: flat grid, one workgroup per virtual block
         return is_f32 ? dispatch_slab_level_f32(variant, a, stream) : dispatch_slab_level_f64(variant, a, stream);
     if (variant >= 8192)
-        return is_f32 ? dispatch_chain_level_f32(variant, a, small_elems, max_grid, stream)
-                      : dispatch_chain_level_f64(variant, a, small_elems, max_grid, stream);
+        return is_f32 ? dispatch_chain_level_f32(variant, a, small_elems, max_grid, grid_cap, stream)
+                      : dispatch_chain_level_f64(variant, a, small_elems, max_grid, grid_cap, stream);
     if (variant >= 4096)
         return is_f32 ? dispatch_stream_level_f32(variant, a, small_elems, max_grid, stream)
                       : dispatch_stream_level_f64(variant, a, small_elems, max_grid, stream);

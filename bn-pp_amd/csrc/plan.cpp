@@ -2810,6 +2810,7 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
                 std::fprintf(stderr, " slots:");
                 for (int q = 0; q < F; ++q) std::fprintf(stderr, " %lld/%lld", (long long)pl[2 * q], (long long)pl[2 * q + 1]);
                 if (d.flags & kChainBel) std::fprintf(stderr, " belief: %d x %d -> %d", d.in_table[d.n_in], d.out_table, d.aux_out);
+                std::fprintf(stderr, " key=%d", g.variant);
                 std::fprintf(stderr, "\n");
             } else if (dump && g.variant >= kXchgKeyBase) {
                 std::fprintf(stderr, "L%d xchg kind=%d mode=%d blocks=%d tables:%d->%d entries=%lld\n", g.level,

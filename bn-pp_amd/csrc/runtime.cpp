@@ -290,7 +290,7 @@ int launch(Context &ctx, Executable &ex, hipStream_t stream, const XchgHooks *ho
             if (rc) return rc;
         } else {
             err = launch_level(ex.dtype == kF32, g.variant, ex.d_desc + g.begin, g.end - g.begin, ex.d_pool, ex.d_meta,
-                               g.vblocks, g.small_elems, ctx.max_grid, st);
+                               g.vblocks, g.small_elems, ctx.max_grid, ctx.grid_cap, st);
             if (err != hipSuccess) return fail(ctx, err, "launch_level");
         }
         if (lanes && ex.g_record[gi] >= 0 && (err = hipEventRecord(ex.events[ex.g_record[gi]], st)) != hipSuccess)

@@ -16,7 +16,8 @@
 namespace bnpp {
 
 hipError_t launch_level(int is_f32, int variant, const BucketDesc *descs, int n_desc, const int64_t *pool,
-                        TableMeta *meta, int64_t total_vblocks, int small_elems, int max_grid, hipStream_t stream);
+                        TableMeta *meta, int64_t total_vblocks, int small_elems, int max_grid, int grid_cap,
+                        hipStream_t stream);
 
 // single bucket with the descriptor passed by value (no device-side metadata,
 // no rescaling): the exact Factor::product / sum_out / conditioning semantics.
@@ -34,7 +35,7 @@ hipError_t launch_single(int is_f32, const SingleArgs &a, int max_grid, hipStrea
 // the kernel a single-op launch runs: family (0 generic, 1 stream, 2 slab) and
 // the key its dispatcher switches on.  launch_single dispatches by it and
 // bnpp_plan_single reports it, so the report is what launches
-enum KernelFamily : int { kFamGeneric = 0, kFamStream = 1, kFamSlab = 2 };
+enum KernelFamily : int { kFamGeneric = 0, kFamStream = 1, kFamSlab = 2, kFamChain = 3 };
 struct SingleKey {
     int family, key;
 };
@@ -49,7 +50,8 @@ inline SingleKey single_key(int is_f32, const SingleArgs &a) {
 }
 // the keys a family's dispatch switch holds (single-op or level launches),
 // appended to `keys`: generated from the X-macro lists of the switches
-// themselves (kernels.cuh, slab.cuh), so the two cannot diverge
+// themselves (kernels.cuh, slab.cuh, chain.cuh, chainsplit.cuh), so the two
+// cannot diverge; chain runs (kFamChain) exist as level launches only
 void kernel_keys(int is_f32, int level, int family, std::vector<int> &keys);
 // the reference's running sum of a single-op call (seqsum.hip): the terms
 // prod_n in[n][pos_n(i, val)] (or in[0] / in[1]) for i over the output dims
@@ -92,7 +94,9 @@ enum DType { kF64 = 0, kF32 = 1 };
 struct Context {
     int device = 0;
     hipStream_t stream = nullptr;
-    int max_grid = 2048;
+    int max_grid = 2048;                // workgroups of a persistent launch (generic, stream, one-thread chain)
+    int default_max_grid = 2048;        // ... as bnpp_ctx_create sized it
+    int grid_cap = 0;                   // bnpp_ctx_set_max_grid (0: none): also caps the split chain launches
     std::string last_error;
     // arena kept between one-shot calls (partition / marginals): mapping and
     // unmapping a few hundred GB of HBM costs ~1 s each way, like a caching

@@ -56,6 +56,7 @@ _SIGS = {
     "bnpp_ctx_destroy": (_I, [_P]),
     "bnpp_ctx_stream": (_I, [_P, C.POINTER(_P)]),
     "bnpp_ctx_trim": (_I, [_P]),
+    "bnpp_ctx_set_max_grid": (_I, [_P, _I]),
     "bnpp_malloc": (_I, [_P, C.c_size_t, C.POINTER(_P)]),
     "bnpp_free": (_I, [_P, _P]),
     "bnpp_memcpy_h2d": (_I, [_P, _P, _P, C.c_size_t]),
@@ -89,6 +90,8 @@ _SIGS = {
     "bnpp_plan_stats": (_I, [_P, _I, _I, _IP, _IP, _I, _IP, _I, _I, _DP, _I]),
     "bnpp_plan_single": (_I, [_I, _I, _IP, _I, _IP, C.POINTER(_IP), _I, _I, _IP, _I, _I, _IP, _IP, _LP, _I]),
     "bnpp_kernel_keys": (_I, [_I, _I, _I, _IP, _I, _IP]),
+    "bnpp_chain_key_supported": (_I, [_I, _I, _IP]),
+    "bnpp_plan_groups": (_I, [_P, _I, _I, _IP, _IP, _I, _IP, _I, _I, _I, _I, _LP, _I, _IP]),
     "bnpp_job_create": (_I, [_P, _P, _I, _I, _IP, _IP, _I, _IP, _I, _I, _IP, _I, C.POINTER(_P)]),
     "bnpp_job_stats": (_I, [_P, _DP, _I]),
     "bnpp_job_launch": (_I, [_P, _P]),
@@ -104,7 +107,7 @@ EXPORTED = sorted(_SIGS)
 
 # The signature table above is for this ABI version (include/bnpp.h
 # BNPP_VERSION); a library of another version would take shifted arguments.
-ABI_VERSION = 203
+ABI_VERSION = 204
 if _lib.bnpp_version() != ABI_VERSION:
     raise ImportError("libbnpp.so ABI version %d, this binding expects %d (%s)"
                       % (_lib.bnpp_version(), ABI_VERSION, LIB_PATH))
@@ -163,6 +166,11 @@ class Context:
     def trim(self) -> None:
         """Release the device memory kept between calls (cached arena, buffers)."""
         _check(_lib.bnpp_ctx_trim(self.handle), "bnpp_ctx_trim")
+
+    def set_max_grid(self, n: int) -> None:
+        """Testing: at most n workgroups per persistent launch from now on (0: the
+        default grids), so that tile loops iterate on small inputs (bnpp_ctx_set_max_grid)."""
+        _check(_lib.bnpp_ctx_set_max_grid(self.handle, n), "bnpp_ctx_set_max_grid")
 
     def stream(self) -> int:
         s = _P()
@@ -296,7 +304,7 @@ def plan_stats(model: Model, kind: int = 0, evidence=None, heuristic: str = "mf"
 
 PLAN_SINGLE_FIELDS = ("family", "key", "n_in", "k", "v1", "v2", "bcls", "o32", "n_tiles", "lanes", "slab_y2",
                       "instantiated")
-FAMILIES = ("generic", "stream", "slab")
+FAMILIES = ("generic", "stream", "slab", "chain")
 
 
 def plan_single(dtype: int, cards: Sequence[int], scopes: Sequence[Sequence[int]], elim: int,
@@ -323,6 +331,36 @@ def kernel_keys(dtype: int, family: int, level: bool = False) -> List[int]:
     out = (C.c_int * max(n.value, 1))()
     _check(_lib.bnpp_kernel_keys(dtype, 1 if level else 0, family, out, n.value, C.byref(n)), "bnpp_kernel_keys")
     return list(out[: n.value])
+
+
+def chain_key_supported(dtype: int, key: int) -> bool:
+    """The planner's chain_supported predicate for a dispatch key (bnpp_chain_key_supported)."""
+    out = C.c_int()
+    _check(_lib.bnpp_chain_key_supported(dtype, key, C.byref(out)), "bnpp_chain_key_supported")
+    return bool(out.value)
+
+
+PLAN_GROUP_FIELDS = ("batch", "level", "key", "n_desc", "vblocks", "lane")
+
+
+def plan_groups(model: Model, kind: int = 0, evidence=None, heuristic: str = "mf", dtype: int = F64,
+                order: Optional[Sequence[int]] = None, part: int = 0, n_parts: int = 1) -> List[Dict[str, int]]:
+    """Planning introspection for tests (bnpp_plan_groups, host only): the launch
+    groups of the plan plan_stats reports on, one dict of PLAN_GROUP_FIELDS
+    each.  n_desc tells which kernel a split chain key runs: 1 its one-run
+    kernel, more its multi-run kernel."""
+    n, ev_v, ev_x = _ev(evidence)
+    oa = _ints(order) if order is not None else None
+    h = ORDER_GIVEN if order is not None else HEURISTICS[heuristic]
+    no = len(order) if order is not None else 0
+    nf = len(PLAN_GROUP_FIELDS)
+    cnt = C.c_int()
+    _check(_lib.bnpp_plan_groups(model.handle, kind, n, ev_v, ev_x, h, oa, no, dtype, part, n_parts, None, 0,
+                                 C.byref(cnt)), "bnpp_plan_groups")
+    rows = (C.c_int64 * max(cnt.value * nf, 1))()
+    _check(_lib.bnpp_plan_groups(model.handle, kind, n, ev_v, ev_x, h, oa, no, dtype, part, n_parts, rows, cnt.value,
+                                 C.byref(cnt)), "bnpp_plan_groups")
+    return [dict(zip(PLAN_GROUP_FIELDS, rows[i * nf:(i + 1) * nf])) for i in range(cnt.value)]
 
 
 def partition(ctx: Context, model: Model, evidence=None, heuristic: str = "mf", dtype: int = F64,

@@ -37,9 +37,10 @@
 extern "C" {
 #endif
 
-#define BNPP_VERSION 203   /* 200: single ops take n_cards (the length of cards); 201: sliced bucket-tree marginals;
+#define BNPP_VERSION 204   /* 200: single ops take n_cards (the length of cards); 201: sliced bucket-tree marginals;
                               202: single ops return the reference's partition sum (out_sum);
-                              203: planning introspection for tests (bnpp_plan_single, bnpp_kernel_keys) */
+                              203: planning introspection for tests (bnpp_plan_single, bnpp_kernel_keys);
+                              204: chain-run introspection (bnpp_plan_groups, chain keys, bnpp_ctx_set_max_grid) */
 
 enum bnpp_status {
     BNPP_OK = 0,
@@ -86,6 +87,12 @@ int bnpp_ctx_stream(bnpp_ctx *ctx, void **stream);
 /* release the device memory the context keeps between calls (the cached arena
  * of the last partition / marginals call and the small-buffer cache) */
 int bnpp_ctx_trim(bnpp_ctx *ctx);
+/* Testing: every persistent launch of this context from now on uses at most n
+ * workgroups (n = 0: the default grids again), so that the kernels' tile loops
+ * iterate on small inputs: the generic, stream and chain launches.  The slab
+ * launches have a flat grid (one workgroup per virtual block) and keep it.
+ * Plans, cached jobs and results do not depend on it. */
+int bnpp_ctx_set_max_grid(bnpp_ctx *ctx, int n);
 int bnpp_malloc(bnpp_ctx *ctx, size_t bytes, void **dptr);
 int bnpp_free(bnpp_ctx *ctx, void *dptr);
 int bnpp_memcpy_h2d(bnpp_ctx *ctx, void *dst, const void *src, size_t bytes);
@@ -303,9 +310,30 @@ int bnpp_plan_single(int dtype, int n_cards, const int *cards, int n_in, const i
                      const int *ev_vals, int64_t *info, int n_info);
 
 /* Planning introspection for tests: the dispatch keys instantiated for a dtype
- * in the generic (0), stream (1) or slab (2) family, for single-op (launch 0)
- * or level (launch 1) launches: *n keys, the first min(*n, cap) in keys. */
+ * in the generic (0), stream (1), slab (2) or chain (3) family, for single-op
+ * (launch 0) or level (launch 1) launches: *n keys, the first min(*n, cap) in
+ * keys.  Chain runs are level launches only (launch 0 lists none); their
+ * fused-belief kernels are listed under their own keys. */
 int bnpp_kernel_keys(int dtype, int launch, int family, int *keys, int cap, int *n);
+
+/* Planning introspection for tests: *supported = 1 when the planner's own
+ * predicate (chain_supported: what build_desc asks before it picks a chain
+ * form) accepts `key` for the dtype.  bnpp_kernel_keys family 3 lists exactly
+ * the keys it accepts. */
+int bnpp_chain_key_supported(int dtype, int key, int *supported);
+
+/* Planning introspection for tests (host only, no device): the launch groups
+ * of the plan bnpp_plan_stats reports on (same kind, evidence, order, dtype
+ * and planning switches; kind 3 also by part of n_parts as
+ * bnpp_plan_tree_part, else part 0 of 1).  One row of BNPP_PLAN_GROUP_FIELDS
+ * values per group, batches in order: [0] batch  [1] level  [2] dispatch key
+ * [3] descriptors in the launch (a split chain key runs its one-run kernel
+ * with 1, its multi-run kernel with more)  [4] virtual blocks  [5] lane.
+ * *n_rows groups, the first min(*n_rows, cap_rows) in rows. */
+#define BNPP_PLAN_GROUP_FIELDS 6
+int bnpp_plan_groups(const bnpp_model *m, int kind, int n_ev, const int *ev_vars, const int *ev_vals, int heuristic,
+                     const int *order, int n_order, int dtype, int part, int n_parts, int64_t *rows, int cap_rows,
+                     int *n_rows);
 
 /* Host-only planning of one part of bnpp_marginals_tree_part (all variables
  * as targets): owned[v] = 1 when this part computes v's marginal; stats as

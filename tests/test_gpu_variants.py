@@ -49,6 +49,13 @@ def stream():
     return s.cuda_stream
 
 
+@pytest.fixture
+def grid_cap(ctx):
+    """ctx.set_max_grid for one test: the default grids are restored after it."""
+    yield ctx.set_max_grid
+    ctx.set_max_grid(0)
+
+
 def _select(entries, family, dt):
     return [(i, e) for i, e in enumerate(entries) if e["family"] == family and e["dtype"] == dt]
 
@@ -89,15 +96,23 @@ def test_single_op_variants(ctx, entries, stream, monkeypatch, family, dt):
 
 
 @pytest.mark.parametrize("dt", ["f64", "f32"])
-@pytest.mark.parametrize("family", ["generic", "stream", "slab"])
-def test_level_twins(ctx, entries, monkeypatch, family, dt):
+@pytest.mark.parametrize("family,cap", [pytest.param("generic", 0, id="generic"), pytest.param("stream", 0, id="stream"),
+                                        pytest.param("slab", 0, id="slab"),
+                                        pytest.param("generic", 1, id="generic-cap1"),
+                                        pytest.param("stream", 1, id="stream-cap1")])
+def test_level_twins(ctx, entries, monkeypatch, grid_cap, family, cap, dt):
     """Every catalogue bucket with a summed variable (found for either dtype),
-    run in `dt`, as a model: its inputs are
+    run in `dt`, as a model -- with the default grids (cap 0) and again on a
+    context capped at one workgroup (bnpp_ctx_set_max_grid), which then walks
+    every virtual block of the launch in the kernel's grid-stride loop; the
+    slab family's grid is flat (one workgroup per virtual block: the cap does
+    not touch it), so it has no capped run.  Its inputs are
     the factors and bnpp_variable_elimination sums the variable out, so the
     bucket runs on a level kernel (uploaded and rescaled by powers of two only:
     runtime.cpp upload_sources, kernels.cuh kScale).  values * 2^exp2 == the
     oracle's variable_elimination in fp64, == the float32 restatement of
     BN::variable_elimination in fp32 (values in [2^-21, 2): no underflow)."""
+    grid_cap(cap)
     done = 0
     for i, e in _select(entries, family, "f64") + _select(entries, family, "f32"):
         if e["elim"] < 0 or e["divide"]:
