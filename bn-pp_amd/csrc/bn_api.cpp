@@ -442,6 +442,24 @@ double Model::partition(const std::unordered_map<unsigned, unsigned> &evidence,
     return z;                                        // part.partition() (model.cpp:289)
 }
 
+std::vector<unsigned> Model::mpe(const std::unordered_map<unsigned, unsigned> &evidence,
+                                 std::unordered_map<std::string, bool> &options, double *log10_value,
+                                 double *uptime) const {
+    auto t0 = std::chrono::steady_clock::now();
+    ModelGuard g{to_engine(_variables, std::vector<const Factor *>(_factors.begin(), _factors.end()))};
+    std::vector<int> ev_vars, ev_vals;
+    split_evidence(evidence, ev_vars, ev_vals);
+    double lv = 0, up = 0;
+    std::vector<int> x(_variables.size() ? _variables.size() : 1, 0);
+    int dt = options["fp32"] ? BNPP_F32 : BNPP_F64;
+    check(bnpp_mpe(ctx(), g.m, (int)ev_vars.size(), ev_vars.data(), ev_vals.data(), heuristic_of(options), nullptr, 0,
+                   dt, &lv, x.data(), &up),
+          "mpe");
+    if (log10_value) *log10_value = lv;
+    if (uptime) *uptime = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return std::vector<unsigned>(x.begin(), x.begin() + _variables.size());
+}
+
 std::vector<const Factor *> Model::marginals(const std::unordered_map<unsigned, unsigned> &evidence,
                                              std::unordered_map<std::string, bool> &options, double &uptime) const {
     auto t0 = std::chrono::steady_clock::now();

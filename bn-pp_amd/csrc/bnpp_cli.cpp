@@ -3,6 +3,8 @@
 // and -uai <base> (UAI-competition result files <base>.PR / <base>.MAR, the
 // format of the reference's models/markovnets/*.PR / *.MAR fixtures: log10 Z;
 // per variable its card and probabilities, evidence variables one-hot).
+// -mpe (no reference counterpart): the most probable explanation, log10 of its
+// value and the assignment; with -uai, <base>.MPE ("MPE", then "N x_0 .. x_{N-1}").
 // BAYES files print like `bn` (raw Z), MARKOV files like `mn` (log10 Z).
 // -ve is accepted and, as in the reference, changes nothing here: bn reads it
 // only for REPL queries (bn.cpp:346); partition / marginals always run VE
@@ -27,6 +29,7 @@ int main(int argc, char **argv) {
         if (p == "-uai" && i + 1 < argc) uai_out = argv[++i];
         else if (p == "-pr") options["partition"] = true;
         else if (p == "-mar") options["marginals"] = true;
+        else if (p == "-mpe") options["mpe"] = true;
         else if (p == "-mar-tree") { options["marginals"] = true; options["bucket-tree"] = true; }
         else if (p == "-ve") options["variable-elimination"] = true;
         else if (p == "-sp") options["sum-product"] = true;      // bn.cpp:177-178: loopy BP marginals
@@ -40,7 +43,7 @@ int main(int argc, char **argv) {
         else positional.push_back(p);
     }
     if (positional.empty() || options["help"]) {
-        std::cout << "usage: " << argv[0] << " /path/to/model.uai [/path/to/evidence.uai.evid] -pr|-mar|-mar-tree [-sp] [-mf|-wmf|-md] [-f32] [-uai base]" << std::endl;
+        std::cout << "usage: " << argv[0] << " /path/to/model.uai [/path/to/evidence.uai.evid] -pr|-mar|-mar-tree|-mpe [-sp] [-mf|-wmf|-md] [-f32] [-uai base]" << std::endl;
         return positional.empty() ? 1 : 0;
     }
     bnpp_model *probe = nullptr;
@@ -108,6 +111,21 @@ int main(int argc, char **argv) {
                 std::fclose(f);
             }
             for (auto pf : marg) delete pf;
+        }
+        if (options["mpe"]) {
+            double lv = 0;
+            const std::vector<unsigned> x = model->mpe(evidence, options, &lv, &uptime);
+            std::cout << ">> MPE log10 value = " << lv << std::endl << ">> MPE assignment:";
+            for (unsigned v : x) std::cout << " " << v;
+            std::cout << std::endl << ">> Executed in " << uptime << "ms." << std::endl << std::endl;
+            if (!uai_out.empty()) {
+                FILE *f = std::fopen((uai_out + ".MPE").c_str(), "w");
+                if (!f) throw std::runtime_error("cannot write " + uai_out + ".MPE");
+                std::fprintf(f, "MPE\n%zu", x.size());
+                for (unsigned v : x) std::fprintf(f, " %u", v);
+                std::fprintf(f, "\n");
+                std::fclose(f);
+            }
         }
     } catch (const std::exception &e) {
         std::cerr << "Error: " << e.what() << std::endl;

@@ -99,7 +99,8 @@ struct BucketDesc {
     // 32 B: each lane then stores 16 B and a wave's store is one contiguous
     // 1-KiB run instead of 16-B pieces at a 32-B stride)
     int32_t lanes;
-    // kChainBel: the belief table the run also writes
+    // kChainBel: the belief table the run also writes; max buckets
+    // (maxout.cuh): the arg table, one byte per output entry
     int32_t aux_out;
     // slab form with outer dims (outer_n > 0 combinations of the output dims
     // slower than the slab dim, each a run of whole virtual blocks):
@@ -196,6 +197,11 @@ __host__ __device__ inline int chain_key(int form, int k, int f, int dep) {
 // a dense backward split run forming a fused belief (kChainBel) launches its
 // own kernel: key chain_key(...) + kChainBelKey (k * 16 + f < 128 leaves the bit free)
 constexpr int kChainBelKey = 128;
+// max-product buckets (maxout.cuh): kMaxKeyBase + the generic key of the same
+// shape (variant_key + kGenericO32); above every sum family's range (generic
+// < 2048, stream 4096.., chain 8192.., slab 16384 .. 32767)
+constexpr int kMaxKeyBase = 65536;
+constexpr int kMaxOutCard = 256;   // the arg of a max bucket is one byte per entry
 // rest entries per thread of the backward form (the forward form has 1)
 __host__ __device__ constexpr int chain_bwd_v(int n, int elem_bytes) {
     return 64 / n < 1 ? 1 : (64 / n > 16 / elem_bytes ? 16 / elem_bytes : 64 / n);

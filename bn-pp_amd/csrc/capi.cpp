@@ -165,6 +165,40 @@ int run_single(bnpp_ctx *ctx, void *stream, int dtype, const std::vector<int> &c
     return BNPP_OK;
 }
 
+// The bucket of a single-op max call (bnpp_bucket_max, bnpp_plan_max_single):
+// validated like bnpp_bucket_eliminate's, with elim_var required and its card
+// checked here, on the host, before anything is planned or launched.
+int max_single_spec(int n_cards, const int *cards, int n_in, const int *in_ndims, const int *const *in_vars,
+                    int elim_var, int out_ndims, const int *out_vars, BucketSpec &b, std::vector<int> &cv) {
+    if (!cards || n_in < 1 || !in_ndims || !in_vars) return set_err(BNPP_ERR_INVALID, "null argument");
+    if (n_in > kMaxIn) return set_err(BNPP_ERR_UNSUPPORTED, "at most 8 inputs per fused call");
+    if (n_cards < 0 || elim_var < 0 || elim_var >= n_cards || cards[elim_var] < 1 || (out_ndims > 0 && !out_vars))
+        return set_err(BNPP_ERR_INVALID, "variable id outside cards[0, n_cards)");
+    for (int i = 0; i < n_in; ++i)
+        if (!valid_scope(in_ndims[i], in_vars[i], cards, n_cards)) return set_err(BNPP_ERR_INVALID, "bad input scope");
+    if (!valid_scope(out_ndims, out_vars, cards, n_cards)) return set_err(BNPP_ERR_INVALID, "bad output scope");
+    cv.assign(cards, cards + n_cards);
+    b = BucketSpec{};
+    bool has_elim = false;
+    for (int i = 0; i < n_in; ++i) {
+        std::vector<int> s(in_vars[i], in_vars[i] + in_ndims[i]);
+        for (int x : s) has_elim = has_elim || x == elim_var;
+        b.in.push_back(natural_view(i, s, cv));
+    }
+    if (has_elim && cv[elim_var] > kMaxOutCard)
+        return set_err(BNPP_ERR_UNSUPPORTED, "max bucket: the maximised variable has more than 256 values (the arg is one byte)");
+    b.elim_var = elim_var;
+    std::vector<int> u = remove_var(chain_scope(b.in), elim_var);
+    std::vector<int> ov(out_vars, out_vars + out_ndims), us = u, os = ov;
+    std::sort(us.begin(), us.end());
+    std::sort(os.begin(), os.end());
+    if (us != os) return set_err(BNPP_ERR_INVALID, "output scope must be the union of the inputs minus elim_var");
+    b.out_vars = ov;
+    b.out_table = n_in;
+    b.max_out = true;
+    return BNPP_OK;
+}
+
 // Factor::_partition of a single-op call (seqsum.hip), enqueued after the op
 // on the same stream: the terms of the inputs' chain product (or in[0] /
 // in[1]) over `dims` -- the reference's output scope order, last fastest --
@@ -302,7 +336,8 @@ uint64_t slot_key(const std::vector<int> &cards, const std::vector<std::vector<i
     return h;
 }
 
-// Build the VE plans for a job: kind 0 = partition, kind 1 = marginals of targets.
+// Build the VE plans for a job: kind 0 = partition, kind 1 = marginals of
+// targets, 2 = caller-chosen variables, 3 = bucket-tree marginals, 4 = MPE.
 int build_plans(const ModelData &d, const std::vector<int> &ev, int kind, int heuristic, const int *order,
                 int n_order, const std::vector<int> &targets, std::vector<VEPlan> &plans, int &max_width,
                 int64_t budget, int eb, int part = 0, int n_parts = 1, int n_slices = 1, int slice_rank = 0) {
@@ -341,6 +376,30 @@ int build_plans(const ModelData &d, const std::vector<int> &ev, int kind, int he
             max_width = elimination_order(nv, d.cards, scopes, vars, (Heuristic)heuristic, ord);
         }
         plans.push_back(plan_ve(d.cards, views, ord, true, chain_eb));
+    } else if (kind == 4) {
+        // most probable explanation: max-product over every non-evidence variable
+        std::vector<int> vars, ord;
+        if (order) {
+            std::vector<char> seen(nv, 0);
+            for (int i = 0; i < n_order; ++i) {
+                int v = order[i];
+                if (v < 0 || v >= nv || seen[v]) return set_err(BNPP_ERR_INVALID, "bad explicit order");
+                seen[v] = 1;
+                if (ev[v] < 0) vars.push_back(v);
+            }
+            for (int v = 0; v < nv; ++v)
+                if (!seen[v] && ev[v] < 0) return set_err(BNPP_ERR_INVALID, "explicit order must cover every non-evidence variable");
+            ord = vars;
+            max_width = order_width(nv, scopes, ord);
+        } else {
+            for (int v = 0; v < nv; ++v)
+                if (ev[v] < 0) vars.push_back(v);
+            max_width = elimination_order(nv, d.cards, scopes, vars, (Heuristic)heuristic, ord);
+        }
+        VEPlan mp;
+        std::string msg;
+        if (!plan_mpe(d.cards, views, ord, ev, eb, mp, &msg)) return set_err(BNPP_ERR_UNSUPPORTED, msg);
+        plans.push_back(std::move(mp));
     } else if (kind == 3) {
         // all marginals from one two-pass bucket tree over the PR ordering
         std::vector<int> vars, ord;
@@ -649,7 +708,7 @@ int plan_schedules(const ModelData &d, const std::vector<int> &ev, int kind, int
     std::vector<int64_t> needs(plans.size());
     parallel_for((int64_t)plans.size(), [&](int64_t i) {
         const VEPlan &p = plans[i];
-        needs[i] = sat_add(kind == 3 ? plan_arena_bytes(p, eb) : plan_peak_bytes(p, eb), (int64_t)p.buckets.size() * 512);
+        needs[i] = sat_add(kind == 3 || kind == 4 ? plan_arena_bytes(p, eb) : plan_peak_bytes(p, eb), (int64_t)p.buckets.size() * 512);
     });
     int64_t acc = 0;
     for (size_t i = 0; i < plans.size(); ++i) {
@@ -659,6 +718,14 @@ int plan_schedules(const ModelData &d, const std::vector<int> &ev, int kind, int
             char m[256];
             std::snprintf(m, sizeof m, "bucket-tree marginals need %.2f GB, budget %.2f GB: the tree is not a "
                           "chain or no checkpoint count fits (per-target marginals or a narrower order)", need / 1e9, budget / 1e9);
+            return set_err(BNPP_ERR_OOM, m);
+        }
+        if (kind == 4 && need > budget) {
+            // every arg table stays resident until the traceback (no checkpointing)
+            char m[256];
+            std::snprintf(m, sizeof m, "MPE needs %.3f GB (messages %.3f GB + arg tables %.3f GB, all resident until the "
+                          "traceback), budget %.3f GB", need / 1e9, std::max<int64_t>(need - p.arg_bytes, 0) / 1e9,
+                          p.arg_bytes / 1e9, budget / 1e9);
             return set_err(BNPP_ERR_OOM, m);
         }
         if (!batches.back().empty() && sat_add(acc, need) > budget) {
@@ -875,7 +942,8 @@ uint64_t call_key(const bnpp_model *m, int kind, int n_ev, const int *ev_vars, c
 }
 
 // results of a launched job: partition -> out[0] = log10 Z (z_out: Z);
-// marginals -> sum(card) normalised values
+// marginals -> sum(card) normalised values; MPE -> out[0] = log10 of the
+// maximum, then the assignment (n_vars values)
 int job_results(bnpp_job *job, hipStream_t stream, double *out, double *z_out, int *owned = nullptr) {
     std::vector<std::vector<double>> vals;
     std::vector<int64_t> exp2;
@@ -886,6 +954,24 @@ int job_results(bnpp_job *job, hipStream_t stream, double *out, double *z_out, i
     for (auto &ex : job->pg.parts) {
         for (auto &v : ex.sched.plan_result_vars) rvars.push_back(&v);
         for (char c : ex.sched.plan_result_owned) mine.push_back(c);
+    }
+    if (job->kind == 4) {
+        // the maximum (a scalar, scaled) and the traceback's assignment: int32
+        // per variable in the program's results buffer, behind the scalar
+        const double p = vals[0].empty() ? 0.0 : vals[0][0];
+        out[0] = p > 0 ? std::log10(p) + (double)exp2[0] * std::log10(2.0) : -INFINITY;
+        const size_t nv = job->cards.size();
+        std::vector<int32_t> x(nv ? nv : 1, 0);
+        const Program &pg = job->pg;
+        if (pg.res_off.empty() || pg.res_off[0].size() < 2 || pg.res_off[0][1] < 0)
+            return set_err(BNPP_ERR_INVALID, "MPE job without an assignment table");
+        if (nv) {
+            hipError_t e = hipMemcpy(x.data(), static_cast<const unsigned char *>(pg.results) + pg.res_off[0][1],
+                                     nv * sizeof(int32_t), hipMemcpyDeviceToHost);
+            if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("hipMemcpy(assignment): ") + hipGetErrorString(e));
+        }
+        for (size_t v = 0; v < nv; ++v) out[1 + v] = (double)x[v];
+        return BNPP_OK;
     }
     if (job->kind == 0) {
         double p = 0;                                   // part.partition(): sequential sum
@@ -1225,6 +1311,47 @@ int bnpp_bucket_eliminate(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, c
     BNPP_GUARD_END
 }
 
+int bnpp_bucket_max(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, int n_in,
+                    const void *const *in_tables, const int *in_ndims, const int *const *in_vars, int elim_var,
+                    void *out_table, int out_ndims, const int *out_vars, uint8_t *out_arg) {
+    BNPP_GUARD_BEGIN
+    if (!ctx || !in_tables || !out_table) return set_err(BNPP_ERR_INVALID, "null argument");
+    BucketSpec b;
+    std::vector<int> cv;
+    if (int rc = max_single_spec(n_cards, cards, n_in, in_ndims, in_vars, elim_var, out_ndims, out_vars, b, cv)) return rc;
+    SingleArgs a;
+    if (int rc = plan_single(dtype, cv, b, a)) return rc;
+    for (int i = 0; i < n_in; ++i) a.meta[i].ptr = const_cast<void *>(in_tables[i]);
+    a.meta[n_in].ptr = out_table;
+    a.arg_out = out_arg;
+    hipError_t e = hipSetDevice(ctx->c.device);
+    if (e == hipSuccess) e = launch_max_single(dtype == BNPP_F32, a, ctx->c.max_grid, pick_stream(ctx, stream));
+    if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+int bnpp_plan_max_single(int dtype, int n_cards, const int *cards, int n_in, const int *in_ndims,
+                         const int *const *in_vars, int elim_var, int out_ndims, const int *out_vars, int64_t *info,
+                         int n_info) {
+    BNPP_GUARD_BEGIN
+    if (!info) return set_err(BNPP_ERR_INVALID, "null argument");
+    BucketSpec b;
+    std::vector<int> cv;
+    if (int rc = max_single_spec(n_cards, cards, n_in, in_ndims, in_vars, elim_var, out_ndims, out_vars, b, cv)) return rc;
+    SingleArgs a;
+    if (int rc = plan_single(dtype, cv, b, a)) return rc;
+    const SingleKey sk = max_single_key(dtype == BNPP_F32, a);
+    std::vector<int> keys;
+    kernel_keys(dtype == BNPP_F32, 0, sk.family, keys);
+    const int64_t v[12] = {sk.family, sk.key, a.d.n_in, a.d.k, a.d.v1, a.d.v2, 0, (sk.key & kGenericO32) ? 1 : 0,
+                           a.d.n_tiles, a.d.lanes, a.d.slab_y2,
+                           std::find(keys.begin(), keys.end(), sk.key) != keys.end() ? 1 : 0};
+    for (int i = 0; i < n_info && i < 12; ++i) info[i] = v[i];
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
 int bnpp_product(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, const void *a, int a_ndims,
                  const int *a_vars, const void *b, int b_ndims, const int *b_vars, void *out, int out_ndims,
                  const int *out_vars, double *out_sum) {
@@ -1443,8 +1570,8 @@ int bnpp_job_create(bnpp_ctx *ctx, const bnpp_model *m, int kind, int n_ev, cons
     BNPP_GUARD_BEGIN
     if (!out) return set_err(BNPP_ERR_INVALID, "null output");
     *out = nullptr;
-    if (kind != 0 && kind != 1 && kind != 3)
-        return set_err(BNPP_ERR_INVALID, "kind must be 0 (partition), 1 (marginals) or 3 (bucket-tree marginals)");
+    if (kind != 0 && kind != 1 && kind != 3 && kind != 4)
+        return set_err(BNPP_ERR_INVALID, "kind must be 0 (partition), 1 (marginals), 3 (bucket-tree marginals) or 4 (MPE)");
     std::unique_ptr<bnpp_job> job;
     int rc = create_job(ctx, m, kind, n_ev, ev_vars, ev_vals, heuristic, order, n_order, n_targets, targets, dtype, job);
     if (rc) {
@@ -1491,7 +1618,7 @@ int bnpp_plan_stats(const bnpp_model *m, int kind, int n_ev, const int *ev_vars,
                     const int *order, int n_order, int dtype, double *stats, int n_stats) {
     BNPP_GUARD_BEGIN
     if (!m || !stats) return set_err(BNPP_ERR_INVALID, "null argument");
-    if (kind < 0 || kind > 3) return set_err(BNPP_ERR_INVALID, "kind must be 0, 1, 2 or 3");
+    if (kind < 0 || kind > 4) return set_err(BNPP_ERR_INVALID, "kind must be 0, 1, 2, 3 or 4");
     std::vector<int> ev, targets;
     std::string msg;
     if (!evidence_array(m->d, n_ev, ev_vars, ev_vals, ev, msg)) return set_err(BNPP_ERR_INVALID, msg);
@@ -1506,12 +1633,12 @@ int bnpp_plan_stats(const bnpp_model *m, int kind, int n_ev, const int *ev_vars,
     BNPP_GUARD_END
 }
 
-int bnpp_plan_groups(const bnpp_model *m, int kind, int n_ev, const int *ev_vars, const int *ev_vals, int heuristic,
-                     const int *order, int n_order, int dtype, int part, int n_parts, int64_t *rows, int cap_rows,
-                     int *n_rows) {
+// the launch groups of a plan (bnpp_plan_groups: kinds 0-3; bnpp_plan_mpe_groups: kind 4)
+static int plan_groups_rows(const bnpp_model *m, int kind, int n_ev, const int *ev_vars, const int *ev_vals,
+                            int heuristic, const int *order, int n_order, int dtype, int part, int n_parts,
+                            int64_t *rows, int cap_rows, int *n_rows) {
     BNPP_GUARD_BEGIN
     if (!m || !n_rows || (cap_rows > 0 && !rows)) return set_err(BNPP_ERR_INVALID, "null argument");
-    if (kind < 0 || kind > 3) return set_err(BNPP_ERR_INVALID, "kind must be 0, 1, 2 or 3");
     if (n_parts < 1 || part < 0 || part >= n_parts || (n_parts > 1 && kind != 3))
         return set_err(BNPP_ERR_INVALID, "bad part / n_parts");
     std::vector<int> ev, targets;
@@ -1537,6 +1664,20 @@ int bnpp_plan_groups(const bnpp_model *m, int kind, int n_ev, const int *ev_vars
     *n_rows = (int)n;
     return BNPP_OK;
     BNPP_GUARD_END
+}
+
+int bnpp_plan_groups(const bnpp_model *m, int kind, int n_ev, const int *ev_vars, const int *ev_vals, int heuristic,
+                     const int *order, int n_order, int dtype, int part, int n_parts, int64_t *rows, int cap_rows,
+                     int *n_rows) {
+    // the sum plans; an MPE plan's groups have an entry point of their own (bnpp_plan_mpe_groups)
+    if (kind < 0 || kind > 3) return set_err(BNPP_ERR_INVALID, "kind must be 0, 1, 2 or 3");
+    return plan_groups_rows(m, kind, n_ev, ev_vars, ev_vals, heuristic, order, n_order, dtype, part, n_parts, rows,
+                            cap_rows, n_rows);
+}
+
+int bnpp_plan_mpe_groups(const bnpp_model *m, int n_ev, const int *ev_vars, const int *ev_vals, int heuristic,
+                         const int *order, int n_order, int dtype, int64_t *rows, int cap_rows, int *n_rows) {
+    return plan_groups_rows(m, 4, n_ev, ev_vars, ev_vals, heuristic, order, n_order, dtype, 0, 1, rows, cap_rows, n_rows);
 }
 
 int bnpp_plan_single(int dtype, int n_cards, const int *cards, int n_in, const int *in_ndims, const int *const *in_vars,
@@ -1594,7 +1735,7 @@ int bnpp_plan_single(int dtype, int n_cards, const int *cards, int n_in, const i
 int bnpp_kernel_keys(int dtype, int launch, int family, int *keys, int cap, int *n) {
     BNPP_GUARD_BEGIN
     if (!n || (cap > 0 && !keys)) return set_err(BNPP_ERR_INVALID, "null argument");
-    if ((dtype != BNPP_F32 && dtype != BNPP_F64) || (launch != 0 && launch != 1) || family < kFamGeneric || family > kFamChain)
+    if ((dtype != BNPP_F32 && dtype != BNPP_F64) || (launch != 0 && launch != 1) || family < kFamGeneric || family > kFamMax)
         return set_err(BNPP_ERR_INVALID, "bad dtype, launch or family");
     std::vector<int> k;
     kernel_keys(dtype == BNPP_F32, launch, family, k);
@@ -1687,6 +1828,39 @@ int bnpp_partition(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_v
     if (rc) return rc;
     if (log10_z) *log10_z = lz;
     if (z) *z = zz;
+    if (uptime_ms) *uptime_ms = now_ms() - t0;
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+int bnpp_mpe(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, const int *ev_vals, int heuristic,
+             const int *order, int n_order, int dtype, double *log10_value, int *assignment, double *uptime_ms) {
+    BNPP_GUARD_BEGIN
+    double t0 = now_ms();
+    if (!ctx || !m) return set_err(BNPP_ERR_INVALID, "null context or model");
+    bnpp_job *job = nullptr;
+    std::unique_lock<std::mutex> lk(ctx->cache_mu, std::try_to_lock);
+    const bool cache_ok = lk.owns_lock();
+    const int64_t budget = memory_budget(ctx, true);
+    // the job kind is part of the key: an MPE call and a PR call on the same model never share a job
+    const uint64_t key = cache_ok ? call_key(m, 4, n_ev, ev_vars, ev_vals, heuristic, order, n_order, 0, nullptr, dtype,
+                                             0, 1) : 0;
+    int rc = oneshot_job(ctx, cache_ok, key, budget, [&](std::unique_ptr<bnpp_job> &j) {
+        return create_job(ctx, m, 4, n_ev, ev_vars, ev_vals, heuristic, order, n_order, 0, nullptr, dtype, j, 0, 1,
+                          cache_ok);
+    }, job);
+    const double t1 = now_ms();
+    if (rc == BNPP_OK) rc = from_ctx(ctx, launch_program(ctx->c, job->pg, ctx->c.stream));
+    const double t2 = now_ms();
+    std::vector<double> res(1 + m->d.cards.size(), 0.0);
+    if (rc == BNPP_OK) rc = job_results(job, ctx->c.stream, res.data(), nullptr);
+    const double t3 = now_ms();
+    oneshot_done(ctx, cache_ok, key, budget, job, rc);
+    record_call_timing(t0, t1, t2, t3);
+    if (rc) return rc;
+    if (log10_value) *log10_value = res[0];
+    if (assignment)
+        for (size_t v = 0; v < m->d.cards.size(); ++v) assignment[v] = (int)res[1 + v];
     if (uptime_ms) *uptime_ms = now_ms() - t0;
     return BNPP_OK;
     BNPP_GUARD_END

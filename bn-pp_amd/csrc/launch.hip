@@ -1,6 +1,6 @@
 // Host-side launchers: route a descriptor to the translation unit that holds
 // its kernel instantiation (k_generic_f32/f64, k_stream_f32/f64, k_slab_f32/f64,
-// k_chain_f32/f64).
+// k_chain_f32/f64, k_max_f32/f64).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,6 +24,11 @@ hipError_t dispatch_chain_level_f32(int key, const LevelArgs &a, int small_elems
 hipError_t dispatch_chain_level_f64(int key, const LevelArgs &a, int small_elems, int max_grid, int grid_cap,
                                     hipStream_t stream);
 
+hipError_t dispatch_max_level_f32(int key, const LevelArgs &a, int max_grid, hipStream_t stream);
+hipError_t dispatch_max_level_f64(int key, const LevelArgs &a, int max_grid, hipStream_t stream);
+hipError_t dispatch_max_single_f32(int key, const SingleArgs &a, int max_grid, hipStream_t stream);
+hipError_t dispatch_max_single_f64(int key, const SingleArgs &a, int max_grid, hipStream_t stream);
+
 hipError_t dispatch_slab_single_f32(int key, const SingleArgs &a, hipStream_t stream);
 hipError_t dispatch_slab_single_f64(int key, const SingleArgs &a, hipStream_t stream);
 hipError_t dispatch_slab_level_f32(int key, const LevelArgs &a, hipStream_t stream);
@@ -39,6 +44,8 @@ void keys_slab_f32(int level, std::vector<int> &keys);
 void keys_slab_f64(int level, std::vector<int> &keys);
 void keys_chain_f32(std::vector<int> &keys);
 void keys_chain_f64(std::vector<int> &keys);
+void keys_max_f32(std::vector<int> &keys);
+void keys_max_f64(std::vector<int> &keys);
 
 // Result tables out of the arena: blockIdx.x picks the table, the
 // kCopyParts workgroups along y share it grid-stride (a multi-GB
@@ -78,10 +85,17 @@ hipError_t launch_single(int is_f32, const SingleArgs &a, int max_grid, hipStrea
     return is_f32 ? dispatch_single_f32(sk.key, a, max_grid, stream) : dispatch_single_f64(sk.key, a, max_grid, stream);
 }
 
+hipError_t launch_max_single(int is_f32, const SingleArgs &a, int max_grid, hipStream_t stream) {
+    if (a.d.n_tiles <= 0) return hipSuccess;
+    const SingleKey sk = max_single_key(is_f32, a);
+    return is_f32 ? dispatch_max_single_f32(sk.key, a, max_grid, stream) : dispatch_max_single_f64(sk.key, a, max_grid, stream);
+}
+
 void kernel_keys(int is_f32, int level, int family, std::vector<int> &keys) {
     if (family == kFamGeneric) is_f32 ? keys_generic_f32(keys) : keys_generic_f64(keys);
     else if (family == kFamStream) is_f32 ? keys_stream_f32(keys) : keys_stream_f64(keys);
     else if (family == kFamSlab) is_f32 ? keys_slab_f32(level, keys) : keys_slab_f64(level, keys);
+    else if (family == kFamMax) is_f32 ? keys_max_f32(keys) : keys_max_f64(keys);
     else if (family == kFamChain && level) is_f32 ? keys_chain_f32(keys) : keys_chain_f64(keys);   // runs are level launches only
 }
 
@@ -90,6 +104,8 @@ hipError_t launch_level(int is_f32, int variant, const BucketDesc *descs, int n_
                         hipStream_t stream) {
     if (n_desc <= 0 || total_vblocks <= 0) return hipSuccess;
     LevelArgs a{descs, n_desc, pool, meta, total_vblocks};
+    if (variant >= kMaxKeyBase)                         // max-product buckets (maxout.cuh)
+        return is_f32 ? dispatch_max_level_f32(variant, a, max_grid, stream) : dispatch_max_level_f64(variant, a, max_grid, stream);
     if (variant >= 16384)                               // slab form: flat grid, one workgroup per virtual block
         return is_f32 ? dispatch_slab_level_f32(variant, a, stream) : dispatch_slab_level_f64(variant, a, stream);
     if (variant >= 8192)

@@ -503,9 +503,58 @@ static bool build_chain_desc(const BucketSpec &b, const std::vector<int> &cards,
     return true;
 }
 
+// The traceback step of an MPE plan: no kernel descriptor, its rows in the
+// dims pool (the layout mpe_decode_kernel reads, maxout.cuh).  d.k rows,
+// d.n_dims tree depths, d.out_size variables.
+static bool build_decode_desc(const BucketSpec &b, BucketDesc &d, std::vector<int64_t> &pool, std::string *msg) {
+    d = BucketDesc{};
+    d.out_table = b.out_table;
+    d.big = -1;
+    d.dim_off = (int64_t)pool.size();
+    const int64_t base = d.dim_off;
+    int n_depths = 0;
+    for (size_t r = 0; r < b.decode_rows.size(); ++r) {
+        const BucketSpec::DecodeRow &row = b.decode_rows[r];
+        if (row.depth < 0 || (r > 0 && row.depth < b.decode_rows[r - 1].depth) || row.vars.size() != row.strides.size()) {
+            if (msg) *msg = "decode rows must be ordered by depth";
+            return false;
+        }
+        n_depths = std::max(n_depths, row.depth + 1);
+    }
+    const int64_t n_vars = (int64_t)b.decode_init.size(), n_rows = (int64_t)b.decode_rows.size();
+    pool.push_back(n_vars);
+    pool.push_back(n_rows);
+    pool.push_back(n_depths);
+    size_t r = 0;
+    for (int dp = 0; dp <= n_depths; ++dp) {          // first row of each depth, then n_rows
+        while (r < b.decode_rows.size() && b.decode_rows[r].depth < dp) ++r;
+        pool.push_back((int64_t)r);
+    }
+    for (int v : b.decode_init) pool.push_back(v);
+    const size_t off_at = pool.size();
+    pool.resize(pool.size() + (size_t)n_rows, 0);
+    for (size_t i = 0; i < b.decode_rows.size(); ++i) {
+        const BucketSpec::DecodeRow &row = b.decode_rows[i];
+        pool[off_at + i] = (int64_t)pool.size() - base;
+        pool.push_back(row.arg_table);
+        pool.push_back(row.elim_var);
+        pool.push_back((int64_t)row.vars.size());
+        for (size_t j = 0; j < row.vars.size(); ++j) {
+            pool.push_back(row.vars[j]);
+            pool.push_back(row.strides[j]);
+        }
+    }
+    d.k = (int32_t)n_rows;
+    d.n_dims = n_depths;
+    d.out_size = n_vars;
+    d.n_tiles = 1;
+    return true;
+}
+
 bool build_desc(const BucketSpec &b, const std::vector<int> &cards, int max_vec, BucketDesc &d,
                 std::vector<int64_t> &pool, std::string *msg, bool slab_outer) {
     if (!b.chain_x.empty()) return build_chain_desc(b, cards, max_vec, d, pool, msg);
+    if (b.decode) return build_decode_desc(b, d, pool, msg);
     const int n = (int)b.in.size();
     if (n < 1 || n > kMaxIn) {
         if (msg) *msg = "bucket needs 1.." + std::to_string(kMaxIn) + " inputs, got " + std::to_string(n);
@@ -574,6 +623,17 @@ bool build_desc(const BucketSpec &b, const std::vector<int> &cards, int max_vec,
                     k = cards[b.elim_var];
                 }
     }
+    if (b.max_out) {
+        if (b.elim_var < 0 || b.divide) {
+            if (msg) *msg = "a max bucket maximises over one variable (no divide)";
+            return false;
+        }
+        if (k > kMaxOutCard) {                  // the arg is one byte per entry
+            if (msg) *msg = "max bucket: variable " + std::to_string(b.elim_var) + " has " + std::to_string(k) +
+                            " values, the arg table holds at most " + std::to_string(kMaxOutCard);
+            return false;
+        }
+    }
     // register tile: v1 entries of the fastest dim (vector loads for stride-1
     // inputs), then v2 entries of the next dim when v1 covers the whole fastest
     // dim (the tile is then v1*v2 contiguous output entries)
@@ -597,7 +657,7 @@ bool build_desc(const BucketSpec &b, const std::vector<int> &cards, int max_vec,
     if (!merged.empty()) {
         for (int v = 4; v >= 2; v >>= 1)
             if (v <= max_tile && merged[0].card % (uint64_t)v == 0 && aligned(0, v)) { v1 = v; break; }
-        if (merged.size() >= 2 && (uint64_t)v1 == merged[0].card) {
+        if (!b.max_out && merged.size() >= 2 && (uint64_t)v1 == merged[0].card) {   // max buckets: V1 x 1 tiles (maxout.cuh)
             const int v2_max = (v1 == 2 && max_tile == 16) ? 8 : 4;   // instantiated tiles (kernels.hip)
             for (int v = max_tile / v1; v >= 2; v >>= 1)
                 if (v <= v2_max && merged[1].card % (uint64_t)v == 0 && aligned(1, v)) { v2 = v; break; }
@@ -613,6 +673,7 @@ bool build_desc(const BucketSpec &b, const std::vector<int> &cards, int max_vec,
     d.k = k;
     d.out_table = b.out_table;
     d.flags = kScale | kTrackMax;
+    d.aux_out = b.max_out ? b.arg_table : 0;
     for (int i = 0; i < kMaxIn; ++i) {
         d.in_table[i] = i < n ? b.in[i].table : 0;
         d.in_base[i] = i < n ? b.in[i].base : 0;
@@ -652,7 +713,7 @@ bool build_desc(const BucketSpec &b, const std::vector<int> &cards, int max_vec,
                               !(os && *os == '1');
         // 5-8 inputs: their own stream instantiations (kStream8In), every tile but 2x8
         const bool nin_ok = n <= 4 || (n <= kMaxIn && !(v1 == 2 && v2 == 8));
-        if (!b.simple && !b.divide && n_big == 1 && nin_ok && small_total * eb <= kStreamLdsBudget && d.n_tiles >= 1024 &&
+        if (!b.simple && !b.divide && !b.max_out && n_big == 1 && nin_ok && small_total * eb <= kStreamLdsBudget && d.n_tiles >= 1024 &&
             !(off && *off == '1') && !odd_rows) {
             int64_t s0 = merged.empty() ? 0 : merged[0].s[big];
             int64_t s1 = merged.size() < 2 ? 0 : merged[1].s[big];
@@ -891,7 +952,7 @@ bool build_desc(const BucketSpec &b, const std::vector<int> &cards, int max_vec,
     // load per input per output; whole-dim tiles decode once per card0
     // outputs and load stride-1 inputs as runs (scalar for odd cards, so no
     // alignment; card 6 as pairs)
-    if (d.big < 0 && v1 == 1 && !merged.empty() && !b.simple) {
+    if (d.big < 0 && v1 == 1 && !merged.empty() && !b.simple && !b.max_out) {
         const uint64_t c0 = merged[0].card;
         if ((c0 == 3 || c0 == 5 || c0 == 7 || (c0 == 6 && aligned(0, 2))) && (int)c0 <= max_tile) {
             v1 = (int)c0;
@@ -990,6 +1051,15 @@ struct PlanBuilder {
         t.vars = vars;
         t.size = table_size(vars, cards);
         p.max_table = std::max(p.max_table, t.size);
+        p.msgs.push_back(t);
+        level.push_back(0);
+        return p.n_src + (int)p.msgs.size() - 1;
+    }
+    // a table that is no message over variables (an MPE plan's arg tables and
+    // assignment): `entries` elements of the plan's dtype, no scope
+    int new_raw(int64_t entries) {
+        MsgTable t;
+        t.size = entries;
         p.msgs.push_back(t);
         level.push_back(0);
         return p.n_src + (int)p.msgs.size() - 1;
@@ -1411,6 +1481,86 @@ VEPlan plan_ve(const std::vector<int> &cards, const std::vector<View> &sources, 
     }
     B.finish();
     return p;
+}
+
+bool plan_mpe(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
+              const std::vector<int> &ev_val, int elem_bytes, VEPlan &out, std::string *msg) {
+    out = VEPlan{};
+    VEPlan &p = out;
+    PlanBuilder B(cards, p, sources, order, true);
+    const int nord = (int)order.size();
+    std::vector<std::vector<View>> buckets(nord);
+    std::vector<View> result;
+    for (const View &s : sources) {
+        int bi = B.first_bucket(s.vars, 0);
+        if (bi >= 0) buckets[bi].push_back(s);
+        else result.push_back(s);
+    }
+    std::vector<BucketSpec::DecodeRow> rows;
+    std::vector<int> row_of(nord, -1);
+    for (int i = 0; i < nord; ++i) {
+        if (buckets[i].empty()) continue;   // a variable in no remaining factor: any value is a maximiser, the traceback keeps 0
+        if (cards[order[i]] > kMaxOutCard) {
+            if (msg) *msg = "MPE: variable " + std::to_string(order[i]) + " has " + std::to_string(cards[order[i]]) +
+                            " values; the arg tables hold one byte per entry (at most " + std::to_string(kMaxOutCard) + ")";
+            return false;
+        }
+        const int t = B.emit(buckets[i], order[i], false);
+        BucketSpec &bk = p.buckets.back();              // the eliminating bucket (prefix products precede it)
+        const int64_t entries = p.msgs[t - p.n_src].size;
+        bk.max_out = true;
+        bk.arg_table = B.new_raw((entries + elem_bytes - 1) / elem_bytes);   // bytes, in whole elements
+        B.level[bk.arg_table] = bk.level;
+        p.arg_bytes = sat_add(p.arg_bytes, (entries + 255) / 256 * 256);
+        BucketSpec::DecodeRow row;
+        row.arg_table = bk.arg_table;
+        row.elim_var = order[i];
+        row.depth = 0;
+        row.vars = bk.out_vars;
+        row.strides = natural_strides(bk.out_vars, cards);
+        row_of[i] = (int)rows.size();
+        rows.push_back(row);
+        View mv = B.view(t);
+        int bi = B.first_bucket(mv.vars, i + 1);
+        if (bi >= 0) buckets[bi].push_back(mv);
+        else result.push_back(mv);
+    }
+    // depth in the elimination tree: a bucket's separator variables are all
+    // maximised in its ancestors, so it decodes one step after the deepest of them
+    for (int i = nord - 1; i >= 0; --i) {
+        if (row_of[i] < 0) continue;
+        BucketSpec::DecodeRow &row = rows[row_of[i]];
+        for (int v : row.vars) {
+            const int r = B.rank[v];
+            if (r > i && row_of[r] >= 0) row.depth = std::max(row.depth, rows[row_of[r]].depth + 1);
+        }
+    }
+    std::stable_sort(rows.begin(), rows.end(),
+                     [](const BucketSpec::DecodeRow &a, const BucketSpec::DecodeRow &b) { return a.depth < b.depth; });
+    if (!result.empty()) {
+        p.result_table = B.emit(result, -1, true);
+        p.result_vars = p.msgs[p.result_table - p.n_src].vars;
+    }
+    BucketSpec dec;
+    dec.decode = true;
+    for (const BucketSpec::DecodeRow &r : rows) {
+        View v;
+        v.table = r.arg_table;
+        dec.in.push_back(v);
+    }
+    dec.decode_rows = std::move(rows);
+    dec.decode_init.resize(cards.size());
+    for (size_t v = 0; v < cards.size(); ++v) dec.decode_init[v] = v < ev_val.size() && ev_val[v] >= 0 ? ev_val[v] : 0;
+    const int64_t xbytes = std::max<int64_t>(4, (int64_t)cards.size() * 4);
+    dec.out_table = B.new_raw((xbytes + elem_bytes - 1) / elem_bytes);
+    dec.level = B.last_level + 1;
+    B.last_level = dec.level;
+    B.level[dec.out_table] = dec.level;
+    p.buckets.push_back(dec);
+    p.results = {p.result_table, dec.out_table};
+    p.results_vars = {p.result_vars, {}};
+    B.finish();
+    return true;
 }
 
 VEPlan plan_bucket_tree(const std::vector<int> &cards, const std::vector<View> &sources,
@@ -2144,6 +2294,7 @@ int64_t plan_peak_bytes(const VEPlan &p, int elem_bytes) {
     for (const BucketSpec &b : p.buckets) {
         born[b.out_table] = b.level;
         if (b.bel_table >= 0) born[b.bel_table] = b.level;
+        if (b.arg_table >= 0) born[b.arg_table] = b.level;
         for (const View &v : b.in) last[v.table] = std::max(last[v.table], b.level);
     }
     if (p.result_table >= 0) last[p.result_table] = p.n_levels + 1;
@@ -2363,6 +2514,7 @@ int64_t plan_arena_bytes(const VEPlan &p, int elem_bytes) {
     for (const BucketSpec &b : p.buckets) {
         born[b.out_table] = b.level;
         if (b.bel_table >= 0) born[b.bel_table] = b.level;
+        if (b.arg_table >= 0) born[b.arg_table] = b.level;
         for (const View &v : b.in) last[v.table] = std::max(last[v.table], b.level);
     }
     std::vector<char> keep(nt, 0);
@@ -2452,7 +2604,7 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
                 mix((uint64_t)(uint32_t)b.elim_var);
                 mix((uint64_t)b.level);
                 mix((uint64_t)(b.xchg * 16 + b.xchg_mode));
-                mix(b.divide ? 1 : 0);
+                mix((b.divide ? 1 : 0) + (b.max_out ? 2 : 0) + (b.decode ? 4 : 0));
                 mix(b.out_vars.size());
                 for (int v : b.out_vars) mix((uint64_t)v);
                 mix(b.chain_x.size() * 131 + b.chain_n.size() * 7 + (uint64_t)b.chain_gmask);
@@ -2550,6 +2702,7 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
             if (!kept(pi, b)) continue;
             born[remap(pi, b.out_table)] = b.level;
             if (b.bel_table >= 0) born[remap(pi, b.bel_table)] = b.level;
+            if (b.arg_table >= 0) born[remap(pi, b.arg_table)] = b.level;
             for (const View &v : b.in) {
                 int *lt = &last[remap(pi, v.table)];
                 int cur = __atomic_load_n(lt, __ATOMIC_RELAXED);
@@ -2570,6 +2723,7 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
             if (!kept(pi, b)) continue;
             lane_of[remap(pi, b.out_table)] = b.lane;
             if (b.bel_table >= 0) lane_of[remap(pi, b.bel_table)] = b.lane;
+            if (b.arg_table >= 0) lane_of[remap(pi, b.arg_table)] = b.lane;
             n_lanes = std::max(n_lanes, b.lane + 1);
         }
     if (n_lanes > 1)
@@ -2723,10 +2877,17 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
         Item &it = items[idx];
         BucketSpec b = *it.b;
         b.simple = simplify && lvl_n[it.level] > 1 && b.chain_x.empty() && !b.divide && !b.xchg &&
-                   plans[it.plan]->msgs[b.out_table - s.n_src].size <= simple_max;
+                   !b.decode && plans[it.plan]->msgs[b.out_table - s.n_src].size <= simple_max;
         for (View &v : b.in) v.table = remap(it.plan, v.table);
         b.out_table = remap(it.plan, b.out_table);
         if (b.bel_table >= 0) b.bel_table = remap(it.plan, b.bel_table);
+        if (b.arg_table >= 0) b.arg_table = remap(it.plan, b.arg_table);
+        if (b.decode) {                      // the MPE traceback: the executor's, its rows in the pool
+            for (BucketSpec::DecodeRow &r : b.decode_rows) r.arg_table = remap(it.plan, r.arg_table);
+            it.ok = build_desc(b, cards, max_vec, it.d, it.pool, &it.msg);
+            it.key = kMpeDecodeKey;
+            return;
+        }
         if (b.xchg) {                        // an exchange step: the executor's, no kernel descriptor
             it.d = BucketDesc{};
             it.d.n_in = (int)b.in.size();
@@ -2751,6 +2912,7 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
                  : it.d.big >= 0 ? stream_key(it.d.bcls, it.d.v1, it.d.v2, it.d.n_in)
                  : b.simple ? generic_variant(kMaxIn, 1, 1, max_in_bytes(b), no_o32)   // the widest input class runs any input count
                             : generic_variant(it.d.n_in, it.d.v1, it.d.v2, max_in_bytes(b), no_o32);
+        if (b.max_out) it.key += kMaxKeyBase;          // build_desc kept it generic-shaped (maxout.cuh)
     });
     const double T2 = clk();
     for (const Item &it : items)

@@ -128,11 +128,33 @@ struct BucketSpec {
     // messages and deliveries): lanes run concurrently, ordered by the
     // cross-lane table dependencies only
     int lane = 0;
+    // max-product (maxout.cuh): the bucket maximises over elim_var instead of
+    // summing, and records the maximising value per output entry in arg_table
+    // (one byte each; -1: a single-op call that passes the address itself).
+    // Generic-shaped kernels only: never the stream, slab or chain forms, tiles
+    // 1x1, 2x1 or 4x1; card(elim_var) <= kMaxOutCard
+    bool max_out = false;
+    int arg_table = -1;
+    // the traceback that ends an MPE plan (plan_mpe): one row per max bucket,
+    // ordered by depth in the elimination tree (roots first); `in` lists every
+    // arg table, so that all of them live to this step; out_table holds the
+    // assignment, int32 per model variable (decode_init: evidence values, 0
+    // for a variable in no factor)
+    struct DecodeRow {
+        int arg_table, elim_var, depth;
+        std::vector<int> vars;              // the bucket's separator, as its output is laid out
+        std::vector<int64_t> strides;
+    };
+    bool decode = false;
+    std::vector<DecodeRow> decode_rows;
+    std::vector<int> decode_init;
 };
 enum XchgKind { kXchgNone = 0, kXchgSync = 1, kXchgPack = 2, kXchgComm = 3, kXchgUnpack = 4 };
 // schedule group variant of an exchange step: kXchgKeyBase + kind * 16 + mode
 // (above every kernel variant key, bnpp_device.h)
 constexpr int kXchgKeyBase = 1 << 24;
+// ... of the MPE traceback (BucketSpec::decode): the executor's too, above the exchange kinds
+constexpr int kMpeDecodeKey = kXchgKeyBase + 4096;
 
 // Compile one bucket into a descriptor + dims-pool rows.  max_vec: 4 (fp32) / 2 (fp64).
 // Returns false (with msg) on an invalid shape.
@@ -178,6 +200,7 @@ struct VEPlan {
     // variable whose value is that bit of the rank)
     int n_slices = 1, slice_rank = 0;
     std::vector<int> results_slice_bit;
+    int64_t arg_bytes = 0;              // plan_mpe: bytes of all arg tables (resident to the traceback)
     int n_xchg = 0;                     // message exchanges (all-to-all / all-gather)
     double xchg_elems = 0;              // entries this rank sends to other ranks
 };
@@ -189,6 +212,17 @@ struct VEPlan {
 // the reference's left-to-right chain.
 VEPlan plan_ve(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                bool canonical, int chain_eb = 0);
+
+// Most probable explanation: plan_ve(canonical) over `order` (every
+// non-evidence variable) with each eliminating bucket maximising (max_out) and
+// recording its argmax in a table of its own, then one traceback step
+// (BucketSpec::decode) that reads every arg table.  results = {the maximum (a
+// scalar), the assignment (int32 per variable, sized in whole elements of
+// elem_bytes)}.  Pure-product prefixes of buckets with more than kMaxIn inputs
+// stay ordinary products.  ev_val: per variable, -1 = no evidence.  Returns
+// false (msg) when a maximised variable has more than kMaxOutCard values.
+bool plan_mpe(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
+              const std::vector<int> &ev_val, int elem_bytes, VEPlan &out, std::string *msg);
 
 // All marginals of `targets` from one two-pass bucket tree over `order`
 // (Shafer-Shenoy on the VE bucket tree; replaces the N independent VEs of

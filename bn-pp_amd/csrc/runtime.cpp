@@ -285,7 +285,11 @@ int launch(Context &ctx, Executable &ex, hipStream_t stream, const XchgHooks *ho
         if (lanes)
             for (int e : ex.g_wait[gi])
                 if ((err = hipStreamWaitEvent(st, ex.events[e], 0)) != hipSuccess) return fail(ctx, err, "lane wait");
-        if (g.variant >= kXchgKeyBase) {
+        if (g.variant == kMpeDecodeKey) {                    // the MPE traceback (maxout.cuh): one workgroup
+            const BucketDesc &d = sc.descs[g.begin];
+            err = launch_mpe_decode(ex.d_pool + d.dim_off, ex.d_meta, static_cast<int32_t *>(ex.h_meta[d.out_table].ptr), st);
+            if (err != hipSuccess) return fail(ctx, err, "launch_mpe_decode");
+        } else if (g.variant >= kXchgKeyBase) {
             int rc = run_xchg(ctx, ex, g, st, hooks);
             if (rc) return rc;
         } else {

@@ -30,12 +30,14 @@ struct SingleArgs {
     BucketDesc d;
     TableMeta meta[kMaxIn + 1];  // inputs 0..n_in-1, output at index n_in
     int64_t pool[kMaxPool];
+    // max buckets (maxout.cuh): the arg table, one byte per output entry (null: values only)
+    void *arg_out;
 };
 hipError_t launch_single(int is_f32, const SingleArgs &a, int max_grid, hipStream_t stream);
 // the kernel a single-op launch runs: family (0 generic, 1 stream, 2 slab) and
 // the key its dispatcher switches on.  launch_single dispatches by it and
 // bnpp_plan_single reports it, so the report is what launches
-enum KernelFamily : int { kFamGeneric = 0, kFamStream = 1, kFamSlab = 2, kFamChain = 3 };
+enum KernelFamily : int { kFamGeneric = 0, kFamStream = 1, kFamSlab = 2, kFamChain = 3, kFamMax = 4 };
 struct SingleKey {
     int family, key;
 };
@@ -48,6 +50,14 @@ inline SingleKey single_key(int is_f32, const SingleArgs &a) {
         in_bytes = in_bytes > a.meta[i].size * (is_f32 ? 4 : 8) ? in_bytes : a.meta[i].size * (is_f32 ? 4 : 8);
     return {kFamGeneric, variant_key(a.d.n_in, a.d.v1, a.d.v2) + (generic_o32(in_bytes) ? kGenericO32 : 0)};   // plan.hpp generic_variant
 }
+// a max bucket (BucketSpec::max_out; build_desc keeps it out of the stream
+// and slab forms): the generic key of its shape above kMaxKeyBase
+inline SingleKey max_single_key(int is_f32, const SingleArgs &a) {
+    return {kFamMax, kMaxKeyBase + single_key(is_f32, a).key};
+}
+hipError_t launch_max_single(int is_f32, const SingleArgs &a, int max_grid, hipStream_t stream);
+// the traceback of a max-product run (maxout.cuh mpe_decode_kernel): one workgroup
+hipError_t launch_mpe_decode(const int64_t *pool, const TableMeta *meta, int32_t *x, hipStream_t stream);
 // the keys a family's dispatch switch holds (single-op or level launches),
 // appended to `keys`: generated from the X-macro lists of the switches
 // themselves (kernels.cuh, slab.cuh, chain.cuh, chainsplit.cuh), so the two

@@ -64,6 +64,7 @@ _SIGS = {
     "bnpp_synchronize": (_I, [_P, _P]),
     "bnpp_out_scope": (_I, [_I, _IP, C.POINTER(_IP), _I, _I, _IP, _IP]),
     "bnpp_bucket_eliminate": (_I, [_P, _P, _I, _I, _IP, _I, C.POINTER(_P), _IP, C.POINTER(_IP), _I, _P, _I, _IP, _P]),
+    "bnpp_bucket_max": (_I, [_P, _P, _I, _I, _IP, _I, C.POINTER(_P), _IP, C.POINTER(_IP), _I, _P, _I, _IP, _P]),
     "bnpp_product": (_I, [_P, _P, _I, _I, _IP, _P, _I, _IP, _P, _I, _IP, _P, _I, _IP, _P]),
     "bnpp_divide": (_I, [_P, _P, _I, _I, _IP, _P, _I, _IP, _P, _I, _IP, _P, _I, _IP, _P]),
     "bnpp_sum_out": (_I, [_P, _P, _I, _I, _IP, _P, _I, _IP, _I, _P, _I, _IP, _P]),
@@ -76,6 +77,7 @@ _SIGS = {
     "bnpp_evidence_load": (_I, [C.c_char_p, _I, _IP, _IP, _IP]),
     "bnpp_ordering": (_I, [_P, _I, _IP, _IP, _I, _IP, _I, _IP, _IP]),
     "bnpp_partition": (_I, [_P, _P, _I, _IP, _IP, _I, _IP, _I, _I, _DP, _DP, _DP]),
+    "bnpp_mpe": (_I, [_P, _P, _I, _IP, _IP, _I, _IP, _I, _I, _DP, _IP, _DP]),
     "bnpp_marginals": (_I, [_P, _P, _I, _IP, _IP, _I, _I, _IP, _I, _DP, _DP]),
     "bnpp_sum_product": (_I, [_P, _P, _I, C.c_double, _DP, _IP, _DP]),
     "bnpp_marginals_tree": (_I, [_P, _P, _I, _IP, _IP, _I, _IP, _I, _I, _IP, _I, _DP, _DP]),
@@ -89,9 +91,11 @@ _SIGS = {
                                        C.POINTER(C.c_int64)]),
     "bnpp_plan_stats": (_I, [_P, _I, _I, _IP, _IP, _I, _IP, _I, _I, _DP, _I]),
     "bnpp_plan_single": (_I, [_I, _I, _IP, _I, _IP, C.POINTER(_IP), _I, _I, _IP, _I, _I, _IP, _IP, _LP, _I]),
+    "bnpp_plan_max_single": (_I, [_I, _I, _IP, _I, _IP, C.POINTER(_IP), _I, _I, _IP, _LP, _I]),
     "bnpp_kernel_keys": (_I, [_I, _I, _I, _IP, _I, _IP]),
     "bnpp_chain_key_supported": (_I, [_I, _I, _IP]),
     "bnpp_plan_groups": (_I, [_P, _I, _I, _IP, _IP, _I, _IP, _I, _I, _I, _I, _LP, _I, _IP]),
+    "bnpp_plan_mpe_groups": (_I, [_P, _I, _IP, _IP, _I, _IP, _I, _I, _LP, _I, _IP]),
     "bnpp_job_create": (_I, [_P, _P, _I, _I, _IP, _IP, _I, _IP, _I, _I, _IP, _I, C.POINTER(_P)]),
     "bnpp_job_stats": (_I, [_P, _DP, _I]),
     "bnpp_job_launch": (_I, [_P, _P]),
@@ -107,7 +111,7 @@ EXPORTED = sorted(_SIGS)
 
 # The signature table above is for this ABI version (include/bnpp.h
 # BNPP_VERSION); a library of another version would take shifted arguments.
-ABI_VERSION = 204
+ABI_VERSION = 205
 if _lib.bnpp_version() != ABI_VERSION:
     raise ImportError("libbnpp.so ABI version %d, this binding expects %d (%s)"
                       % (_lib.bnpp_version(), ABI_VERSION, LIB_PATH))
@@ -304,7 +308,7 @@ def plan_stats(model: Model, kind: int = 0, evidence=None, heuristic: str = "mf"
 
 PLAN_SINGLE_FIELDS = ("family", "key", "n_in", "k", "v1", "v2", "bcls", "o32", "n_tiles", "lanes", "slab_y2",
                       "instantiated")
-FAMILIES = ("generic", "stream", "slab", "chain")
+FAMILIES = ("generic", "stream", "slab", "chain", "max")
 
 
 def plan_single(dtype: int, cards: Sequence[int], scopes: Sequence[Sequence[int]], elim: int,
@@ -320,6 +324,19 @@ def plan_single(dtype: int, cards: Sequence[int], scopes: Sequence[Sequence[int]
     _check(_lib.bnpp_plan_single(dtype, len(cards), _ints(cards), len(scopes), _ints([len(s) for s in scopes]), ptrs,
                                  elim, len(out_vars), _ints(out_vars), 1 if divide else 0, n, ev_v, ev_x, info,
                                  len(PLAN_SINGLE_FIELDS)), "bnpp_plan_single")
+    return dict(zip(PLAN_SINGLE_FIELDS, list(info)))
+
+
+def plan_max_single(dtype: int, cards: Sequence[int], scopes: Sequence[Sequence[int]], elim: int,
+                    out_vars: Sequence[int]) -> Dict[str, int]:
+    """Planning introspection for tests (bnpp_plan_max_single, host only): the
+    max-family kernel bucket_max would launch, as a dict of PLAN_SINGLE_FIELDS."""
+    arrs = [_ints(s) for s in scopes]
+    ptrs = (_IP * max(len(arrs), 1))(*[C.cast(a, _IP) for a in arrs])
+    info = (C.c_int64 * len(PLAN_SINGLE_FIELDS))()
+    _check(_lib.bnpp_plan_max_single(dtype, len(cards), _ints(cards), len(scopes), _ints([len(s) for s in scopes]),
+                                     ptrs, elim, len(out_vars), _ints(out_vars), info, len(PLAN_SINGLE_FIELDS)),
+           "bnpp_plan_max_single")
     return dict(zip(PLAN_SINGLE_FIELDS, list(info)))
 
 
@@ -363,6 +380,24 @@ def plan_groups(model: Model, kind: int = 0, evidence=None, heuristic: str = "mf
     return [dict(zip(PLAN_GROUP_FIELDS, rows[i * nf:(i + 1) * nf])) for i in range(cnt.value)]
 
 
+def plan_mpe_groups(model: Model, evidence=None, heuristic: str = "mf", dtype: int = F64,
+                    order: Optional[Sequence[int]] = None) -> List[Dict[str, int]]:
+    """The launch groups of the plan mpe() runs (bnpp_plan_mpe_groups, host
+    only), one dict of PLAN_GROUP_FIELDS each; plan_groups takes the sum plans only."""
+    n, ev_v, ev_x = _ev(evidence)
+    oa = _ints(order) if order is not None else None
+    h = ORDER_GIVEN if order is not None else HEURISTICS[heuristic]
+    no = len(order) if order is not None else 0
+    nf = len(PLAN_GROUP_FIELDS)
+    cnt = C.c_int()
+    _check(_lib.bnpp_plan_mpe_groups(model.handle, n, ev_v, ev_x, h, oa, no, dtype, None, 0, C.byref(cnt)),
+           "bnpp_plan_mpe_groups")
+    rows = (C.c_int64 * max(cnt.value * nf, 1))()
+    _check(_lib.bnpp_plan_mpe_groups(model.handle, n, ev_v, ev_x, h, oa, no, dtype, rows, cnt.value, C.byref(cnt)),
+           "bnpp_plan_mpe_groups")
+    return [dict(zip(PLAN_GROUP_FIELDS, rows[i * nf:(i + 1) * nf])) for i in range(cnt.value)]
+
+
 def partition(ctx: Context, model: Model, evidence=None, heuristic: str = "mf", dtype: int = F64,
               order: Optional[Sequence[int]] = None):
     """BN::partition (model.cpp:250-301) -> (log10 Z, Z, uptime_ms)."""
@@ -376,6 +411,21 @@ def partition(ctx: Context, model: Model, evidence=None, heuristic: str = "mf", 
         _check(_lib.bnpp_partition(ctx.handle, model.handle, n, ev_v, ev_x, HEURISTICS[heuristic], None, 0, dtype,
                                    C.byref(lz), C.byref(z), C.byref(up)), "bnpp_partition")
     return lz.value, z.value, up.value
+
+
+def mpe(ctx: Context, model: Model, evidence=None, heuristic: str = "mf", dtype: int = F64,
+        order: Optional[Sequence[int]] = None):
+    """Most probable explanation (bnpp_mpe; no reference counterpart) ->
+    (log10 of the maximum, [x_0 .. x_{n-1}] with evidence values kept, uptime_ms).
+    Ties resolve to the lowest value of each variable as it is maximised."""
+    n, ev_v, ev_x = _ev(evidence)
+    lv, up = C.c_double(), C.c_double()
+    x = (C.c_int * max(model.n_vars, 1))()
+    oa = _ints(order) if order is not None else None
+    h = ORDER_GIVEN if order is not None else HEURISTICS[heuristic]
+    _check(_lib.bnpp_mpe(ctx.handle, model.handle, n, ev_v, ev_x, h, oa, len(order) if order is not None else 0, dtype,
+                         C.byref(lv), x, C.byref(up)), "bnpp_mpe")
+    return lv.value, list(x[: model.n_vars]), up.value
 
 
 def marginals(ctx: Context, model: Model, evidence=None, heuristic: str = "mf", dtype: int = F64,
@@ -544,7 +594,7 @@ class Job:
                  dtype: int = F64, order: Optional[Sequence[int]] = None, targets: Optional[Sequence[int]] = None):
         n, ev_v, ev_x = _ev(evidence)
         self.model = model
-        self.kind = {"pr": 0, "mar": 1, "mar_tree": 3}[kind]
+        self.kind = {"pr": 0, "mar": 1, "mar_tree": 3, "mpe": 4}[kind]
         self.targets = list(range(model.n_vars)) if targets is None else list(targets)
         self._h = _P()
         order_arr = _ints(order) if order is not None else None
@@ -565,6 +615,11 @@ class Job:
             out = (C.c_double * 1)()
             _check(_lib.bnpp_job_results(self._h, _P(stream) if stream else None, out), "bnpp_job_results")
             return out[0]
+        if self.kind == 4:                   # (log10 of the maximum, the assignment)
+            nv = self.model.n_vars
+            out = (C.c_double * (1 + nv))()
+            _check(_lib.bnpp_job_results(self._h, _P(stream) if stream else None, out), "bnpp_job_results")
+            return out[0], [int(v) for v in out[1:1 + nv]]
         total = sum(self.model.cards[t] for t in self.targets)
         out = (C.c_double * max(total, 1))()
         _check(_lib.bnpp_job_results(self._h, _P(stream) if stream else None, out), "bnpp_job_results")
@@ -598,6 +653,20 @@ def bucket_eliminate(ctx: Context, dtype: int, cards: Sequence[int], tables: Seq
     _check(_lib.bnpp_bucket_eliminate(ctx.handle, _P(stream) if stream else None, dtype, len(cards), _ints(cards), len(tables),
                                       tabs, _ints([len(s) for s in scopes]), ptrs, elim, _P(out), len(out_vars),
                                       _ints(out_vars), _P(out_sum) if out_sum else None), "bnpp_bucket_eliminate")
+
+
+def bucket_max(ctx: Context, dtype: int, cards: Sequence[int], tables: Sequence[int],
+               scopes: Sequence[Sequence[int]], elim: int, out: int, out_vars: Sequence[int],
+               out_arg: Optional[int] = None, stream: Optional[int] = None) -> None:
+    """Max bucket on caller-owned device buffers (bnpp_bucket_max): out = the
+    maximum over `elim` of the inputs' chain product, out_arg (uint8 per output
+    entry, may be None) the lowest maximising value.  Only enqueues on `stream`."""
+    arrs = [_ints(s) for s in scopes]
+    ptrs = (_IP * len(arrs))(*[C.cast(a, _IP) for a in arrs])
+    tabs = (_P * len(tables))(*[_P(t) for t in tables])
+    _check(_lib.bnpp_bucket_max(ctx.handle, _P(stream) if stream else None, dtype, len(cards), _ints(cards), len(tables),
+                                tabs, _ints([len(s) for s in scopes]), ptrs, elim, _P(out), len(out_vars),
+                                _ints(out_vars), _P(out_arg) if out_arg else None), "bnpp_bucket_max")
 
 
 def divide(ctx: Context, dtype: int, cards: Sequence[int], a: int, a_scope: Sequence[int], b: int,

@@ -37,10 +37,11 @@
 extern "C" {
 #endif
 
-#define BNPP_VERSION 204   /* 200: single ops take n_cards (the length of cards); 201: sliced bucket-tree marginals;
+#define BNPP_VERSION 205   /* 200: single ops take n_cards (the length of cards); 201: sliced bucket-tree marginals;
                               202: single ops return the reference's partition sum (out_sum);
                               203: planning introspection for tests (bnpp_plan_single, bnpp_kernel_keys);
-                              204: chain-run introspection (bnpp_plan_groups, chain keys, bnpp_ctx_set_max_grid) */
+                              204: chain-run introspection (bnpp_plan_groups, chain keys, bnpp_ctx_set_max_grid);
+                              205: MPE (bnpp_mpe, bnpp_bucket_max, bnpp_plan_max_single, bnpp_plan_mpe_groups, job kind 4, kernel family 4) */
 
 enum bnpp_status {
     BNPP_OK = 0,
@@ -138,6 +139,21 @@ int bnpp_bucket_eliminate(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, c
                           const void *const *in_tables, const int *in_ndims, const int *const *in_vars,
                           int elim_var, void *out_table, int out_ndims, const int *out_vars, double *out_sum);
 
+/* Max bucket (no reference counterpart: bn-pp has no MPE):
+ *     out[e] = max_{elim_var} prod_i in_i,   out_arg[e] = the maximising value
+ * the arithmetic of bnpp_bucket_eliminate with max in place of the sum: per
+ * value v of elim_var the chain product ((1 * in_0) * in_1) ..., each product
+ * rounded (no contraction); best starts as the product at v = 0 and a later v
+ * replaces it only when its product is strictly greater, so ties keep the
+ * LOWEST v (an all-zero row has arg 0).  out_arg: a DEVICE array of one uint8
+ * per output entry, laid out as out_table, or NULL (values only).  elim_var is
+ * required; absent from every input the call is a copy with arg 0.  A maximised
+ * variable of more than 256 values: BNPP_ERR_UNSUPPORTED (checked on the host,
+ * nothing is launched).  Unscaled, like every single op. */
+int bnpp_bucket_max(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, int n_in,
+                    const void *const *in_tables, const int *in_ndims, const int *const *in_vars, int elim_var,
+                    void *out_table, int out_ndims, const int *out_vars, uint8_t *out_arg /* device, may be NULL */);
+
 /* Factor::product (factor.cpp:117-147; factor.hh:35) */
 int bnpp_product(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, const void *a, int a_ndims,
                  const int *a_vars, const void *b, int b_ndims, const int *b_vars, void *out, int out_ndims,
@@ -193,6 +209,30 @@ int bnpp_ordering(const bnpp_model *m, int n_ev, const int *ev_vars, const int *
 int bnpp_partition(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, const int *ev_vals,
                    int heuristic, const int *order, int n_order, int dtype, double *log10_z, double *z,
                    double *uptime_ms);
+
+/* Most probable explanation (no reference counterpart: bn-pp has no MPE): the
+ * joint assignment of all non-evidence variables with the largest unnormalised
+ * probability given the evidence, by max-product bucket elimination over the
+ * partition's elimination order and a traceback on the device.
+ * Arithmetic: bnpp_partition's with max in place of + (same chain order, same
+ * exact power-of-two rescaling, which max commutes with); every eliminating
+ * bucket records its argmax (bnpp_bucket_max's tie rule: strict >, the lowest
+ * value wins), and one workgroup then walks the elimination tree from the
+ * roots, one tree depth per step.  *log10_value: log10 of the maximum (finite
+ * unless it is 0).  assignment: n_vars values, evidence variables keep their
+ * evidence value, a variable in no factor reads 0.  With ties, the assignment
+ * is one maximiser (which one depends on the elimination order).
+ * Limits: every maximised variable has at most 256 values
+ * (BNPP_ERR_UNSUPPORTED otherwise, before anything is launched); all arg
+ * tables (one byte per entry of every message) stay resident until the
+ * traceback, beside the messages: BNPP_ERR_OOM, naming both sizes, when that
+ * exceeds the memory budget (no checkpointing).  order: explicit order covering
+ * every non-evidence variable (BNPP_ORDER_GIVEN), or NULL.  The planned job
+ * stays with the context and an identical call relaunches it; the job kind is
+ * part of the cache key, so it never shares a job with bnpp_partition. */
+int bnpp_mpe(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, const int *ev_vals, int heuristic,
+             const int *order, int n_order, int dtype, double *log10_value, int *assignment /* n_vars, evidence included */,
+             double *uptime_ms);
 
 /* BN::marginals (model.cpp:303-346), VE branch: one VE per target with every
  * other variable eliminated, then Factor::normalize (factor.cpp:244-255).  All
@@ -291,7 +331,8 @@ int bnpp_variable_elimination(bnpp_ctx *ctx, const bnpp_model *m, int n_vars, co
 /* Host-only planning statistics (no device needed): kind 0 partition (explicit
  * order if `order` is non-NULL), 1 marginals of all variables (one VE each),
  * 2 bnpp_variable_elimination of the variables in `order`, 3 bucket-tree
- * marginals of all variables.  stats as bnpp_job_stats. */
+ * marginals of all variables, 4 MPE (the arena bytes then hold the messages
+ * and every arg table).  stats as bnpp_job_stats. */
 int bnpp_plan_stats(const bnpp_model *m, int kind, int n_ev, const int *ev_vars, const int *ev_vals, int heuristic,
                     const int *order, int n_order, int dtype, double *stats, int n_stats);
 
@@ -309,8 +350,15 @@ int bnpp_plan_single(int dtype, int n_cards, const int *cards, int n_in, const i
                      int elim_var, int out_ndims, const int *out_vars, int divide, int n_ev, const int *ev_vars,
                      const int *ev_vals, int64_t *info, int n_info);
 
+/* The same for bnpp_bucket_max (its arguments without tables or stream): the
+ * max-family kernel the call launches, info laid out as bnpp_plan_single's
+ * ([0] family = 4, [6] = 0).  It fails exactly where the call would. */
+int bnpp_plan_max_single(int dtype, int n_cards, const int *cards, int n_in, const int *in_ndims,
+                         const int *const *in_vars, int elim_var, int out_ndims, const int *out_vars, int64_t *info,
+                         int n_info);
+
 /* Planning introspection for tests: the dispatch keys instantiated for a dtype
- * in the generic (0), stream (1), slab (2) or chain (3) family, for single-op
+ * in the generic (0), stream (1), slab (2), chain (3) or max (4) family, for single-op
  * (launch 0) or level (launch 1) launches: *n keys, the first min(*n, cap) in
  * keys.  Chain runs are level launches only (launch 0 lists none); their
  * fused-belief kernels are listed under their own keys. */
@@ -335,6 +383,14 @@ int bnpp_plan_groups(const bnpp_model *m, int kind, int n_ev, const int *ev_vars
                      const int *order, int n_order, int dtype, int part, int n_parts, int64_t *rows, int cap_rows,
                      int *n_rows);
 
+/* The same for the plan of bnpp_mpe (bnpp_plan_stats kind 4; bnpp_plan_groups
+ * itself takes the sum plans, kinds 0-3, only): rows as bnpp_plan_groups's,
+ * one batch, lane 0.  Keys: max buckets 65536 + the generic key of their
+ * shape (bnpp_kernel_keys family 4), the traceback 2^24 + 4096 (one group, the
+ * last), pure-product prefixes and the final product ordinary generic keys. */
+int bnpp_plan_mpe_groups(const bnpp_model *m, int n_ev, const int *ev_vars, const int *ev_vals, int heuristic,
+                         const int *order, int n_order, int dtype, int64_t *rows, int cap_rows, int *n_rows);
+
 /* Host-only planning of one part of bnpp_marginals_tree_part (all variables
  * as targets): owned[v] = 1 when this part computes v's marginal; stats as
  * bnpp_job_stats for this part's plan (may be NULL).  The memory budget is
@@ -355,7 +411,8 @@ int bnpp_plan_tree_sliced(const bnpp_model *m, int n_ev, const int *ev_vars, con
 /* A planned, device-resident inference that can be launched repeatedly. */
 typedef struct bnpp_job bnpp_job;
 /* kind 0: partition (targets ignored)   kind 1: marginals of `targets` (one VE
- * each)   kind 3: marginals of `targets` from one bucket tree */
+ * each)   kind 3: marginals of `targets` from one bucket tree   kind 4: MPE
+ * (targets ignored) */
 int bnpp_job_create(bnpp_ctx *ctx, const bnpp_model *m, int kind, int n_ev, const int *ev_vars,
                     const int *ev_vals, int heuristic, const int *order, int n_order, int n_targets,
                     const int *targets, int dtype, bnpp_job **out);
@@ -364,7 +421,8 @@ int bnpp_job_create(bnpp_ctx *ctx, const bnpp_model *m, int kind, int n_ev, cons
  *        [7] target batches */
 int bnpp_job_stats(const bnpp_job *job, double *stats, int n_stats);
 int bnpp_job_launch(bnpp_job *job, void *stream);
-/* waits on stream; partition: out[0] = log10 Z; marginals: sum(card) values */
+/* waits on stream; partition: out[0] = log10 Z; marginals: sum(card) values;
+ * MPE: out[0] = log10 of the maximum, then the n_vars assignment entries */
 int bnpp_job_results(bnpp_job *job, void *stream, double *out);
 int bnpp_job_free(bnpp_job *job);
 

@@ -128,6 +128,16 @@ public:
     // log10 of the partition function (finite beyond the double range)
     double log10_partition(const std::unordered_map<unsigned, unsigned> &evidence,
                            std::unordered_map<std::string, bool> &options, double &uptime) const;
+    // EXTENSION beyond the reference's class API (bn-pp has no MPE): the most
+    // probable explanation given the evidence (bnpp_mpe): one value per
+    // variable, in variables() order, evidence variables keeping theirs.
+    // Max-product elimination with a traceback on the device; ties resolve to
+    // the lowest value of a variable as it is maximised.  Every non-evidence
+    // variable needs a size <= 256.  log10_value (optional): log10 of the
+    // maximum, the assignment's unnormalised probability.
+    std::vector<unsigned> mpe(const std::unordered_map<unsigned, unsigned> &evidence,
+                              std::unordered_map<std::string, bool> &options, double *log10_value = nullptr,
+                              double *uptime = nullptr) const;
     virtual void write(std::ostream &) const {}
 
 protected:
