@@ -460,6 +460,28 @@ std::vector<unsigned> Model::mpe(const std::unordered_map<unsigned, unsigned> &e
     return std::vector<unsigned>(x.begin(), x.begin() + _variables.size());
 }
 
+std::vector<std::vector<unsigned char>> Model::sample(const std::unordered_map<unsigned, unsigned> &evidence,
+                                                      std::unordered_map<std::string, bool> &options, size_t n,
+                                                      unsigned long long seed, double *log10_z, double *uptime) const {
+    auto t0 = std::chrono::steady_clock::now();
+    ModelGuard g{to_engine(_variables, std::vector<const Factor *>(_factors.begin(), _factors.end()))};
+    std::vector<int> ev_vars, ev_vals;
+    split_evidence(evidence, ev_vars, ev_vals);
+    double lz = 0, up = 0;
+    const size_t nv = _variables.size();
+    std::vector<unsigned char> x(std::max<size_t>(nv * n, 1), 0);
+    int dt = options["fp32"] ? BNPP_F32 : BNPP_F64;
+    check(bnpp_sample(ctx(), g.m, (int)ev_vars.size(), ev_vars.data(), ev_vals.data(), heuristic_of(options), nullptr, 0,
+                      dt, (int64_t)n, 0, seed, x.data(), &lz, nullptr, &up),
+          "sample");
+    std::vector<std::vector<unsigned char>> out(n, std::vector<unsigned char>(nv));
+    for (size_t v = 0; v < nv; ++v)
+        for (size_t s = 0; s < n; ++s) out[s][v] = x[v * n + s];
+    if (log10_z) *log10_z = lz;
+    if (uptime) *uptime = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return out;
+}
+
 std::vector<const Factor *> Model::marginals(const std::unordered_map<unsigned, unsigned> &evidence,
                                              std::unordered_map<std::string, bool> &options, double &uptime) const {
     auto t0 = std::chrono::steady_clock::now();

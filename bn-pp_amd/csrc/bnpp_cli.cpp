@@ -5,12 +5,16 @@
 // per variable its card and probabilities, evidence variables one-hot).
 // -mpe (no reference counterpart): the most probable explanation, log10 of its
 // value and the assignment; with -uai, <base>.MPE ("MPE", then "N x_0 .. x_{N-1}").
+// -sample N [-seed S] (no reference counterpart): N exact joint samples of the
+// posterior, log10 Z and the first sample; with -uai, <base>.SAMPLES ("SAMPLES",
+// then "N n_vars", then one line of n_vars values per sample).
 // BAYES files print like `bn` (raw Z), MARKOV files like `mn` (log10 Z).
 // -ve is accepted and, as in the reference, changes nothing here: bn reads it
 // only for REPL queries (bn.cpp:346); partition / marginals always run VE
 // (model.cpp:275, 319).
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <iostream>
 #include <string>
@@ -24,12 +28,15 @@ int main(int argc, char **argv) {
     std::unordered_map<std::string, bool> options;
     std::vector<std::string> positional;
     std::string uai_out;
+    unsigned long long n_samples = 0, seed = 0;
     for (int i = 1; i < argc; ++i) {
         std::string p(argv[i]);
         if (p == "-uai" && i + 1 < argc) uai_out = argv[++i];
         else if (p == "-pr") options["partition"] = true;
         else if (p == "-mar") options["marginals"] = true;
         else if (p == "-mpe") options["mpe"] = true;
+        else if (p == "-sample" && i + 1 < argc) { options["sample"] = true; n_samples = std::strtoull(argv[++i], nullptr, 10); }
+        else if (p == "-seed" && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
         else if (p == "-mar-tree") { options["marginals"] = true; options["bucket-tree"] = true; }
         else if (p == "-ve") options["variable-elimination"] = true;
         else if (p == "-sp") options["sum-product"] = true;      // bn.cpp:177-178: loopy BP marginals
@@ -43,7 +50,7 @@ int main(int argc, char **argv) {
         else positional.push_back(p);
     }
     if (positional.empty() || options["help"]) {
-        std::cout << "usage: " << argv[0] << " /path/to/model.uai [/path/to/evidence.uai.evid] -pr|-mar|-mar-tree|-mpe [-sp] [-mf|-wmf|-md] [-f32] [-uai base]" << std::endl;
+        std::cout << "usage: " << argv[0] << " /path/to/model.uai [/path/to/evidence.uai.evid] -pr|-mar|-mar-tree|-mpe|-sample N [-seed S] [-sp] [-mf|-wmf|-md] [-f32] [-uai base]" << std::endl;
         return positional.empty() ? 1 : 0;
     }
     bnpp_model *probe = nullptr;
@@ -124,6 +131,24 @@ int main(int argc, char **argv) {
                 std::fprintf(f, "MPE\n%zu", x.size());
                 for (unsigned v : x) std::fprintf(f, " %u", v);
                 std::fprintf(f, "\n");
+                std::fclose(f);
+            }
+        }
+        if (options["sample"]) {
+            double lz = 0;
+            const std::vector<std::vector<unsigned char>> xs = model->sample(evidence, options, n_samples, seed, &lz, &uptime);
+            std::cout << ">> log10 Z = " << lz << std::endl << ">> First of " << xs.size() << " samples:";
+            if (!xs.empty())
+                for (unsigned char v : xs[0]) std::cout << " " << (unsigned)v;
+            std::cout << std::endl << ">> Executed in " << uptime << "ms." << std::endl << std::endl;
+            if (!uai_out.empty()) {
+                FILE *f = std::fopen((uai_out + ".SAMPLES").c_str(), "w");
+                if (!f) throw std::runtime_error("cannot write " + uai_out + ".SAMPLES");
+                std::fprintf(f, "SAMPLES\n%zu %zu\n", xs.size(), model->variables().size());
+                for (const auto &x : xs) {
+                    for (size_t v = 0; v < x.size(); ++v) std::fprintf(f, v ? " %u" : "%u", (unsigned)x[v]);
+                    std::fprintf(f, "\n");
+                }
                 std::fclose(f);
             }
         }

@@ -337,10 +337,14 @@ uint64_t slot_key(const std::vector<int> &cards, const std::vector<std::vector<i
 }
 
 // Build the VE plans for a job: kind 0 = partition, kind 1 = marginals of
-// targets, 2 = caller-chosen variables, 3 = bucket-tree marginals, 4 = MPE.
+// targets, 2 = caller-chosen variables, 3 = bucket-tree marginals, 4 = MPE,
+// 5 = posterior sampling of n_samples samples (internal: no public plan or job
+// call takes it, bnpp_sample and bnpp_plan_sample do).
+constexpr int kKindSample = 5;
 int build_plans(const ModelData &d, const std::vector<int> &ev, int kind, int heuristic, const int *order,
                 int n_order, const std::vector<int> &targets, std::vector<VEPlan> &plans, int &max_width,
-                int64_t budget, int eb, int part = 0, int n_parts = 1, int n_slices = 1, int slice_rank = 0) {
+                int64_t budget, int eb, int part = 0, int n_parts = 1, int n_slices = 1, int slice_rank = 0,
+                int64_t n_samples = 0) {
     const int nv = (int)d.cards.size();
     auto scopes = conditioned_scopes(d, ev);
     auto views = source_views(d, ev);
@@ -376,8 +380,9 @@ int build_plans(const ModelData &d, const std::vector<int> &ev, int kind, int he
             max_width = elimination_order(nv, d.cards, scopes, vars, (Heuristic)heuristic, ord);
         }
         plans.push_back(plan_ve(d.cards, views, ord, true, chain_eb));
-    } else if (kind == 4) {
-        // most probable explanation: max-product over every non-evidence variable
+    } else if (kind == 4 || kind == kKindSample) {
+        // most probable explanation: max-product over every non-evidence variable;
+        // posterior sampling: the sum pass over the same order, then the draws
         std::vector<int> vars, ord;
         if (order) {
             std::vector<char> seen(nv, 0);
@@ -398,7 +403,9 @@ int build_plans(const ModelData &d, const std::vector<int> &ev, int kind, int he
         }
         VEPlan mp;
         std::string msg;
-        if (!plan_mpe(d.cards, views, ord, ev, eb, mp, &msg)) return set_err(BNPP_ERR_UNSUPPORTED, msg);
+        if (kind == kKindSample ? !plan_sample(d.cards, views, ord, ev, eb, n_samples, mp, &msg)
+                                : !plan_mpe(d.cards, views, ord, ev, eb, mp, &msg))
+            return set_err(BNPP_ERR_UNSUPPORTED, msg);
         plans.push_back(std::move(mp));
     } else if (kind == 3) {
         // all marginals from one two-pass bucket tree over the PR ordering
@@ -692,15 +699,19 @@ void arena_profile(const Schedule &s, int eb, const char *path) {
 int plan_schedules(const ModelData &d, const std::vector<int> &ev, int kind, int heuristic, const int *order,
                    int n_order, const std::vector<int> &targets, int dtype, int64_t budget,
                    std::vector<Schedule> &out, double *stats, int part = 0, int n_parts = 1, int n_slices = 1,
-                   int slice_rank = 0) {
+                   int slice_rank = 0, int64_t n_samples = 0, double *sample_stats = nullptr) {
     std::vector<VEPlan> plans;
     int width = 0;
     const bool timing = std::getenv("BNPP_TIMING") != nullptr;
     double t0 = now_ms();
     const int eb = dtype == BNPP_F32 ? 4 : 8;
     int rc = build_plans(d, ev, kind, heuristic, order, n_order, targets, plans, width, budget, eb, part, n_parts,
-                         n_slices, slice_rank);
+                         n_slices, slice_rank, n_samples);
     if (rc) return rc;
+    if (sample_stats && !plans.empty() && !plans[0].buckets.empty()) {
+        sample_stats[0] = (double)plans[0].buckets.back().sample_rows.size();
+        sample_stats[1] = (double)plans[0].sample_bytes;
+    }
     if (timing) std::fprintf(stderr, "[bnpp] plans %.1f ms\n", now_ms() - t0);
     std::vector<int64_t> src_sizes;
     for (auto &v : d.values) src_sizes.push_back((int64_t)v.size());
@@ -708,7 +719,8 @@ int plan_schedules(const ModelData &d, const std::vector<int> &ev, int kind, int
     std::vector<int64_t> needs(plans.size());
     parallel_for((int64_t)plans.size(), [&](int64_t i) {
         const VEPlan &p = plans[i];
-        needs[i] = sat_add(kind == 3 || kind == 4 ? plan_arena_bytes(p, eb) : plan_peak_bytes(p, eb), (int64_t)p.buckets.size() * 512);
+        needs[i] = sat_add(kind == 3 || kind == 4 || kind == kKindSample ? plan_arena_bytes(p, eb) : plan_peak_bytes(p, eb),
+                           (int64_t)p.buckets.size() * 512);
     });
     int64_t acc = 0;
     for (size_t i = 0; i < plans.size(); ++i) {
@@ -726,6 +738,14 @@ int plan_schedules(const ModelData &d, const std::vector<int> &ev, int kind, int
             std::snprintf(m, sizeof m, "MPE needs %.3f GB (messages %.3f GB + arg tables %.3f GB, all resident until the "
                           "traceback), budget %.3f GB", need / 1e9, std::max<int64_t>(need - p.arg_bytes, 0) / 1e9,
                           p.arg_bytes / 1e9, budget / 1e9);
+            return set_err(BNPP_ERR_OOM, m);
+        }
+        if (kind == kKindSample && need > budget) {
+            // every message stays resident until the draws (no checkpointing), beside the samples
+            char m[256];
+            std::snprintf(m, sizeof m, "sampling needs %.3f GB (messages %.3f GB + samples %.3f GB, all resident until "
+                          "the draws), budget %.3f GB", need / 1e9, std::max<int64_t>(need - p.sample_bytes, 0) / 1e9,
+                          p.sample_bytes / 1e9, budget / 1e9);
             return set_err(BNPP_ERR_OOM, m);
         }
         if (!batches.back().empty() && sat_add(acc, need) > budget) {
@@ -847,7 +867,7 @@ void evict_cached_job(bnpp_ctx *ctx);
 int create_job(bnpp_ctx *ctx, const bnpp_model *m, int kind, int n_ev, const int *ev_vars, const int *ev_vals,
                int heuristic, const int *order, int n_order, int n_targets, const int *targets, int dtype,
                std::unique_ptr<bnpp_job> &job, int part = 0, int n_parts = 1, bool use_cache = false, int n_slices = 1,
-               int slice_rank = 0, int64_t budget = 0) {
+               int slice_rank = 0, int64_t budget = 0, int64_t n_samples = 0) {
     if (!ctx || !m) return set_err(BNPP_ERR_INVALID, "null context or model");
     if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
     const ModelData &d = m->d;
@@ -876,7 +896,7 @@ int create_job(bnpp_ctx *ctx, const bnpp_model *m, int kind, int n_ev, const int
     const double tp = now_ms();
     int rc = plan_schedules(d, job->ev_val, kind, heuristic, order, n_order, job->targets, dtype,
                             budget > 0 ? budget : memory_budget(ctx, use_cache), batches, job->stats, part, n_parts,
-                            n_slices, slice_rank);
+                            n_slices, slice_rank, n_samples);
     if (rc) return rc;
     const double t0 = now_ms();
     rc = cached_sources(ctx, m, dtype, job->src);
@@ -1352,6 +1372,59 @@ int bnpp_plan_max_single(int dtype, int n_cards, const int *cards, int n_in, con
     BNPP_GUARD_END
 }
 
+int bnpp_bucket_sample(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, int n_in,
+                       const void *const *in_tables, const int *in_ndims, const int *const *in_vars, int var,
+                       int64_t n_samples, int64_t first_sample, uint64_t seed, uint8_t *x, int64_t *n_degenerate) {
+    BNPP_GUARD_BEGIN
+    if (!ctx || !cards || !x || (n_in > 0 && (!in_tables || !in_ndims || !in_vars)))
+        return set_err(BNPP_ERR_INVALID, "null argument");
+    if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "dtype must be BNPP_F64 or BNPP_F32");
+    if (n_in < 0) return set_err(BNPP_ERR_INVALID, "negative input count");
+    if (n_in > kMaxIn) return set_err(BNPP_ERR_UNSUPPORTED, "at most 8 inputs per fused call");
+    if (n_cards < 0 || var < 0 || var >= n_cards || cards[var] < 1)
+        return set_err(BNPP_ERR_INVALID, "variable id outside cards[0, n_cards)");
+    if (n_samples < 1 || first_sample < 0) return set_err(BNPP_ERR_INVALID, "n_samples must be at least 1, first_sample at least 0");
+    for (int i = 0; i < n_in; ++i) {
+        if (!valid_scope(in_ndims[i], in_vars[i], cards, n_cards)) return set_err(BNPP_ERR_INVALID, "bad input scope");
+        if (!in_tables[i]) return set_err(BNPP_ERR_INVALID, "null input table");
+        // every variable whose row of x the draw reads or writes holds one byte per value
+        for (int j = 0; j < in_ndims[i]; ++j)
+            if (cards[in_vars[i][j]] > kMaxOutCard)
+                return set_err(BNPP_ERR_UNSUPPORTED, "sampling: a scope variable has more than 256 values (x holds one byte per variable)");
+    }
+    if (cards[var] > kMaxOutCard)
+        return set_err(BNPP_ERR_UNSUPPORTED, "sampling: the sampled variable has more than 256 values (x holds one byte per variable)");
+    std::vector<int> cv(cards, cards + n_cards);
+    BucketSpec b;
+    b.sample = true;
+    b.n_samples = n_samples;
+    BucketSpec::SampleRow row;
+    row.var = var;
+    for (int i = 0; i < n_in; ++i) row.in.push_back(natural_view(i, std::vector<int>(in_vars[i], in_vars[i] + in_ndims[i]), cv));
+    b.sample_rows.push_back(row);
+    BucketDesc d;
+    std::vector<int64_t> pool;
+    std::string msg;
+    if (!build_desc(b, cv, max_vec_for(dtype), d, pool, &msg)) return set_err(BNPP_ERR_INVALID, msg);
+    if (pool.size() > (size_t)kMaxPool) return set_err(BNPP_ERR_UNSUPPORTED, "too many scope variables for a single-op call");
+    SampleSingleArgs a;
+    std::memset(&a, 0, sizeof a);
+    std::copy(pool.begin(), pool.end(), a.pool);
+    for (int i = 0; i < n_in; ++i) a.meta[i].ptr = const_cast<void *>(in_tables[i]);
+    a.x = x;
+    a.n = n_samples;
+    a.first = first_sample;
+    a.seed = seed;
+    a.n_degenerate = reinterpret_cast<unsigned long long *>(n_degenerate);
+    hipStream_t st = pick_stream(ctx, stream);
+    hipError_t e = hipSetDevice(ctx->c.device);
+    if (e == hipSuccess && n_degenerate) e = hipMemsetAsync(n_degenerate, 0, sizeof(int64_t), st);
+    if (e == hipSuccess) e = launch_sample_single(dtype == BNPP_F32, a, ctx->c.max_grid, st);
+    if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
 int bnpp_product(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, const void *a, int a_ndims,
                  const int *a_vars, const void *b, int b_ndims, const int *b_vars, void *out, int out_ndims,
                  const int *out_vars, double *out_sum) {
@@ -1680,6 +1753,38 @@ int bnpp_plan_mpe_groups(const bnpp_model *m, int n_ev, const int *ev_vars, cons
     return plan_groups_rows(m, 4, n_ev, ev_vars, ev_vals, heuristic, order, n_order, dtype, 0, 1, rows, cap_rows, n_rows);
 }
 
+int bnpp_plan_sample(const bnpp_model *m, int n_ev, const int *ev_vars, const int *ev_vals, int heuristic,
+                     const int *order, int n_order, int dtype, int64_t n_samples, double *stats, int n_stats,
+                     int64_t *rows, int cap_rows, int *n_rows) {
+    BNPP_GUARD_BEGIN
+    if (!m || !n_rows || (cap_rows > 0 && !rows) || (n_stats > 0 && !stats)) return set_err(BNPP_ERR_INVALID, "null argument");
+    if (n_samples < 1) return set_err(BNPP_ERR_INVALID, "n_samples must be at least 1");
+    std::vector<int> ev, targets;
+    std::string msg;
+    if (!evidence_array(m->d, n_ev, ev_vars, ev_vals, ev, msg)) return set_err(BNPP_ERR_INVALID, msg);
+    std::vector<Schedule> batches;
+    double st[12] = {0};
+    int rc = plan_schedules(m->d, ev, kKindSample, heuristic, order, n_order, targets, dtype, memory_budget(nullptr), batches,
+                            st, 0, 1, 1, 0, n_samples, st + 10);
+    if (rc) return rc;
+    st[8] = st[10];                                  // rows of the sampling step
+    st[9] = st[11];                                  // bytes of x
+    for (int i = 0; i < n_stats && i < 10; ++i) stats[i] = st[i];
+    int64_t n = 0;
+    for (size_t b = 0; b < batches.size(); ++b)
+        for (const Schedule::Group &g : batches[b].groups) {
+            if (n < cap_rows) {
+                const int64_t v[BNPP_PLAN_GROUP_FIELDS] = {(int64_t)b, g.level, g.variant, g.end - g.begin, g.vblocks, g.lane};
+                std::copy(v, v + BNPP_PLAN_GROUP_FIELDS, rows + n * BNPP_PLAN_GROUP_FIELDS);
+            }
+            ++n;
+        }
+    if (n > INT32_MAX) return set_err(BNPP_ERR_UNSUPPORTED, "more launch groups than the count can hold");
+    *n_rows = (int)n;
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
 int bnpp_plan_single(int dtype, int n_cards, const int *cards, int n_in, const int *in_ndims, const int *const *in_vars,
                      int elim_var, int out_ndims, const int *out_vars, int divide, int n_ev, const int *ev_vars,
                      const int *ev_vals, int64_t *info, int n_info) {
@@ -1861,6 +1966,78 @@ int bnpp_mpe(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, c
     if (log10_value) *log10_value = res[0];
     if (assignment)
         for (size_t v = 0; v < m->d.cards.size(); ++v) assignment[v] = (int)res[1 + v];
+    if (uptime_ms) *uptime_ms = now_ms() - t0;
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+int bnpp_sample(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, const int *ev_vals, int heuristic,
+                const int *order, int n_order, int dtype, int64_t n_samples, int64_t first_sample, uint64_t seed,
+                uint8_t *out, double *log10_z, int64_t *n_degenerate, double *uptime_ms) {
+    BNPP_GUARD_BEGIN
+    double t0 = now_ms();
+    if (!ctx || !m) return set_err(BNPP_ERR_INVALID, "null context or model");
+    if (n_samples < 1 || first_sample < 0) return set_err(BNPP_ERR_INVALID, "n_samples must be at least 1, first_sample at least 0");
+    bnpp_job *job = nullptr;
+    std::unique_lock<std::mutex> lk(ctx->cache_mu, std::try_to_lock);
+    const bool cache_ok = lk.owns_lock();
+    const int64_t budget = memory_budget(ctx, true);
+    // the job kind and n_samples are part of the key, seed and first_sample are
+    // not: another seed relaunches the cached job
+    uint64_t key = cache_ok ? call_key(m, kKindSample, n_ev, ev_vars, ev_vals, heuristic, order, n_order, 0, nullptr, dtype,
+                                       0, 1) : 0;
+    if (key) {
+        key = (key ^ (uint64_t)n_samples) * 1099511628211ull;
+        key = key ? key : 1;
+    }
+    int rc = oneshot_job(ctx, cache_ok, key, budget, [&](std::unique_ptr<bnpp_job> &j) {
+        return create_job(ctx, m, kKindSample, n_ev, ev_vars, ev_vals, heuristic, order, n_order, 0, nullptr, dtype, j, 0, 1,
+                          cache_ok, 1, 0, 0, n_samples);
+    }, job);
+    const double t1 = now_ms();
+    // the sampling step: the last launch group of the (one) schedule
+    const BucketDesc *sd = nullptr;
+    Executable *ex = nullptr;
+    if (rc == BNPP_OK) {
+        if (job->pg.parts.size() == 1 && !job->pg.parts[0].sched.groups.empty() &&
+            job->pg.parts[0].sched.groups.back().variant == kSampleKey) {
+            ex = &job->pg.parts[0];
+            sd = &ex->sched.descs[ex->sched.groups.back().begin];
+            ex->sample_seed = seed;
+            ex->sample_first = first_sample;
+        } else {
+            rc = set_err(BNPP_ERR_INVALID, "sampling job without a sampling step");
+        }
+    }
+    if (rc == BNPP_OK) rc = from_ctx(ctx, launch_program(ctx->c, job->pg, ctx->c.stream));
+    const double t2 = now_ms();
+    double lz = 0;
+    if (rc == BNPP_OK) {
+        std::vector<std::vector<double>> vals;
+        std::vector<int64_t> exp2;
+        rc = from_ctx(ctx, fetch_program(ctx->c, job->pg, ctx->c.stream, vals, exp2));   // waits for the stream
+        if (rc == BNPP_OK) {
+            double p = 0;
+            for (double v : vals[0]) p += v;
+            lz = p > 0 ? std::log10(p) + (double)exp2[0] * std::log10(2.0) : -INFINITY;
+        }
+    }
+    if (rc == BNPP_OK) {
+        const uint8_t *x = static_cast<const uint8_t *>(ex->h_meta[sd->out_table].ptr);
+        const int64_t bytes = (int64_t)m->d.cards.size() * n_samples;
+        hipError_t e = hipSuccess;
+        if (out && bytes > 0) e = hipMemcpy(out, x, (size_t)bytes, hipMemcpyDeviceToHost);
+        int64_t cnt = 0;
+        if (e == hipSuccess)
+            e = hipMemcpy(&cnt, x + sample_counter_offset((int64_t)m->d.cards.size(), n_samples), sizeof cnt, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = set_err(BNPP_ERR_HIP, std::string("hipMemcpy(samples): ") + hipGetErrorString(e));
+        else if (n_degenerate) *n_degenerate = cnt;
+    }
+    const double t3 = now_ms();
+    oneshot_done(ctx, cache_ok, key, budget, job, rc);
+    record_call_timing(t0, t1, t2, t3);
+    if (rc) return rc;
+    if (log10_z) *log10_z = lz;
     if (uptime_ms) *uptime_ms = now_ms() - t0;
     return BNPP_OK;
     BNPP_GUARD_END

@@ -1,6 +1,6 @@
 // Host-side launchers: route a descriptor to the translation unit that holds
 // its kernel instantiation (k_generic_f32/f64, k_stream_f32/f64, k_slab_f32/f64,
-// k_chain_f32/f64, k_max_f32/f64).
+// k_chain_f32/f64, k_max_f32/f64, k_sample_f32/f64).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,6 +28,13 @@ hipError_t dispatch_max_level_f32(int key, const LevelArgs &a, int max_grid, hip
 hipError_t dispatch_max_level_f64(int key, const LevelArgs &a, int max_grid, hipStream_t stream);
 hipError_t dispatch_max_single_f32(int key, const SingleArgs &a, int max_grid, hipStream_t stream);
 hipError_t dispatch_max_single_f64(int key, const SingleArgs &a, int max_grid, hipStream_t stream);
+
+hipError_t dispatch_sample_rows_f32(const int64_t *pool, const TableMeta *meta, uint8_t *x, int64_t n, int64_t first,
+                                    uint64_t seed, unsigned long long *n_degenerate, int max_grid, hipStream_t stream);
+hipError_t dispatch_sample_rows_f64(const int64_t *pool, const TableMeta *meta, uint8_t *x, int64_t n, int64_t first,
+                                    uint64_t seed, unsigned long long *n_degenerate, int max_grid, hipStream_t stream);
+hipError_t dispatch_sample_single_f32(const SampleSingleArgs &a, int max_grid, hipStream_t stream);
+hipError_t dispatch_sample_single_f64(const SampleSingleArgs &a, int max_grid, hipStream_t stream);
 
 hipError_t dispatch_slab_single_f32(int key, const SingleArgs &a, hipStream_t stream);
 hipError_t dispatch_slab_single_f64(int key, const SingleArgs &a, hipStream_t stream);
@@ -89,6 +96,19 @@ hipError_t launch_max_single(int is_f32, const SingleArgs &a, int max_grid, hipS
     if (a.d.n_tiles <= 0) return hipSuccess;
     const SingleKey sk = max_single_key(is_f32, a);
     return is_f32 ? dispatch_max_single_f32(sk.key, a, max_grid, stream) : dispatch_max_single_f64(sk.key, a, max_grid, stream);
+}
+
+hipError_t launch_sample_rows(int is_f32, const int64_t *pool, const TableMeta *meta, uint8_t *x, int64_t n,
+                              int64_t first, uint64_t seed, unsigned long long *n_degenerate, int max_grid,
+                              hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    return is_f32 ? dispatch_sample_rows_f32(pool, meta, x, n, first, seed, n_degenerate, max_grid, stream)
+                  : dispatch_sample_rows_f64(pool, meta, x, n, first, seed, n_degenerate, max_grid, stream);
+}
+
+hipError_t launch_sample_single(int is_f32, const SampleSingleArgs &a, int max_grid, hipStream_t stream) {
+    if (a.n <= 0) return hipSuccess;
+    return is_f32 ? dispatch_sample_single_f32(a, max_grid, stream) : dispatch_sample_single_f64(a, max_grid, stream);
 }
 
 void kernel_keys(int is_f32, int level, int family, std::vector<int> &keys) {

@@ -551,10 +551,60 @@ static bool build_decode_desc(const BucketSpec &b, BucketDesc &d, std::vector<in
     return true;
 }
 
+// The sampling step of a sampling plan: no kernel descriptor, its rows in the
+// dims pool (the layout sample_rows reads, sample.cuh).  d.k rows, d.out_size
+// variables, d.n_tiles samples.
+static bool build_sample_desc(const BucketSpec &b, const std::vector<int> &cards, BucketDesc &d,
+                              std::vector<int64_t> &pool, std::string *msg) {
+    d = BucketDesc{};
+    d.out_table = b.out_table;
+    d.big = -1;
+    d.dim_off = (int64_t)pool.size();
+    pool.push_back((int64_t)cards.size());
+    pool.push_back((int64_t)b.sample_rows.size());
+    pool.push_back((int64_t)b.sample_ev.size());
+    pool.push_back(0);
+    for (const auto &e : b.sample_ev) {
+        pool.push_back(e.first);
+        pool.push_back(e.second);
+    }
+    for (const BucketSpec::SampleRow &row : b.sample_rows) {
+        if (row.var < 0 || row.var >= (int)cards.size() || cards[row.var] > kMaxOutCard || (int)row.in.size() > kMaxIn) {
+            if (msg) *msg = "sampling row: variable " + std::to_string(row.var) + " needs at most " +
+                            std::to_string(kMaxOutCard) + " values and " + std::to_string(kMaxIn) + " inputs";
+            return false;
+        }
+        pool.push_back(row.var);
+        pool.push_back(cards[row.var]);
+        pool.push_back((int64_t)row.in.size());
+        for (const View &v : row.in) {
+            int64_t es = 0, n = 0;
+            for (size_t j = 0; j < v.vars.size(); ++j) {
+                if (v.vars[j] == row.var) es = v.strides[j];
+                else ++n;
+            }
+            pool.push_back(v.table);
+            pool.push_back(v.base);
+            pool.push_back(es);
+            pool.push_back(n);
+            for (size_t j = 0; j < v.vars.size(); ++j)
+                if (v.vars[j] != row.var) {
+                    pool.push_back(v.vars[j]);
+                    pool.push_back(v.strides[j]);
+                }
+        }
+    }
+    d.k = (int32_t)b.sample_rows.size();
+    d.out_size = (int64_t)cards.size();
+    d.n_tiles = b.n_samples;
+    return true;
+}
+
 bool build_desc(const BucketSpec &b, const std::vector<int> &cards, int max_vec, BucketDesc &d,
                 std::vector<int64_t> &pool, std::string *msg, bool slab_outer) {
     if (!b.chain_x.empty()) return build_chain_desc(b, cards, max_vec, d, pool, msg);
     if (b.decode) return build_decode_desc(b, d, pool, msg);
+    if (b.sample) return build_sample_desc(b, cards, d, pool, msg);
     const int n = (int)b.in.size();
     if (n < 1 || n > kMaxIn) {
         if (msg) *msg = "bucket needs 1.." + std::to_string(kMaxIn) + " inputs, got " + std::to_string(n);
@@ -1559,6 +1609,67 @@ bool plan_mpe(const std::vector<int> &cards, const std::vector<View> &sources, c
     p.buckets.push_back(dec);
     p.results = {p.result_table, dec.out_table};
     p.results_vars = {p.result_vars, {}};
+    B.finish();
+    return true;
+}
+
+bool plan_sample(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
+                 const std::vector<int> &ev_val, int elem_bytes, int64_t n_samples, VEPlan &out, std::string *msg) {
+    out = VEPlan{};
+    VEPlan &p = out;
+    PlanBuilder B(cards, p, sources, order, true);   // chain_eb stays 0: no fused runs
+    const int nord = (int)order.size();
+    std::vector<std::vector<View>> buckets(nord);
+    std::vector<View> result;
+    for (const View &s : sources) {
+        int bi = B.first_bucket(s.vars, 0);
+        if (bi >= 0) buckets[bi].push_back(s);
+        else result.push_back(s);
+    }
+    std::vector<BucketSpec::SampleRow> rows(nord);
+    for (int i = 0; i < nord; ++i) {
+        if (cards[order[i]] > kMaxOutCard) {
+            if (msg) *msg = "sampling: variable " + std::to_string(order[i]) + " has " + std::to_string(cards[order[i]]) +
+                            " values; the samples hold one byte per variable (at most " + std::to_string(kMaxOutCard) + ")";
+            return false;
+        }
+        rows[i].var = order[i];
+        if (buckets[i].empty()) continue;   // a variable in no remaining factor: an input-less row, a uniform draw
+        const int t = B.emit(buckets[i], order[i], false);
+        rows[i].in = p.buckets.back().in;   // the eliminating bucket's own views (pure-product prefixes precede it)
+        View mv = B.view(t);
+        int bi = B.first_bucket(mv.vars, i + 1);
+        if (bi >= 0) buckets[bi].push_back(mv);
+        else result.push_back(mv);
+    }
+    if (!result.empty()) {
+        p.result_table = B.emit(result, -1, true);
+        p.result_vars = p.msgs[p.result_table - p.n_src].vars;
+    }
+    BucketSpec smp;
+    smp.sample = true;
+    smp.n_samples = n_samples;
+    std::vector<char> listed(p.n_src + p.msgs.size(), 0);
+    for (const BucketSpec::SampleRow &r : rows)
+        for (const View &v : r.in)
+            if (!listed[v.table]) {
+                listed[v.table] = 1;
+                View t;
+                t.table = v.table;
+                smp.in.push_back(t);
+            }
+    smp.sample_rows.assign(rows.rbegin(), rows.rend());
+    for (size_t v = 0; v < cards.size(); ++v)
+        if (v < ev_val.size() && ev_val[v] >= 0) smp.sample_ev.push_back({(int)v, ev_val[v]});
+    p.sample_bytes = sat_mul((int64_t)cards.size(), n_samples);
+    const int64_t xbytes = sat_add(sample_counter_offset(1, p.sample_bytes), 8);
+    smp.out_table = B.new_raw((xbytes + elem_bytes - 1) / elem_bytes);
+    smp.level = B.last_level + 1;
+    B.last_level = smp.level;
+    B.level[smp.out_table] = smp.level;
+    p.buckets.push_back(smp);
+    p.results = {p.result_table};
+    p.results_vars = {p.result_vars};
     B.finish();
     return true;
 }
@@ -2604,7 +2715,7 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
                 mix((uint64_t)(uint32_t)b.elim_var);
                 mix((uint64_t)b.level);
                 mix((uint64_t)(b.xchg * 16 + b.xchg_mode));
-                mix((b.divide ? 1 : 0) + (b.max_out ? 2 : 0) + (b.decode ? 4 : 0));
+                mix((b.divide ? 1 : 0) + (b.max_out ? 2 : 0) + (b.decode ? 4 : 0) + (b.sample ? 8 : 0));
                 mix(b.out_vars.size());
                 for (int v : b.out_vars) mix((uint64_t)v);
                 mix(b.chain_x.size() * 131 + b.chain_n.size() * 7 + (uint64_t)b.chain_gmask);
@@ -2877,7 +2988,7 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
         Item &it = items[idx];
         BucketSpec b = *it.b;
         b.simple = simplify && lvl_n[it.level] > 1 && b.chain_x.empty() && !b.divide && !b.xchg &&
-                   !b.decode && plans[it.plan]->msgs[b.out_table - s.n_src].size <= simple_max;
+                   !b.decode && !b.sample && plans[it.plan]->msgs[b.out_table - s.n_src].size <= simple_max;
         for (View &v : b.in) v.table = remap(it.plan, v.table);
         b.out_table = remap(it.plan, b.out_table);
         if (b.bel_table >= 0) b.bel_table = remap(it.plan, b.bel_table);
@@ -2886,6 +2997,13 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
             for (BucketSpec::DecodeRow &r : b.decode_rows) r.arg_table = remap(it.plan, r.arg_table);
             it.ok = build_desc(b, cards, max_vec, it.d, it.pool, &it.msg);
             it.key = kMpeDecodeKey;
+            return;
+        }
+        if (b.sample) {                      // the sampling step: the executor's, its rows in the pool
+            for (BucketSpec::SampleRow &r : b.sample_rows)
+                for (View &v : r.in) v.table = remap(it.plan, v.table);
+            it.ok = build_desc(b, cards, max_vec, it.d, it.pool, &it.msg);
+            it.key = kSampleKey;
             return;
         }
         if (b.xchg) {                        // an exchange step: the executor's, no kernel descriptor

@@ -148,6 +148,22 @@ struct BucketSpec {
     bool decode = false;
     std::vector<DecodeRow> decode_rows;
     std::vector<int> decode_init;
+    // the sampling step that ends a sampling plan (plan_sample, sample.cuh):
+    // one row per non-evidence variable in REVERSE elimination order, each
+    // with the views of the variable's eliminating bucket exactly as that
+    // bucket read them (so p_v has the bits of the term the sum kernel added;
+    // no views: a variable in no remaining factor, drawn uniformly); `in`
+    // lists every table the rows read, so that all of them live to this step;
+    // out_table holds x = uint8[n_vars][n_samples] and, behind it at the next
+    // multiple of 8 bytes, the 8-byte counter of degenerate draws
+    struct SampleRow {
+        int var;
+        std::vector<View> in;
+    };
+    bool sample = false;
+    std::vector<SampleRow> sample_rows;
+    std::vector<std::pair<int, int>> sample_ev;   // (evidence variable, value): rows of x filled as they are
+    int64_t n_samples = 0;
 };
 enum XchgKind { kXchgNone = 0, kXchgSync = 1, kXchgPack = 2, kXchgComm = 3, kXchgUnpack = 4 };
 // schedule group variant of an exchange step: kXchgKeyBase + kind * 16 + mode
@@ -155,6 +171,10 @@ enum XchgKind { kXchgNone = 0, kXchgSync = 1, kXchgPack = 2, kXchgComm = 3, kXch
 constexpr int kXchgKeyBase = 1 << 24;
 // ... of the MPE traceback (BucketSpec::decode): the executor's too, above the exchange kinds
 constexpr int kMpeDecodeKey = kXchgKeyBase + 4096;
+// ... of the sampling step (BucketSpec::sample): the executor's as well
+constexpr int kSampleKey = kXchgKeyBase + 8192;
+// byte offset of the degenerate-draw counter in a sampling step's out_table
+inline int64_t sample_counter_offset(int64_t n_vars, int64_t n_samples) { return (n_vars * n_samples + 7) / 8 * 8; }
 
 // Compile one bucket into a descriptor + dims-pool rows.  max_vec: 4 (fp32) / 2 (fp64).
 // Returns false (with msg) on an invalid shape.
@@ -201,6 +221,7 @@ struct VEPlan {
     int n_slices = 1, slice_rank = 0;
     std::vector<int> results_slice_bit;
     int64_t arg_bytes = 0;              // plan_mpe: bytes of all arg tables (resident to the traceback)
+    int64_t sample_bytes = 0;           // plan_sample: bytes of the sample state x (n_vars * n_samples)
     int n_xchg = 0;                     // message exchanges (all-to-all / all-gather)
     double xchg_elems = 0;              // entries this rank sends to other ranks
 };
@@ -223,6 +244,18 @@ VEPlan plan_ve(const std::vector<int> &cards, const std::vector<View> &sources, 
 // false (msg) when a maximised variable has more than kMaxOutCard values.
 bool plan_mpe(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
               const std::vector<int> &ev_val, int elem_bytes, VEPlan &out, std::string *msg);
+
+// Posterior sampling: plan_ve(canonical) over `order` (every non-evidence
+// variable) with no fused chain runs -- every eliminating bucket's inputs must
+// exist as tables -- then one sampling step (BucketSpec::sample) that draws
+// each variable from its bucket's inputs in reverse elimination order, for
+// n_samples samples.  The step names every table its rows read as an input, so
+// the lifetime analysis keeps all messages to the end (no checkpointing).
+// results = {the partition function (a scalar)}; x is the step's out_table.
+// ev_val: per variable, -1 = no evidence.  Returns false (msg) when a sampled
+// variable has more than kMaxOutCard values (x holds one byte per value).
+bool plan_sample(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
+                 const std::vector<int> &ev_val, int elem_bytes, int64_t n_samples, VEPlan &out, std::string *msg);
 
 // All marginals of `targets` from one two-pass bucket tree over `order`
 // (Shafer-Shenoy on the VE bucket tree; replaces the N independent VEs of

@@ -289,6 +289,15 @@ int launch(Context &ctx, Executable &ex, hipStream_t stream, const XchgHooks *ho
             const BucketDesc &d = sc.descs[g.begin];
             err = launch_mpe_decode(ex.d_pool + d.dim_off, ex.d_meta, static_cast<int32_t *>(ex.h_meta[d.out_table].ptr), st);
             if (err != hipSuccess) return fail(ctx, err, "launch_mpe_decode");
+        } else if (g.variant == kSampleKey) {                // the sampling step (sample.cuh): all rows, one launch
+            const BucketDesc &d = sc.descs[g.begin];
+            uint8_t *x = static_cast<uint8_t *>(ex.h_meta[d.out_table].ptr);
+            unsigned long long *cnt =
+                reinterpret_cast<unsigned long long *>(x + sample_counter_offset(d.out_size, d.n_tiles));
+            if ((err = hipMemsetAsync(cnt, 0, sizeof *cnt, st)) != hipSuccess) return fail(ctx, err, "hipMemsetAsync(n_degenerate)");
+            err = launch_sample_rows(ex.dtype == kF32, ex.d_pool + d.dim_off, ex.d_meta, x, d.n_tiles, ex.sample_first,
+                                     ex.sample_seed, cnt, ctx.max_grid, st);
+            if (err != hipSuccess) return fail(ctx, err, "launch_sample_rows");
         } else if (g.variant >= kXchgKeyBase) {
             int rc = run_xchg(ctx, ex, g, st, hooks);
             if (rc) return rc;

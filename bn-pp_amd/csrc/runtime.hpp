@@ -58,6 +58,23 @@ inline SingleKey max_single_key(int is_f32, const SingleArgs &a) {
 hipError_t launch_max_single(int is_f32, const SingleArgs &a, int max_grid, hipStream_t stream);
 // the traceback of a max-product run (maxout.cuh mpe_decode_kernel): one workgroup
 hipError_t launch_mpe_decode(const int64_t *pool, const TableMeta *meta, int32_t *x, hipStream_t stream);
+// posterior sampling (sample.cuh): all rows of a sampling step (pool: the
+// step's words in the dims pool) for samples [0, n) of x = uint8[n_vars][n],
+// global sample index first + s.  seed and first are launch arguments, not
+// plan data; n_degenerate (device, may be null) is added to, never cleared
+hipError_t launch_sample_rows(int is_f32, const int64_t *pool, const TableMeta *meta, uint8_t *x, int64_t n,
+                              int64_t first, uint64_t seed, unsigned long long *n_degenerate, int max_grid,
+                              hipStream_t stream);
+// ... and one row with its metadata in the kernel-argument segment (bnpp_bucket_sample)
+struct SampleSingleArgs {
+    int64_t pool[kMaxPool];
+    TableMeta meta[kMaxIn];
+    uint8_t *x;
+    int64_t n, first;
+    uint64_t seed;
+    unsigned long long *n_degenerate;
+};
+hipError_t launch_sample_single(int is_f32, const SampleSingleArgs &a, int max_grid, hipStream_t stream);
 // the keys a family's dispatch switch holds (single-op or level launches),
 // appended to `keys`: generated from the X-macro lists of the switches
 // themselves (kernels.cuh, slab.cuh, chain.cuh, chainsplit.cuh), so the two
@@ -171,6 +188,9 @@ struct Executable {
     // lanes' windows alternating (lane_order.hpp)
     std::vector<int> g_order;
     size_t cap_meta = 0, cap_meta0 = 0, cap_desc = 0, cap_pool = 0, cap_copies = 0;   // buffer capacities
+    // a sampling step (kSampleKey) draws with these at the next launch (bnpp_sample sets them per call)
+    uint64_t sample_seed = 0;
+    int64_t sample_first = 0;
 };
 
 // Several schedules (target batches of one MAR job) run back to back in one

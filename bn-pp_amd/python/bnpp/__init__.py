@@ -65,6 +65,8 @@ _SIGS = {
     "bnpp_out_scope": (_I, [_I, _IP, C.POINTER(_IP), _I, _I, _IP, _IP]),
     "bnpp_bucket_eliminate": (_I, [_P, _P, _I, _I, _IP, _I, C.POINTER(_P), _IP, C.POINTER(_IP), _I, _P, _I, _IP, _P]),
     "bnpp_bucket_max": (_I, [_P, _P, _I, _I, _IP, _I, C.POINTER(_P), _IP, C.POINTER(_IP), _I, _P, _I, _IP, _P]),
+    "bnpp_bucket_sample": (_I, [_P, _P, _I, _I, _IP, _I, C.POINTER(_P), _IP, C.POINTER(_IP), _I, C.c_int64, C.c_int64,
+                                C.c_uint64, _P, _P]),
     "bnpp_product": (_I, [_P, _P, _I, _I, _IP, _P, _I, _IP, _P, _I, _IP, _P, _I, _IP, _P]),
     "bnpp_divide": (_I, [_P, _P, _I, _I, _IP, _P, _I, _IP, _P, _I, _IP, _P, _I, _IP, _P]),
     "bnpp_sum_out": (_I, [_P, _P, _I, _I, _IP, _P, _I, _IP, _I, _P, _I, _IP, _P]),
@@ -78,6 +80,7 @@ _SIGS = {
     "bnpp_ordering": (_I, [_P, _I, _IP, _IP, _I, _IP, _I, _IP, _IP]),
     "bnpp_partition": (_I, [_P, _P, _I, _IP, _IP, _I, _IP, _I, _I, _DP, _DP, _DP]),
     "bnpp_mpe": (_I, [_P, _P, _I, _IP, _IP, _I, _IP, _I, _I, _DP, _IP, _DP]),
+    "bnpp_sample": (_I, [_P, _P, _I, _IP, _IP, _I, _IP, _I, _I, C.c_int64, C.c_int64, C.c_uint64, _P, _DP, _LP, _DP]),
     "bnpp_marginals": (_I, [_P, _P, _I, _IP, _IP, _I, _I, _IP, _I, _DP, _DP]),
     "bnpp_sum_product": (_I, [_P, _P, _I, C.c_double, _DP, _IP, _DP]),
     "bnpp_marginals_tree": (_I, [_P, _P, _I, _IP, _IP, _I, _IP, _I, _I, _IP, _I, _DP, _DP]),
@@ -96,6 +99,7 @@ _SIGS = {
     "bnpp_chain_key_supported": (_I, [_I, _I, _IP]),
     "bnpp_plan_groups": (_I, [_P, _I, _I, _IP, _IP, _I, _IP, _I, _I, _I, _I, _LP, _I, _IP]),
     "bnpp_plan_mpe_groups": (_I, [_P, _I, _IP, _IP, _I, _IP, _I, _I, _LP, _I, _IP]),
+    "bnpp_plan_sample": (_I, [_P, _I, _IP, _IP, _I, _IP, _I, _I, C.c_int64, _DP, _I, _LP, _I, _IP]),
     "bnpp_job_create": (_I, [_P, _P, _I, _I, _IP, _IP, _I, _IP, _I, _I, _IP, _I, C.POINTER(_P)]),
     "bnpp_job_stats": (_I, [_P, _DP, _I]),
     "bnpp_job_launch": (_I, [_P, _P]),
@@ -428,6 +432,52 @@ def mpe(ctx: Context, model: Model, evidence=None, heuristic: str = "mf", dtype:
     return lv.value, list(x[: model.n_vars]), up.value
 
 
+SAMPLE_KEY = (1 << 24) + 8192      # the launch-group key of the sampling step (plan.hpp kSampleKey)
+PLAN_SAMPLE_STATS = ("entries", "arena_bytes", "levels", "buckets", "width", "max_table", "bytes_moved", "batches",
+                     "sample_rows", "sample_bytes")
+
+
+def plan_sample(model: Model, n: int, evidence=None, heuristic: str = "mf", dtype: int = F64,
+                order: Optional[Sequence[int]] = None):
+    """Host-only planning of sample() (bnpp_plan_sample) -> (stats, groups):
+    stats a dict of PLAN_SAMPLE_STATS, groups one dict of PLAN_GROUP_FIELDS per
+    launch group; the sampling step is the last group, key SAMPLE_KEY."""
+    ne, ev_v, ev_x = _ev(evidence)
+    oa = _ints(order) if order is not None else None
+    h = ORDER_GIVEN if order is not None else HEURISTICS[heuristic]
+    no = len(order) if order is not None else 0
+    nf = len(PLAN_GROUP_FIELDS)
+    st = (C.c_double * len(PLAN_SAMPLE_STATS))()
+    cnt = C.c_int()
+    _check(_lib.bnpp_plan_sample(model.handle, ne, ev_v, ev_x, h, oa, no, dtype, n, st, len(PLAN_SAMPLE_STATS), None, 0,
+                                 C.byref(cnt)), "bnpp_plan_sample")
+    rows = (C.c_int64 * max(cnt.value * nf, 1))()
+    _check(_lib.bnpp_plan_sample(model.handle, ne, ev_v, ev_x, h, oa, no, dtype, n, st, len(PLAN_SAMPLE_STATS), rows,
+                                 cnt.value, C.byref(cnt)), "bnpp_plan_sample")
+    return (dict(zip(PLAN_SAMPLE_STATS, list(st))),
+            [dict(zip(PLAN_GROUP_FIELDS, rows[i * nf:(i + 1) * nf])) for i in range(cnt.value)])
+
+
+def sample(ctx: Context, model: Model, n: int, evidence=None, seed: int = 0, first_sample: int = 0,
+           heuristic: str = "mf", dtype: int = F64, order: Optional[Sequence[int]] = None):
+    """n exact joint samples of P(x | evidence) (bnpp_sample; no reference
+    counterpart) -> (samples, log10 Z, n_degenerate).  samples: a numpy uint8
+    view of shape (n, n_vars), the transpose of the fetched variable-major
+    buffer; evidence variables keep their value.  Sample s has the global index
+    first_sample + s and depends on (seed, that index) only."""
+    import numpy as np
+    ne, ev_v, ev_x = _ev(evidence)
+    oa = _ints(order) if order is not None else None
+    h = ORDER_GIVEN if order is not None else HEURISTICS[heuristic]
+    buf = np.zeros((max(model.n_vars, 1), max(int(n), 1)), dtype=np.uint8)
+    lz, up = C.c_double(), C.c_double()
+    deg = C.c_int64()
+    _check(_lib.bnpp_sample(ctx.handle, model.handle, ne, ev_v, ev_x, h, oa, len(order) if order is not None else 0,
+                            dtype, int(n), int(first_sample), int(seed) & 0xFFFFFFFFFFFFFFFF, _P(buf.ctypes.data),
+                            C.byref(lz), C.byref(deg), C.byref(up)), "bnpp_sample")
+    return buf[: model.n_vars].T, lz.value, deg.value
+
+
 def marginals(ctx: Context, model: Model, evidence=None, heuristic: str = "mf", dtype: int = F64,
               targets: Optional[Sequence[int]] = None):
     """BN::marginals (model.cpp:303-346) -> ({var: [p_0..p_k-1]}, uptime_ms)."""
@@ -667,6 +717,22 @@ def bucket_max(ctx: Context, dtype: int, cards: Sequence[int], tables: Sequence[
     _check(_lib.bnpp_bucket_max(ctx.handle, _P(stream) if stream else None, dtype, len(cards), _ints(cards), len(tables),
                                 tabs, _ints([len(s) for s in scopes]), ptrs, elim, _P(out), len(out_vars),
                                 _ints(out_vars), _P(out_arg) if out_arg else None), "bnpp_bucket_max")
+
+
+def bucket_sample(ctx: Context, dtype: int, cards: Sequence[int], tables: Sequence[int],
+                  scopes: Sequence[Sequence[int]], var: int, n_samples: int, x: int, seed: int = 0,
+                  first_sample: int = 0, n_degenerate: Optional[int] = None, stream: Optional[int] = None) -> None:
+    """One posterior-sampling draw per sample on caller-owned device buffers
+    (bnpp_bucket_sample): reads the rows of the other scope variables from x
+    (uint8[len(cards)][n_samples], variable-major) and writes row `var`;
+    n_degenerate: a device int64 (may be None).  Only enqueues on `stream`."""
+    arrs = [_ints(s) for s in scopes]
+    ptrs = (_IP * max(len(arrs), 1))(*[C.cast(a, _IP) for a in arrs])
+    tabs = (_P * max(len(tables), 1))(*[_P(t) for t in tables])
+    _check(_lib.bnpp_bucket_sample(ctx.handle, _P(stream) if stream else None, dtype, len(cards), _ints(cards),
+                                   len(tables), tabs, _ints([len(s) for s in scopes]), ptrs, var, int(n_samples),
+                                   int(first_sample), int(seed) & 0xFFFFFFFFFFFFFFFF, _P(x),
+                                   _P(n_degenerate) if n_degenerate else None), "bnpp_bucket_sample")
 
 
 def divide(ctx: Context, dtype: int, cards: Sequence[int], a: int, a_scope: Sequence[int], b: int,

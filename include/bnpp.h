@@ -41,7 +41,9 @@ extern "C" {
                               202: single ops return the reference's partition sum (out_sum);
                               203: planning introspection for tests (bnpp_plan_single, bnpp_kernel_keys);
                               204: chain-run introspection (bnpp_plan_groups, chain keys, bnpp_ctx_set_max_grid);
-                              205: MPE (bnpp_mpe, bnpp_bucket_max, bnpp_plan_max_single, bnpp_plan_mpe_groups, job kind 4, kernel family 4) */
+                              205: MPE (bnpp_mpe, bnpp_bucket_max, bnpp_plan_max_single, bnpp_plan_mpe_groups, job kind 4, kernel family 4);
+                              still 205: posterior sampling (bnpp_sample, bnpp_bucket_sample, bnpp_plan_sample) only
+                              adds symbols and shifts no argument of an existing one */
 
 enum bnpp_status {
     BNPP_OK = 0,
@@ -154,6 +156,41 @@ int bnpp_bucket_max(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const i
                     const void *const *in_tables, const int *in_ndims, const int *const *in_vars, int elim_var,
                     void *out_table, int out_ndims, const int *out_vars, uint8_t *out_arg /* device, may be NULL */);
 
+/* One posterior-sampling draw per sample (no reference counterpart: bn-pp
+ * samples the prior only, from random_device).  State: x, a DEVICE array
+ * uint8[n_cards][n_samples], variable-major: row v holds the value of variable
+ * v in every sample.  For sample s and variable `var` of k = cards[var] values,
+ * with the inputs in the given order, for v = 0 .. k-1:
+ *     p_v = ((1 * in_0[..]) * in_1[..]) ...   dtype, each product rounded, no
+ *                                             contraction; the other scope
+ *                                             variables are read from x[.][s]
+ *     c_v = c_{v-1} + (double)p_v             c_{-1} = 0.0, fp64, in order of v
+ * t = u * c_{k-1} (one fp64 product); the drawn value is the LOWEST v with
+ * c_v > t.  The comparison is strict, so a value with p_v == 0 is never drawn,
+ * even for u == 0 (the reference's `prob <= p`, factor.cpp:279, would draw it).
+ * If no v qualifies (c_{k-1} == 0, or NaN) the value is 0 and the draw is
+ * counted in *n_degenerate (a DEVICE int64, may be NULL; the call clears it
+ * first).  No inputs: p_v = 1, a uniform draw.  A common power-of-two scale of
+ * the inputs changes no draw.
+ * u: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments
+ * 0x9E3779B9, 0xBB67AE85; round c' = (hi(M1 c2)^c1^k0, lo(M1 c2), hi(M0 c0)^c3^k1,
+ * lo(M0 c0)), the key bumped after each of 10 rounds) with key (seed &
+ * 0xffffffff, seed >> 32) and counter (g & 0xffffffff, g >> 32, var, 0), g =
+ * first_sample + s; from the output words r0..r3, u = (((uint64)r0 << 32 | r1)
+ * >> 11) * 2^-53, in [0, 1).  A draw depends on (seed, g, var) and the state
+ * only: not on the grid, bnpp_ctx_set_max_grid, n_samples or how a range of g
+ * is split over calls.
+ * Tables are whole, in the given scope order; 0 to 8 inputs.  The call reads
+ * the rows of the other scope variables and writes row `var`, nothing else.
+ * Refused: ids outside [0, n_cards), n_samples < 1 (BNPP_ERR_INVALID); `var` or
+ * a scope variable of more than 256 values (BNPP_ERR_UNSUPPORTED, before any
+ * launch).  The state values in x are NOT checked, on the host or the device:
+ * a value at or above its variable's card reads outside the tables. */
+int bnpp_bucket_sample(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, int n_in,
+                       const void *const *in_tables, const int *in_ndims, const int *const *in_vars, int var,
+                       int64_t n_samples, int64_t first_sample, uint64_t seed,
+                       uint8_t *x /* device [n_cards][n_samples] */, int64_t *n_degenerate /* device, may be NULL */);
+
 /* Factor::product (factor.cpp:117-147; factor.hh:35) */
 int bnpp_product(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, const void *a, int a_ndims,
                  const int *a_vars, const void *b, int b_ndims, const int *b_vars, void *out, int out_ndims,
@@ -233,6 +270,34 @@ int bnpp_partition(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_v
 int bnpp_mpe(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, const int *ev_vals, int heuristic,
              const int *order, int n_order, int dtype, double *log10_value, int *assignment /* n_vars, evidence included */,
              double *uptime_ms);
+
+/* Exact joint samples of P(x | evidence) (no reference counterpart: the
+ * reference's logical sampling, likelihood weighting and Gibbs, model.cpp:541-720,
+ * sample the prior and reject or weight, from random_device).
+ * 1. Forward pass: bnpp_partition's elimination over the same order, with no
+ *    fused chain runs (every eliminating bucket's inputs exist as tables); the
+ *    sum kernels run unchanged.  *log10_z is the partition function's.
+ * 2. One sampling step: one row per non-evidence variable, in REVERSE
+ *    elimination order, each a bnpp_bucket_sample draw over the views of the
+ *    variable's eliminating bucket as that bucket read them (after the forward
+ *    pass they are P(x_i | separator) up to a constant).  Evidence variables
+ *    keep their value; a variable in no remaining factor is drawn uniformly.
+ * Samples are independent and exact: no burn-in, no rejection.  Sample s of the
+ * call has the global index g = first_sample + s and depends on (seed, g) only,
+ * so a range of g may be split over calls (or devices) in any way.
+ * out: HOST array uint8[n_vars][n_samples], variable-major.  *n_degenerate:
+ * draws whose weights summed to 0 or NaN (value 0 taken); 0 on a consistent
+ * model with possible evidence.
+ * Limits: every sampled variable has at most 256 values (BNPP_ERR_UNSUPPORTED
+ * otherwise, before anything is launched); all messages stay resident until
+ * the draws, beside n_vars * n_samples bytes of samples: BNPP_ERR_OOM, naming
+ * both sizes, when that exceeds the memory budget (no checkpointing).
+ * n_samples < 1: BNPP_ERR_INVALID.  The planned job stays with the context; the
+ * cache key holds the job kind and n_samples but neither seed nor first_sample,
+ * so a call with another seed relaunches the cached job. */
+int bnpp_sample(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, const int *ev_vals, int heuristic,
+                const int *order, int n_order, int dtype, int64_t n_samples, int64_t first_sample, uint64_t seed,
+                uint8_t *out /* host, [n_vars][n_samples] */, double *log10_z, int64_t *n_degenerate, double *uptime_ms);
 
 /* BN::marginals (model.cpp:303-346), VE branch: one VE per target with every
  * other variable eliminated, then Factor::normalize (factor.cpp:244-255).  All
@@ -390,6 +455,16 @@ int bnpp_plan_groups(const bnpp_model *m, int kind, int n_ev, const int *ev_vars
  * last), pure-product prefixes and the final product ordinary generic keys. */
 int bnpp_plan_mpe_groups(const bnpp_model *m, int n_ev, const int *ev_vars, const int *ev_vals, int heuristic,
                          const int *order, int n_order, int dtype, int64_t *rows, int cap_rows, int *n_rows);
+
+/* Host-only planning of bnpp_sample (its plan has no kind in bnpp_plan_stats,
+ * bnpp_plan_groups or bnpp_job_create): stats[0..8) as bnpp_job_stats (the
+ * arena bytes hold the messages and the n_vars * n_samples sample bytes), then
+ * [8] rows of the sampling step, [9] bytes of the samples; rows as
+ * bnpp_plan_groups's.  Every key but the last is an ordinary sum-plan key (no
+ * chain key); the sampling step is the last group, key 2^24 + 8192. */
+int bnpp_plan_sample(const bnpp_model *m, int n_ev, const int *ev_vars, const int *ev_vals, int heuristic,
+                     const int *order, int n_order, int dtype, int64_t n_samples, double *stats, int n_stats,
+                     int64_t *rows, int cap_rows, int *n_rows);
 
 /* Host-only planning of one part of bnpp_marginals_tree_part (all variables
  * as targets): owned[v] = 1 when this part computes v's marginal; stats as

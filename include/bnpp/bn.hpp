@@ -138,6 +138,16 @@ public:
     std::vector<unsigned> mpe(const std::unordered_map<unsigned, unsigned> &evidence,
                               std::unordered_map<std::string, bool> &options, double *log10_value = nullptr,
                               double *uptime = nullptr) const;
+    // EXTENSION beyond the reference's class API (BN::sampling and the
+    // estimators of model.cpp:541-720 sample the prior from random_device):
+    // n exact joint samples of P(x | evidence) (bnpp_sample), reproducible
+    // from `seed`; result[s] holds one value per variable, in variables()
+    // order, evidence variables keeping theirs.  Every non-evidence variable
+    // needs a size <= 256.  log10_z (optional): log10 of the partition function.
+    std::vector<std::vector<unsigned char>> sample(const std::unordered_map<unsigned, unsigned> &evidence,
+                                                   std::unordered_map<std::string, bool> &options, size_t n,
+                                                   unsigned long long seed = 0, double *log10_z = nullptr,
+                                                   double *uptime = nullptr) const;
     virtual void write(std::ostream &) const {}
 
 protected:
