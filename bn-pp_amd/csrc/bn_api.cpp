@@ -460,6 +460,60 @@ std::vector<unsigned> Model::mpe(const std::unordered_map<unsigned, unsigned> &e
     return std::vector<unsigned>(x.begin(), x.begin() + _variables.size());
 }
 
+namespace {
+// rows[r][j]: the value of ev_vars[j] in row r, flattened row-major
+std::vector<int> flatten_rows(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<unsigned>> &rows) {
+    std::vector<int> flat;
+    flat.reserve(rows.size() * ev_vars.size());
+    for (const auto &r : rows) {
+        if (r.size() != ev_vars.size()) throw std::runtime_error("evidence row of another length than the variable set");
+        for (unsigned x : r) flat.push_back((int)x);
+    }
+    return flat;
+}
+}  // namespace
+
+std::vector<double> Model::partition_batch(const std::vector<unsigned> &ev_vars,
+                                           const std::vector<std::vector<unsigned>> &rows,
+                                           std::unordered_map<std::string, bool> &options, std::vector<double> *z,
+                                           double *uptime) const {
+    auto t0 = std::chrono::steady_clock::now();
+    ModelGuard g{to_engine(_variables, std::vector<const Factor *>(_factors.begin(), _factors.end()))};
+    const std::vector<int> vars(ev_vars.begin(), ev_vars.end()), flat = flatten_rows(ev_vars, rows);
+    std::vector<double> lz(rows.size() ? rows.size() : 1, 0.0), zz(lz.size(), 0.0);
+    double up = 0;
+    int dt = options["fp32"] ? BNPP_F32 : BNPP_F64;
+    check(bnpp_partition_batch(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(),
+                               heuristic_of(options), nullptr, 0, dt, 0, lz.data(), zz.data(), &up),
+          "partition_batch");
+    lz.resize(rows.size());
+    zz.resize(rows.size());
+    if (z) *z = zz;
+    if (uptime) *uptime = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return lz;
+}
+
+std::vector<std::vector<double>> Model::posterior_batch(const std::vector<unsigned> &ev_vars,
+                                                        const std::vector<std::vector<unsigned>> &rows, unsigned target,
+                                                        std::unordered_map<std::string, bool> &options,
+                                                        double *uptime) const {
+    auto t0 = std::chrono::steady_clock::now();
+    ModelGuard g{to_engine(_variables, std::vector<const Factor *>(_factors.begin(), _factors.end()))};
+    const std::vector<int> vars(ev_vars.begin(), ev_vars.end()), flat = flatten_rows(ev_vars, rows);
+    if (target >= _variables.size()) throw std::runtime_error("posterior_batch: bad target");
+    const size_t k = _variables[target]->size();
+    std::vector<double> flat_out(std::max<size_t>(rows.size() * k, 1), 0.0);
+    double up = 0;
+    int dt = options["fp32"] ? BNPP_F32 : BNPP_F64;
+    check(bnpp_posterior_batch(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(),
+                               heuristic_of(options), (int)target, dt, 0, flat_out.data(), &up),
+          "posterior_batch");
+    std::vector<std::vector<double>> out(rows.size());
+    for (size_t r = 0; r < rows.size(); ++r) out[r].assign(flat_out.begin() + r * k, flat_out.begin() + (r + 1) * k);
+    if (uptime) *uptime = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return out;
+}
+
 std::vector<std::vector<unsigned char>> Model::sample(const std::unordered_map<unsigned, unsigned> &evidence,
                                                       std::unordered_map<std::string, bool> &options, size_t n,
                                                       unsigned long long seed, double *log10_z, double *uptime) const {

@@ -8,6 +8,11 @@
 // -sample N [-seed S] (no reference counterpart): N exact joint samples of the
 // posterior, log10 Z and the first sample; with -uai, <base>.SAMPLES ("SAMPLES",
 // then "N n_vars", then one line of n_vars values per sample).
+// -pr-batch / -post-batch T (no reference counterpart): the evidence file holds
+// any number of samples over one variable set (bnpp_evidence_load_batch); log10 Z
+// per sample, or P(T | sample); with -uai, <base>.PR ("PR", the sample count,
+// one log10 Z per line) or <base>.MAR ("MAR", the sample count, then per sample
+// "1 card(T) p_0 .. p_{card-1}").
 // BAYES files print like `bn` (raw Z), MARKOV files like `mn` (log10 Z).
 // -ve is accepted and, as in the reference, changes nothing here: bn reads it
 // only for REPL queries (bn.cpp:346); partition / marginals always run VE
@@ -29,12 +34,15 @@ int main(int argc, char **argv) {
     std::vector<std::string> positional;
     std::string uai_out;
     unsigned long long n_samples = 0, seed = 0;
+    unsigned post_target = 0;
     for (int i = 1; i < argc; ++i) {
         std::string p(argv[i]);
         if (p == "-uai" && i + 1 < argc) uai_out = argv[++i];
         else if (p == "-pr") options["partition"] = true;
         else if (p == "-mar") options["marginals"] = true;
         else if (p == "-mpe") options["mpe"] = true;
+        else if (p == "-pr-batch") options["partition-batch"] = true;
+        else if (p == "-post-batch" && i + 1 < argc) { options["posterior-batch"] = true; post_target = (unsigned)std::strtoul(argv[++i], nullptr, 10); }
         else if (p == "-sample" && i + 1 < argc) { options["sample"] = true; n_samples = std::strtoull(argv[++i], nullptr, 10); }
         else if (p == "-seed" && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
         else if (p == "-mar-tree") { options["marginals"] = true; options["bucket-tree"] = true; }
@@ -50,7 +58,7 @@ int main(int argc, char **argv) {
         else positional.push_back(p);
     }
     if (positional.empty() || options["help"]) {
-        std::cout << "usage: " << argv[0] << " /path/to/model.uai [/path/to/evidence.uai.evid] -pr|-mar|-mar-tree|-mpe|-sample N [-seed S] [-sp] [-mf|-wmf|-md] [-f32] [-uai base]" << std::endl;
+        std::cout << "usage: " << argv[0] << " /path/to/model.uai [/path/to/evidence.uai.evid] -pr|-mar|-mar-tree|-mpe|-sample N [-seed S]|-pr-batch|-post-batch T [-sp] [-mf|-wmf|-md] [-f32] [-uai base]" << std::endl;
         return positional.empty() ? 1 : 0;
     }
     bnpp_model *probe = nullptr;
@@ -150,6 +158,49 @@ int main(int argc, char **argv) {
                     std::fprintf(f, "\n");
                 }
                 std::fclose(f);
+            }
+        }
+        if (options["partition-batch"] || options["posterior-batch"]) {
+            if (positional.size() < 2) throw std::runtime_error("-pr-batch / -post-batch need an evidence file");
+            int n_ev = 0;
+            int64_t n_rows = 0;
+            bnpp_evidence_load_batch(positional[1].c_str(), 0, 0, &n_ev, nullptr, &n_rows, nullptr);   // the sizes
+            std::vector<int> ev_vars(n_ev > 0 ? n_ev : 1), flat((size_t)(n_ev > 0 ? n_ev : 1) * (size_t)(n_rows > 0 ? n_rows : 1));
+            if (bnpp_evidence_load_batch(positional[1].c_str(), n_ev, n_rows, &n_ev, ev_vars.data(), &n_rows, flat.data()) != BNPP_OK)
+                throw std::runtime_error(bnpp_last_error());
+            const std::vector<unsigned> vars(ev_vars.begin(), ev_vars.begin() + n_ev);
+            std::vector<std::vector<unsigned>> rows((size_t)n_rows);
+            for (int64_t r = 0; r < n_rows; ++r) rows[r].assign(flat.begin() + r * n_ev, flat.begin() + (r + 1) * n_ev);
+            if (options["partition-batch"]) {
+                const std::vector<double> lz = model->partition_batch(vars, rows, options, nullptr, &uptime);
+                std::cout << ">> log10 Z of " << lz.size() << " evidence rows:";
+                for (size_t r = 0; r < lz.size() && r < 8; ++r) std::cout << " " << lz[r];
+                std::cout << (lz.size() > 8 ? " ..." : "") << std::endl << ">> Executed in " << uptime << "ms." << std::endl << std::endl;
+                if (!uai_out.empty()) {
+                    FILE *f = std::fopen((uai_out + ".PR").c_str(), "w");
+                    if (!f) throw std::runtime_error("cannot write " + uai_out + ".PR");
+                    std::fprintf(f, "PR\n%zu\n", lz.size());
+                    for (double v : lz) std::fprintf(f, "%.17g\n", v);
+                    std::fclose(f);
+                }
+            }
+            if (options["posterior-batch"]) {
+                const std::vector<std::vector<double>> post = model->posterior_batch(vars, rows, post_target, options, &uptime);
+                std::cout << ">> P(" << post_target << " | row) of " << post.size() << " evidence rows; row 0:";
+                if (!post.empty())
+                    for (double v : post[0]) std::cout << " " << v;
+                std::cout << std::endl << ">> Executed in " << uptime << "ms." << std::endl << std::endl;
+                if (!uai_out.empty()) {
+                    FILE *f = std::fopen((uai_out + ".MAR").c_str(), "w");
+                    if (!f) throw std::runtime_error("cannot write " + uai_out + ".MAR");
+                    std::fprintf(f, "MAR\n%zu\n", post.size());
+                    for (const auto &row : post) {
+                        std::fprintf(f, "1 %zu", row.size());
+                        for (double v : row) std::fprintf(f, " %.17g", v);
+                        std::fprintf(f, "\n");
+                    }
+                    std::fclose(f);
+                }
             }
         }
     } catch (const std::exception &e) {

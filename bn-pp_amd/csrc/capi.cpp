@@ -76,6 +76,7 @@ struct bnpp_job {
     std::vector<int> cards;
     int n_slices = 1, slice_rank = 0;  // message-sliced bucket tree (bnpp_marginals_tree_sliced)
     double stats[10] = {0};            // bnpp_job_stats [0..8), then n_xchg, exchange bytes sent
+    int64_t batch_rows = 0;            // batched evidence (kind 6): rows per launch
 };
 
 namespace {
@@ -1122,6 +1123,269 @@ void record_call_timing(double t0, double t1, double t2, double t3) {
     g_timing[6] = now_ms() - t0;
 }
 
+// ---- batched evidence (bnpp_partition_batch, bnpp_posterior_batch, bnpp_plan_batch) ----
+// job kind 6 (internal, like kKindSample): one plan_batch plan of R rows per launch
+constexpr int kKindBatch = 6;
+constexpr int64_t kBatchAutoRows = (int64_t)1 << 16;   // the automatic R's cap
+
+// the evidence variable set (no values) and the target: ids in range, no duplicates
+int batch_check_vars(const ModelData &d, int n_ev, const int *ev_vars, int target, bool posterior) {
+    const int nv = (int)d.cards.size();
+    if (n_ev < 0 || (n_ev > 0 && !ev_vars)) return set_err(BNPP_ERR_INVALID, "bad evidence arrays");
+    std::vector<char> seen(nv, 0);
+    for (int j = 0; j < n_ev; ++j) {
+        const int v = ev_vars[j];
+        if (v < 0 || v >= nv) return set_err(BNPP_ERR_INVALID, "evidence variable " + std::to_string(v) + " out of range");
+        if (seen[v]) return set_err(BNPP_ERR_INVALID, "evidence variable " + std::to_string(v) + " is listed twice");
+        seen[v] = 1;
+    }
+    if (posterior) {
+        if (target < 0 || target >= nv) return set_err(BNPP_ERR_INVALID, "bad target");
+        if (seen[target]) return set_err(BNPP_ERR_INVALID, "the target " + std::to_string(target) + " is an evidence variable");
+    }
+    return BNPP_OK;
+}
+
+// Plan one launch: the elimination order the single call uses for this
+// evidence variable set, then plan_batch for R rows.  rows_per_launch 0: the
+// largest power of two <= auto_cap (kBatchAutoRows, or less for a call of
+// fewer rows: batch_auto_cap) whose arena fits `budget`.
+int plan_batch_schedule(const ModelData &d, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
+                        int target, int dtype, int64_t budget, int64_t rows_per_launch, Schedule &out, double *stats,
+                        int64_t &R, int &width, int64_t auto_cap = kBatchAutoRows) {
+    const int nv = (int)d.cards.size();
+    const int eb = dtype == BNPP_F32 ? 4 : 8;
+    if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
+    if (heuristic < BNPP_ORDER_GIVEN || heuristic > BNPP_MIN_DEGREE) return set_err(BNPP_ERR_INVALID, "unknown heuristic");
+    if (rows_per_launch < 0 || rows_per_launch > (int64_t)INT32_MAX)
+        return set_err(BNPP_ERR_INVALID, "rows_per_launch must be 0 (automatic) or in [1, 2^31)");
+    std::vector<int> ev(nv, -1), evv(ev_vars, ev_vars + n_ev);
+    for (int v : evv) ev[v] = 0;                            // the order depends on which variables are observed only
+    auto scopes = conditioned_scopes(d, ev);
+    std::vector<int> vars, ord;
+    if (target < 0 && order) {                              // as build_plans, kind 0
+        std::vector<char> seen(nv, 0);
+        for (int i = 0; i < n_order; ++i) {
+            int v = order[i];
+            if (v < 0 || v >= nv || seen[v]) return set_err(BNPP_ERR_INVALID, "bad explicit order");
+            seen[v] = 1;
+            if (ev[v] < 0) vars.push_back(v);
+        }
+        ord = vars;
+        width = order_width(nv, scopes, ord);
+    } else {                                                // kind 0 / kind 1 (every variable but the target)
+        for (int v = 0; v < nv; ++v)
+            if (v != target && ev[v] < 0) vars.push_back(v);
+        width = elimination_order(nv, d.cards, scopes, vars, (Heuristic)heuristic, ord);
+    }
+    std::vector<View> views;
+    for (size_t f = 0; f < d.scopes.size(); ++f) views.push_back(natural_view((int)f, d.scopes[f], d.cards));
+    VEPlan plan;
+    std::string msg;
+    auto need_of = [&](const VEPlan &p) { return sat_add(plan_arena_bytes(p, eb), (int64_t)p.buckets.size() * 512); };
+    int64_t need = 0;
+    if (rows_per_launch > 0) {
+        R = rows_per_launch;
+        if (!plan_batch(d.cards, views, ord, evv, R, target, eb, plan, &msg)) return set_err(BNPP_ERR_UNSUPPORTED, msg);
+        need = need_of(plan);
+    } else {
+        for (R = auto_cap; R >= 1; R /= 2) {
+            if (!plan_batch(d.cards, views, ord, evv, R, target, eb, plan, &msg)) return set_err(BNPP_ERR_UNSUPPORTED, msg);
+            need = need_of(plan);
+            if (need <= budget || R == 1) break;
+        }
+    }
+    if (need > budget) {
+        char m[256];
+        std::snprintf(m, sizeof m, "batched evidence needs %.6f GB for %lld row%s per launch, budget %.6f GB", need / 1e9,
+                      (long long)R, R == 1 ? "" : "s", budget / 1e9);
+        return set_err(BNPP_ERR_OOM, m);
+    }
+    std::vector<int64_t> src_sizes;
+    for (auto &v : d.values) src_sizes.push_back((int64_t)v.size());
+    if (!build_schedule({&plan}, d.cards, src_sizes, eb, max_vec_for(dtype), out, &msg, budget))
+        return set_err(out.arena_bytes >= kSatMax ? BNPP_ERR_OOM : BNPP_ERR_INVALID, msg);
+    int64_t n_gather = 0;
+    for (const Schedule::Group &g : out.groups) n_gather += g.variant == kCondBatchKey;
+    stats[0] = out.entries;
+    stats[1] = (double)out.arena_bytes;
+    stats[2] = out.n_levels;
+    stats[3] = (double)out.descs.size();
+    stats[4] = width;
+    stats[5] = (double)plan.max_table;
+    stats[6] = out.elems_moved * eb;
+    stats[7] = 1;
+    stats[8] = (double)R;
+    stats[9] = (double)n_gather;
+    return BNPP_OK;
+}
+
+// the automatic R never exceeds the smallest power of two that holds the
+// call's rows: a launch should not work on padding mostly
+int64_t batch_auto_cap(int64_t n_rows) {
+    int64_t c = 1;
+    while (c < n_rows && c < kBatchAutoRows) c *= 2;
+    return c;
+}
+
+uint64_t batch_call_key(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
+                        int target, int dtype, int64_t rows_per_launch) {
+    if (std::getenv("BNPP_NO_JOB_CACHE")) return 0;
+    uint64_t h = 1469598103934665603ull;
+    auto mix = [&](uint64_t x) { h = (h ^ x) * 1099511628211ull; };
+    mix(m->uid);
+    mix((uint64_t)kKindBatch);
+    mix((uint64_t)n_ev);
+    for (int i = 0; i < n_ev; ++i) mix((uint32_t)ev_vars[i]);   // the set and its column order; never the values
+    mix((uint64_t)heuristic);
+    mix((uint64_t)n_order);
+    for (int i = 0; i < n_order && order; ++i) mix((uint32_t)order[i]);
+    mix((uint64_t)(int64_t)target);
+    mix((uint64_t)dtype);
+    mix((uint64_t)rows_per_launch);
+    mix_plan_knobs(mix);
+    return h ? h : 1;
+}
+
+// target < 0: log10 Z and Z per row; else the posterior of target per row
+int run_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const int *ev_vals,
+              int heuristic, const int *order, int n_order, int target, bool posterior, int dtype,
+              int64_t rows_per_launch, double *log10_z, double *z, double *post, double *uptime_ms) {
+    const double t0 = now_ms();
+    // the arguments are checked before the context is looked at: a bad row fails the same with or without a device
+    if (!m) return set_err(BNPP_ERR_INVALID, "null context or model");
+    const ModelData &d = m->d;
+    if (n_rows < 1) return set_err(BNPP_ERR_INVALID, "n_rows must be at least 1");
+    if (posterior ? !post : !log10_z) return set_err(BNPP_ERR_INVALID, "null output");
+    if (int rc = batch_check_vars(d, n_ev, ev_vars, target, posterior)) return rc;
+    if (n_ev > 0 && !ev_vals) return set_err(BNPP_ERR_INVALID, "bad evidence arrays");
+    for (int64_t r = 0; r < n_rows; ++r)
+        for (int j = 0; j < n_ev; ++j) {
+            const int x = ev_vals[r * n_ev + j];
+            if (x < 0 || x >= d.cards[ev_vars[j]])
+                return set_err(BNPP_ERR_INVALID, "evidence row " + std::to_string(r) + ": value " + std::to_string(x) +
+                                                     " of variable " + std::to_string(ev_vars[j]) + " is outside [0, " +
+                                                     std::to_string(d.cards[ev_vars[j]]) + ")");
+        }
+    if (!posterior) target = -1;
+    if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
+    if (!ctx) return set_err(BNPP_ERR_INVALID, "null context or model");
+    bnpp_job *job = nullptr;
+    std::unique_lock<std::mutex> lk(ctx->cache_mu, std::try_to_lock);
+    const bool cache_ok = lk.owns_lock();
+    const int64_t budget = memory_budget(ctx, true);
+    // an automatic R is keyed by its cap, so calls of 2^16 rows or more, or of one size, share a job
+    const int64_t auto_cap = batch_auto_cap(n_rows);
+    const uint64_t key = cache_ok ? batch_call_key(m, n_ev, ev_vars, heuristic, order, n_order, target, dtype,
+                                                   rows_per_launch > 0 ? rows_per_launch : -auto_cap) : 0;
+    int rc = oneshot_job(ctx, cache_ok, key, budget, [&](std::unique_ptr<bnpp_job> &j) {
+        j.reset(new bnpp_job);
+        j->ctx = ctx;
+        j->kind = kKindBatch;
+        j->model_uid = m->uid;
+        j->cards = d.cards;
+        if (cache_ok) evict_cached_job(ctx);       // it runs in the arena this job may replace
+        const double tp = now_ms();
+        std::vector<Schedule> batches(1);
+        int width = 0;
+        int rc2 = plan_batch_schedule(d, n_ev, ev_vars, heuristic, order, n_order, target, dtype, budget, rows_per_launch,
+                                      batches[0], j->stats, j->batch_rows, width, auto_cap);
+        if (rc2) return rc2;
+        const double ta = now_ms();
+        rc2 = cached_sources(ctx, m, dtype, j->src);
+        if (rc2) return rc2;
+        const double tb = now_ms();
+        rc2 = from_ctx(ctx, make_program(ctx->c, *j->src, std::move(batches), j->pg, cache_ok));
+        if (rc2) return rc2;
+        g_timing[0] = ta - tp;
+        g_timing[1] = tb - ta;
+        g_timing[2] = now_ms() - tb;
+        g_timing[7] = j->pg.arena_reused ? 1.0 : 0.0;
+        g_timing[8] = j->pg.arena_alloc_ms;
+        return (int)BNPP_OK;
+    }, job);
+    const double t1 = now_ms();
+    double launch_ms = 0, fetch_ms = 0;
+    if (rc == BNPP_OK && (job->pg.parts.size() != 1 || job->batch_rows < 1))
+        rc = set_err(BNPP_ERR_INVALID, "batch job without a plan");
+    if (rc == BNPP_OK) {
+        Executable &ex = job->pg.parts[0];
+        const Schedule &sc = ex.sched;
+        const int64_t R = job->batch_rows, n_launch = (n_rows + R - 1) / R;
+        // the evidence table of the gather steps (none: no factor mentions an evidence variable)
+        int32_t *d_ev = nullptr;
+        for (const Schedule::Group &g : sc.groups)
+            if (g.variant == kCondBatchKey && sc.descs[g.begin].in_table[1] >= 0)
+                d_ev = static_cast<int32_t *>(ex.h_meta[sc.descs[g.begin].in_table[1]].ptr);
+        // every launch's rows, variable-major, the last launch padded with its last row;
+        // kept to the end of the call (the copies are enqueued)
+        std::vector<int32_t> hev;
+        if (d_ev) {
+            hev.resize((size_t)(n_launch * n_ev * R));
+            for (int64_t L = 0; L < n_launch; ++L)
+                for (int j = 0; j < n_ev; ++j)
+                    for (int64_t b = 0; b < R; ++b)
+                        hev[(size_t)((L * n_ev + j) * R + b)] = ev_vals[std::min(L * R + b, n_rows - 1) * n_ev + j];
+        }
+        const std::vector<int> &rv = sc.plan_result_vars[0];
+        const int Bv = (int)d.cards.size();
+        const bool has_b = std::find(rv.begin(), rv.end(), Bv) != rv.end();
+        const bool has_t = posterior && std::find(rv.begin(), rv.end(), target) != rv.end();
+        const int k = posterior ? d.cards[target] : 1;
+        const int64_t nb = has_b ? R : 1;
+        hipError_t e = hipSetDevice(ctx->c.device);
+        if (e != hipSuccess) rc = set_err(BNPP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+        for (int64_t L = 0; L < n_launch && rc == BNPP_OK; ++L) {
+            const double ta = now_ms();
+            if (d_ev) {
+                e = hipMemcpyAsync(d_ev, hev.data() + (size_t)(L * n_ev * R), (size_t)(n_ev * R) * sizeof(int32_t),
+                                   hipMemcpyHostToDevice, ctx->c.stream);
+                if (e != hipSuccess) {
+                    rc = set_err(BNPP_ERR_HIP, std::string("hipMemcpyAsync(evidence): ") + hipGetErrorString(e));
+                    break;
+                }
+            }
+            rc = from_ctx(ctx, launch_program(ctx->c, job->pg, ctx->c.stream));
+            const double tb = now_ms();
+            launch_ms += tb - ta;
+            if (rc) break;
+            std::vector<std::vector<double>> vals;
+            std::vector<int64_t> exp2;
+            rc = from_ctx(ctx, fetch_program(ctx->c, job->pg, ctx->c.stream, vals, exp2));   // waits for the stream
+            if (rc) break;
+            const std::vector<double> &r = vals[0];
+            const int64_t rows = std::min(R, n_rows - L * R);
+            if ((int64_t)r.size() != nb * (has_t ? k : 1)) {
+                rc = set_err(BNPP_ERR_INVALID, "batch result table of an unexpected size");
+                break;
+            }
+            for (int64_t b = 0; b < rows; ++b) {
+                const int64_t row = L * R + b, c = has_b ? b : 0;
+                if (!posterior) {                           // job_results, kind 0
+                    double p = 0;
+                    p += r[c];
+                    log10_z[row] = p > 0 ? std::log10(p) + (double)exp2[0] * std::log10(2.0) : -INFINITY;
+                    if (z) z[row] = std::ldexp(p, (int)std::max<int64_t>(std::min<int64_t>(exp2[0], 1 << 20), -(1 << 20)));
+                } else if (has_t && k > 0) {                // Factor::normalize (factor.cpp:244-255), as job_results
+                    double part = 0;
+                    for (int s = 0; s < k; ++s) part += r[s * nb + c];
+                    for (int s = 0; s < k; ++s) post[row * k + s] = r[s * nb + c] / part;
+                } else {                                    // variable in no factor
+                    for (int s = 0; s < k; ++s) post[row * k + s] = 1.0 / k;
+                }
+            }
+            fetch_ms += now_ms() - tb;
+        }
+    }
+    const double t3 = now_ms();
+    oneshot_done(ctx, cache_ok, key, budget, job, rc);
+    record_call_timing(t0, t1, t1 + launch_ms, t3);
+    g_timing[4] = fetch_ms;
+    if (rc) return rc;
+    if (uptime_ms) *uptime_ms = now_ms() - t0;
+    return BNPP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1610,6 +1874,72 @@ int bnpp_evidence_load(const char *path, int cap, int *n, int *vars, int *vals) 
     BNPP_GUARD_END
 }
 
+int bnpp_evidence_load_batch(const char *path, int cap_vars, int64_t cap_rows, int *n_ev, int *ev_vars,
+                             int64_t *n_rows, int *ev_vals) {
+    BNPP_GUARD_BEGIN
+    if (!path || !n_ev || !n_rows) return set_err(BNPP_ERR_INVALID, "null argument");
+    std::vector<int> vars, vals;
+    int64_t rows = 0;
+    std::string msg;
+    const int rc = load_evidence_batch(path, vars, vals, rows, &msg);
+    if (rc == -1) return set_err(BNPP_ERR_IO, std::string("couldn't read file ") + path);
+    if (rc == -3) return set_err(BNPP_ERR_UNSUPPORTED, msg);
+    if (rc) return set_err(BNPP_ERR_IO, msg);
+    *n_ev = (int)vars.size();
+    *n_rows = rows;
+    if ((int)vars.size() > cap_vars || rows > cap_rows) return set_err(BNPP_ERR_INVALID, "evidence larger than cap");
+    if ((!vars.empty() && !ev_vars) || (!vals.empty() && !ev_vals)) return set_err(BNPP_ERR_INVALID, "null argument");
+    std::copy(vars.begin(), vars.end(), ev_vars);
+    std::copy(vals.begin(), vals.end(), ev_vals);
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+int bnpp_condition_batch(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, const void *in,
+                         int ndims, const int *vars, int n_ev, const int *ev_vars, int64_t n_rows, const int32_t *ev,
+                         void *out) {
+    BNPP_GUARD_BEGIN
+    if (!ctx || !cards || !in || !out || (n_ev > 0 && (!ev_vars || !ev))) return set_err(BNPP_ERR_INVALID, "null argument");
+    if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "dtype must be BNPP_F64 or BNPP_F32");
+    if (n_cards < 0 || !valid_scope(ndims, vars, cards, n_cards)) return set_err(BNPP_ERR_INVALID, "bad input scope");
+    if (n_ev < 0 || !valid_scope(n_ev, ev_vars, cards, n_cards)) return set_err(BNPP_ERR_INVALID, "bad evidence variables");
+    if (n_rows < 1 || n_rows > (int64_t)INT32_MAX) return set_err(BNPP_ERR_INVALID, "n_rows must be in [1, 2^31)");
+    std::vector<int> cv(cards, cards + n_cards);
+    cv.push_back((int)n_rows);                              // the row variable
+    BucketSpec b;
+    b.cond_batch = true;
+    b.in.push_back(natural_view(0, std::vector<int>(vars, vars + ndims), cv));
+    int n_in_scope = 0;
+    for (int j = 0; j < ndims; ++j) {
+        int row = -1;
+        for (int e = 0; e < n_ev; ++e)
+            if (ev_vars[e] == vars[j]) row = e;
+        b.cond_rows.push_back(row);
+        if (row < 0) b.out_vars.push_back(vars[j]);
+        else ++n_in_scope;
+    }
+    if (n_in_scope > kCondMaxEv) return set_err(BNPP_ERR_UNSUPPORTED, "at most 32 evidence variables in the scope of a single-op call");
+    b.out_vars.push_back(n_cards);
+    b.out_table = 1;
+    BucketDesc d;
+    std::vector<int64_t> pool;
+    std::string msg;
+    if (!build_desc(b, cv, max_vec_for(dtype), d, pool, &msg)) return set_err(BNPP_ERR_UNSUPPORTED, msg);
+    CondBatchSingleArgs a;
+    std::memset(&a, 0, sizeof a);
+    if (pool.size() > sizeof a.pool / sizeof a.pool[0]) return set_err(BNPP_ERR_UNSUPPORTED, "scope too wide for a single-op call");
+    std::copy(pool.begin(), pool.end(), a.pool);
+    a.src = in;
+    a.out = out;
+    a.ev = ev;
+    a.n_rows = n_rows;
+    hipError_t e = hipSetDevice(ctx->c.device);
+    if (e == hipSuccess) e = launch_cond_batch_single(dtype == BNPP_F32, a, ctx->c.max_grid, pick_stream(ctx, stream));
+    if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
 int bnpp_ordering(const bnpp_model *m, int n_ev, const int *ev_vars, const int *ev_vals, int n_vars,
                   const int *vars, int heuristic, int *order_out, int *width_out) {
     BNPP_GUARD_BEGIN
@@ -2039,6 +2369,55 @@ int bnpp_sample(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars
     if (rc) return rc;
     if (log10_z) *log10_z = lz;
     if (uptime_ms) *uptime_ms = now_ms() - t0;
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+int bnpp_partition_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                         const int *ev_vals, int heuristic, const int *order, int n_order, int dtype,
+                         int64_t rows_per_launch, double *log10_z, double *z, double *uptime_ms) {
+    BNPP_GUARD_BEGIN
+    return run_batch(ctx, m, n_ev, ev_vars, n_rows, ev_vals, heuristic, order, n_order, -1, false, dtype, rows_per_launch,
+                     log10_z, z, nullptr, uptime_ms);
+    BNPP_GUARD_END
+}
+
+int bnpp_posterior_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                         const int *ev_vals, int heuristic, int target, int dtype, int64_t rows_per_launch, double *out,
+                         double *uptime_ms) {
+    BNPP_GUARD_BEGIN
+    return run_batch(ctx, m, n_ev, ev_vars, n_rows, ev_vals, heuristic, nullptr, 0, target, true, dtype, rows_per_launch,
+                     nullptr, nullptr, out, uptime_ms);
+    BNPP_GUARD_END
+}
+
+int bnpp_plan_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
+                    int target, int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows,
+                    int cap_rows, int *n_rows, int *result_scope, int *n_result_scope) {
+    BNPP_GUARD_BEGIN
+    if (!m || !n_rows || (cap_rows > 0 && !rows) || (n_stats > 0 && !stats)) return set_err(BNPP_ERR_INVALID, "null argument");
+    if (int rc = batch_check_vars(m->d, n_ev, ev_vars, target, target >= 0)) return rc;
+    Schedule s;
+    double st[10] = {0};
+    int64_t R = 0;
+    int width = 0;
+    int rc = plan_batch_schedule(m->d, n_ev, ev_vars, heuristic, target >= 0 ? nullptr : order, target >= 0 ? 0 : n_order,
+                                 target >= 0 ? target : -1, dtype, memory_budget(nullptr), rows_per_launch, s, st, R, width);
+    if (rc) return rc;
+    for (int i = 0; i < n_stats && i < 10; ++i) stats[i] = st[i];
+    int64_t n = 0;
+    for (const Schedule::Group &g : s.groups) {
+        if (n < cap_rows) {
+            const int64_t v[BNPP_PLAN_GROUP_FIELDS] = {0, g.level, g.variant, g.end - g.begin, g.vblocks, g.lane};
+            std::copy(v, v + BNPP_PLAN_GROUP_FIELDS, rows + n * BNPP_PLAN_GROUP_FIELDS);
+        }
+        ++n;
+    }
+    *n_rows = (int)n;
+    const std::vector<int> &rv = s.plan_result_vars[0];
+    if (n_result_scope) *n_result_scope = (int)rv.size();
+    if (result_scope)
+        for (size_t i = 0; i < rv.size() && i < 2; ++i) result_scope[i] = rv[i];
     return BNPP_OK;
     BNPP_GUARD_END
 }

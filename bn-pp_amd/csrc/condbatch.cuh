@@ -1,0 +1,177 @@
+// Batched conditioning (gfx950): a source table gathered into a table over its
+// non-evidence variables and the virtual variable B = "which evidence row".
+//
+//   out[rest][b] = src[ sum_e ev[row_e][b] * stride_e + offset(rest) ]
+//
+// src is a source table in its natural layout, rest its non-evidence variables
+// (row-major, adjacent ones merged on the host), b the fastest output dim of
+// R rows.  ev is int32[n_ev_rows][R], variable-major: a wave reads 64 rows of
+// one evidence variable as 256 contiguous bytes.  A thread owns V consecutive
+// b (V = 16 bytes of T when R is a multiple of it and the tables are 16-byte
+// aligned, else 1), computes its V base offsets once and walks a chunk of
+// rest: stores are contiguous in b (a wave writes 64 * V consecutive
+// entries), reads are per-lane gathers at 64-bit offsets from a table that is
+// usually cache-resident.  An evidence value is clamped into its variable's
+// range, so no value can send a read outside src.  The kernel moves values
+// and does no arithmetic on them.
+//
+// Work: virtual blocks of (kBlock * V rows) x (kCondRestChunk rest entries),
+// row blocks fastest, walked grid-stride by a persistent grid.  The rest
+// offset is an odometer over the (wave-uniform) rest dims: scalar registers.
+//
+// pool (int64 words, plan.cpp build_condb_desc):
+//   [0] source table  [1] n_e  [2] n_rest  [3] rest entries
+//   n_e x (row of ev, stride in src, card)     evidence variables in the scope
+//   n_rest x (card, stride in src)             fastest first, at most kCondMaxRest
+#pragma once
+#include "kernels.cuh"
+
+namespace bnpp {
+
+constexpr int kCondRestChunk = 32;     // rest entries per virtual block
+constexpr int kCondBatchU = 4;         // rest entries whose gathers are in flight together
+
+template <typename T, int V>
+__device__ __forceinline__ void cond_batch(cst_t<int64_t> *pool, const T *src, T *out, const int32_t *ev, int64_t R) {
+    const int n_e = (int)pool[1], n_rest = (int)pool[2];
+    const int64_t n_r = pool[3];
+    cst_t<int64_t> *ew = pool + 4, *rw = ew + 3 * n_e;
+    const int64_t nbb = (R / V + kBlock - 1) / kBlock;
+    const int64_t nrc = (n_r + kCondRestChunk - 1) / kCondRestChunk;
+    for (int64_t vb = blockIdx.x; vb < nbb * nrc; vb += gridDim.x) {
+        const int64_t rc = vb / nbb, bb = vb - rc * nbb;
+        const int64_t b = (bb * kBlock + threadIdx.x) * V;
+        const bool live = b < R;
+        int64_t base[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) base[j] = 0;
+        if (live) {
+            for (int e = 0; e < n_e; ++e) {
+                int32_t x[V];
+                load_n<int32_t, V, false, true>(ev + ew[3 * e] * R + b, x);
+                const int32_t top = (int32_t)ew[3 * e + 2] - 1;
+                const int64_t st = ew[3 * e + 1];
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    const int32_t c = x[j] < 0 ? 0 : x[j] > top ? top : x[j];
+                    base[j] += (int64_t)c * st;
+                }
+            }
+        }
+        // the odometer at the chunk's first rest entry (uniform)
+        const int64_t r0 = rc * kCondRestChunk;
+        const int64_t r1 = r0 + kCondRestChunk < n_r ? r0 + kCondRestChunk : n_r;
+        int64_t dig[kCondMaxRest];
+        int64_t off = 0, q = r0;
+#pragma unroll
+        for (int d = 0; d < kCondMaxRest; ++d) {
+            dig[d] = 0;
+            if (d < n_rest) {
+                const int64_t c = rw[2 * d];
+                dig[d] = q % c;
+                q /= c;
+                off += dig[d] * rw[2 * d + 1];
+            }
+        }
+        for (int64_t r = r0; r < r1; r += kCondBatchU) {
+            int64_t offs[kCondBatchU];
+#pragma unroll
+            for (int u = 0; u < kCondBatchU; ++u) {
+                offs[u] = off;
+                bool carry = true;
+#pragma unroll
+                for (int d = 0; d < kCondMaxRest; ++d) {
+                    if (carry && d < n_rest) {
+                        const int64_t c = rw[2 * d], st = rw[2 * d + 1];
+                        ++dig[d];
+                        off += st;
+                        if (dig[d] == c) {
+                            dig[d] = 0;
+                            off -= c * st;
+                        } else {
+                            carry = false;
+                        }
+                    }
+                }
+            }
+            T x[kCondBatchU][V];
+#pragma unroll
+            for (int u = 0; u < kCondBatchU; ++u)
+                if (live && r + u < r1) {
+#pragma unroll
+                    for (int j = 0; j < V; ++j) x[u][j] = gload(src + base[j] + offs[u]);
+                }
+#pragma unroll
+            for (int u = 0; u < kCondBatchU; ++u)
+                if (live && r + u < r1) store_n<T, V, false, true>(out + (r + u) * R + b, x[u]);
+        }
+    }
+}
+
+// The gather step of a batch plan: tables and their metadata from `meta`.  The
+// gathered table carries the source's exp2 and maxbits -- the bound the single
+// call's conditioned view of the same table carries.
+template <typename T, int V>
+__global__ __launch_bounds__(kBlock) void cond_batch_kernel(const int64_t *pool_, TableMeta *meta, int out_table,
+                                                            const int32_t *ev, int64_t R) {
+    cst_t<int64_t> *pool = as_const(pool_);
+    const int src_table = (int)pool[0];
+    cst_t<TableMeta> &ms = *as_const(meta + src_table);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        meta[out_table].exp2 = ms.exp2;
+        meta[out_table].maxbits = ms.maxbits;
+    }
+    cond_batch<T, V>(pool, static_cast<const T *>(ms.ptr), static_cast<T *>(as_const(meta + out_table)->ptr), ev, R);
+}
+
+// One gather with its metadata in the kernel-argument segment (bnpp_condition_batch).
+template <typename T, int V>
+__global__ __launch_bounds__(kBlock) void cond_batch_single_kernel(const CondBatchSingleArgs args) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    (void)args;
+    cst_t<CondBatchSingleArgs> &a = *(cst_t<CondBatchSingleArgs> *)__builtin_amdgcn_kernarg_segment_ptr();
+#else
+    cst_t<CondBatchSingleArgs> &a = *(cst_t<CondBatchSingleArgs> *)&args;
+#endif
+    cond_batch<T, V>(a.pool, static_cast<const T *>(a.src), static_cast<T *>(a.out), a.ev, a.n_rows);
+}
+
+// persistent: the grid capped like the other persistent launches
+template <int V>
+static inline int64_t cond_batch_grid(int64_t rest, int64_t R, int max_grid) {
+    const int64_t nbb = (R / V + kBlock - 1) / kBlock, nrc = (rest + kCondRestChunk - 1) / kCondRestChunk;
+    const int64_t blocks = nbb * nrc;
+    return blocks < 1 ? 1 : blocks < max_grid ? blocks : max_grid;
+}
+// wide accesses: R a multiple of 16 bytes of T, every address 16-byte aligned
+template <typename T>
+static inline bool cond_batch_wide(int64_t R, const void *a, const void *b) {
+    constexpr int V = 16 / (int)sizeof(T);
+    return R % V == 0 && (reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) % 16 == 0;
+}
+
+template <typename T>
+static hipError_t go_cond_batch(const int64_t *pool, int64_t rest, TableMeta *meta, int out_table, const void *out_ptr,
+                                const int32_t *ev, int64_t R, int max_grid, hipStream_t stream) {
+    constexpr int V = 16 / (int)sizeof(T);
+    if (cond_batch_wide<T>(R, out_ptr, ev))
+        hipLaunchKernelGGL((cond_batch_kernel<T, V>), dim3((unsigned)cond_batch_grid<V>(rest, R, max_grid)), dim3(kBlock), 0,
+                           stream, pool, meta, out_table, ev, R);
+    else
+        hipLaunchKernelGGL((cond_batch_kernel<T, 1>), dim3((unsigned)cond_batch_grid<1>(rest, R, max_grid)), dim3(kBlock), 0,
+                           stream, pool, meta, out_table, ev, R);
+    return hipGetLastError();
+}
+template <typename T>
+static hipError_t go_cond_batch_single(const CondBatchSingleArgs &a, int max_grid, hipStream_t stream) {
+    constexpr int V = 16 / (int)sizeof(T);
+    if (cond_batch_wide<T>(a.n_rows, a.out, a.ev))
+        hipLaunchKernelGGL((cond_batch_single_kernel<T, V>), dim3((unsigned)cond_batch_grid<V>(a.pool[3], a.n_rows, max_grid)),
+                           dim3(kBlock), 0, stream, a);
+    else
+        hipLaunchKernelGGL((cond_batch_single_kernel<T, 1>), dim3((unsigned)cond_batch_grid<1>(a.pool[3], a.n_rows, max_grid)),
+                           dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace bnpp

@@ -1,6 +1,6 @@
 // Host-side launchers: route a descriptor to the translation unit that holds
 // its kernel instantiation (k_generic_f32/f64, k_stream_f32/f64, k_slab_f32/f64,
-// k_chain_f32/f64, k_max_f32/f64, k_sample_f32/f64).
+// k_chain_f32/f64, k_max_f32/f64, k_sample_f32/f64, k_condb_f32/f64).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,6 +35,13 @@ hipError_t dispatch_sample_rows_f64(const int64_t *pool, const TableMeta *meta, 
                                     uint64_t seed, unsigned long long *n_degenerate, int max_grid, hipStream_t stream);
 hipError_t dispatch_sample_single_f32(const SampleSingleArgs &a, int max_grid, hipStream_t stream);
 hipError_t dispatch_sample_single_f64(const SampleSingleArgs &a, int max_grid, hipStream_t stream);
+
+hipError_t dispatch_cond_batch_f32(const int64_t *pool, int64_t rest, TableMeta *meta, int out_table, const void *out_ptr,
+                                   const int32_t *ev, int64_t n_rows, int max_grid, hipStream_t stream);
+hipError_t dispatch_cond_batch_f64(const int64_t *pool, int64_t rest, TableMeta *meta, int out_table, const void *out_ptr,
+                                   const int32_t *ev, int64_t n_rows, int max_grid, hipStream_t stream);
+hipError_t dispatch_cond_batch_single_f32(const CondBatchSingleArgs &a, int max_grid, hipStream_t stream);
+hipError_t dispatch_cond_batch_single_f64(const CondBatchSingleArgs &a, int max_grid, hipStream_t stream);
 
 hipError_t dispatch_slab_single_f32(int key, const SingleArgs &a, hipStream_t stream);
 hipError_t dispatch_slab_single_f64(int key, const SingleArgs &a, hipStream_t stream);
@@ -109,6 +116,18 @@ hipError_t launch_sample_rows(int is_f32, const int64_t *pool, const TableMeta *
 hipError_t launch_sample_single(int is_f32, const SampleSingleArgs &a, int max_grid, hipStream_t stream) {
     if (a.n <= 0) return hipSuccess;
     return is_f32 ? dispatch_sample_single_f32(a, max_grid, stream) : dispatch_sample_single_f64(a, max_grid, stream);
+}
+
+hipError_t launch_cond_batch(int is_f32, const int64_t *pool, int64_t rest, TableMeta *meta, int out_table,
+                             const void *out_ptr, const int32_t *ev, int64_t n_rows, int max_grid, hipStream_t stream) {
+    if (n_rows <= 0 || rest <= 0) return hipSuccess;
+    return is_f32 ? dispatch_cond_batch_f32(pool, rest, meta, out_table, out_ptr, ev, n_rows, max_grid, stream)
+                  : dispatch_cond_batch_f64(pool, rest, meta, out_table, out_ptr, ev, n_rows, max_grid, stream);
+}
+
+hipError_t launch_cond_batch_single(int is_f32, const CondBatchSingleArgs &a, int max_grid, hipStream_t stream) {
+    if (a.n_rows <= 0) return hipSuccess;
+    return is_f32 ? dispatch_cond_batch_single_f32(a, max_grid, stream) : dispatch_cond_batch_single_f64(a, max_grid, stream);
 }
 
 void kernel_keys(int is_f32, int level, int family, std::vector<int> &keys) {

@@ -1,5 +1,6 @@
 #include "model_io.hpp"
 
+#include <algorithm>
 #include <cstdlib>
 #include <fstream>
 
@@ -95,6 +96,52 @@ int load_evidence(const std::string &path, std::vector<std::pair<int, int>> &ev)
                 if (p.first == id) { p.second = (int)val; found = true; }
             if (!found) ev.push_back({(int)id, (int)val});
         }
+    }
+    return 0;
+}
+
+int load_evidence_batch(const std::string &path, std::vector<int> &vars, std::vector<int> &vals, int64_t &n_rows,
+                        std::string *err) {
+    std::ifstream in(path);
+    if (!in.is_open()) return -1;
+    vars.clear();
+    vals.clear();
+    n_rows = 0;
+    long n;
+    if (!next_long(in, n) || n < 0) {
+        if (err) *err = "malformed evidence file " + path;
+        return -2;
+    }
+    for (long s = 0; s < n; ++s) {
+        long size;
+        if (!next_long(in, size) || size < 0) {
+            if (err) *err = "malformed evidence file " + path + ": sample " + std::to_string(s) + " is missing";
+            return -2;
+        }
+        std::vector<std::pair<int, int>> ev;
+        for (long i = 0; i < size; ++i) {
+            long id, val;
+            if (!next_long(in, id) || !next_long(in, val)) {
+                if (err) *err = "malformed evidence file " + path + ": sample " + std::to_string(s) + " is cut short";
+                return -2;
+            }
+            bool found = false;
+            for (auto &p : ev)
+                if (p.first == id) { p.second = (int)val; found = true; }   // a repeated id: the last value (io.cpp:171)
+            if (!found) ev.push_back({(int)id, (int)val});
+        }
+        std::sort(ev.begin(), ev.end());
+        if (s == 0)
+            for (auto &p : ev) vars.push_back(p.first);
+        bool same = ev.size() == vars.size();
+        for (size_t i = 0; same && i < ev.size(); ++i) same = ev[i].first == vars[i];
+        if (!same) {
+            if (err) *err = "evidence file " + path + ": sample " + std::to_string(s) +
+                            " observes another variable set than sample 0";
+            return -3;
+        }
+        for (auto &p : ev) vals.push_back(p.second);
+        ++n_rows;
     }
     return 0;
 }

@@ -1,5 +1,6 @@
 // Host data model + UAI reader (io.cpp:14-180 token rules).
 #pragma once
+#include <cstdint>
 #include <string>
 #include <utility>
 #include <vector>
@@ -20,6 +21,12 @@ int load_uai(const std::string &path, ModelData &m, std::string *err);
 // read_uai_evidence (io.cpp:157-180): pairs are read only when the first integer
 // is 1; a repeated id keeps the last value.  Returns 0 or -1 (cannot open).
 int load_evidence(const std::string &path, std::vector<std::pair<int, int>> &ev);
+// an .evid file of any number of samples (the count, then per sample
+// `k v_1 x_1 ... v_k x_k`), every sample over the same variable set: vars
+// ascending, vals[row][vars.size()] row-major.  Returns 0, -1 (cannot open), -2
+// (malformed), -3 (a sample observes another variable set than the first; err names it)
+int load_evidence_batch(const std::string &path, std::vector<int> &vars, std::vector<int> &vals, int64_t &n_rows,
+                        std::string *err);
 // validate shapes (scope ids in range, table sizes = prod(card))
 bool validate(const ModelData &m, std::string *err);
 

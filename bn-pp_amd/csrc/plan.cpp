@@ -600,11 +600,71 @@ static bool build_sample_desc(const BucketSpec &b, const std::vector<int> &cards
     return true;
 }
 
+// A gather step of a batch plan: no kernel descriptor, its words in the dims
+// pool (the layout cond_batch reads, condbatch.cuh).  in_table[0] the source,
+// in_table[1] the evidence table (-1: a single-op call), out_size the output's
+// entries, k the rest entries, n_tiles the rows.
+static bool build_condb_desc(const BucketSpec &b, const std::vector<int> &cards, BucketDesc &d,
+                             std::vector<int64_t> &pool, std::string *msg) {
+    d = BucketDesc{};
+    d.out_table = b.out_table;
+    d.big = -1;
+    d.dim_off = (int64_t)pool.size();
+    if (b.in.empty() || b.cond_rows.size() != b.in[0].vars.size() || b.out_vars.empty()) {
+        if (msg) *msg = "gather step: a source view, one evidence row per scope variable and the row variable are needed";
+        return false;
+    }
+    const View &v = b.in[0];
+    // rest dims, fastest first; a variable whose stride continues the previous (faster) one's block is merged into it
+    std::vector<std::pair<int64_t, int64_t>> rest, evs;     // (card, stride)
+    std::vector<int64_t> ev_row;
+    for (int j = (int)v.vars.size() - 1; j >= 0; --j) {
+        const int64_t c = cards[v.vars[j]], st = v.strides[j];
+        if (b.cond_rows[j] >= 0) {
+            evs.push_back({c, st});
+            ev_row.push_back(b.cond_rows[j]);
+        } else if (!rest.empty() && rest.back().second * rest.back().first == st) {
+            rest.back().first *= c;
+        } else {
+            rest.push_back({c, st});
+        }
+    }
+    if ((int)rest.size() > kCondMaxRest) {
+        if (msg) *msg = "gather step: the scope's non-evidence variables form " + std::to_string(rest.size()) +
+                        " separate runs between evidence variables (at most " + std::to_string(kCondMaxRest) + ")";
+        return false;
+    }
+    int64_t n_rest = 1;
+    for (const auto &r : rest) n_rest = sat_mul(n_rest, r.first);
+    pool.push_back(v.table);
+    pool.push_back((int64_t)evs.size());
+    pool.push_back((int64_t)rest.size());
+    pool.push_back(n_rest);
+    for (size_t e = 0; e < evs.size(); ++e) {
+        pool.push_back(ev_row[e]);
+        pool.push_back(evs[e].second);
+        pool.push_back(evs[e].first);
+    }
+    for (const auto &r : rest) {
+        pool.push_back(r.first);
+        pool.push_back(r.second);
+    }
+    const int64_t rows = cards[b.out_vars.back()];
+    d.n_in = (int)std::min<size_t>(b.in.size(), 2);
+    d.in_table[0] = v.table;
+    d.in_table[1] = b.in.size() > 1 ? b.in[1].table : -1;
+    d.out_size = sat_mul(n_rest, rows);
+    d.k = (int32_t)std::min<int64_t>(n_rest, INT32_MAX);
+    d.n_tiles = rows;
+    return true;
+}
+
 bool build_desc(const BucketSpec &b, const std::vector<int> &cards, int max_vec, BucketDesc &d,
                 std::vector<int64_t> &pool, std::string *msg, bool slab_outer) {
     if (!b.chain_x.empty()) return build_chain_desc(b, cards, max_vec, d, pool, msg);
     if (b.decode) return build_decode_desc(b, d, pool, msg);
     if (b.sample) return build_sample_desc(b, cards, d, pool, msg);
+    if (b.cond_batch) return build_condb_desc(b, cards, d, pool, msg);
     const int n = (int)b.in.size();
     if (n < 1 || n > kMaxIn) {
         if (msg) *msg = "bucket needs 1.." + std::to_string(kMaxIn) + " inputs, got " + std::to_string(n);
@@ -1674,6 +1734,84 @@ bool plan_sample(const std::vector<int> &cards, const std::vector<View> &sources
     return true;
 }
 
+bool plan_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
+                const std::vector<int> &ev_vars, int64_t rows, int target, int elem_bytes, VEPlan &out,
+                std::string *msg) {
+    out = VEPlan{};
+    VEPlan &p = out;
+    if (rows < 1 || rows > (int64_t)INT32_MAX) {
+        if (msg) *msg = "rows per launch must be in [1, 2^31)";
+        return false;
+    }
+    const int nv = (int)cards.size(), Bv = nv;              // the row variable follows the model's
+    std::vector<int> ce = cards;
+    ce.push_back((int)rows);
+    PlanBuilder B(ce, p, sources, order, true);             // chain_eb stays 0: no fused runs
+    B.n_real = nv;                                          // finish() records cards_ext
+    std::vector<int> row_of(nv, -1);
+    for (size_t i = 0; i < ev_vars.size(); ++i) row_of[ev_vars[i]] = (int)i;
+    (void)target;                                           // kept: it is not in `order`, canon() lays it before B
+    // level 0: one gather step per source that mentions an evidence variable
+    std::vector<View> placed;
+    for (const View &s : sources) {
+        bool any = false;
+        for (int v : s.vars) any = any || row_of[v] >= 0;
+        if (!any) {
+            placed.push_back(s);
+            continue;
+        }
+        if (p.batch_ev_table < 0) {
+            const int64_t bytes = sat_mul(sat_mul((int64_t)ev_vars.size(), rows), 4);
+            p.batch_ev_table = B.new_raw((bytes + elem_bytes - 1) / elem_bytes);
+            B.level[p.batch_ev_table] = 0;
+        }
+        BucketSpec g;
+        g.cond_batch = true;
+        g.in.push_back(s);
+        View evt;
+        evt.table = p.batch_ev_table;
+        g.in.push_back(evt);
+        for (int v : s.vars) {
+            g.cond_rows.push_back(row_of[v]);
+            if (row_of[v] < 0) g.out_vars.push_back(v);
+        }
+        g.out_vars.push_back(Bv);
+        {
+            BucketDesc d;
+            std::vector<int64_t> pool;
+            if (!build_desc(g, ce, 1, d, pool, msg)) return false;
+        }
+        g.out_table = B.new_msg(g.out_vars);
+        g.level = 0;
+        B.level[g.out_table] = 0;
+        p.elems_moved += 2.0 * (double)p.msgs[g.out_table - p.n_src].size;
+        p.buckets.push_back(g);
+        placed.push_back(B.view(g.out_table));
+    }
+    const int nord = (int)order.size();
+    std::vector<std::vector<View>> buckets(nord);
+    std::vector<View> result;
+    for (const View &s : placed) {
+        int bi = B.first_bucket(s.vars, 0);
+        if (bi >= 0) buckets[bi].push_back(s);
+        else result.push_back(s);
+    }
+    for (int i = 0; i < nord; ++i) {
+        if (buckets[i].empty()) continue;
+        const int t = B.emit(buckets[i], order[i], false);
+        View mv = B.view(t);
+        int bi = B.first_bucket(mv.vars, i + 1);
+        if (bi >= 0) buckets[bi].push_back(mv);
+        else result.push_back(mv);
+    }
+    if (!result.empty()) {
+        p.result_table = B.emit(result, -1, false);         // canonical: (target, B)
+        p.result_vars = p.msgs[p.result_table - p.n_src].vars;
+    }
+    B.finish();
+    return true;
+}
+
 VEPlan plan_bucket_tree(const std::vector<int> &cards, const std::vector<View> &sources,
                         const std::vector<int> &order, const std::vector<int> &targets, int part, int n_parts) {
     VEPlan p;
@@ -2500,7 +2638,8 @@ struct Arena {
 };
 
 // Place the tables of one arena level by level (born_at[L] allocated, then
-// dies_at[L] released): off[t - t_base] for every table t placed.  Two
+// dies_at[L] released): off[t - t_base] for every table t placed.  Level 0
+// holds only a batch plan's evidence table and gathered sources.  Two
 // placements are made and the one with the lower top kept: (a) one best-fit
 // arena; (b) the tables of the largest size first, by interval colouring into
 // K slots of that size (K = the most of them live at once: no fragmentation
@@ -2517,12 +2656,12 @@ int64_t place_levels(int n_levels, const std::vector<std::vector<int>> &born_at,
     auto rnd = [](int64_t n) { return (n + 255) & ~(int64_t)255; };
     int64_t big = 0;
     size_t n_tab = 0;
-    for (int L = 1; L <= n_levels; ++L) {
+    for (int L = 0; L <= n_levels; ++L) {
         n_tab += born_at[L].size();
         for (int t : born_at[L]) big = std::max(big, rnd(bytes(t)));
     }
     Arena one;
-    for (int L = 1; L <= n_levels; ++L) {
+    for (int L = 0; L <= n_levels; ++L) {
         for (int t : born_at[L]) off[t - t_base] = one.alloc(bytes(t));
         for (int t : dies_at[L]) one.release(off[t - t_base], bytes(t));
     }
@@ -2531,14 +2670,14 @@ int64_t place_levels(int n_levels, const std::vector<std::vector<int>> &born_at,
     if (one.saturated || big <= 0 || one.top <= big || big >= kSatMax / 4 || n_tab > 50000) return one.top;
     const int kLive = INT_MAX;
     std::vector<int> die(off.size(), kLive);
-    for (int L = 1; L <= n_levels; ++L)
+    for (int L = 0; L <= n_levels; ++L)
         for (int t : dies_at[L]) die[t - t_base] = L;
     auto is_big = [&](int t) { return rnd(bytes(t)) == big; };
     // large tables: interval colouring (allocations of a level before its releases)
     std::vector<int> slot(off.size(), -1);
     std::vector<std::vector<std::pair<int, int>>> busy;          // per slot: (born, dies) of its large tables
     std::vector<int> free_slots;                                 // a min-heap of slot ids
-    for (int L = 1; L <= n_levels; ++L) {
+    for (int L = 0; L <= n_levels; ++L) {
         for (int t : born_at[L]) {
             if (!is_big(t)) continue;
             int k;
@@ -2563,7 +2702,7 @@ int64_t place_levels(int n_levels, const std::vector<std::vector<int>> &born_at,
     std::vector<Arena> in_slot(K);
     Arena above;
     std::vector<int64_t> off2(off.size(), 0);
-    for (int L = 1; L <= n_levels; ++L) {
+    for (int L = 0; L <= n_levels; ++L) {
         for (int t : born_at[L]) {
             const int i = t - t_base;
             if (is_big(t)) {
@@ -2610,7 +2749,7 @@ int64_t place_levels(int n_levels, const std::vector<std::vector<int>> &born_at,
         std::fprintf(stderr, "[bnpp] placement: one arena %.2f GB, %d slots of %.2f GB + %.2f GB above\n", one.top / 1e9,
                      K, big / 1e9, above.top / 1e9);
     if (above.saturated || sat_add(base_above, above.top) > one.top + one.top / 100) return one.top;
-    for (int L = 1; L <= n_levels; ++L)
+    for (int L = 0; L <= n_levels; ++L)
         for (int t : born_at[L]) {
             const int i = t - t_base;
             off[i] = slot[i] == -2 ? base_above + off2[i] : off2[i];
@@ -2643,7 +2782,7 @@ int64_t plan_arena_bytes(const VEPlan &p, int elem_bytes) {
     const int64_t top = place_levels(p.n_levels, born_at, dies_at, bytes, 0, off, sat);
     if (std::getenv("BNPP_DEBUG_ARENA")) {
         int64_t live = 0, peak = 0;
-        for (int L = 1; L <= p.n_levels; ++L) {
+        for (int L = 0; L <= p.n_levels; ++L) {
             for (int t : born_at[L]) live += bytes(t);
             peak = std::max(peak, live);
             for (int t : dies_at[L]) live -= bytes(t);
@@ -2715,7 +2854,7 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
                 mix((uint64_t)(uint32_t)b.elim_var);
                 mix((uint64_t)b.level);
                 mix((uint64_t)(b.xchg * 16 + b.xchg_mode));
-                mix((b.divide ? 1 : 0) + (b.max_out ? 2 : 0) + (b.decode ? 4 : 0) + (b.sample ? 8 : 0));
+                mix((b.divide ? 1 : 0) + (b.max_out ? 2 : 0) + (b.decode ? 4 : 0) + (b.sample ? 8 : 0) + (b.cond_batch ? 16 : 0));
                 mix(b.out_vars.size());
                 for (int v : b.out_vars) mix((uint64_t)v);
                 mix(b.chain_x.size() * 131 + b.chain_n.size() * 7 + (uint64_t)b.chain_gmask);
@@ -2891,7 +3030,7 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
             bool st = false;
             tops[pi] = place_levels(n_levels, ba, da, [&](int t) { return sat_mul(s.table_size[t], elem_bytes); }, t0,
                                     lo, st);
-            for (int L = 1; L <= n_levels; ++L)
+            for (int L = 0; L <= n_levels; ++L)
                 for (int t : ba[L]) offs[t] = lo[t - t0];
             sat[pi] = st;
         });
@@ -2929,12 +3068,12 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
             bool st = false;
             const int64_t top = place_levels(n_levels, ba, da, [&](int t) { return sat_mul(s.table_size[t], elem_bytes); },
                                              s.n_src, lo, st);
-            for (int L = 1; L <= n_levels; ++L)
+            for (int L = 0; L <= n_levels; ++L)
                 for (int t : ba[L]) s.table_offset[t] = lo[t - s.n_src];
             // a lane's arena starts at a multiple of its largest table (up to
             // 1 GiB): its messages keep the alignment place_levels gave them
             int64_t big = 256;
-            for (int L = 1; L <= n_levels; ++L)
+            for (int L = 0; L <= n_levels; ++L)
                 for (int t : ba[L]) big = std::max(big, sat_mul(s.table_size[t], elem_bytes));
             big = std::min<int64_t>(big, (int64_t)1 << 30);
             if (l > 0 && base % big) base = sat_add(base, big - base % big);
@@ -2988,7 +3127,7 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
         Item &it = items[idx];
         BucketSpec b = *it.b;
         b.simple = simplify && lvl_n[it.level] > 1 && b.chain_x.empty() && !b.divide && !b.xchg &&
-                   !b.decode && !b.sample && plans[it.plan]->msgs[b.out_table - s.n_src].size <= simple_max;
+                   !b.decode && !b.sample && !b.cond_batch && plans[it.plan]->msgs[b.out_table - s.n_src].size <= simple_max;
         for (View &v : b.in) v.table = remap(it.plan, v.table);
         b.out_table = remap(it.plan, b.out_table);
         if (b.bel_table >= 0) b.bel_table = remap(it.plan, b.bel_table);
@@ -3004,6 +3143,12 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
                 for (View &v : r.in) v.table = remap(it.plan, v.table);
             it.ok = build_desc(b, cards, max_vec, it.d, it.pool, &it.msg);
             it.key = kSampleKey;
+            return;
+        }
+        if (b.cond_batch) {                  // a gather step of a batch plan: the executor's, its words in the pool
+            it.ok = build_desc(b, plans[it.plan]->cards_ext.empty() ? cards : plans[it.plan]->cards_ext, max_vec, it.d,
+                               it.pool, &it.msg);
+            it.key = kCondBatchKey;
             return;
         }
         if (b.xchg) {                        // an exchange step: the executor's, no kernel descriptor
@@ -3064,7 +3209,7 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
         Schedule::Group g{first.level, first.key, (int)i, 0, 0, 0, first.b->lane};
         int64_t vb = 0;
         for (; i < ord.size() && items[ord[i]].level == g.level && items[ord[i]].key == g.variant &&
-               items[ord[i]].b->lane == g.lane;
+               items[ord[i]].b->lane == g.lane && !(g.variant == kCondBatchKey && (int)i > g.begin);   // one launch per gather step
              ++i) {
             const Item &it = items[ord[i]];
             BucketDesc &d = s.descs[i];

@@ -164,6 +164,15 @@ struct BucketSpec {
     std::vector<SampleRow> sample_rows;
     std::vector<std::pair<int, int>> sample_ev;   // (evidence variable, value): rows of x filled as they are
     int64_t n_samples = 0;
+    // a gather step of a batch plan (plan_batch, condbatch.cuh): in[0] is the
+    // natural view of a source that mentions evidence variables, in[1] the
+    // evidence table (int32[n_ev][rows], variable-major, uploaded per launch);
+    // out_table, over out_vars = the source's other variables then the row
+    // variable B, holds per row the entries the single call's conditioned view
+    // of that source reaches.  cond_rows[j]: the row of the evidence table that
+    // holds the values of in[0].vars[j] (-1: not an evidence variable)
+    bool cond_batch = false;
+    std::vector<int> cond_rows;
 };
 enum XchgKind { kXchgNone = 0, kXchgSync = 1, kXchgPack = 2, kXchgComm = 3, kXchgUnpack = 4 };
 // schedule group variant of an exchange step: kXchgKeyBase + kind * 16 + mode
@@ -173,6 +182,10 @@ constexpr int kXchgKeyBase = 1 << 24;
 constexpr int kMpeDecodeKey = kXchgKeyBase + 4096;
 // ... of the sampling step (BucketSpec::sample): the executor's as well
 constexpr int kSampleKey = kXchgKeyBase + 8192;
+// ... of a gather step of a batch plan (BucketSpec::cond_batch): the executor's, one group per step
+constexpr int kCondBatchKey = kXchgKeyBase + 12288;
+constexpr int kCondMaxRest = 8;     // rest dims of a gather step after merging adjacent ones
+constexpr int kCondMaxEv = 32;      // evidence variables in one scope of a single-op gather
 // byte offset of the degenerate-draw counter in a sampling step's out_table
 inline int64_t sample_counter_offset(int64_t n_vars, int64_t n_samples) { return (n_vars * n_samples + 7) / 8 * 8; }
 
@@ -222,6 +235,7 @@ struct VEPlan {
     std::vector<int> results_slice_bit;
     int64_t arg_bytes = 0;              // plan_mpe: bytes of all arg tables (resident to the traceback)
     int64_t sample_bytes = 0;           // plan_sample: bytes of the sample state x (n_vars * n_samples)
+    int batch_ev_table = -1;            // plan_batch: the evidence table (-1: no gather step)
     int n_xchg = 0;                     // message exchanges (all-to-all / all-gather)
     double xchg_elems = 0;              // entries this rank sends to other ranks
 };
@@ -256,6 +270,27 @@ bool plan_mpe(const std::vector<int> &cards, const std::vector<View> &sources, c
 // variable has more than kMaxOutCard values (x holds one byte per value).
 bool plan_sample(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                  const std::vector<int> &ev_val, int elem_bytes, int64_t n_samples, VEPlan &out, std::string *msg);
+
+// Batched evidence: one plan for `rows` evidence assignments over the evidence
+// variables ev_vars.  `sources` are the NATURAL views of the model's factors.
+// A virtual variable B (id cards.size(), card = rows) stands for "which row":
+// every source that mentions an evidence variable gets one gather step
+// (BucketSpec::cond_batch, level 0) whose table over (the source's other
+// variables, B) takes exactly the place the conditioned view of that source has
+// in the single call's plan; then plan_ve(canonical)'s elimination over `order`
+// with cards_ext = cards + {rows}.  B is never eliminated, so it is the fastest
+// dimension of every message that evidence reaches; messages that no evidence
+// reaches carry no B and are computed once.  No fused chain runs (as the
+// per-target plans of bnpp_marginals): a gathered table is a message, not a
+// source, to the chain matcher, and the unfused buckets perform the same
+// arithmetic in the same order.  target >= 0: kept (never in `order`), the
+// result is a table over (target, B); else over (B); a result that evidence
+// does not reach lacks B.  The evidence table is the last raw table of the
+// plan (VEPlan::batch_ev_table).  Returns false (msg) when a source has more
+// than kCondMaxRest runs of non-evidence variables between evidence variables.
+bool plan_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
+                const std::vector<int> &ev_vars, int64_t rows, int target, int elem_bytes, VEPlan &out,
+                std::string *msg);
 
 // All marginals of `targets` from one two-pass bucket tree over `order`
 // (Shafer-Shenoy on the VE bucket tree; replaces the N independent VEs of

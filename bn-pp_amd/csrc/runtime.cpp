@@ -298,6 +298,13 @@ int launch(Context &ctx, Executable &ex, hipStream_t stream, const XchgHooks *ho
             err = launch_sample_rows(ex.dtype == kF32, ex.d_pool + d.dim_off, ex.d_meta, x, d.n_tiles, ex.sample_first,
                                      ex.sample_seed, cnt, ctx.max_grid, st);
             if (err != hipSuccess) return fail(ctx, err, "launch_sample_rows");
+        } else if (g.variant == kCondBatchKey) {             // a gather step of a batch plan (condbatch.cuh)
+            const BucketDesc &d = sc.descs[g.begin];
+            if (d.in_table[1] < 0) return fail(ctx, hipErrorInvalidValue, "gather step without an evidence table");
+            err = launch_cond_batch(ex.dtype == kF32, ex.d_pool + d.dim_off, sc.pool[d.dim_off + 3], ex.d_meta, d.out_table,
+                                    ex.h_meta[d.out_table].ptr, static_cast<const int32_t *>(ex.h_meta[d.in_table[1]].ptr),
+                                    d.n_tiles, ctx.max_grid, st);
+            if (err != hipSuccess) return fail(ctx, err, "launch_cond_batch");
         } else if (g.variant >= kXchgKeyBase) {
             int rc = run_xchg(ctx, ex, g, st, hooks);
             if (rc) return rc;

@@ -75,6 +75,20 @@ struct SampleSingleArgs {
     unsigned long long *n_degenerate;
 };
 hipError_t launch_sample_single(int is_f32, const SampleSingleArgs &a, int max_grid, hipStream_t stream);
+// batched conditioning (condbatch.cuh): one gather step of a batch plan (pool:
+// the step's words in the dims pool, rest: its rest entries) into table
+// out_table (at out_ptr) for the n_rows rows of ev = int32[.][n_rows]
+hipError_t launch_cond_batch(int is_f32, const int64_t *pool, int64_t rest, TableMeta *meta, int out_table,
+                             const void *out_ptr, const int32_t *ev, int64_t n_rows, int max_grid, hipStream_t stream);
+// ... and one gather with its metadata in the kernel-argument segment (bnpp_condition_batch)
+struct CondBatchSingleArgs {
+    int64_t pool[4 + 3 * kCondMaxEv + 2 * kCondMaxRest];
+    const void *src;
+    void *out;
+    const int32_t *ev;
+    int64_t n_rows;
+};
+hipError_t launch_cond_batch_single(int is_f32, const CondBatchSingleArgs &a, int max_grid, hipStream_t stream);
 // the keys a family's dispatch switch holds (single-op or level launches),
 // appended to `keys`: generated from the X-macro lists of the switches
 // themselves (kernels.cuh, slab.cuh, chain.cuh, chainsplit.cuh), so the two

@@ -100,6 +100,11 @@ _SIGS = {
     "bnpp_plan_groups": (_I, [_P, _I, _I, _IP, _IP, _I, _IP, _I, _I, _I, _I, _LP, _I, _IP]),
     "bnpp_plan_mpe_groups": (_I, [_P, _I, _IP, _IP, _I, _IP, _I, _I, _LP, _I, _IP]),
     "bnpp_plan_sample": (_I, [_P, _I, _IP, _IP, _I, _IP, _I, _I, C.c_int64, _DP, _I, _LP, _I, _IP]),
+    "bnpp_condition_batch": (_I, [_P, _P, _I, _I, _IP, _P, _I, _IP, _I, _IP, C.c_int64, _P, _P]),
+    "bnpp_evidence_load_batch": (_I, [C.c_char_p, _I, C.c_int64, _IP, _IP, _LP, _IP]),
+    "bnpp_partition_batch": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _I, _IP, _I, _I, C.c_int64, _DP, _DP, _DP]),
+    "bnpp_posterior_batch": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _I, _I, _I, C.c_int64, _DP, _DP]),
+    "bnpp_plan_batch": (_I, [_P, _I, _IP, _I, _IP, _I, _I, _I, C.c_int64, _DP, _I, _LP, _I, _IP, _IP, _IP]),
     "bnpp_job_create": (_I, [_P, _P, _I, _I, _IP, _IP, _I, _IP, _I, _I, _IP, _I, C.POINTER(_P)]),
     "bnpp_job_stats": (_I, [_P, _DP, _I]),
     "bnpp_job_launch": (_I, [_P, _P]),
@@ -478,6 +483,97 @@ def sample(ctx: Context, model: Model, n: int, evidence=None, seed: int = 0, fir
     return buf[: model.n_vars].T, lz.value, deg.value
 
 
+COND_BATCH_KEY = (1 << 24) + 12288   # the launch-group key of a gather step (plan.hpp kCondBatchKey)
+PLAN_BATCH_STATS = ("entries", "arena_bytes", "levels", "buckets", "width", "max_table", "bytes_moved", "batches",
+                    "rows_per_launch", "gather_steps")
+
+
+def _ev_rows(ev_vars: Sequence[int], rows):
+    """(n_ev, ev_vars as c ints, n_rows, the rows as a C-contiguous int32 array, its pointer)."""
+    import numpy as np
+    ev_vars = [int(v) for v in ev_vars]
+    a = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, len(ev_vars)) if len(ev_vars)
+                             else np.zeros((len(rows), 0), dtype=np.int64))
+    if a.size and (a.max() > 2 ** 31 - 1 or a.min() < -2 ** 31):
+        raise ValueError("evidence values must fit an int32")
+    a32 = np.ascontiguousarray(a.astype(np.intc))
+    return len(ev_vars), _ints(ev_vars), a32.shape[0], a32, a32.ctypes.data_as(_IP)
+
+
+def load_evidence_batch(path: str):
+    """An .evid file of any number of samples over one variable set
+    (bnpp_evidence_load_batch) -> (ev_vars ascending, rows as an (n, n_ev) numpy int array)."""
+    import numpy as np
+    n_ev, n_rows = C.c_int(), C.c_int64()
+    rc = _lib.bnpp_evidence_load_batch(path.encode(), 0, 0, C.byref(n_ev), None, C.byref(n_rows), None)
+    if rc != OK and not (rc == ERR_INVALID and (n_ev.value > 0 or n_rows.value > 0)):
+        raise BnppError(rc, "bnpp_evidence_load_batch")
+    vs = (C.c_int * max(n_ev.value, 1))()
+    rows = np.zeros((n_rows.value, n_ev.value), dtype=np.intc)
+    _check(_lib.bnpp_evidence_load_batch(path.encode(), n_ev.value, n_rows.value, C.byref(n_ev), vs, C.byref(n_rows),
+                                         rows.ctypes.data_as(_IP)), "bnpp_evidence_load_batch")
+    return [vs[i] for i in range(n_ev.value)], rows
+
+
+def plan_batch(model: Model, ev_vars: Sequence[int], target: Optional[int] = None, heuristic: str = "mf",
+               dtype: int = F64, rows_per_launch: int = 0, order: Optional[Sequence[int]] = None):
+    """Host-only planning of partition_batch (target None) or posterior_batch
+    (bnpp_plan_batch) -> (stats, groups, result_scope): stats a dict of
+    PLAN_BATCH_STATS, groups one dict of PLAN_GROUP_FIELDS per launch group (the
+    gather steps: level 0, key COND_BATCH_KEY), result_scope the result
+    table's variables with the row variable B reported as model.n_vars."""
+    ev_vars = [int(v) for v in ev_vars]
+    oa = _ints(order) if order is not None else None
+    h = ORDER_GIVEN if order is not None else HEURISTICS[heuristic]
+    no = len(order) if order is not None else 0
+    nf = len(PLAN_GROUP_FIELDS)
+    st = (C.c_double * len(PLAN_BATCH_STATS))()
+    cnt, nrs = C.c_int(), C.c_int()
+    rs = (C.c_int * 2)()
+    t = -1 if target is None else int(target)
+    args = (model.handle, len(ev_vars), _ints(ev_vars), h, oa, no, t, dtype, int(rows_per_launch), st, len(PLAN_BATCH_STATS))
+    _check(_lib.bnpp_plan_batch(*args, None, 0, C.byref(cnt), rs, C.byref(nrs)), "bnpp_plan_batch")
+    rows = (C.c_int64 * max(cnt.value * nf, 1))()
+    _check(_lib.bnpp_plan_batch(*args, rows, cnt.value, C.byref(cnt), rs, C.byref(nrs)), "bnpp_plan_batch")
+    return (dict(zip(PLAN_BATCH_STATS, list(st))),
+            [dict(zip(PLAN_GROUP_FIELDS, rows[i * nf:(i + 1) * nf])) for i in range(cnt.value)],
+            [rs[i] for i in range(min(nrs.value, 2))])
+
+
+def partition_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, heuristic: str = "mf", dtype: int = F64,
+                    rows_per_launch: int = 0, order: Optional[Sequence[int]] = None):
+    """log10 Z and Z of every evidence row from one plan (bnpp_partition_batch)
+    -> (log10_z, z, uptime_ms), numpy float64 arrays of length n.  rows: an
+    (n, len(ev_vars)) integer array, rows[r][j] the value of ev_vars[j]."""
+    import numpy as np
+    ne, ev_v, n, keep, ev_x = _ev_rows(ev_vars, rows)
+    oa = _ints(order) if order is not None else None
+    h = ORDER_GIVEN if order is not None else HEURISTICS[heuristic]
+    lz, z = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+    up = C.c_double()
+    _check(_lib.bnpp_partition_batch(ctx.handle, model.handle, ne, ev_v, n, ev_x, h, oa,
+                                     len(order) if order is not None else 0, dtype, int(rows_per_launch),
+                                     lz.ctypes.data_as(_DP), z.ctypes.data_as(_DP), C.byref(up)), "bnpp_partition_batch")
+    del keep
+    return lz[:n], z[:n], up.value
+
+
+def posterior_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, target: int, heuristic: str = "mf",
+                    dtype: int = F64, rows_per_launch: int = 0):
+    """P(target | evidence row) for every row from one plan (bnpp_posterior_batch)
+    -> (an (n, card(target)) numpy float64 array, uptime_ms)."""
+    import numpy as np
+    ne, ev_v, n, keep, ev_x = _ev_rows(ev_vars, rows)
+    t = int(target)
+    k = model.cards[t] if 0 <= t < model.n_vars else 1
+    out = np.zeros((max(n, 1), max(k, 1)))
+    up = C.c_double()
+    _check(_lib.bnpp_posterior_batch(ctx.handle, model.handle, ne, ev_v, n, ev_x, HEURISTICS[heuristic], t, dtype,
+                                     int(rows_per_launch), out.ctypes.data_as(_DP), C.byref(up)), "bnpp_posterior_batch")
+    del keep
+    return out[:n, :k], up.value
+
+
 def marginals(ctx: Context, model: Model, evidence=None, heuristic: str = "mf", dtype: int = F64,
               targets: Optional[Sequence[int]] = None):
     """BN::marginals (model.cpp:303-346) -> ({var: [p_0..p_k-1]}, uptime_ms)."""
@@ -743,6 +839,16 @@ def divide(ctx: Context, dtype: int, cards: Sequence[int], a: int, a_scope: Sequ
     _check(_lib.bnpp_divide(ctx.handle, _P(stream) if stream else None, dtype, len(cards), _ints(cards), _P(a), len(a_scope),
                             _ints(a_scope), _P(b), len(b_scope), _ints(b_scope), _P(out), len(out_vars),
                             _ints(out_vars), _P(out_sum) if out_sum else None), "bnpp_divide")
+
+
+def condition_batch(ctx: Context, dtype: int, cards: Sequence[int], table: int, scope: Sequence[int],
+                    ev_vars: Sequence[int], n_rows: int, ev: int, out: int, stream: Optional[int] = None) -> None:
+    """Batched conditioning on caller-owned device buffers (bnpp_condition_batch):
+    out[rest][b] = table conditioned on evidence row b; ev: a device
+    int32[len(ev_vars)][n_rows], variable-major.  Only enqueues on `stream`."""
+    _check(_lib.bnpp_condition_batch(ctx.handle, _P(stream) if stream else None, dtype, len(cards), _ints(cards), _P(table),
+                                     len(scope), _ints(scope), len(ev_vars), _ints(ev_vars), int(n_rows), _P(ev), _P(out)),
+           "bnpp_condition_batch")
 
 
 def condition(ctx: Context, dtype: int, cards: Sequence[int], table: int, scope: Sequence[int],

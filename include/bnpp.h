@@ -43,7 +43,9 @@ extern "C" {
                               204: chain-run introspection (bnpp_plan_groups, chain keys, bnpp_ctx_set_max_grid);
                               205: MPE (bnpp_mpe, bnpp_bucket_max, bnpp_plan_max_single, bnpp_plan_mpe_groups, job kind 4, kernel family 4);
                               still 205: posterior sampling (bnpp_sample, bnpp_bucket_sample, bnpp_plan_sample) only
-                              adds symbols and shifts no argument of an existing one */
+                              adds symbols and shifts no argument of an existing one; likewise batched evidence
+                              (bnpp_condition_batch, bnpp_partition_batch, bnpp_posterior_batch, bnpp_plan_batch,
+                              bnpp_evidence_load_batch) */
 
 enum bnpp_status {
     BNPP_OK = 0,
@@ -212,6 +214,23 @@ int bnpp_sum_out(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int 
 int bnpp_condition(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, const void *in, int ndims,
                    const int *vars, int n_ev, const int *ev_vars, const int *ev_vals, void *out, double *out_sum);
 
+/* Batched conditioning (no reference counterpart): the conditioning of `in` on
+ * n_rows evidence assignments at once,
+ *   out[rest][b] = in[ sum_j ev[j][b] * stride(ev_vars[j]) + offset(rest) ]
+ * in: a table over vars in its natural layout; rest: its variables that are not
+ * in ev_vars, order preserved, row-major; b, the evidence row, is the fastest
+ * dimension of out (entries(rest) * n_rows elements).  ev: DEVICE
+ * int32[n_ev][n_rows], variable-major.  Evidence variables outside the scope
+ * are ignored, as in bnpp_condition.  The kernel moves values and does no
+ * arithmetic on them.  A value outside its variable's range is clamped into
+ * it (no read leaves `in`); the model-level calls below reject such rows on
+ * the host.  At most 32 evidence variables may lie in the scope, and the
+ * other variables may form at most 8 separate runs between them
+ * (BNPP_ERR_UNSUPPORTED).  Only enqueues on `stream`. */
+int bnpp_condition_batch(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, const void *in,
+                         int ndims, const int *vars, int n_ev, const int *ev_vars, int64_t n_rows,
+                         const int32_t *ev /* device, [n_ev][n_rows] */, void *out);
+
 /* ------------------------------------------------------ models (host) */
 typedef struct bnpp_model bnpp_model;
 
@@ -229,6 +248,16 @@ int bnpp_model_info(const bnpp_model *m, int *is_bayes, int *n_vars, int *n_fact
 int bnpp_model_cards(const bnpp_model *m, int *cards);
 /* read_uai_evidence (io.cpp:157-180): *n pairs (0 unless the first integer is 1) */
 int bnpp_evidence_load(const char *path, int cap, int *n, int *vars, int *vals);
+/* An .evid file of any number of samples: the sample count, then per sample
+ * `k v_1 x_1 ... v_k x_k`.  Every sample must observe the same variable set
+ * (in any order); the variables are sorted per sample.  *n_ev variables into
+ * ev_vars (ascending), *n_rows rows into ev_vals[row][*n_ev] (row-major).  A
+ * sample observing another variable set than the first: BNPP_ERR_UNSUPPORTED
+ * naming that sample.  More variables than cap_vars or samples than cap_rows:
+ * BNPP_ERR_INVALID with *n_ev and *n_rows set (call again with room).
+ * bnpp_evidence_load is unchanged: it reads such a file only when the count is 1. */
+int bnpp_evidence_load_batch(const char *path, int cap_vars, int64_t cap_rows, int *n_ev, int *ev_vars,
+                             int64_t *n_rows, int *ev_vals);
 
 /* Graph::ordering (graph.cpp:41-101) over the graph of the evidence-conditioned
  * factors, as BN::variable_elimination builds it (model.cpp:360-369).
@@ -298,6 +327,60 @@ int bnpp_mpe(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, c
 int bnpp_sample(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, const int *ev_vals, int heuristic,
                 const int *order, int n_order, int dtype, int64_t n_samples, int64_t first_sample, uint64_t seed,
                 uint8_t *out /* host, [n_vars][n_samples] */, double *log10_z, int64_t *n_degenerate, double *uptime_ms);
+
+/* Batched evidence (no reference counterpart): the partition function, or the
+ * posterior of one target, for n_rows evidence assignments over ONE set of
+ * evidence variables ev_vars[n_ev], values ev_vals[n_rows][n_ev] (row-major,
+ * host), from one plan.
+ * Plan: a virtual variable B ("which row", card = R rows per launch) is added.
+ * Every factor that mentions an evidence variable is gathered once per launch
+ * into a table over (its other variables, B) (bnpp_condition_batch's kernel);
+ * that table takes exactly the place the conditioned view of the factor has in
+ * the single call's plan.  The elimination then is the single call's: the
+ * order depends on the evidence VARIABLES only (bnpp_partition's order over the
+ * non-evidence variables; bnpp_marginals' over those but the target), bucket
+ * assignment and chain order are the single call's, the sum kernels run
+ * unchanged with B as the fastest dimension of every message evidence reaches;
+ * a message no evidence reaches carries no B and is computed once per launch.
+ * No fused chain runs (the unfused buckets do the same arithmetic).
+ * Arithmetic: messages are rescaled by exact powers of two per table, so the
+ * scale is shared by the rows of a launch and differs from the single call's;
+ * mantissas do not, as long as nothing goes subnormal.  In fp64 z[b] is
+ * bit-identical to bnpp_partition's z for row b; log10_z[b] = log10(p) + exp2 *
+ * log10(2) may differ from the single call's by the rounding of those three
+ * operations.  Posteriors are normalised per row on the host as bnpp_marginals
+ * does (sequential sum, one division; the scale cancels exactly): fp64
+ * posteriors are bit-identical to bnpp_marginals with targets = {target}.
+ * Z_b == 0: log10_z = -inf, z = 0; the posterior row is what bnpp_marginals
+ * returns for that evidence (0 / 0: NaN in every entry).
+ * Shared scale (a limit): a row whose messages lie more than the dtype's
+ * exponent range below the largest row of the same launch loses bits or
+ * flushes to zero -- 2^-1022 in fp64, out of reach of real models; 2^-126 in
+ * fp32, reachable when a launch mixes a near-certain row with a very unlikely
+ * one (use fp64, or group such rows into calls of their own).
+ * rows_per_launch: 0 = the largest power of two, at most 2^16, whose arena fits
+ * the memory budget (BNPP_MEM_BUDGET_GB, else the device's free memory) -- and
+ * no larger than the smallest power of two that holds n_rows, so that no
+ * launch works mostly on padding; R >= 1 is used as given.  One plan of card(B) = R is launched
+ * ceil(n_rows / R) times, each launch on the next R rows; the last launch is
+ * padded by repeating its last row.  Results do not depend on R (fp64: bit for
+ * bit).  Even R = 1 over the budget: BNPP_ERR_OOM naming both sizes.
+ * BNPP_ERR_INVALID: n_rows < 1; a duplicate or out-of-range evidence variable;
+ * an evidence value outside its variable's range in any row (the message names
+ * the row and the variable; nothing is launched); target out of range or an
+ * evidence variable.  Values are int: no limit on cardinalities.
+ * The planned job stays with the context; the cache key holds the job kind, the
+ * evidence variable set, R and the target but not the values, which are launch
+ * data: a call with other values relaunches the cached job (plan time 0).
+ * order (partition only): explicit order (BNPP_ORDER_GIVEN) or NULL.
+ * bnpp_last_timing covers the whole call (every launch). */
+int bnpp_partition_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                         const int *ev_vals /* [n_rows][n_ev] */, int heuristic, const int *order, int n_order,
+                         int dtype, int64_t rows_per_launch, double *log10_z /* [n_rows] */,
+                         double *z /* [n_rows], may be NULL */, double *uptime_ms);
+int bnpp_posterior_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                         const int *ev_vals /* [n_rows][n_ev] */, int heuristic, int target, int dtype,
+                         int64_t rows_per_launch, double *out /* [n_rows][card(target)] */, double *uptime_ms);
 
 /* BN::marginals (model.cpp:303-346), VE branch: one VE per target with every
  * other variable eliminated, then Factor::normalize (factor.cpp:244-255).  All
@@ -465,6 +548,20 @@ int bnpp_plan_mpe_groups(const bnpp_model *m, int n_ev, const int *ev_vars, cons
 int bnpp_plan_sample(const bnpp_model *m, int n_ev, const int *ev_vars, const int *ev_vals, int heuristic,
                      const int *order, int n_order, int dtype, int64_t n_samples, double *stats, int n_stats,
                      int64_t *rows, int cap_rows, int *n_rows);
+
+/* Host-only planning of bnpp_partition_batch (target < 0) or
+ * bnpp_posterior_batch (target >= 0; order is then ignored): stats[0..8) as
+ * bnpp_job_stats for the plan of one launch, then [8] the rows per launch R
+ * (rows_per_launch, or the automatic choice for 0 under BNPP_MEM_BUDGET_GB or
+ * 64 GB: no device is consulted), [9] the gather steps; rows as
+ * bnpp_plan_groups's.  The gather steps are the groups of level 0, one each,
+ * key 2^24 + 12288; every other key is an ordinary sum-plan key (no chain key).
+ * result_scope (room for 2 ids, may be NULL): the scope of the result table,
+ * slowest first, B reported as the id n_vars -- (B), (target, B), or without B
+ * when no evidence reaches the result. */
+int bnpp_plan_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
+                    int target, int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows,
+                    int cap_rows, int *n_rows, int *result_scope, int *n_result_scope);
 
 /* Host-only planning of one part of bnpp_marginals_tree_part (all variables
  * as targets): owned[v] = 1 when this part computes v's marginal; stats as

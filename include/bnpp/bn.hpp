@@ -148,6 +148,20 @@ public:
                                                    std::unordered_map<std::string, bool> &options, size_t n,
                                                    unsigned long long seed = 0, double *log10_z = nullptr,
                                                    double *uptime = nullptr) const;
+    // EXTENSION beyond the reference's class API: batched evidence
+    // (bnpp_partition_batch / bnpp_posterior_batch).  rows[r][j] is the value
+    // of variable ev_vars[j] in evidence row r; every row observes the same
+    // variables.  partition_batch returns log10 Z per row (z, optional: Z per
+    // row); posterior_batch returns P(target | row r) per row.  In fp64 each
+    // row carries the bits of partition() / marginals() for that evidence.
+    std::vector<double> partition_batch(const std::vector<unsigned> &ev_vars,
+                                        const std::vector<std::vector<unsigned>> &rows,
+                                        std::unordered_map<std::string, bool> &options, std::vector<double> *z = nullptr,
+                                        double *uptime = nullptr) const;
+    std::vector<std::vector<double>> posterior_batch(const std::vector<unsigned> &ev_vars,
+                                                     const std::vector<std::vector<unsigned>> &rows, unsigned target,
+                                                     std::unordered_map<std::string, bool> &options,
+                                                     double *uptime = nullptr) const;
     virtual void write(std::ostream &) const {}
 
 protected:
