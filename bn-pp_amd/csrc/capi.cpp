@@ -1364,7 +1364,11 @@ int run_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, 
                 if (!posterior) {                           // job_results, kind 0
                     double p = 0;
                     p += r[c];
-                    log10_z[row] = p > 0 ? std::log10(p) + (double)exp2[0] * std::log10(2.0) : -INFINITY;
+                    // the table's scale is shared by the rows of a launch, so p * 2^exp2 splits the same Z
+                    // differently at another R: take the logarithm of the split frexp gives, which Z alone decides
+                    int pe = 0;
+                    const double pm = std::frexp(p, &pe);
+                    log10_z[row] = p > 0 ? std::log10(pm) + (double)(exp2[0] + pe) * std::log10(2.0) : -INFINITY;
                     if (z) z[row] = std::ldexp(p, (int)std::max<int64_t>(std::min<int64_t>(exp2[0], 1 << 20), -(1 << 20)));
                 } else if (has_t && k > 0) {                // Factor::normalize (factor.cpp:244-255), as job_results
                     double part = 0;

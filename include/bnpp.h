@@ -348,7 +348,8 @@ int bnpp_sample(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars
  * mantissas do not, as long as nothing goes subnormal.  In fp64 z[b] is
  * bit-identical to bnpp_partition's z for row b; log10_z[b] = log10(p) + exp2 *
  * log10(2) may differ from the single call's by the rounding of those three
- * operations.  Posteriors are normalised per row on the host as bnpp_marginals
+ * operations (it is taken of the split of Z that frexp gives, so it depends on
+ * rows_per_launch no more than z does).  Posteriors are normalised per row on the host as bnpp_marginals
  * does (sequential sum, one division; the scale cancels exactly): fp64
  * posteriors are bit-identical to bnpp_marginals with targets = {target}.
  * Z_b == 0: log10_z = -inf, z = 0; the posterior row is what bnpp_marginals

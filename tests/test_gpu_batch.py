@@ -202,14 +202,22 @@ def test_rows_per_launch_fp64(ctx, R):
     _check_fp64(c, lz, z)
 
 
+def _possible_rows(ctx, c):
+    """The possible rows of a case's set (alarm's uniform rows hit other zero entries too), repeated to 67
+    rows; their single-call fp32 Z values span less than 2^40 (asserted).  Computed once per case."""
+    if "rows32" not in c:
+        good = c["rows"][c["z1"] > 0]
+        assert len(good) >= N_ROWS // 2
+        rows = good[np.arange(N_ROWS) % len(good)]
+        z1 = np.array([bnpp.partition(ctx, c["m"], dict(zip(c["ev_vars"], (int(x) for x in r))), "mf", bnpp.F32)[1] for r in rows])
+        assert (z1 > 0).all() and z1.max() / z1.min() < 2.0 ** 40, (z1.min(), z1.max())
+        c["rows32"] = rows
+    return c["rows32"]
+
+
 def test_rows_per_launch_fp32(ctx):
     c = _case(ctx, "alarm")
-    # the possible rows of the set (alarm's uniform rows hit other zero entries too), repeated to 67 rows
-    good = c["rows"][c["z1"] > 0]
-    assert len(good) >= N_ROWS // 2
-    rows = good[np.arange(N_ROWS) % len(good)]
-    z1 = np.array([bnpp.partition(ctx, c["m"], dict(zip(c["ev_vars"], (int(x) for x in r))), "mf", bnpp.F32)[1] for r in rows])
-    assert (z1 > 0).all() and z1.max() / z1.min() < 2.0 ** 40, (z1.min(), z1.max())
+    rows = _possible_rows(ctx, c)
     ref = None
     for R in (1, 16, 64, 0):
         lz, z, _ = bnpp.partition_batch(ctx, c["m"], c["ev_vars"], rows, dtype=bnpp.F32, rows_per_launch=R)
