@@ -514,6 +514,38 @@ std::vector<std::vector<double>> Model::posterior_batch(const std::vector<unsign
     return out;
 }
 
+std::vector<std::vector<double>> Model::expected_counts(const std::vector<unsigned> &ev_vars,
+                                                        const std::vector<std::vector<unsigned>> &rows,
+                                                        const std::vector<double> &weights,
+                                                        std::unordered_map<std::string, bool> &options,
+                                                        std::vector<double> *log10_z, long long *n_impossible,
+                                                        double *uptime) const {
+    auto t0 = std::chrono::steady_clock::now();
+    ModelGuard g{to_engine(_variables, std::vector<const Factor *>(_factors.begin(), _factors.end()))};
+    const std::vector<int> vars(ev_vars.begin(), ev_vars.end()), flat = flatten_rows(ev_vars, rows);
+    if (!weights.empty() && weights.size() != rows.size()) throw std::runtime_error("expected_counts: one weight per row");
+    int64_t total = 0, n_imp = 0;
+    check(bnpp_counts_size(g.m, &total), "counts_size");
+    std::vector<double> flat_out((size_t)std::max<int64_t>(total, 1), 0.0), lz(rows.size() ? rows.size() : 1, 0.0);
+    double up = 0;
+    int dt = options["fp32"] ? BNPP_F32 : BNPP_F64;
+    check(bnpp_expected_counts(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(),
+                               weights.empty() ? nullptr : weights.data(), heuristic_of(options), nullptr, 0, dt, 0,
+                               flat_out.data(), lz.data(), &n_imp, &up),
+          "expected_counts");
+    std::vector<std::vector<double>> out;
+    size_t at = 0;
+    for (const Factor *f : _factors) {
+        out.emplace_back(flat_out.begin() + at, flat_out.begin() + at + f->size());
+        at += f->size();
+    }
+    lz.resize(rows.size());
+    if (log10_z) *log10_z = lz;
+    if (n_impossible) *n_impossible = n_imp;
+    if (uptime) *uptime = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return out;
+}
+
 std::vector<std::vector<unsigned char>> Model::sample(const std::unordered_map<unsigned, unsigned> &evidence,
                                                       std::unordered_map<std::string, bool> &options, size_t n,
                                                       unsigned long long seed, double *log10_z, double *uptime) const {

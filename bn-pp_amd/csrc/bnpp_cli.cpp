@@ -13,6 +13,10 @@
 // per sample, or P(T | sample); with -uai, <base>.PR ("PR", the sample count,
 // one log10 Z per line) or <base>.MAR ("MAR", the sample count, then per sample
 // "1 card(T) p_0 .. p_{card-1}").
+// -counts (no reference counterpart): the expected sufficient statistics of the
+// evidence file's samples (bnpp_expected_counts); prints the total log10-
+// likelihood of the possible samples and n_impossible; with -uai, <base>.COUNTS
+// ("COUNTS", the factor count, then per factor "size v_0 .. v_{size-1}", %.17g).
 // BAYES files print like `bn` (raw Z), MARKOV files like `mn` (log10 Z).
 // -ve is accepted and, as in the reference, changes nothing here: bn reads it
 // only for REPL queries (bn.cpp:346); partition / marginals always run VE
@@ -42,6 +46,7 @@ int main(int argc, char **argv) {
         else if (p == "-mar") options["marginals"] = true;
         else if (p == "-mpe") options["mpe"] = true;
         else if (p == "-pr-batch") options["partition-batch"] = true;
+        else if (p == "-counts") options["counts"] = true;
         else if (p == "-post-batch" && i + 1 < argc) { options["posterior-batch"] = true; post_target = (unsigned)std::strtoul(argv[++i], nullptr, 10); }
         else if (p == "-sample" && i + 1 < argc) { options["sample"] = true; n_samples = std::strtoull(argv[++i], nullptr, 10); }
         else if (p == "-seed" && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
@@ -58,7 +63,7 @@ int main(int argc, char **argv) {
         else positional.push_back(p);
     }
     if (positional.empty() || options["help"]) {
-        std::cout << "usage: " << argv[0] << " /path/to/model.uai [/path/to/evidence.uai.evid] -pr|-mar|-mar-tree|-mpe|-sample N [-seed S]|-pr-batch|-post-batch T [-sp] [-mf|-wmf|-md] [-f32] [-uai base]" << std::endl;
+        std::cout << "usage: " << argv[0] << " /path/to/model.uai [/path/to/evidence.uai.evid] -pr|-mar|-mar-tree|-mpe|-sample N [-seed S]|-pr-batch|-post-batch T|-counts [-sp] [-mf|-wmf|-md] [-f32] [-uai base]" << std::endl;
         return positional.empty() ? 1 : 0;
     }
     bnpp_model *probe = nullptr;
@@ -160,8 +165,8 @@ int main(int argc, char **argv) {
                 std::fclose(f);
             }
         }
-        if (options["partition-batch"] || options["posterior-batch"]) {
-            if (positional.size() < 2) throw std::runtime_error("-pr-batch / -post-batch need an evidence file");
+        if (options["partition-batch"] || options["posterior-batch"] || options["counts"]) {
+            if (positional.size() < 2) throw std::runtime_error("-pr-batch / -post-batch / -counts need an evidence file");
             int n_ev = 0;
             int64_t n_rows = 0;
             bnpp_evidence_load_batch(positional[1].c_str(), 0, 0, &n_ev, nullptr, &n_rows, nullptr);   // the sizes
@@ -181,6 +186,28 @@ int main(int argc, char **argv) {
                     if (!f) throw std::runtime_error("cannot write " + uai_out + ".PR");
                     std::fprintf(f, "PR\n%zu\n", lz.size());
                     for (double v : lz) std::fprintf(f, "%.17g\n", v);
+                    std::fclose(f);
+                }
+            }
+            if (options["counts"]) {
+                std::vector<double> lz;
+                long long n_impossible = 0;
+                const std::vector<std::vector<double>> counts =
+                    model->expected_counts(vars, rows, {}, options, &lz, &n_impossible, &uptime);
+                double ll = 0;
+                for (double v : lz)
+                    if (std::isfinite(v)) ll += v;
+                std::printf(">> log10-likelihood of %zu evidence rows = %.17g\n>> n_impossible %lld\n", lz.size(), ll, n_impossible);
+                std::cout << ">> Executed in " << uptime << "ms." << std::endl << std::endl;
+                if (!uai_out.empty()) {
+                    FILE *f = std::fopen((uai_out + ".COUNTS").c_str(), "w");
+                    if (!f) throw std::runtime_error("cannot write " + uai_out + ".COUNTS");
+                    std::fprintf(f, "COUNTS\n%zu\n", counts.size());
+                    for (const auto &t : counts) {
+                        std::fprintf(f, "%zu", t.size());
+                        for (double v : t) std::fprintf(f, " %.17g", v);
+                        std::fprintf(f, "\n");
+                    }
                     std::fclose(f);
                 }
             }

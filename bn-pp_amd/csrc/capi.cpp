@@ -1152,7 +1152,8 @@ int batch_check_vars(const ModelData &d, int n_ev, const int *ev_vars, int targe
 // fewer rows: batch_auto_cap) whose arena fits `budget`.
 int plan_batch_schedule(const ModelData &d, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
                         int target, int dtype, int64_t budget, int64_t rows_per_launch, Schedule &out, double *stats,
-                        int64_t &R, int &width, int64_t auto_cap = kBatchAutoRows) {
+                        int64_t &R, int &width, int64_t auto_cap = kBatchAutoRows, bool counts = false,
+                        VEPlan *plan_out = nullptr) {
     const int nv = (int)d.cards.size();
     const int eb = dtype == BNPP_F32 ? 4 : 8;
     if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
@@ -1184,20 +1185,26 @@ int plan_batch_schedule(const ModelData &d, int n_ev, const int *ev_vars, int he
     std::string msg;
     auto need_of = [&](const VEPlan &p) { return sat_add(plan_arena_bytes(p, eb), (int64_t)p.buckets.size() * 512); };
     int64_t need = 0;
+    // counts: the batched bucket tree (plan_counts), every forward message resident through the backward pass
+    auto make = [&](int64_t rows) {
+        return counts ? plan_counts(d.cards, views, ord, evv, rows, eb, plan, &msg)
+                      : plan_batch(d.cards, views, ord, evv, rows, target, eb, plan, &msg);
+    };
     if (rows_per_launch > 0) {
         R = rows_per_launch;
-        if (!plan_batch(d.cards, views, ord, evv, R, target, eb, plan, &msg)) return set_err(BNPP_ERR_UNSUPPORTED, msg);
+        if (!make(R)) return set_err(BNPP_ERR_UNSUPPORTED, msg);
         need = need_of(plan);
     } else {
         for (R = auto_cap; R >= 1; R /= 2) {
-            if (!plan_batch(d.cards, views, ord, evv, R, target, eb, plan, &msg)) return set_err(BNPP_ERR_UNSUPPORTED, msg);
+            if (!make(R)) return set_err(BNPP_ERR_UNSUPPORTED, msg);
             need = need_of(plan);
             if (need <= budget || R == 1) break;
         }
     }
     if (need > budget) {
         char m[256];
-        std::snprintf(m, sizeof m, "batched evidence needs %.6f GB for %lld row%s per launch, budget %.6f GB", need / 1e9,
+        std::snprintf(m, sizeof m, "%s %.6f GB for %lld row%s per launch, budget %.6f GB",
+                      counts ? "expected counts need" : "batched evidence needs", need / 1e9,
                       (long long)R, R == 1 ? "" : "s", budget / 1e9);
         return set_err(BNPP_ERR_OOM, m);
     }
@@ -1217,6 +1224,7 @@ int plan_batch_schedule(const ModelData &d, int n_ev, const int *ev_vars, int he
     stats[7] = 1;
     stats[8] = (double)R;
     stats[9] = (double)n_gather;
+    if (plan_out) *plan_out = std::move(plan);
     return BNPP_OK;
 }
 
@@ -1390,9 +1398,297 @@ int run_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, 
     return BNPP_OK;
 }
 
+// ---- expected counts (bnpp_expected_counts, bnpp_plan_counts) ----
+// job kind 7 (internal): one plan_counts plan of R rows per launch
+constexpr int kKindCounts = 7;
+
+int run_counts(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const int *ev_vals,
+               const double *weights, int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch,
+               double *counts, double *log10_z, int64_t *n_impossible, double *uptime_ms) {
+    const double t0 = now_ms();
+    // the arguments are checked before the context is looked at, as run_batch does
+    if (!m) return set_err(BNPP_ERR_INVALID, "null context or model");
+    const ModelData &d = m->d;
+    if (n_rows < 1) return set_err(BNPP_ERR_INVALID, "n_rows must be at least 1");
+    if (!counts) return set_err(BNPP_ERR_INVALID, "null output");
+    if (int rc = batch_check_vars(d, n_ev, ev_vars, -1, false)) return rc;
+    if (n_ev > 0 && !ev_vals) return set_err(BNPP_ERR_INVALID, "bad evidence arrays");
+    for (int64_t r = 0; r < n_rows; ++r)
+        for (int j = 0; j < n_ev; ++j) {
+            const int x = ev_vals[r * n_ev + j];
+            if (x < 0 || x >= d.cards[ev_vars[j]])
+                return set_err(BNPP_ERR_INVALID, "evidence row " + std::to_string(r) + ": value " + std::to_string(x) +
+                                                     " of variable " + std::to_string(ev_vars[j]) + " is outside [0, " +
+                                                     std::to_string(d.cards[ev_vars[j]]) + ")");
+        }
+    for (int64_t r = 0; weights && r < n_rows; ++r)
+        if (!(weights[r] >= 0) || !std::isfinite(weights[r]))
+            return set_err(BNPP_ERR_INVALID, "evidence row " + std::to_string(r) + ": the weight must be finite and not negative");
+    if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
+    if (!ctx) return set_err(BNPP_ERR_INVALID, "null context or model");
+    int64_t total = 0;
+    for (const auto &v : d.values) total += (int64_t)v.size();
+    bnpp_job *job = nullptr;
+    std::unique_lock<std::mutex> lk(ctx->cache_mu, std::try_to_lock);
+    const bool cache_ok = lk.owns_lock();
+    const int64_t budget = memory_budget(ctx, true);
+    const int64_t auto_cap = batch_auto_cap(n_rows);
+    const uint64_t key = cache_ok ? batch_call_key(m, n_ev, ev_vars, heuristic, order, n_order, -1 - kKindCounts, dtype,
+                                                   rows_per_launch > 0 ? rows_per_launch : -auto_cap) : 0;
+    int rc = oneshot_job(ctx, cache_ok, key, budget, [&](std::unique_ptr<bnpp_job> &j) {
+        j.reset(new bnpp_job);
+        j->ctx = ctx;
+        j->kind = kKindCounts;
+        j->model_uid = m->uid;
+        j->cards = d.cards;
+        if (cache_ok) evict_cached_job(ctx);       // it runs in the arena this job may replace
+        const double tp = now_ms();
+        std::vector<Schedule> batches(1);
+        int width = 0;
+        int rc2 = plan_batch_schedule(d, n_ev, ev_vars, heuristic, order, n_order, -1, dtype, budget, rows_per_launch,
+                                      batches[0], j->stats, j->batch_rows, width, auto_cap, true);
+        if (rc2) return rc2;
+        const double ta = now_ms();
+        rc2 = cached_sources(ctx, m, dtype, j->src);
+        if (rc2) return rc2;
+        const double tb = now_ms();
+        rc2 = from_ctx(ctx, make_program(ctx->c, *j->src, std::move(batches), j->pg, cache_ok));
+        if (rc2) return rc2;
+        g_timing[0] = ta - tp;
+        g_timing[1] = tb - ta;
+        g_timing[2] = now_ms() - tb;
+        g_timing[7] = j->pg.arena_reused ? 1.0 : 0.0;
+        g_timing[8] = j->pg.arena_alloc_ms;
+        return (int)BNPP_OK;
+    }, job);
+    const double t1 = now_ms();
+    double launch_ms = 0, fetch_ms = 0;
+    if (rc == BNPP_OK && (job->pg.parts.size() != 1 || job->batch_rows < 1))
+        rc = set_err(BNPP_ERR_INVALID, "counts job without a plan");
+    void *d_acc = nullptr;
+    size_t acc_cap = 0;
+    if (rc == BNPP_OK) {
+        Executable &ex = job->pg.parts[0];
+        const Schedule &sc = ex.sched;
+        const int64_t R = job->batch_rows, n_launch = (n_rows + R - 1) / R;
+        // the evidence table of the gather steps and the weights table of the accumulate steps
+        int32_t *d_ev = nullptr;
+        double *d_w = nullptr;
+        for (const Schedule::Group &g : sc.groups) {
+            const BucketDesc &bd = sc.descs[g.begin];
+            if (g.variant == kCondBatchKey && bd.in_table[1] >= 0) d_ev = static_cast<int32_t *>(ex.h_meta[bd.in_table[1]].ptr);
+            if (g.variant == kCountsKey && sc.pool[bd.dim_off + 8] >= 0)
+                d_w = static_cast<double *>(ex.h_meta[sc.pool[bd.dim_off + 8]].ptr);
+        }
+        // every launch's rows, variable-major, the last launch padded with its last row, and its
+        // weights; kept to the end of the call (the copies are enqueued)
+        std::vector<int32_t> hev;
+        if (d_ev) {
+            hev.resize((size_t)(n_launch * n_ev * R));
+            for (int64_t L = 0; L < n_launch; ++L)
+                for (int j = 0; j < n_ev; ++j)
+                    for (int64_t b = 0; b < R; ++b)
+                        hev[(size_t)((L * n_ev + j) * R + b)] = ev_vals[std::min(L * R + b, n_rows - 1) * n_ev + j];
+        }
+        std::vector<double> hw((size_t)(n_launch * R), 0.0);
+        for (int64_t r = 0; r < n_rows; ++r) hw[(size_t)r] = weights ? weights[r] : 1.0;
+        const std::vector<int> &rv = sc.plan_result_vars[0];
+        const int Bv = (int)d.cards.size();
+        const bool has_b = std::find(rv.begin(), rv.end(), Bv) != rv.end();
+        const int64_t nb = has_b ? R : 1;
+        if (n_impossible) *n_impossible = 0;
+        hipError_t e = hipSetDevice(ctx->c.device);
+        if (e == hipSuccess) e = get_buffer(ctx->c, (size_t)std::max<int64_t>(total, 1) * sizeof(double), &d_acc, &acc_cap);
+        if (e == hipSuccess) e = hipMemsetAsync(d_acc, 0, (size_t)std::max<int64_t>(total, 1) * sizeof(double), ctx->c.stream);
+        if (e != hipSuccess) rc = set_err(e == hipErrorOutOfMemory ? BNPP_ERR_OOM : BNPP_ERR_HIP,
+                                          std::string("accumulators: ") + hipGetErrorString(e));
+        ex.counts_acc = static_cast<double *>(d_acc);
+        for (int64_t L = 0; L < n_launch && rc == BNPP_OK; ++L) {
+            const double ta = now_ms();
+            if (d_ev) e = hipMemcpyAsync(d_ev, hev.data() + (size_t)(L * n_ev * R), (size_t)(n_ev * R) * sizeof(int32_t),
+                                         hipMemcpyHostToDevice, ctx->c.stream);
+            if (e == hipSuccess && d_w)
+                e = hipMemcpyAsync(d_w, hw.data() + (size_t)(L * R), (size_t)R * sizeof(double), hipMemcpyHostToDevice,
+                                   ctx->c.stream);
+            if (e != hipSuccess) {
+                rc = set_err(BNPP_ERR_HIP, std::string("hipMemcpyAsync(evidence): ") + hipGetErrorString(e));
+                break;
+            }
+            const int64_t rows = std::min(R, n_rows - L * R);
+            ex.counts_rows = rows;
+            rc = from_ctx(ctx, launch_program(ctx->c, job->pg, ctx->c.stream));
+            const double tb = now_ms();
+            launch_ms += tb - ta;
+            if (rc) break;
+            std::vector<std::vector<double>> vals;
+            std::vector<int64_t> exp2;
+            rc = from_ctx(ctx, fetch_program(ctx->c, job->pg, ctx->c.stream, vals, exp2));   // waits for the stream
+            if (rc) break;
+            const std::vector<double> &r = vals[0];
+            if ((int64_t)r.size() != nb) {
+                rc = set_err(BNPP_ERR_INVALID, "counts result table of an unexpected size");
+                break;
+            }
+            for (int64_t b = 0; b < rows; ++b) {            // as run_batch
+                double p = 0;
+                p += r[has_b ? b : 0];
+                int pe = 0;
+                const double pm = std::frexp(p, &pe);
+                if (log10_z) log10_z[L * R + b] = p > 0 ? std::log10(pm) + (double)(exp2[0] + pe) * std::log10(2.0) : -INFINITY;
+                if (n_impossible && !(p > 0)) ++*n_impossible;
+            }
+            fetch_ms += now_ms() - tb;
+        }
+        ex.counts_acc = nullptr;
+        if (rc == BNPP_OK && total > 0) {
+            e = hipMemcpy(counts, d_acc, (size_t)total * sizeof(double), hipMemcpyDeviceToHost);
+            if (e != hipSuccess) rc = set_err(BNPP_ERR_HIP, std::string("hipMemcpy(counts): ") + hipGetErrorString(e));
+        }
+    }
+    if (d_acc) {
+        (void)hipStreamSynchronize(ctx->c.stream);
+        put_buffer(ctx->c, d_acc, acc_cap);
+    }
+    const double t3 = now_ms();
+    oneshot_done(ctx, cache_ok, key, budget, job, rc);
+    record_call_timing(t0, t1, t1 + launch_ms, t3);
+    g_timing[4] = fetch_ms;
+    if (rc) return rc;
+    if (uptime_ms) *uptime_ms = now_ms() - t0;
+    return BNPP_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int bnpp_counts_size(const bnpp_model *m, int64_t *n) {
+    if (!m || !n) return set_err(BNPP_ERR_INVALID, "null argument");
+    *n = 0;
+    for (const auto &v : m->d.values) *n += (int64_t)v.size();
+    return BNPP_OK;
+}
+
+int bnpp_expected_counts(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                         const int *ev_vals, const double *weights, int heuristic, const int *order, int n_order,
+                         int dtype, int64_t rows_per_launch, double *counts, double *log10_z, int64_t *n_impossible,
+                         double *uptime_ms) {
+    BNPP_GUARD_BEGIN
+    return run_counts(ctx, m, n_ev, ev_vars, n_rows, ev_vals, weights, heuristic, order, n_order, dtype, rows_per_launch,
+                      counts, log10_z, n_impossible, uptime_ms);
+    BNPP_GUARD_END
+}
+
+int bnpp_plan_counts(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
+                     int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows, int cap_rows,
+                     int *n_rows, int *belief_off, int *belief_vars, int cap_belief, int *n_belief, int *no_b_elim) {
+    BNPP_GUARD_BEGIN
+    if (!m || !n_rows || (cap_rows > 0 && !rows) || (n_stats > 0 && !stats)) return set_err(BNPP_ERR_INVALID, "null argument");
+    if (int rc = batch_check_vars(m->d, n_ev, ev_vars, -1, false)) return rc;
+    Schedule s;
+    VEPlan plan;
+    double st[12] = {0};
+    int64_t R = 0;
+    int width = 0;
+    int rc = plan_batch_schedule(m->d, n_ev, ev_vars, heuristic, order, n_order, -1, dtype, memory_budget(nullptr),
+                                 rows_per_launch, s, st, R, width, kBatchAutoRows, true, &plan);
+    if (rc) return rc;
+    int64_t n = 0;
+    for (const Schedule::Group &g : s.groups) {
+        if (n < cap_rows) {
+            const int64_t v[BNPP_PLAN_GROUP_FIELDS] = {0, g.level, g.variant, g.end - g.begin, g.vblocks, g.lane};
+            std::copy(v, v + BNPP_PLAN_GROUP_FIELDS, rows + n * BNPP_PLAN_GROUP_FIELDS);
+        }
+        st[10] += g.variant == kCountsKey;
+        ++n;
+    }
+    st[11] = plan.counts_fwd_levels;
+    for (int i = 0; i < n_stats && i < 12; ++i) stats[i] = st[i];
+    *n_rows = (int)n;
+    const int Bv = (int)m->d.cards.size();
+    int nb = 0;
+    for (size_t f = 0; f < plan.counts_belief_vars.size(); ++f) {
+        if (belief_off) belief_off[f] = nb;
+        for (int v : plan.counts_belief_vars[f]) {
+            if (belief_vars && nb < cap_belief) belief_vars[nb] = v;
+            ++nb;
+        }
+    }
+    if (belief_off) belief_off[plan.counts_belief_vars.size()] = nb;
+    if (n_belief) *n_belief = nb;
+    if (no_b_elim) {
+        // B is summed nowhere and enters no composite: a bucket one of whose input TABLES carries B keeps it
+        *no_b_elim = 1;
+        for (const BucketSpec &b : plan.buckets) {
+            if (b.counts || b.cond_batch) continue;
+            bool carries = false;
+            for (const View &v : b.in)
+                if (v.table >= plan.n_src) {
+                    const std::vector<int> &tv = plan.msgs[v.table - plan.n_src].vars;
+                    carries = carries || std::find(tv.begin(), tv.end(), Bv) != tv.end();
+                }
+            if (b.elim_var == Bv || (carries && std::find(b.out_vars.begin(), b.out_vars.end(), Bv) == b.out_vars.end()))
+                *no_b_elim = 0;
+        }
+    }
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+int bnpp_bucket_counts(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, const void *table,
+                       int n_scope, const int *scope, int n_ev, const int *ev_vars, int64_t n_rows, int64_t rows_live,
+                       const int32_t *ev, const double *weights, const void *valid, int has_b, double *acc) {
+    BNPP_GUARD_BEGIN
+    if (!ctx || !cards || !table || !acc || (n_ev > 0 && !ev_vars)) return set_err(BNPP_ERR_INVALID, "null argument");
+    if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "dtype must be BNPP_F64 or BNPP_F32");
+    if (n_cards < 0 || !valid_scope(n_scope, scope, cards, n_cards)) return set_err(BNPP_ERR_INVALID, "bad factor scope");
+    if (n_ev < 0 || !valid_scope(n_ev, ev_vars, cards, n_cards)) return set_err(BNPP_ERR_INVALID, "bad evidence variables");
+    if (n_rows < 1 || n_rows > (int64_t)INT32_MAX) return set_err(BNPP_ERR_INVALID, "n_rows must be in [1, 2^31)");
+    if (rows_live < 0 || rows_live > n_rows) return set_err(BNPP_ERR_INVALID, "rows_live must be in [0, n_rows]");
+    std::vector<int> cv(cards, cards + n_cards);
+    cv.push_back((int)n_rows);                              // the row variable
+    BucketSpec b;
+    b.counts = true;
+    b.counts_scope.assign(scope, scope + n_scope);
+    std::vector<int> tv;
+    bool any_ev = false;
+    for (int j = 0; j < n_scope; ++j) {
+        int row = -1;
+        for (int e = 0; e < n_ev; ++e)
+            if (ev_vars[e] == scope[j]) row = e;
+        b.counts_rows.push_back(row);
+        if (row < 0) tv.push_back(scope[j]);
+        any_ev = any_ev || row >= 0;
+    }
+    if (any_ev && !ev) return set_err(BNPP_ERR_INVALID, "null argument");
+    if (has_b) tv.push_back(n_cards);
+    b.in.push_back(natural_view(0, tv, cv));
+    b.out_vars = {n_cards};
+    b.out_table = 1;
+    b.counts_valid_b = true;
+    BucketDesc d;
+    std::vector<int64_t> pool;
+    std::string msg;
+    if (!build_desc(b, cv, max_vec_for(dtype), d, pool, &msg)) return set_err(BNPP_ERR_UNSUPPORTED, msg);
+    hipError_t e = hipSetDevice(ctx->c.device);
+    const size_t need = (size_t)(n_rows * kCountsScratchPerRow);
+    if (e == hipSuccess && ctx->c.counts_scratch_cap < need) {
+        if (ctx->c.counts_scratch) (void)hipFree(ctx->c.counts_scratch);   // waits for the kernels that use it
+        ctx->c.counts_scratch = nullptr;
+        ctx->c.counts_scratch_cap = 0;
+        e = hipMalloc(&ctx->c.counts_scratch, need);
+        if (e == hipSuccess) ctx->c.counts_scratch_cap = need;
+    }
+    if (e != hipSuccess) return set_err(e == hipErrorOutOfMemory ? BNPP_ERR_OOM : BNPP_ERR_HIP,
+                                        std::string("scratch: ") + hipGetErrorString(e));
+    CountsArgs a;
+    if (!counts_args(pool.data(), n_rows, rows_live, table, ev, weights, valid, acc, ctx->c.counts_scratch, a))
+        return set_err(BNPP_ERR_INVALID, "bad accumulate step");
+    e = launch_counts(dtype == BNPP_F32, a, ctx->c.max_grid, pick_stream(ctx, stream));
+    if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
 
 const char *bnpp_strerror(int status) {
     switch (status) {
@@ -1470,6 +1766,7 @@ int bnpp_ctx_destroy(bnpp_ctx *ctx) {
     }
     if (ctx->c.stream) (void)hipStreamDestroy(ctx->c.stream);
     if (ctx->c.lane_stream) (void)hipStreamDestroy(ctx->c.lane_stream);
+    if (ctx->c.counts_scratch) (void)hipFree(ctx->c.counts_scratch);
     ctx->srcs.clear();
     drop_arena_cache(ctx->c);
     drop_buffer_cache(ctx->c);

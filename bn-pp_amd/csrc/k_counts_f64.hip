@@ -1,0 +1,14 @@
+// Kernel instantiations compiled as a separate translation unit (parallel build).
+// Expected-counts accumulate kernels (counts.cuh).
+#include "counts.cuh"
+
+namespace bnpp {
+
+hipError_t dispatch_counts_f64(const CountsArgs &a, int max_grid, hipStream_t stream) {
+    return go_counts<double>(a, max_grid, stream);
+}
+hipError_t dispatch_counts_list_f64(const CountsArgs *list, int n, int64_t rows_max, int64_t rest_max, int max_grid,
+                                    hipStream_t stream) {
+    return go_counts_list<double>(list, n, rows_max, rest_max, max_grid, stream);
+}
+}  // namespace bnpp

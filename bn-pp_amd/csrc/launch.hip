@@ -43,6 +43,13 @@ hipError_t dispatch_cond_batch_f64(const int64_t *pool, int64_t rest, TableMeta 
 hipError_t dispatch_cond_batch_single_f32(const CondBatchSingleArgs &a, int max_grid, hipStream_t stream);
 hipError_t dispatch_cond_batch_single_f64(const CondBatchSingleArgs &a, int max_grid, hipStream_t stream);
 
+hipError_t dispatch_counts_f32(const CountsArgs &a, int max_grid, hipStream_t stream);
+hipError_t dispatch_counts_f64(const CountsArgs &a, int max_grid, hipStream_t stream);
+hipError_t dispatch_counts_list_f32(const CountsArgs *list, int n, int64_t rows_max, int64_t rest_max, int max_grid,
+                                    hipStream_t stream);
+hipError_t dispatch_counts_list_f64(const CountsArgs *list, int n, int64_t rows_max, int64_t rest_max, int max_grid,
+                                    hipStream_t stream);
+
 hipError_t dispatch_slab_single_f32(int key, const SingleArgs &a, hipStream_t stream);
 hipError_t dispatch_slab_single_f64(int key, const SingleArgs &a, hipStream_t stream);
 hipError_t dispatch_slab_level_f32(int key, const LevelArgs &a, hipStream_t stream);
@@ -128,6 +135,18 @@ hipError_t launch_cond_batch(int is_f32, const int64_t *pool, int64_t rest, Tabl
 hipError_t launch_cond_batch_single(int is_f32, const CondBatchSingleArgs &a, int max_grid, hipStream_t stream) {
     if (a.n_rows <= 0) return hipSuccess;
     return is_f32 ? dispatch_cond_batch_single_f32(a, max_grid, stream) : dispatch_cond_batch_single_f64(a, max_grid, stream);
+}
+
+hipError_t launch_counts(int is_f32, const CountsArgs &a, int max_grid, hipStream_t stream) {
+    if (a.rows_live <= 0 || a.n_rest_entries <= 0) return hipSuccess;
+    return is_f32 ? dispatch_counts_f32(a, max_grid, stream) : dispatch_counts_f64(a, max_grid, stream);
+}
+
+hipError_t launch_counts_list(int is_f32, const CountsArgs *list, int n, int64_t rows_max, int64_t rest_max,
+                              int max_grid, hipStream_t stream) {
+    if (n <= 0 || rows_max <= 0 || rest_max <= 0) return hipSuccess;
+    return is_f32 ? dispatch_counts_list_f32(list, n, rows_max, rest_max, max_grid, stream)
+                  : dispatch_counts_list_f64(list, n, rows_max, rest_max, max_grid, stream);
 }
 
 void kernel_keys(int is_f32, int level, int family, std::vector<int> &keys) {

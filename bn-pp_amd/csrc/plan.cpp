@@ -659,8 +659,91 @@ static bool build_condb_desc(const BucketSpec &b, const std::vector<int> &cards,
     return true;
 }
 
+// An accumulate step of a counts plan: no kernel descriptor, its words in the
+// dims pool, read on the host when the step is launched (runtime.cpp) and by
+// bnpp_bucket_counts.  kCountsPoolHead words:
+//   [0] belief table  [1] n_e  [2] n_rest  [3] rest entries  [4] has B
+//   [5] first accumulator entry  [6] validity table (-1: none)  [7] ... is over (B)
+//   [8] weights table (-1: none)  [9] evidence table (-1: none)  [10] scratch table
+//   [11] keys (product of the evidence cards in the scope)
+//   n_e x (row of ev, stride in the factor, card)    evidence variables in the scope
+//   n_rest x (card, stride in the factor)            the belief's other dims, fastest first
+// k the rest entries, n_tiles the rows.
+static bool build_counts_desc(const BucketSpec &b, const std::vector<int> &cards, BucketDesc &d,
+                              std::vector<int64_t> &pool, std::string *msg) {
+    d = BucketDesc{};
+    d.out_table = b.out_table;
+    d.big = -1;
+    d.dim_off = (int64_t)pool.size();
+    if (b.in.empty() || b.counts_rows.size() != b.counts_scope.size()) {
+        if (msg) *msg = "accumulate step: a belief view and one evidence row per scope variable are needed";
+        return false;
+    }
+    const View &v = b.in[0];
+    const int Bv = b.out_vars.empty() ? -1 : b.out_vars.back();       // the row variable (out_vars = {B})
+    const std::vector<int64_t> fs = natural_strides(b.counts_scope, cards);
+    auto in_scope = [&](int x) {
+        for (size_t j = 0; j < b.counts_scope.size(); ++j)
+            if (b.counts_scope[j] == x) return (int)j;
+        return -1;
+    };
+    const bool has_b = !v.vars.empty() && v.vars.back() == Bv;
+    std::vector<int64_t> words;
+    int n_e = 0, n_rest = 0;
+    int64_t keys = 1, n_r = 1;
+    for (size_t j = 0; j < b.counts_scope.size(); ++j)
+        if (b.counts_rows[j] >= 0) {
+            words.push_back(b.counts_rows[j]);
+            words.push_back(fs[j]);
+            words.push_back(cards[b.counts_scope[j]]);
+            keys = sat_mul(keys, cards[b.counts_scope[j]]);
+            ++n_e;
+        }
+    for (int j = (int)v.vars.size() - (has_b ? 2 : 1); j >= 0; --j) {
+        const int at = in_scope(v.vars[j]);
+        if (at < 0 || b.counts_rows[at] >= 0 || v.vars[j] == Bv) {
+            if (msg) *msg = "accumulate step: the belief's variables must be the scope's non-evidence variables, then B";
+            return false;
+        }
+        words.push_back(cards[v.vars[j]]);
+        words.push_back(fs[at]);
+        n_r = sat_mul(n_r, cards[v.vars[j]]);
+        ++n_rest;
+    }
+    if (n_e + n_rest != (int)b.counts_scope.size() || table_size(v.vars, cards) != sat_mul(n_r, has_b ? cards[Bv] : 1)) {
+        if (msg) *msg = "accumulate step: the belief must cover every non-evidence variable of the scope";
+        return false;
+    }
+    if (n_e > kCountsMaxDims || n_rest > kCountsMaxDims) {
+        if (msg) *msg = "accumulate step: at most " + std::to_string(kCountsMaxDims) +
+                        " evidence variables and as many others in one factor scope";
+        return false;
+    }
+    const int64_t rows = Bv >= 0 ? cards[Bv] : 1;
+    pool.push_back(v.table);
+    pool.push_back(n_e);
+    pool.push_back(n_rest);
+    pool.push_back(n_r);
+    pool.push_back(has_b ? 1 : 0);
+    pool.push_back(b.counts_acc_off);
+    pool.push_back(b.counts_valid_table);
+    pool.push_back(b.counts_valid_b ? 1 : 0);
+    pool.push_back(b.counts_w_table);
+    pool.push_back(b.counts_ev_table);
+    pool.push_back(b.counts_scratch_table);
+    pool.push_back(keys);
+    pool.insert(pool.end(), words.begin(), words.end());
+    d.n_in = 1;
+    d.in_table[0] = v.table;
+    d.out_size = 1;
+    d.k = (int32_t)std::min<int64_t>(n_r, INT32_MAX);
+    d.n_tiles = rows;
+    return true;
+}
+
 bool build_desc(const BucketSpec &b, const std::vector<int> &cards, int max_vec, BucketDesc &d,
                 std::vector<int64_t> &pool, std::string *msg, bool slab_outer) {
+    if (b.counts) return build_counts_desc(b, cards, d, pool, msg);
     if (!b.chain_x.empty()) return build_chain_desc(b, cards, max_vec, d, pool, msg);
     if (b.decode) return build_decode_desc(b, d, pool, msg);
     if (b.sample) return build_sample_desc(b, cards, d, pool, msg);
@@ -1136,6 +1219,7 @@ struct PlanBuilder {
     int free_base = 0;
     int last_level = 0;
     int lane = 0;                           // BucketSpec::lane of the buckets emitted now
+    int floor_level = 0;                    // buckets emitted now run after this level (plan_counts: the forward pass)
 
     PlanBuilder(const std::vector<int> &c, VEPlan &plan, const std::vector<View> &sources,
                 const std::vector<int> &order, bool canon_layout)
@@ -1194,6 +1278,7 @@ struct PlanBuilder {
         b.out_table = new_msg(ov);
         const bool small = free_small && table_size(ov, cards) <= free_max;
         int lv = sequential && !free_level ? (small ? free_base : last_level) : 0;
+        lv = std::max(lv, floor_level);
         for (const View &v : in) lv = std::max(lv, level[v.table]);
         b.level = lv + 1;
         last_level = std::max(last_level, b.level);
@@ -1808,6 +1893,174 @@ bool plan_batch(const std::vector<int> &cards, const std::vector<View> &sources,
         p.result_table = B.emit(result, -1, false);         // canonical: (target, B)
         p.result_vars = p.msgs[p.result_table - p.n_src].vars;
     }
+    B.finish();
+    return true;
+}
+
+bool plan_counts(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
+                 const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg) {
+    out = VEPlan{};
+    VEPlan &p = out;
+    if (rows < 1 || rows > (int64_t)INT32_MAX) {
+        if (msg) *msg = "rows per launch must be in [1, 2^31)";
+        return false;
+    }
+    const int nv = (int)cards.size(), Bv = nv;              // the row variable follows the model's
+    std::vector<int> ce = cards;
+    ce.push_back((int)rows);
+    PlanBuilder B(ce, p, sources, order, true);             // chain_eb stays 0: no fused runs
+    B.n_real = nv;                                          // finish() records cards_ext
+    std::vector<int> row_of(nv, -1);
+    for (size_t i = 0; i < ev_vars.size(); ++i) row_of[ev_vars[i]] = (int)i;
+    auto raw_bytes = [&](int64_t bytes) {
+        const int t = B.new_raw((bytes + elem_bytes - 1) / elem_bytes);
+        B.level[t] = 0;
+        return t;
+    };
+    // level 0: plan_batch's gather steps, in its order
+    std::vector<View> placed;
+    for (const View &s : sources) {
+        bool any = false;
+        for (int v : s.vars) any = any || row_of[v] >= 0;
+        if (!any) {
+            placed.push_back(s);
+            continue;
+        }
+        if (p.batch_ev_table < 0) p.batch_ev_table = raw_bytes(sat_mul(sat_mul((int64_t)ev_vars.size(), rows), 4));
+        BucketSpec g;
+        g.cond_batch = true;
+        g.in.push_back(s);
+        View evt;
+        evt.table = p.batch_ev_table;
+        g.in.push_back(evt);
+        for (int v : s.vars) {
+            g.cond_rows.push_back(row_of[v]);
+            if (row_of[v] < 0) g.out_vars.push_back(v);
+        }
+        g.out_vars.push_back(Bv);
+        {
+            BucketDesc d;
+            std::vector<int64_t> pool;
+            if (!build_desc(g, ce, 1, d, pool, msg)) return false;
+        }
+        g.out_table = B.new_msg(g.out_vars);
+        g.level = 0;
+        B.level[g.out_table] = 0;
+        p.elems_moved += 2.0 * (double)p.msgs[g.out_table - p.n_src].size;
+        p.buckets.push_back(g);
+        placed.push_back(B.view(g.out_table));
+    }
+    // forward (collect) pass: plan_batch's buckets, remembering the tree
+    const int nord = (int)order.size();
+    std::vector<std::vector<View>> src_in(nord);
+    std::vector<std::vector<int>> children(nord);
+    std::vector<int> lam(nord, -1), bucket_of(placed.size(), -1);
+    std::vector<View> result;
+    for (size_t f = 0; f < placed.size(); ++f) {
+        const View &s = placed[f];
+        for (int v : s.vars)
+            if (v != Bv && B.rank[v] < 0) {
+                if (msg) *msg = "the order leaves out variable " + std::to_string(v) + ", which is no evidence variable";
+                return false;
+            }
+        const int bi = B.first_bucket(s.vars, 0);
+        bucket_of[f] = bi;
+        if (bi >= 0) src_in[bi].push_back(s);
+        else result.push_back(s);
+    }
+    auto lam_view = [&](int c) { return B.view(lam[c]); };
+    for (int i = 0; i < nord; ++i) {
+        std::vector<View> in = src_in[i];
+        for (int c : children[i]) in.push_back(lam_view(c));
+        if (in.empty()) continue;
+        lam[i] = B.emit(in, order[i], false);
+        const int par = B.first_bucket(p.msgs[lam[i] - p.n_src].vars, i + 1);
+        if (par >= 0) children[par].push_back(i);
+        else result.push_back(lam_view(i));
+    }
+    if (!result.empty()) {
+        p.result_table = B.emit(result, -1, false);         // over (B), or a scalar
+        p.result_vars = p.msgs[p.result_table - p.n_src].vars;
+    }
+    p.counts_fwd_levels = B.last_level;
+    B.floor_level = B.last_level;                           // the backward pass and the beliefs: levels of their own
+    // what a reduction keeps: `keep` and, when any input carries it, B
+    auto with_b = [&](const std::vector<View> &in, std::vector<int> keep) {
+        for (const View &v : in)
+            if (contains(v.vars, Bv) && !contains(keep, Bv)) keep.push_back(Bv);
+        return keep;
+    };
+    // backward (distribute) pass, parents before children (plan_bucket_tree)
+    std::vector<View> pi(nord);
+    std::vector<char> has_pi(nord, 0);
+    for (int q = nord - 1; q >= 0; --q) {
+        if (lam[q] < 0) continue;
+        for (int i : children[q]) {
+            std::vector<View> in = src_in[q];
+            if (has_pi[q]) in.push_back(pi[q]);
+            for (int c : children[q])
+                if (c != i) in.push_back(lam_view(c));
+            if (in.empty()) continue;                        // constant 1
+            pi[i] = B.view(B.reduce_keep(in, with_b(in, p.msgs[lam[i] - p.n_src].vars)));
+            has_pi[i] = 1;
+        }
+    }
+    // per factor: the belief of its bucket summed down to (scope minus evidence, B), then its accumulate step
+    p.counts_w_table = raw_bytes(sat_mul(rows, 8));
+    const bool valid_b = contains(p.result_vars, Bv);
+    int64_t acc_off = 0;
+    std::vector<BucketSpec> steps;
+    for (size_t f = 0; f < sources.size(); ++f) {
+        const int i = bucket_of[f];
+        View belief = placed[f];                            // no variable left: the factor is its own belief
+        if (i >= 0) {
+            std::vector<View> in = src_in[i];
+            if (has_pi[i]) in.push_back(pi[i]);
+            for (int c : children[i]) in.push_back(lam_view(c));
+            std::vector<int> keep;
+            for (int v : sources[f].vars)
+                if (row_of[v] < 0) keep.push_back(v);
+            belief = B.view(B.reduce_keep(in, with_b(in, keep)));
+        }
+        BucketSpec c;
+        c.counts = true;
+        c.counts_factor = (int)f;
+        c.counts_scope = sources[f].vars;
+        for (int v : sources[f].vars) c.counts_rows.push_back(row_of[v]);
+        c.counts_acc_off = acc_off;
+        acc_off = sat_add(acc_off, table_size(sources[f].vars, cards));
+        c.counts_ev_table = p.batch_ev_table;
+        c.counts_w_table = p.counts_w_table;
+        c.counts_scratch_table = raw_bytes(sat_mul(rows, 24));   // of its own: the steps run in one launch
+        if (p.counts_scratch_table < 0) p.counts_scratch_table = c.counts_scratch_table;
+        c.counts_valid_table = p.result_table;
+        c.counts_valid_b = valid_b;
+        c.in.push_back(belief);
+        for (int t : {c.counts_ev_table, c.counts_w_table, c.counts_scratch_table, c.counts_valid_table})
+            if (t >= 0) {
+                View named;
+                named.table = t;
+                c.in.push_back(named);
+            }
+        c.out_vars = {Bv};
+        {
+            BucketDesc d;
+            std::vector<int64_t> pool;
+            if (!build_desc(c, ce, 1, d, pool, msg)) return false;
+        }
+        c.out_table = B.new_raw(1);
+        p.elems_moved += (double)table_size(belief.vars, ce);
+        steps.push_back(c);
+        p.counts_belief_vars.push_back(belief.vars);
+    }
+    // all accumulate steps share the plan's last level: adjacent in the schedule, they run as one launch
+    const int last = B.last_level + 1;
+    for (BucketSpec &c : steps) {
+        c.level = last;
+        B.level[c.out_table] = last;
+        p.buckets.push_back(c);
+    }
+    B.last_level = last;
     B.finish();
     return true;
 }
@@ -3127,7 +3380,8 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
         Item &it = items[idx];
         BucketSpec b = *it.b;
         b.simple = simplify && lvl_n[it.level] > 1 && b.chain_x.empty() && !b.divide && !b.xchg &&
-                   !b.decode && !b.sample && !b.cond_batch && plans[it.plan]->msgs[b.out_table - s.n_src].size <= simple_max;
+                   !b.decode && !b.sample && !b.cond_batch && !b.counts &&
+                   plans[it.plan]->msgs[b.out_table - s.n_src].size <= simple_max;
         for (View &v : b.in) v.table = remap(it.plan, v.table);
         b.out_table = remap(it.plan, b.out_table);
         if (b.bel_table >= 0) b.bel_table = remap(it.plan, b.bel_table);
@@ -3149,6 +3403,14 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
             it.ok = build_desc(b, plans[it.plan]->cards_ext.empty() ? cards : plans[it.plan]->cards_ext, max_vec, it.d,
                                it.pool, &it.msg);
             it.key = kCondBatchKey;
+            return;
+        }
+        if (b.counts) {                      // an accumulate step of a counts plan: the executor's, its words in the pool
+            for (int *t : {&b.counts_ev_table, &b.counts_w_table, &b.counts_valid_table, &b.counts_scratch_table})
+                if (*t >= 0) *t = remap(it.plan, *t);
+            it.ok = build_desc(b, plans[it.plan]->cards_ext.empty() ? cards : plans[it.plan]->cards_ext, max_vec, it.d,
+                               it.pool, &it.msg);
+            it.key = kCountsKey;
             return;
         }
         if (b.xchg) {                        // an exchange step: the executor's, no kernel descriptor
@@ -3209,7 +3471,8 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
         Schedule::Group g{first.level, first.key, (int)i, 0, 0, 0, first.b->lane};
         int64_t vb = 0;
         for (; i < ord.size() && items[ord[i]].level == g.level && items[ord[i]].key == g.variant &&
-               items[ord[i]].b->lane == g.lane && !(g.variant == kCondBatchKey && (int)i > g.begin);   // one launch per gather step
+               items[ord[i]].b->lane == g.lane &&
+               !((g.variant == kCondBatchKey || g.variant == kCountsKey) && (int)i > g.begin);   // one launch per gather / accumulate step
              ++i) {
             const Item &it = items[ord[i]];
             BucketDesc &d = s.descs[i];

@@ -173,6 +173,21 @@ struct BucketSpec {
     // holds the values of in[0].vars[j] (-1: not an evidence variable)
     bool cond_batch = false;
     std::vector<int> cond_rows;
+    // an accumulate step of a counts plan (plan_counts, counts.cuh): in[0] is
+    // the belief of one factor over (its non-evidence variables, B) -- B the
+    // fastest dim, absent when no evidence reaches the belief -- and the other
+    // inputs name the raw tables below, so that all of them live to this step.
+    // counts_scope is the factor's own scope, counts_rows[j] the row of the
+    // evidence table that holds counts_scope[j] (-1: not an evidence variable),
+    // counts_acc_off the factor's first entry in the accumulator buffer.
+    // out_table is a one-entry placeholder: the step writes the accumulators,
+    // which live outside the arena
+    bool counts = false;
+    int counts_factor = -1;
+    std::vector<int> counts_scope, counts_rows;
+    int64_t counts_acc_off = 0;
+    int counts_ev_table = -1, counts_w_table = -1, counts_valid_table = -1, counts_scratch_table = -1;
+    bool counts_valid_b = false;        // the validity table is over (B) (else one entry)
 };
 enum XchgKind { kXchgNone = 0, kXchgSync = 1, kXchgPack = 2, kXchgComm = 3, kXchgUnpack = 4 };
 // schedule group variant of an exchange step: kXchgKeyBase + kind * 16 + mode
@@ -184,6 +199,10 @@ constexpr int kMpeDecodeKey = kXchgKeyBase + 4096;
 constexpr int kSampleKey = kXchgKeyBase + 8192;
 // ... of a gather step of a batch plan (BucketSpec::cond_batch): the executor's, one group per step
 constexpr int kCondBatchKey = kXchgKeyBase + 12288;
+// ... of an accumulate step of a counts plan (BucketSpec::counts): the executor's, one group per step
+constexpr int kCountsKey = kXchgKeyBase + 16384;
+constexpr int kCountsMaxDims = 32;  // evidence variables, and other variables, in one factor scope of an accumulate step
+constexpr int kCountsPoolHead = 12; // words before the per-variable rows of an accumulate step's pool
 constexpr int kCondMaxRest = 8;     // rest dims of a gather step after merging adjacent ones
 constexpr int kCondMaxEv = 32;      // evidence variables in one scope of a single-op gather
 // byte offset of the degenerate-draw counter in a sampling step's out_table
@@ -236,6 +255,13 @@ struct VEPlan {
     int64_t arg_bytes = 0;              // plan_mpe: bytes of all arg tables (resident to the traceback)
     int64_t sample_bytes = 0;           // plan_sample: bytes of the sample state x (n_vars * n_samples)
     int batch_ev_table = -1;            // plan_batch: the evidence table (-1: no gather step)
+    // plan_counts: the per-launch weights (double[rows]) and the first
+    // accumulate step's scratch (3 x 8 bytes per row; one per step), raw tables; per factor the
+    // variables of its belief table (B = cards.size() last when carried);
+    // the last level of the forward pass (plan_batch's own buckets)
+    int counts_w_table = -1, counts_scratch_table = -1;
+    std::vector<std::vector<int>> counts_belief_vars;
+    int counts_fwd_levels = 0;
     int n_xchg = 0;                     // message exchanges (all-to-all / all-gather)
     double xchg_elems = 0;              // entries this rank sends to other ranks
 };
@@ -291,6 +317,25 @@ bool plan_sample(const std::vector<int> &cards, const std::vector<View> &sources
 bool plan_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                 const std::vector<int> &ev_vars, int64_t rows, int target, int elem_bytes, VEPlan &out,
                 std::string *msg);
+
+// Expected sufficient statistics: a batched bucket tree.  plan_batch's gather
+// steps (level 0) and forward pass -- the same buckets in the same order, the
+// final product of the root messages included: the plan's result is plan_batch's
+// table over (B) -- then plan_bucket_tree's backward pass over cards_ext =
+// cards + {rows}, at levels after the forward pass.  B is never in `order`
+// (rank -1) and is never summed: it is kept by every reduction one of whose
+// inputs carries it, so a pi gains B even where its separator has none, and it
+// enters no composite variable.  For every factor the belief of its bucket is
+// summed down to (scope minus evidence, B) and one BucketSpec::counts step
+// folds it into the factor's accumulator; the steps share the
+// plan's last level and have scratch of their own, so they run in one launch.  A factor with no
+// variable left is its own belief (the gathered table over (B), or the source).
+// No fused chain runs, no checkpointing: every forward message stays resident.
+// Returns false (msg) as plan_batch does, when a factor scope holds more than
+// kCountsMaxDims evidence (or other) variables, or when `order` leaves out a
+// non-evidence variable of a factor.
+bool plan_counts(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
+                 const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg);
 
 // All marginals of `targets` from one two-pass bucket tree over `order`
 // (Shafer-Shenoy on the VE bucket tree; replaces the N independent VEs of

@@ -174,6 +174,15 @@ int make_executable(Context &ctx, const DeviceSources &src, Schedule &&s, Execut
     if (!sc.pool.empty() && (err = hipMemcpy(ex.d_pool, sc.pool.data(), sizeof(int64_t) * sc.pool.size(),
                                              hipMemcpyHostToDevice)) != hipSuccess)
         return fail(ctx, err, "hipMemcpy(pool)");
+    size_t n_counts = 0;
+    for (const Schedule::Group &g : sc.groups) n_counts += g.variant == kCountsKey;
+    if (n_counts) {                                          // the accumulate steps' arguments, staged per launch
+        void *pa = nullptr;
+        if ((err = get_buffer(ctx, sizeof(CountsArgs) * n_counts, &pa, &ex.cap_counts_args)) != hipSuccess)
+            return fail(ctx, err, "hipMalloc(accumulate steps)");
+        ex.d_counts_args = static_cast<CountsArgs *>(pa);
+        ex.h_counts_args.reserve(ex.cap_counts_args / sizeof(CountsArgs));
+    }
     if (sc.n_lanes > 1) {
         if (sc.n_lanes > 2) return fail(ctx, hipErrorInvalidValue, "more than two lanes");
         if (!ctx.lane_stream && (err = hipStreamCreateWithFlags(&ctx.lane_stream, hipStreamNonBlocking)) != hipSuccess)
@@ -220,6 +229,40 @@ int make_executable(Context &ctx, const DeviceSources &src, Schedule &&s, Execut
                 return fail(ctx, err, "hipEventCreate");
     }
     return 0;
+}
+
+bool counts_args(const int64_t *w, int64_t n_rows, int64_t rows_live, const void *table, const int32_t *ev,
+                 const double *weights, const void *valid, double *acc, void *scratch, CountsArgs &a) {
+    std::memset(&a, 0, sizeof a);
+    const int64_t n_e = w[1], n_rest = w[2];
+    if (n_e < 0 || n_e > kCountsMaxDims || n_rest < 0 || n_rest > kCountsMaxDims || !table || !acc || !scratch ||
+        (n_e > 0 && !ev) || rows_live < 0 || rows_live > n_rows)
+        return false;
+    a.table = table;
+    a.ev = ev;
+    a.weights = weights;
+    a.valid = valid;
+    a.acc = acc;
+    a.scratch = scratch;
+    a.n_rows = n_rows;
+    a.rows_live = rows_live;
+    a.n_rest_entries = w[3];
+    a.n_keys = w[11];
+    a.n_e = (int32_t)n_e;
+    a.n_rest = (int32_t)n_rest;
+    a.has_b = (int32_t)w[4];
+    a.valid_b = (int32_t)w[7];
+    const int64_t *e = w + kCountsPoolHead, *r = e + 3 * n_e;
+    for (int j = 0; j < n_e; ++j) {
+        a.e_row[j] = e[3 * j];
+        a.e_stride[j] = e[3 * j + 1];
+        a.e_card[j] = e[3 * j + 2];
+    }
+    for (int j = 0; j < n_rest; ++j) {
+        a.r_card[j] = r[2 * j];
+        a.r_stride[j] = r[2 * j + 1];
+    }
+    return true;
 }
 
 // one exchange step of a sliced run (plan.hpp BucketSpec::xchg, xchg.hip)
@@ -278,6 +321,7 @@ int launch(Context &ctx, Executable &ex, hipStream_t stream, const XchgHooks *ho
                   (err = hipStreamWaitEvent(ls[1], ex.events[0], 0)) != hipSuccess))
         return fail(ctx, err, "lane start");
     const bool reorder = lanes && ex.g_order.size() == sc.groups.size();
+    ex.h_counts_args.clear();                                // the previous launch's copies have been waited for
     for (size_t oi = 0; oi < sc.groups.size(); ++oi) {
         const size_t gi = reorder ? (size_t)ex.g_order[oi] : oi;
         const Schedule::Group &g = sc.groups[gi];
@@ -305,6 +349,33 @@ int launch(Context &ctx, Executable &ex, hipStream_t stream, const XchgHooks *ho
                                     ex.h_meta[d.out_table].ptr, static_cast<const int32_t *>(ex.h_meta[d.in_table[1]].ptr),
                                     d.n_tiles, ctx.max_grid, st);
             if (err != hipSuccess) return fail(ctx, err, "launch_cond_batch");
+        } else if (g.variant == kCountsKey) {                // accumulate steps of a counts plan (counts.cuh)
+            // the consecutive accumulate groups (one step each, scratch of their own) run as ONE launch of each pass
+            if (!ex.counts_acc || !ex.d_counts_args) return fail(ctx, hipErrorInvalidValue, "accumulate step without accumulators");
+            size_t last = oi;
+            while (!reorder && last + 1 < sc.groups.size() && sc.groups[last + 1].variant == kCountsKey &&
+                   last + 1 - oi < (size_t)kCountsListMax)
+                ++last;
+            const size_t n = last - oi + 1, at = ex.h_counts_args.size();
+            if (at + n > ex.cap_counts_args / sizeof(CountsArgs)) return fail(ctx, hipErrorInvalidValue, "accumulate steps beyond the plan's");
+            int64_t rest_max = 0;
+            for (size_t k = oi; k <= last; ++k) {
+                const BucketDesc &d = sc.descs[sc.groups[k].begin];
+                const int64_t *w = sc.pool.data() + d.dim_off;
+                auto ptr = [&](int64_t t) { return t >= 0 ? ex.h_meta[t].ptr : nullptr; };
+                CountsArgs a;
+                if (!counts_args(w, d.n_tiles, ex.counts_rows, ptr(w[0]), static_cast<const int32_t *>(ptr(w[9])),
+                                 static_cast<const double *>(ptr(w[8])), ptr(w[6]), ex.counts_acc + w[5], ptr(w[10]), a))
+                    return fail(ctx, hipErrorInvalidValue, "accumulate step: bad descriptor");
+                rest_max = std::max(rest_max, a.n_rest_entries);
+                ex.h_counts_args.push_back(a);
+            }
+            if ((err = hipMemcpyAsync(ex.d_counts_args + at, ex.h_counts_args.data() + at, n * sizeof(CountsArgs),
+                                      hipMemcpyHostToDevice, st)) != hipSuccess)
+                return fail(ctx, err, "hipMemcpyAsync(accumulate steps)");
+            err = launch_counts_list(ex.dtype == kF32, ex.d_counts_args + at, (int)n, ex.counts_rows, rest_max, ctx.max_grid, st);
+            if (err != hipSuccess) return fail(ctx, err, "launch_counts_list");
+            oi = last;
         } else if (g.variant >= kXchgKeyBase) {
             int rc = run_xchg(ctx, ex, g, st, hooks);
             if (rc) return rc;
@@ -367,6 +438,7 @@ void free_executable(Context &ctx, Executable &ex) {
     put_buffer(ctx, ex.d_desc, ex.cap_desc);
     put_buffer(ctx, ex.d_pool, ex.cap_pool);
     put_buffer(ctx, ex.d_copies, ex.cap_copies);
+    put_buffer(ctx, ex.d_counts_args, ex.cap_counts_args);
     ex = Executable{};
 }
 

@@ -89,6 +89,32 @@ struct CondBatchSingleArgs {
     int64_t n_rows;
 };
 hipError_t launch_cond_batch_single(int is_f32, const CondBatchSingleArgs &a, int max_grid, hipStream_t stream);
+// expected counts (counts.cuh): one factor's belief T over (rest, b) folded
+// into its accumulator, normalised row by row (include/bnpp.h,
+// bnpp_bucket_counts, states the arithmetic).  Everything by value in the
+// kernel-argument segment; scratch holds 3 x 8 bytes per row
+struct CountsArgs {
+    const void *table;                  // T, b fastest (row stride n_rows, or 0 without B)
+    const int32_t *ev;                  // int32[.][n_rows], variable-major (unused when n_e == 0)
+    const double *weights;              // double[n_rows], null: all 1
+    const void *valid;                  // table of the dtype, null: every row valid
+    double *acc;                        // the factor's accumulator, natural layout over its scope
+    void *scratch;
+    int64_t n_rows, rows_live, n_rest_entries, n_keys;
+    int32_t n_e, n_rest, has_b, valid_b;
+    int64_t e_row[kCountsMaxDims], e_stride[kCountsMaxDims], e_card[kCountsMaxDims];   // evidence variables in the scope
+    int64_t r_card[kCountsMaxDims], r_stride[kCountsMaxDims];                           // T's other dims, fastest first
+};
+constexpr int64_t kCountsScratchPerRow = 24;
+// the arguments of one accumulate step from its pool words (plan.cpp
+// build_counts_desc) and its device addresses; false: a malformed descriptor
+bool counts_args(const int64_t *words, int64_t n_rows, int64_t rows_live, const void *table, const int32_t *ev,
+                 const double *weights, const void *valid, double *acc, void *scratch, CountsArgs &a);
+hipError_t launch_counts(int is_f32, const CountsArgs &a, int max_grid, hipStream_t stream);
+// ... and n steps (device array, at most kCountsListMax, scratch of its own each) in one launch of each pass
+constexpr int kCountsListMax = 65535;
+hipError_t launch_counts_list(int is_f32, const CountsArgs *list, int n, int64_t rows_max, int64_t rest_max,
+                              int max_grid, hipStream_t stream);
 // the keys a family's dispatch switch holds (single-op or level launches),
 // appended to `keys`: generated from the X-macro lists of the switches
 // themselves (kernels.cuh, slab.cuh, chain.cuh, chainsplit.cuh), so the two
@@ -153,6 +179,9 @@ struct Context {
     size_t buf_free_bytes = 0;
     // the second lane of two-front schedules (Schedule::n_lanes), made on first use
     hipStream_t lane_stream = nullptr;
+    // scratch of the single-op accumulate step (bnpp_bucket_counts), grown on demand
+    void *counts_scratch = nullptr;
+    size_t counts_scratch_cap = 0;
 };
 
 // a device buffer of at least `bytes` from the context's cache (or hipMalloc);
@@ -205,6 +234,13 @@ struct Executable {
     // a sampling step (kSampleKey) draws with these at the next launch (bnpp_sample sets them per call)
     uint64_t sample_seed = 0;
     int64_t sample_first = 0;
+    // the accumulate steps (kCountsKey) add into counts_acc for the first counts_rows rows of the next launch
+    double *counts_acc = nullptr;
+    int64_t counts_rows = 0;
+    // their arguments: staged here per launch, copied to d_counts_args (one entry per accumulate step)
+    std::vector<CountsArgs> h_counts_args;
+    CountsArgs *d_counts_args = nullptr;
+    size_t cap_counts_args = 0;
 };
 
 // Several schedules (target batches of one MAR job) run back to back in one

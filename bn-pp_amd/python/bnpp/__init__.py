@@ -105,6 +105,10 @@ _SIGS = {
     "bnpp_partition_batch": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _I, _IP, _I, _I, C.c_int64, _DP, _DP, _DP]),
     "bnpp_posterior_batch": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _I, _I, _I, C.c_int64, _DP, _DP]),
     "bnpp_plan_batch": (_I, [_P, _I, _IP, _I, _IP, _I, _I, _I, C.c_int64, _DP, _I, _LP, _I, _IP, _IP, _IP]),
+    "bnpp_counts_size": (_I, [_P, _LP]),
+    "bnpp_expected_counts": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _DP, _I, _IP, _I, _I, C.c_int64, _DP, _DP, _LP, _DP]),
+    "bnpp_plan_counts": (_I, [_P, _I, _IP, _I, _IP, _I, _I, C.c_int64, _DP, _I, _LP, _I, _IP, _IP, _IP, _I, _IP, _IP]),
+    "bnpp_bucket_counts": (_I, [_P, _P, _I, _I, _IP, _P, _I, _IP, _I, _IP, C.c_int64, C.c_int64, _P, _P, _P, _I, _P]),
     "bnpp_job_create": (_I, [_P, _P, _I, _I, _IP, _IP, _I, _IP, _I, _I, _IP, _I, C.POINTER(_P)]),
     "bnpp_job_stats": (_I, [_P, _DP, _I]),
     "bnpp_job_launch": (_I, [_P, _P]),
@@ -574,6 +578,88 @@ def posterior_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, ta
     return out[:n, :k], up.value
 
 
+COUNTS_KEY = (1 << 24) + 16384       # the launch-group key of an accumulate step (plan.hpp kCountsKey)
+PLAN_COUNTS_STATS = PLAN_BATCH_STATS + ("count_steps", "forward_levels")
+
+
+def plan_counts(model: Model, ev_vars: Sequence[int], heuristic: str = "mf", dtype: int = F64,
+                rows_per_launch: int = 0, order: Optional[Sequence[int]] = None):
+    """Host-only planning of expected_counts (bnpp_plan_counts) -> (stats,
+    groups, beliefs, no_b_elim): stats a dict of PLAN_COUNTS_STATS, groups one
+    dict of PLAN_GROUP_FIELDS per launch group (the accumulate steps: key
+    COUNTS_KEY, one group per factor; the groups up to level
+    stats["forward_levels"] are plan_batch's), beliefs per factor the variables
+    of the belief table its accumulate step reads (B reported as model.n_vars),
+    no_b_elim whether no bucket sums B or merges it into a composite."""
+    ev_vars = [int(v) for v in ev_vars]
+    oa = _ints(order) if order is not None else None
+    h = ORDER_GIVEN if order is not None else HEURISTICS[heuristic]
+    no = len(order) if order is not None else 0
+    nf = len(PLAN_GROUP_FIELDS)
+    st = (C.c_double * len(PLAN_COUNTS_STATS))()
+    cnt, nb, flag = C.c_int(), C.c_int(), C.c_int()
+    off = (C.c_int * (model.n_factors + 1))()
+    args = (model.handle, len(ev_vars), _ints(ev_vars), h, oa, no, dtype, int(rows_per_launch), st, len(PLAN_COUNTS_STATS))
+    _check(_lib.bnpp_plan_counts(*args, None, 0, C.byref(cnt), off, None, 0, C.byref(nb), C.byref(flag)), "bnpp_plan_counts")
+    rows = (C.c_int64 * max(cnt.value * nf, 1))()
+    bv = (C.c_int * max(nb.value, 1))()
+    _check(_lib.bnpp_plan_counts(*args, rows, cnt.value, C.byref(cnt), off, bv, nb.value, C.byref(nb), C.byref(flag)),
+           "bnpp_plan_counts")
+    return (dict(zip(PLAN_COUNTS_STATS, list(st))),
+            [dict(zip(PLAN_GROUP_FIELDS, rows[i * nf:(i + 1) * nf])) for i in range(cnt.value)],
+            [[bv[j] for j in range(off[f], off[f + 1])] for f in range(model.n_factors)],
+            bool(flag.value))
+
+
+def expected_counts(ctx: Context, model: Model, ev_vars: Sequence[int], rows, weights=None, heuristic: str = "mf",
+                    dtype: int = F64, rows_per_launch: int = 0, order: Optional[Sequence[int]] = None):
+    """Expected sufficient statistics of the evidence rows (bnpp_expected_counts)
+    -> (counts, log10_z, n_impossible): counts one flat float64 array, the
+    factors in model order, each N_f(x_S) = sum_b w_b P(x_S | row b) in its
+    natural layout over its full scope (split_counts shapes them); log10_z per
+    row as partition_batch's; n_impossible the rows with Z = 0, which count
+    nowhere.  weights: None (all 1) or one finite weight >= 0 per row.  All
+    rows share the evidence variables ev_vars: group rows with different missing
+    patterns by pattern, call once per pattern and add the counts."""
+    import numpy as np
+    ne, ev_v, n, keep, ev_x = _ev_rows(ev_vars, rows)
+    oa = _ints(order) if order is not None else None
+    h = ORDER_GIVEN if order is not None else HEURISTICS[heuristic]
+    total = C.c_int64()
+    _check(_lib.bnpp_counts_size(model.handle, C.byref(total)), "bnpp_counts_size")
+    counts, lz = np.zeros(max(total.value, 1)), np.zeros(max(n, 1))
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w.shape[0] != n:
+            raise ValueError("one weight per row is needed")
+    ni = C.c_int64()
+    up = C.c_double()
+    _check(_lib.bnpp_expected_counts(ctx.handle if ctx is not None else None, model.handle, ne, ev_v, n, ev_x,
+                                     w.ctypes.data_as(_DP) if w is not None else None, h, oa,
+                                     len(order) if order is not None else 0, dtype, int(rows_per_launch),
+                                     counts.ctypes.data_as(_DP), lz.ctypes.data_as(_DP), C.byref(ni), C.byref(up)),
+           "bnpp_expected_counts")
+    del keep
+    return counts[:total.value], lz[:n], ni.value
+
+
+def split_counts(model_dict: dict, counts):
+    """The flat counts of expected_counts as one array per factor, shaped by
+    the cards of the factor's scope (model_dict: cards, scopes)."""
+    import numpy as np
+    counts = np.asarray(counts, dtype=np.float64).reshape(-1)
+    out, at = [], 0
+    for s in model_dict["scopes"]:
+        shape = tuple(model_dict["cards"][v] for v in s)
+        size = int(np.prod(shape, dtype=np.int64)) if shape else 1
+        out.append(counts[at:at + size].reshape(shape))
+        at += size
+    if at != counts.shape[0]:
+        raise ValueError("counts do not match the model's factors")
+    return out
+
+
 def marginals(ctx: Context, model: Model, evidence=None, heuristic: str = "mf", dtype: int = F64,
               targets: Optional[Sequence[int]] = None):
     """BN::marginals (model.cpp:303-346) -> ({var: [p_0..p_k-1]}, uptime_ms)."""
@@ -849,6 +935,21 @@ def condition_batch(ctx: Context, dtype: int, cards: Sequence[int], table: int, 
     _check(_lib.bnpp_condition_batch(ctx.handle, _P(stream) if stream else None, dtype, len(cards), _ints(cards), _P(table),
                                      len(scope), _ints(scope), len(ev_vars), _ints(ev_vars), int(n_rows), _P(ev), _P(out)),
            "bnpp_condition_batch")
+
+
+def bucket_counts(ctx: Context, dtype: int, cards: Sequence[int], table: int, scope: Sequence[int],
+                  ev_vars: Sequence[int], n_rows: int, rows_live: int, ev: int, acc: int, weights: int = 0,
+                  valid: int = 0, has_b: bool = True, stream: Optional[int] = None) -> None:
+    """The accumulate step of expected_counts on caller-owned device buffers
+    (bnpp_bucket_counts): the belief `table` over (scope minus ev_vars, b) is
+    normalised row by row and added, times the row's weight, into `acc`, the
+    factor's float64 table over `scope`.  ev: a device int32[len(ev_vars)][n_rows];
+    weights: a device float64[n_rows] (0: all 1); valid: a device table of
+    n_rows entries of the dtype (0: none).  Only enqueues on `stream`."""
+    _check(_lib.bnpp_bucket_counts(ctx.handle, _P(stream) if stream else None, dtype, len(cards), _ints(cards), _P(table),
+                                   len(scope), _ints(scope), len(ev_vars), _ints(ev_vars), int(n_rows), int(rows_live),
+                                   _P(ev) if ev else None, _P(weights) if weights else None,
+                                   _P(valid) if valid else None, 1 if has_b else 0, _P(acc)), "bnpp_bucket_counts")
 
 
 def condition(ctx: Context, dtype: int, cards: Sequence[int], table: int, scope: Sequence[int],

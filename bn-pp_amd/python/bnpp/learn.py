@@ -1,0 +1,61 @@
+"""Parameter learning on top of expected_counts: the M step of a Bayesian
+network's CPTs and a small EM driver.
+
+All rows of one call share their evidence variables.  Rows with different
+missing patterns are the caller's to group by pattern: counts add, so call
+expected_counts once per pattern, sum the counts and pass the sum to m_step.
+There is no "missing" evidence value.
+"""
+from typing import List, Sequence, Tuple
+
+import numpy as np
+
+from . import F64, Context, Model, expected_counts, split_counts
+
+
+def m_step(model_dict: dict, counts, prior: float = 0.0) -> dict:
+    """New CPTs from expected counts: theta = (N + prior) / sum over the child.
+
+    model_dict is a BAYES model (type, cards, scopes, values): each factor is
+    a CPT whose child is the LAST variable of its scope (the UAI convention).
+    counts is the flat array of expected_counts, or its split_counts.  A
+    parent configuration whose total is zero keeps its old row.  MARKOV models
+    raise ValueError (iterative fitting is out of scope).
+    """
+    if model_dict.get("type") != "BAYES":
+        raise ValueError("m_step fits the CPTs of a BAYES model; Markov networks need iterative fitting")
+    per = counts if isinstance(counts, (list, tuple)) else split_counts(model_dict, counts)
+    if len(per) != len(model_dict["scopes"]):
+        raise ValueError("one count table per factor is needed")
+    values = []
+    for scope, old, n in zip(model_dict["scopes"], model_dict["values"], per):
+        k = model_dict["cards"][scope[-1]] if len(scope) else 1
+        old = np.asarray(old, dtype=np.float64).reshape(-1, k)
+        num = np.asarray(n, dtype=np.float64).reshape(-1, k) + float(prior)
+        tot = num.sum(axis=1, keepdims=True)
+        new = np.where(tot > 0, num / np.where(tot > 0, tot, 1.0), old)
+        values.append(new.reshape(-1).tolist())
+    out = dict(model_dict)
+    out["values"] = values
+    return out
+
+
+def em(ctx: Context, model_dict: dict, ev_vars: Sequence[int], rows, iters: int, weights=None, dtype: int = F64,
+       prior: float = 0.0) -> Tuple[dict, List[float]]:
+    """`iters` EM iterations on the rows -> (the fitted model_dict, the
+    weighted log-likelihood in log10 of the model each iteration started from).
+
+    Every iteration builds a new Model, takes its expected counts (the E step,
+    on the device) and refits the CPTs with m_step.  Impossible rows (Z = 0)
+    count nowhere and are left out of the log-likelihood.  All rows share
+    ev_vars; group rows with different missing patterns by pattern yourself
+    (see the module docstring).
+    """
+    w = None if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+    cur, lls = model_dict, []
+    for _ in range(int(iters)):
+        counts, lz, _ = expected_counts(ctx, Model.from_dict(cur), ev_vars, rows, weights=w, dtype=dtype)
+        ok = np.isfinite(lz)
+        lls.append(float(np.sum((lz if w is None else w * np.where(ok, lz, 0.0))[ok])))
+        cur = m_step(cur, counts, prior)
+    return cur, lls

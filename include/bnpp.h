@@ -45,7 +45,8 @@ extern "C" {
                               still 205: posterior sampling (bnpp_sample, bnpp_bucket_sample, bnpp_plan_sample) only
                               adds symbols and shifts no argument of an existing one; likewise batched evidence
                               (bnpp_condition_batch, bnpp_partition_batch, bnpp_posterior_batch, bnpp_plan_batch,
-                              bnpp_evidence_load_batch) */
+                              bnpp_evidence_load_batch) and expected counts (bnpp_bucket_counts,
+                              bnpp_expected_counts, bnpp_plan_counts) */
 
 enum bnpp_status {
     BNPP_OK = 0,
@@ -383,6 +384,65 @@ int bnpp_posterior_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int
                          const int *ev_vals /* [n_rows][n_ev] */, int heuristic, int target, int dtype,
                          int64_t rows_per_launch, double *out /* [n_rows][card(target)] */, double *uptime_ms);
 
+/* Expected sufficient statistics (no reference counterpart): for every factor f
+ * with scope S_f, N_f(x_S) = sum_b w_b P(x_S | evidence row b) -- what EM's E
+ * step and the gradient of sum_b w_b log Z_b need (N_f = theta_f * d/d theta_f).
+ * Plan: bnpp_partition_batch's plan (gather steps, the same forward buckets in
+ * the same order, the same result table over (B)) continued by the backward
+ * pass of the bucket tree with B kept in every message evidence reaches; for
+ * every factor the belief of its bucket, summed down to (S_f minus evidence, B),
+ * is folded into a persistent fp64 accumulator by the accumulate step below
+ * (all factors' steps in one launch of each of its two passes).
+ * counts: host, sum over factors of the table sizes, factors in model order,
+ * each in its natural layout over its full scope (evidence variables included).
+ * weights: n_rows doubles, NULL = all 1; a negative or non-finite weight is
+ * BNPP_ERR_INVALID naming the row.  log10_z[b] (may be NULL) is computed
+ * exactly as bnpp_partition_batch's; *n_impossible (may be NULL) counts the rows
+ * with Z_b == 0, which contribute to no factor.  Arguments are checked before
+ * the context is looked at.  rows_per_launch and BNPP_ERR_OOM as
+ * bnpp_partition_batch, but every forward message stays resident through the
+ * backward pass (no checkpointing).  The fp64 counts do not depend on
+ * rows_per_launch, bit for bit (the accumulate step's order of additions, below;
+ * the shared-scale limit of bnpp_partition_batch applies: a row whose belief
+ * underflows to zeros beside a much likelier row of its launch is skipped).
+ * Rows with different missing patterns are the caller's to group by pattern:
+ * counts add, so call once per pattern and sum.
+ * The planned job stays with the context, keyed like a batch job (the evidence
+ * variable set, never the values or the weights). */
+int bnpp_counts_size(const bnpp_model *m, int64_t *n /* the doubles bnpp_expected_counts writes */);
+int bnpp_expected_counts(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                         const int *ev_vals /* [n_rows][n_ev] */, const double *weights /* [n_rows] or NULL */,
+                         int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch,
+                         double *counts, double *log10_z /* [n_rows] or NULL */, int64_t *n_impossible,
+                         double *uptime_ms);
+
+/* The accumulate step on caller-owned device buffers (what bnpp_condition_batch
+ * is to the gather kernel): only enqueues on `stream`, adds into acc (the
+ * caller zeroes it).  table: the belief T over (scope minus the evidence
+ * variables, in scope order, then b), b fastest, n_rows = R rows; has_b = 0: T
+ * has no b dimension and is read with row stride 0.  ev: device
+ * int32[n_ev][R], variable-major; weights: device double[R] or NULL (all 1);
+ * valid: device table of the dtype, R entries, or NULL; acc: device double[],
+ * the factor's natural layout over scope[n_scope].
+ * Contract -- all arithmetic in fp64 on values converted from T, every
+ * operation rounded once, no contraction, in this order:
+ *   c[b] = sum over rest, ascending linear rest index, sequentially from 0.0,
+ *          of (double)T[rest][b];
+ *   row b is skipped when b >= rows_live, w[b] == 0, c[b] == 0 or NaN, or
+ *          valid[b] == 0;
+ *   else   acc[offset(rest, evidence values of row b)] += w[b] * ((double)T[rest][b] / c[b]);
+ *   the contributions to one entry are added in ascending row order, one at a
+ *   time, continuing from the entry's value in acc.
+ * Hence the result depends on neither the grid (bnpp_ctx_set_max_grid) nor R
+ * nor how rows split over calls; a belief's scale cancels in t / c.  An
+ * evidence value is clamped into its variable's range.  At most 32 evidence
+ * variables and 32 others in the scope.  The step keeps 24 bytes per row of
+ * scratch with the context: calls that share a context must be ordered on one
+ * stream. */
+int bnpp_bucket_counts(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, const void *table,
+                       int n_scope, const int *scope, int n_ev, const int *ev_vars, int64_t n_rows, int64_t rows_live,
+                       const int32_t *ev, const double *weights, const void *valid, int has_b, double *acc);
+
 /* BN::marginals (model.cpp:303-346), VE branch: one VE per target with every
  * other variable eliminated, then Factor::normalize (factor.cpp:244-255).  All
  * targets run as one batched device schedule.  targets NULL: all variables.
@@ -563,6 +623,19 @@ int bnpp_plan_sample(const bnpp_model *m, int n_ev, const int *ev_vars, const in
 int bnpp_plan_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
                     int target, int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows,
                     int cap_rows, int *n_rows, int *result_scope, int *n_result_scope);
+
+/* Host-only planning of bnpp_expected_counts, modelled on bnpp_plan_batch:
+ * stats[0..10) as bnpp_plan_batch's, then [10] the accumulate steps (one per
+ * factor, key 2^24 + 16384, one group each) and [11] the last level of the
+ * forward pass -- the groups up to that level are bnpp_plan_batch's for the
+ * same arguments; rows as bnpp_plan_groups's.  belief_off[n_factors + 1] and
+ * belief_vars[cap_belief] (may be NULL): per factor the variables of the
+ * belief table its accumulate step reads, slowest first, B reported as the id
+ * n_vars; *n_belief the ids in all.  no_b_elim (may be NULL): 1 when no bucket
+ * of the plan sums B or holds it inside a composite variable. */
+int bnpp_plan_counts(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
+                     int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows, int cap_rows,
+                     int *n_rows, int *belief_off, int *belief_vars, int cap_belief, int *n_belief, int *no_b_elim);
 
 /* Host-only planning of one part of bnpp_marginals_tree_part (all variables
  * as targets): owned[v] = 1 when this part computes v's marginal; stats as

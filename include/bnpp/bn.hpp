@@ -162,6 +162,18 @@ public:
                                                      const std::vector<std::vector<unsigned>> &rows, unsigned target,
                                                      std::unordered_map<std::string, bool> &options,
                                                      double *uptime = nullptr) const;
+    // EXTENSION: expected sufficient statistics (bnpp_expected_counts).  Per
+    // factor, in model order, N_f(x_S) = sum_r w_r P(x_S | row r) in the
+    // factor's own layout over its whole scope; weights empty: all 1.
+    // log10_z (optional) per row; n_impossible (optional) the rows with Z = 0,
+    // which count nowhere.  Every row observes the same variables: group rows
+    // with different missing patterns by pattern and add the counts.
+    std::vector<std::vector<double>> expected_counts(const std::vector<unsigned> &ev_vars,
+                                                     const std::vector<std::vector<unsigned>> &rows,
+                                                     const std::vector<double> &weights,
+                                                     std::unordered_map<std::string, bool> &options,
+                                                     std::vector<double> *log10_z = nullptr,
+                                                     long long *n_impossible = nullptr, double *uptime = nullptr) const;
     virtual void write(std::ostream &) const {}
 
 protected:
