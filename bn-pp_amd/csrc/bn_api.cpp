@@ -493,6 +493,29 @@ std::vector<double> Model::partition_batch(const std::vector<unsigned> &ev_vars,
     return lz;
 }
 
+std::vector<std::vector<unsigned>> Model::mpe_batch(const std::vector<unsigned> &ev_vars,
+                                                    const std::vector<std::vector<unsigned>> &rows,
+                                                    std::unordered_map<std::string, bool> &options,
+                                                    std::vector<double> *log10_value, double *uptime) const {
+    auto t0 = std::chrono::steady_clock::now();
+    ModelGuard g{to_engine(_variables, std::vector<const Factor *>(_factors.begin(), _factors.end()))};
+    const std::vector<int> vars(ev_vars.begin(), ev_vars.end()), flat = flatten_rows(ev_vars, rows);
+    const size_t nv = _variables.size();
+    std::vector<double> lv(rows.size() ? rows.size() : 1, 0.0);
+    std::vector<int> x(std::max<size_t>(rows.size() * nv, 1), 0);
+    double up = 0;
+    int dt = options["fp32"] ? BNPP_F32 : BNPP_F64;
+    check(bnpp_mpe_batch(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(),
+                         heuristic_of(options), nullptr, 0, dt, 0, lv.data(), x.data(), &up),
+          "mpe_batch");
+    lv.resize(rows.size());
+    if (log10_value) *log10_value = lv;
+    std::vector<std::vector<unsigned>> out(rows.size());
+    for (size_t r = 0; r < rows.size(); ++r) out[r].assign(x.begin() + r * nv, x.begin() + (r + 1) * nv);
+    if (uptime) *uptime = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return out;
+}
+
 std::vector<std::vector<double>> Model::posterior_batch(const std::vector<unsigned> &ev_vars,
                                                         const std::vector<std::vector<unsigned>> &rows, unsigned target,
                                                         std::unordered_map<std::string, bool> &options,

@@ -13,6 +13,9 @@
 // per sample, or P(T | sample); with -uai, <base>.PR ("PR", the sample count,
 // one log10 Z per line) or <base>.MAR ("MAR", the sample count, then per sample
 // "1 card(T) p_0 .. p_{card-1}").
+// -mpe-batch (no reference counterpart): the most probable completion of every
+// sample of the evidence file (bnpp_mpe_batch), one line per sample; with -uai,
+// <base>.MPE ("MPE", the sample count, then per sample "N x_0 .. x_{N-1}").
 // -counts (no reference counterpart): the expected sufficient statistics of the
 // evidence file's samples (bnpp_expected_counts); prints the total log10-
 // likelihood of the possible samples and n_impossible; with -uai, <base>.COUNTS
@@ -46,6 +49,7 @@ int main(int argc, char **argv) {
         else if (p == "-mar") options["marginals"] = true;
         else if (p == "-mpe") options["mpe"] = true;
         else if (p == "-pr-batch") options["partition-batch"] = true;
+        else if (p == "-mpe-batch") options["mpe-batch"] = true;
         else if (p == "-counts") options["counts"] = true;
         else if (p == "-post-batch" && i + 1 < argc) { options["posterior-batch"] = true; post_target = (unsigned)std::strtoul(argv[++i], nullptr, 10); }
         else if (p == "-sample" && i + 1 < argc) { options["sample"] = true; n_samples = std::strtoull(argv[++i], nullptr, 10); }
@@ -63,7 +67,7 @@ int main(int argc, char **argv) {
         else positional.push_back(p);
     }
     if (positional.empty() || options["help"]) {
-        std::cout << "usage: " << argv[0] << " /path/to/model.uai [/path/to/evidence.uai.evid] -pr|-mar|-mar-tree|-mpe|-sample N [-seed S]|-pr-batch|-post-batch T|-counts [-sp] [-mf|-wmf|-md] [-f32] [-uai base]" << std::endl;
+        std::cout << "usage: " << argv[0] << " /path/to/model.uai [/path/to/evidence.uai.evid] -pr|-mar|-mar-tree|-mpe|-sample N [-seed S]|-pr-batch|-post-batch T|-mpe-batch|-counts [-sp] [-mf|-wmf|-md] [-f32] [-uai base]" << std::endl;
         return positional.empty() ? 1 : 0;
     }
     bnpp_model *probe = nullptr;
@@ -165,8 +169,9 @@ int main(int argc, char **argv) {
                 std::fclose(f);
             }
         }
-        if (options["partition-batch"] || options["posterior-batch"] || options["counts"]) {
-            if (positional.size() < 2) throw std::runtime_error("-pr-batch / -post-batch / -counts need an evidence file");
+        if (options["partition-batch"] || options["posterior-batch"] || options["counts"] || options["mpe-batch"]) {
+            if (positional.size() < 2)
+                throw std::runtime_error("-pr-batch / -post-batch / -mpe-batch / -counts need an evidence file");
             int n_ev = 0;
             int64_t n_rows = 0;
             bnpp_evidence_load_batch(positional[1].c_str(), 0, 0, &n_ev, nullptr, &n_rows, nullptr);   // the sizes
@@ -186,6 +191,27 @@ int main(int argc, char **argv) {
                     if (!f) throw std::runtime_error("cannot write " + uai_out + ".PR");
                     std::fprintf(f, "PR\n%zu\n", lz.size());
                     for (double v : lz) std::fprintf(f, "%.17g\n", v);
+                    std::fclose(f);
+                }
+            }
+            if (options["mpe-batch"]) {
+                std::vector<double> lv;
+                const std::vector<std::vector<unsigned>> xs = model->mpe_batch(vars, rows, options, &lv, &uptime);
+                for (size_t r = 0; r < xs.size(); ++r) {
+                    std::cout << ">> MPE row " << r << " log10 value = " << lv[r] << " assignment:";
+                    for (unsigned v : xs[r]) std::cout << " " << v;
+                    std::cout << std::endl;
+                }
+                std::cout << ">> Executed in " << uptime << "ms." << std::endl << std::endl;
+                if (!uai_out.empty()) {
+                    FILE *f = std::fopen((uai_out + ".MPE").c_str(), "w");
+                    if (!f) throw std::runtime_error("cannot write " + uai_out + ".MPE");
+                    std::fprintf(f, "MPE\n%zu\n", xs.size());
+                    for (const auto &x : xs) {
+                        std::fprintf(f, "%zu", x.size());
+                        for (unsigned v : x) std::fprintf(f, " %u", v);
+                        std::fprintf(f, "\n");
+                    }
                     std::fclose(f);
                 }
             }

@@ -1146,14 +1146,18 @@ int batch_check_vars(const ModelData &d, int n_ev, const int *ev_vars, int targe
     return BNPP_OK;
 }
 
+// what plan_batch_schedule plans: plan_batch, plan_counts (the batched bucket tree) or plan_mpe_batch
+enum BatchMode { kBatchSum = 0, kBatchCounts = 1, kBatchMpe = 2 };
+
 // Plan one launch: the elimination order the single call uses for this
 // evidence variable set, then plan_batch for R rows.  rows_per_launch 0: the
 // largest power of two <= auto_cap (kBatchAutoRows, or less for a call of
 // fewer rows: batch_auto_cap) whose arena fits `budget`.
 int plan_batch_schedule(const ModelData &d, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
                         int target, int dtype, int64_t budget, int64_t rows_per_launch, Schedule &out, double *stats,
-                        int64_t &R, int &width, int64_t auto_cap = kBatchAutoRows, bool counts = false,
+                        int64_t &R, int &width, int64_t auto_cap = kBatchAutoRows, int mode = kBatchSum,
                         VEPlan *plan_out = nullptr) {
+    const bool counts = mode == kBatchCounts, mpe = mode == kBatchMpe;
     const int nv = (int)d.cards.size();
     const int eb = dtype == BNPP_F32 ? 4 : 8;
     if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
@@ -1172,6 +1176,10 @@ int plan_batch_schedule(const ModelData &d, int n_ev, const int *ev_vars, int he
             seen[v] = 1;
             if (ev[v] < 0) vars.push_back(v);
         }
+        if (mpe)                                            // as build_plans, kind 4
+            for (int v = 0; v < nv; ++v)
+                if (!seen[v] && ev[v] < 0)
+                    return set_err(BNPP_ERR_INVALID, "explicit order must cover every non-evidence variable");
         ord = vars;
         width = order_width(nv, scopes, ord);
     } else {                                                // kind 0 / kind 1 (every variable but the target)
@@ -1188,6 +1196,7 @@ int plan_batch_schedule(const ModelData &d, int n_ev, const int *ev_vars, int he
     // counts: the batched bucket tree (plan_counts), every forward message resident through the backward pass
     auto make = [&](int64_t rows) {
         return counts ? plan_counts(d.cards, views, ord, evv, rows, eb, plan, &msg)
+               : mpe  ? plan_mpe_batch(d.cards, views, ord, evv, rows, eb, plan, &msg)
                       : plan_batch(d.cards, views, ord, evv, rows, target, eb, plan, &msg);
     };
     if (rows_per_launch > 0) {
@@ -1200,6 +1209,15 @@ int plan_batch_schedule(const ModelData &d, int n_ev, const int *ev_vars, int he
             need = need_of(plan);
             if (need <= budget || R == 1) break;
         }
+    }
+    if (need > budget && mpe) {
+        // every arg table stays resident until the traceback (no checkpointing)
+        char m[320];
+        std::snprintf(m, sizeof m, "batched MPE needs %.6f GB (messages %lld bytes + arg tables %lld bytes, all resident "
+                      "until the traceback) for %lld row%s per launch, budget %.6f GB", need / 1e9,
+                      (long long)std::max<int64_t>(need - plan.arg_bytes, 0), (long long)plan.arg_bytes, (long long)R,
+                      R == 1 ? "" : "s", budget / 1e9);
+        return set_err(BNPP_ERR_OOM, m);
     }
     if (need > budget) {
         char m[256];
@@ -1398,6 +1416,192 @@ int run_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, 
     return BNPP_OK;
 }
 
+// ---- batched MPE (bnpp_mpe_batch, bnpp_plan_mpe_batch) ----
+// job kind 8 (internal): one plan_mpe_batch plan of R rows per launch
+constexpr int kKindMpeBatch = 8;
+
+// the arguments of a batched call, checked before the context is looked at (run_batch's checks and messages)
+int batch_check_rows(const ModelData &d, int n_ev, const int *ev_vars, int64_t n_rows, const int *ev_vals) {
+    if (n_rows < 1) return set_err(BNPP_ERR_INVALID, "n_rows must be at least 1");
+    if (int rc = batch_check_vars(d, n_ev, ev_vars, -1, false)) return rc;
+    if (n_ev > 0 && !ev_vals) return set_err(BNPP_ERR_INVALID, "bad evidence arrays");
+    for (int64_t r = 0; r < n_rows; ++r)
+        for (int j = 0; j < n_ev; ++j) {
+            const int x = ev_vals[r * n_ev + j];
+            if (x < 0 || x >= d.cards[ev_vars[j]])
+                return set_err(BNPP_ERR_INVALID, "evidence row " + std::to_string(r) + ": value " + std::to_string(x) +
+                                                     " of variable " + std::to_string(ev_vars[j]) + " is outside [0, " +
+                                                     std::to_string(d.cards[ev_vars[j]]) + ")");
+        }
+    return BNPP_OK;
+}
+
+int run_mpe_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const int *ev_vals,
+                  int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch, double *log10_value,
+                  int *assignment, double *uptime_ms) {
+    const double t0 = now_ms();
+    if (!m) return set_err(BNPP_ERR_INVALID, "null context or model");
+    const ModelData &d = m->d;
+    if (int rc = batch_check_rows(d, n_ev, ev_vars, n_rows, ev_vals)) return rc;
+    if (!log10_value && !assignment) return set_err(BNPP_ERR_INVALID, "null output");
+    if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
+    if (!ctx) {                                            // no context can exist without a device: say which it is
+        int c = 0;
+        if (hipGetDeviceCount(&c) != hipSuccess || c <= 0)
+            return set_err(BNPP_ERR_NO_DEVICE, "no HIP device visible (the engine has no CPU fallback)");
+        return set_err(BNPP_ERR_INVALID, "null context or model");
+    }
+    const int64_t nv = (int64_t)d.cards.size();
+    bnpp_job *job = nullptr;
+    std::unique_lock<std::mutex> lk(ctx->cache_mu, std::try_to_lock);
+    const bool cache_ok = lk.owns_lock();
+    const int64_t budget = memory_budget(ctx, true);
+    const int64_t auto_cap = batch_auto_cap(n_rows);
+    // keyed like a batch job (the evidence variable set and R, never the values) under a kind of its own
+    uint64_t key = cache_ok ? batch_call_key(m, n_ev, ev_vars, heuristic, order, n_order, -1, dtype,
+                                             rows_per_launch > 0 ? rows_per_launch : -auto_cap) : 0;
+    if (key) {
+        key = (key ^ (uint64_t)kKindMpeBatch) * 1099511628211ull;
+        key = key ? key : 1;
+    }
+    int rc = oneshot_job(ctx, cache_ok, key, budget, [&](std::unique_ptr<bnpp_job> &j) {
+        j.reset(new bnpp_job);
+        j->ctx = ctx;
+        j->kind = kKindMpeBatch;
+        j->model_uid = m->uid;
+        j->cards = d.cards;
+        if (cache_ok) evict_cached_job(ctx);       // it runs in the arena this job may replace
+        const double tp = now_ms();
+        std::vector<Schedule> batches(1);
+        int width = 0;
+        int rc2 = plan_batch_schedule(d, n_ev, ev_vars, heuristic, order, n_order, -1, dtype, budget, rows_per_launch,
+                                      batches[0], j->stats, j->batch_rows, width, auto_cap, kBatchMpe);
+        if (rc2) return rc2;
+        const double ta = now_ms();
+        rc2 = cached_sources(ctx, m, dtype, j->src);
+        if (rc2) return rc2;
+        const double tb = now_ms();
+        rc2 = from_ctx(ctx, make_program(ctx->c, *j->src, std::move(batches), j->pg, cache_ok));
+        if (rc2) return rc2;
+        g_timing[0] = ta - tp;
+        g_timing[1] = tb - ta;
+        g_timing[2] = now_ms() - tb;
+        g_timing[7] = j->pg.arena_reused ? 1.0 : 0.0;
+        g_timing[8] = j->pg.arena_alloc_ms;
+        return (int)BNPP_OK;
+    }, job);
+    const double t1 = now_ms();
+    double launch_ms = 0, fetch_ms = 0;
+    const BucketDesc *dd = nullptr;
+    if (rc == BNPP_OK) {
+        const Program &pg = job->pg;
+        if (pg.parts.size() == 1 && job->batch_rows >= 1 && !pg.parts[0].sched.groups.empty() &&
+            pg.parts[0].sched.groups.back().variant == kMpeDecodeBatchKey && pg.res_off.size() == 1 &&
+            pg.res_off[0].size() == 2 && pg.res_off[0][1] >= 0)
+            dd = &pg.parts[0].sched.descs[pg.parts[0].sched.groups.back().begin];
+        else
+            rc = set_err(BNPP_ERR_INVALID, "batched MPE job without a traceback step");
+    }
+    if (rc == BNPP_OK) {
+        Program &pg = job->pg;
+        Executable &ex = pg.parts[0];
+        const Schedule &sc = ex.sched;
+        const int64_t R = job->batch_rows, n_launch = (n_rows + R - 1) / R;
+        const int64_t eb = dtype == BNPP_F32 ? 4 : 8;
+        int32_t *d_ev = nullptr;
+        for (const Schedule::Group &g : sc.groups)
+            if (g.variant == kCondBatchKey && sc.descs[g.begin].in_table[1] >= 0)
+                d_ev = static_cast<int32_t *>(ex.h_meta[sc.descs[g.begin].in_table[1]].ptr);
+        // every launch's rows, variable-major, the last launch padded with its last row;
+        // kept to the end of the call (the copies are enqueued)
+        std::vector<int32_t> hev;
+        if (d_ev) {
+            hev.resize((size_t)(n_launch * n_ev * R));
+            for (int64_t L = 0; L < n_launch; ++L)
+                for (int j = 0; j < n_ev; ++j)
+                    for (int64_t b = 0; b < R; ++b)
+                        hev[(size_t)((L * n_ev + j) * R + b)] = ev_vals[std::min(L * R + b, n_rows - 1) * n_ev + j];
+        }
+        // the variables the traceback writes (the rest: evidence values, 0 for a variable in no factor)
+        std::vector<char> decoded((size_t)nv, 0);
+        {
+            const int64_t *w = sc.pool.data() + dd->dim_off;
+            const int64_t *row = w + kDecodeBatchPoolHead;
+            for (int64_t r = 0; r < w[1]; ++r) {
+                decoded[(size_t)row[1]] = 1;
+                row += 4 + 2 * row[3];
+            }
+        }
+        std::vector<int> ev_col((size_t)nv, -1);
+        for (int j = 0; j < n_ev; ++j) ev_col[(size_t)ev_vars[j]] = j;
+        const int rt = sc.plan_result_table[0];
+        const std::vector<int> &rv = sc.plan_result_vars[0];
+        const bool has_b = std::find(rv.begin(), rv.end(), (int)nv) != rv.end();
+        const int64_t nb = rt < 0 ? 1 : pg.res_size[0][0];
+        if (nb != (has_b ? R : 1)) rc = set_err(BNPP_ERR_INVALID, "batched MPE result table of an unexpected size");
+        std::vector<unsigned char> raw((size_t)std::max<int64_t>(pg.results_bytes, 1));
+        hipError_t e = hipSetDevice(ctx->c.device);
+        if (e != hipSuccess) rc = set_err(BNPP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+        for (int64_t L = 0; L < n_launch && rc == BNPP_OK; ++L) {
+            const double ta = now_ms();
+            if (d_ev) {
+                e = hipMemcpyAsync(d_ev, hev.data() + (size_t)(L * n_ev * R), (size_t)(n_ev * R) * sizeof(int32_t),
+                                   hipMemcpyHostToDevice, ctx->c.stream);
+                if (e != hipSuccess) {
+                    rc = set_err(BNPP_ERR_HIP, std::string("hipMemcpyAsync(evidence): ") + hipGetErrorString(e));
+                    break;
+                }
+            }
+            rc = from_ctx(ctx, launch_program(ctx->c, pg, ctx->c.stream));
+            const double tb = now_ms();
+            launch_ms += tb - ta;
+            if (rc) break;
+            // the maxima table and x in one copy of the results buffer, and the maxima table's scale
+            TableMeta tm{};
+            if ((e = hipStreamSynchronize(ctx->c.stream)) != hipSuccess ||
+                (e = hipMemcpy(raw.data(), pg.results, (size_t)pg.results_bytes, hipMemcpyDeviceToHost)) != hipSuccess ||
+                (rt >= 0 && (e = hipMemcpy(&tm, ex.d_meta + rt, sizeof tm, hipMemcpyDeviceToHost)) != hipSuccess)) {
+                rc = set_err(BNPP_ERR_HIP, std::string("batched MPE fetch: ") + hipGetErrorString(e));
+                break;
+            }
+            const unsigned char *vals = rt >= 0 ? raw.data() + pg.res_off[0][0] : nullptr;
+            const uint8_t *x = raw.data() + pg.res_off[0][1];
+            const int64_t rows = std::min(R, n_rows - L * R);
+            for (int64_t b = 0; b < rows; ++b) {
+                const int64_t row = L * R + b, c = has_b ? b : 0;
+                if (log10_value) {
+                    double p = 1.0;                             // no factor at all: the empty product
+                    if (vals && eb == 4) {
+                        float f;
+                        std::memcpy(&f, vals + c * 4, 4);
+                        p = f;
+                    } else if (vals) {
+                        std::memcpy(&p, vals + c * 8, 8);
+                    }
+                    // as run_batch: the launch's rows share the table's scale, so take the logarithm of the
+                    // split frexp gives, which the maximum alone decides
+                    int pe = 0;
+                    const double pm = std::frexp(p, &pe);
+                    log10_value[row] = p > 0 ? std::log10(pm) + (double)(tm.exp2 + pe) * std::log10(2.0) : -INFINITY;
+                }
+                if (assignment)
+                    for (int64_t v = 0; v < nv; ++v)
+                        assignment[row * nv + v] = decoded[(size_t)v]        ? (int)x[v * R + b]
+                                                   : ev_col[(size_t)v] >= 0 ? ev_vals[row * n_ev + ev_col[(size_t)v]]
+                                                                            : 0;
+            }
+            fetch_ms += now_ms() - tb;
+        }
+    }
+    const double t3 = now_ms();
+    oneshot_done(ctx, cache_ok, key, budget, job, rc);
+    record_call_timing(t0, t1, t1 + launch_ms, t3);
+    g_timing[4] = fetch_ms;
+    if (rc) return rc;
+    if (uptime_ms) *uptime_ms = now_ms() - t0;
+    return BNPP_OK;
+}
+
 // ---- expected counts (bnpp_expected_counts, bnpp_plan_counts) ----
 // job kind 7 (internal): one plan_counts plan of R rows per launch
 constexpr int kKindCounts = 7;
@@ -1446,7 +1650,7 @@ int run_counts(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars,
         std::vector<Schedule> batches(1);
         int width = 0;
         int rc2 = plan_batch_schedule(d, n_ev, ev_vars, heuristic, order, n_order, -1, dtype, budget, rows_per_launch,
-                                      batches[0], j->stats, j->batch_rows, width, auto_cap, true);
+                                      batches[0], j->stats, j->batch_rows, width, auto_cap, kBatchCounts);
         if (rc2) return rc2;
         const double ta = now_ms();
         rc2 = cached_sources(ctx, m, dtype, j->src);
@@ -1591,7 +1795,7 @@ int bnpp_plan_counts(const bnpp_model *m, int n_ev, const int *ev_vars, int heur
     int64_t R = 0;
     int width = 0;
     int rc = plan_batch_schedule(m->d, n_ev, ev_vars, heuristic, order, n_order, -1, dtype, memory_budget(nullptr),
-                                 rows_per_launch, s, st, R, width, kBatchAutoRows, true, &plan);
+                                 rows_per_launch, s, st, R, width, kBatchAutoRows, kBatchCounts, &plan);
     if (rc) return rc;
     int64_t n = 0;
     for (const Schedule::Group &g : s.groups) {
@@ -2689,6 +2893,49 @@ int bnpp_posterior_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int
     BNPP_GUARD_BEGIN
     return run_batch(ctx, m, n_ev, ev_vars, n_rows, ev_vals, heuristic, nullptr, 0, target, true, dtype, rows_per_launch,
                      nullptr, nullptr, out, uptime_ms);
+    BNPP_GUARD_END
+}
+
+int bnpp_mpe_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const int *ev_vals,
+                   int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch, double *log10_value,
+                   int *assignment, double *uptime_ms) {
+    BNPP_GUARD_BEGIN
+    return run_mpe_batch(ctx, m, n_ev, ev_vars, n_rows, ev_vals, heuristic, order, n_order, dtype, rows_per_launch,
+                         log10_value, assignment, uptime_ms);
+    BNPP_GUARD_END
+}
+
+int bnpp_plan_mpe_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
+                        int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows, int cap_rows,
+                        int *n_rows) {
+    BNPP_GUARD_BEGIN
+    if (!m || !n_rows || (cap_rows > 0 && !rows) || (n_stats > 0 && !stats)) return set_err(BNPP_ERR_INVALID, "null argument");
+    if (int rc = batch_check_vars(m->d, n_ev, ev_vars, -1, false)) return rc;
+    Schedule s;
+    VEPlan plan;
+    double st[BNPP_PLAN_MPE_BATCH_STATS] = {0};
+    int64_t R = 0;
+    int width = 0;
+    int rc = plan_batch_schedule(m->d, n_ev, ev_vars, heuristic, order, n_order, -1, dtype, memory_budget(nullptr),
+                                 rows_per_launch, s, st, R, width, kBatchAutoRows, kBatchMpe, &plan);
+    if (rc) return rc;
+    st[10] = (double)plan.arg_bytes;
+    st[11] = plan.n_max_buckets;
+    st[12] = plan.n_arg_b;
+    st[13] = plan.n_arg_nob;
+    st[14] = (double)plan.arg_b_entries;
+    st[15] = (double)plan.arg_nob_entries;
+    for (int i = 0; i < n_stats && i < BNPP_PLAN_MPE_BATCH_STATS; ++i) stats[i] = st[i];
+    int64_t n = 0;
+    for (const Schedule::Group &g : s.groups) {
+        if (n < cap_rows) {
+            const int64_t v[BNPP_PLAN_GROUP_FIELDS] = {0, g.level, g.variant, g.end - g.begin, g.vblocks, g.lane};
+            std::copy(v, v + BNPP_PLAN_GROUP_FIELDS, rows + n * BNPP_PLAN_GROUP_FIELDS);
+        }
+        ++n;
+    }
+    *n_rows = (int)n;
+    return BNPP_OK;
     BNPP_GUARD_END
 }
 

@@ -551,6 +551,55 @@ static bool build_decode_desc(const BucketSpec &b, BucketDesc &d, std::vector<in
     return true;
 }
 
+// The traceback step of a batched MPE plan: no kernel descriptor, its rows in
+// the dims pool (the layout mpe_decode_batch_kernel reads, maxbatch.cuh):
+//   [0] n_vars  [1] n_rows  [2] R  [3] 0
+//   per row: arg table, eliminated variable, carries B (0 / 1), n, n x (variable, stride)
+// the pairs are the bucket's separator without B (B's stride is 1 where carried).
+// d.k rows, d.out_size variables, d.n_tiles = R.  cards: the plan's (B last).
+static bool build_decode_batch_desc(const BucketSpec &b, const std::vector<int> &cards, BucketDesc &d,
+                                    std::vector<int64_t> &pool, std::string *msg) {
+    d = BucketDesc{};
+    d.out_table = b.out_table;
+    d.big = -1;
+    d.dim_off = (int64_t)pool.size();
+    const int Bv = (int)cards.size() - 1, n_vars = Bv;
+    if (Bv < 0 || b.decode_batch_rows < 1 || cards[Bv] != b.decode_batch_rows) {
+        if (msg) *msg = "batched traceback: the plan's last variable must be the row variable";
+        return false;
+    }
+    pool.push_back(n_vars);
+    pool.push_back((int64_t)b.decode_rows.size());
+    pool.push_back(b.decode_batch_rows);
+    pool.push_back(0);
+    std::vector<char> done(n_vars, 0);
+    for (const BucketSpec::DecodeRow &row : b.decode_rows) {
+        const bool has_b = !row.vars.empty() && row.vars.back() == Bv;
+        const size_t n = row.vars.size() - (has_b ? 1 : 0);
+        bool ok = row.vars.size() == row.strides.size() && row.elim_var >= 0 && row.elim_var < n_vars &&
+                  cards[row.elim_var] <= kMaxOutCard && (!has_b || row.strides.back() == 1);
+        // a separator variable is one an earlier row decoded: a lane reads only what it wrote
+        for (size_t j = 0; ok && j < n; ++j) ok = row.vars[j] >= 0 && row.vars[j] < n_vars && done[row.vars[j]];
+        if (!ok) {
+            if (msg) *msg = "batched traceback: a row must follow the rows that decode its separator, B last with stride 1";
+            return false;
+        }
+        done[row.elim_var] = 1;
+        pool.push_back(row.arg_table);
+        pool.push_back(row.elim_var);
+        pool.push_back(has_b ? 1 : 0);
+        pool.push_back((int64_t)n);
+        for (size_t j = 0; j < n; ++j) {
+            pool.push_back(row.vars[j]);
+            pool.push_back(row.strides[j]);
+        }
+    }
+    d.k = (int32_t)b.decode_rows.size();
+    d.out_size = n_vars;
+    d.n_tiles = b.decode_batch_rows;
+    return true;
+}
+
 // The sampling step of a sampling plan: no kernel descriptor, its rows in the
 // dims pool (the layout sample_rows reads, sample.cuh).  d.k rows, d.out_size
 // variables, d.n_tiles samples.
@@ -746,6 +795,7 @@ bool build_desc(const BucketSpec &b, const std::vector<int> &cards, int max_vec,
     if (b.counts) return build_counts_desc(b, cards, d, pool, msg);
     if (!b.chain_x.empty()) return build_chain_desc(b, cards, max_vec, d, pool, msg);
     if (b.decode) return build_decode_desc(b, d, pool, msg);
+    if (b.decode_batch) return build_decode_batch_desc(b, cards, d, pool, msg);
     if (b.sample) return build_sample_desc(b, cards, d, pool, msg);
     if (b.cond_batch) return build_condb_desc(b, cards, d, pool, msg);
     const int n = (int)b.in.size();
@@ -1819,25 +1869,15 @@ bool plan_sample(const std::vector<int> &cards, const std::vector<View> &sources
     return true;
 }
 
-bool plan_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
-                const std::vector<int> &ev_vars, int64_t rows, int target, int elem_bytes, VEPlan &out,
-                std::string *msg) {
-    out = VEPlan{};
-    VEPlan &p = out;
-    if (rows < 1 || rows > (int64_t)INT32_MAX) {
-        if (msg) *msg = "rows per launch must be in [1, 2^31)";
-        return false;
-    }
-    const int nv = (int)cards.size(), Bv = nv;              // the row variable follows the model's
-    std::vector<int> ce = cards;
-    ce.push_back((int)rows);
-    PlanBuilder B(ce, p, sources, order, true);             // chain_eb stays 0: no fused runs
-    B.n_real = nv;                                          // finish() records cards_ext
+// level 0 of a batch plan: one gather step per source that mentions an
+// evidence variable (`placed`: per source, the view that takes its place);
+// ce: the model's cards, then the rows
+static bool gather_steps(PlanBuilder &B, VEPlan &p, const std::vector<int> &ce, const std::vector<View> &sources,
+                         const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, std::vector<View> &placed,
+                         std::string *msg) {
+    const int nv = (int)ce.size() - 1, Bv = nv;
     std::vector<int> row_of(nv, -1);
     for (size_t i = 0; i < ev_vars.size(); ++i) row_of[ev_vars[i]] = (int)i;
-    (void)target;                                           // kept: it is not in `order`, canon() lays it before B
-    // level 0: one gather step per source that mentions an evidence variable
-    std::vector<View> placed;
     for (const View &s : sources) {
         bool any = false;
         for (int v : s.vars) any = any || row_of[v] >= 0;
@@ -1873,6 +1913,26 @@ bool plan_batch(const std::vector<int> &cards, const std::vector<View> &sources,
         p.buckets.push_back(g);
         placed.push_back(B.view(g.out_table));
     }
+    return true;
+}
+
+bool plan_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
+                const std::vector<int> &ev_vars, int64_t rows, int target, int elem_bytes, VEPlan &out,
+                std::string *msg) {
+    out = VEPlan{};
+    VEPlan &p = out;
+    if (rows < 1 || rows > (int64_t)INT32_MAX) {
+        if (msg) *msg = "rows per launch must be in [1, 2^31)";
+        return false;
+    }
+    const int nv = (int)cards.size();
+    std::vector<int> ce = cards;
+    ce.push_back((int)rows);                                // the row variable follows the model's
+    PlanBuilder B(ce, p, sources, order, true);             // chain_eb stays 0: no fused runs
+    B.n_real = nv;                                          // finish() records cards_ext
+    (void)target;                                           // kept: it is not in `order`, canon() lays it before B
+    std::vector<View> placed;
+    if (!gather_steps(B, p, ce, sources, ev_vars, rows, elem_bytes, placed, msg)) return false;
     const int nord = (int)order.size();
     std::vector<std::vector<View>> buckets(nord);
     std::vector<View> result;
@@ -1893,6 +1953,94 @@ bool plan_batch(const std::vector<int> &cards, const std::vector<View> &sources,
         p.result_table = B.emit(result, -1, false);         // canonical: (target, B)
         p.result_vars = p.msgs[p.result_table - p.n_src].vars;
     }
+    B.finish();
+    return true;
+}
+
+bool plan_mpe_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
+                    const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg) {
+    out = VEPlan{};
+    VEPlan &p = out;
+    if (rows < 1 || rows > (int64_t)INT32_MAX) {
+        if (msg) *msg = "rows per launch must be in [1, 2^31)";
+        return false;
+    }
+    const int nv = (int)cards.size(), Bv = nv;
+    std::vector<int> ce = cards;
+    ce.push_back((int)rows);
+    PlanBuilder B(ce, p, sources, order, true);             // chain_eb stays 0: no fused runs
+    B.n_real = nv;
+    std::vector<View> placed;
+    if (!gather_steps(B, p, ce, sources, ev_vars, rows, elem_bytes, placed, msg)) return false;
+    const int nord = (int)order.size();
+    std::vector<std::vector<View>> buckets(nord);
+    std::vector<View> result;
+    for (const View &s : placed) {
+        int bi = B.first_bucket(s.vars, 0);
+        if (bi >= 0) buckets[bi].push_back(s);
+        else result.push_back(s);
+    }
+    std::vector<BucketSpec::DecodeRow> drows;
+    for (int i = 0; i < nord; ++i) {
+        if (buckets[i].empty()) continue;   // a variable in no remaining factor: the assignment keeps 0
+        if (cards[order[i]] > kMaxOutCard) {
+            if (msg) *msg = "MPE: variable " + std::to_string(order[i]) + " has " + std::to_string(cards[order[i]]) +
+                            " values; the arg tables hold one byte per entry (at most " + std::to_string(kMaxOutCard) + ")";
+            return false;
+        }
+        const int t = B.emit(buckets[i], order[i], false);
+        BucketSpec &bk = p.buckets.back();              // the eliminating bucket (prefix products precede it)
+        const int64_t entries = p.msgs[t - p.n_src].size;
+        bk.max_out = true;
+        bk.arg_table = B.new_raw((entries + elem_bytes - 1) / elem_bytes);   // bytes, in whole elements
+        B.level[bk.arg_table] = bk.level;
+        p.arg_bytes = sat_add(p.arg_bytes, entries);
+        ++p.n_max_buckets;
+        if (!bk.out_vars.empty() && bk.out_vars.back() == Bv) {
+            ++p.n_arg_b;
+            p.arg_b_entries = sat_add(p.arg_b_entries, entries / rows);
+        } else {
+            ++p.n_arg_nob;
+            p.arg_nob_entries = sat_add(p.arg_nob_entries, entries);
+        }
+        BucketSpec::DecodeRow row;
+        row.arg_table = bk.arg_table;
+        row.elim_var = order[i];
+        row.depth = 0;
+        row.vars = bk.out_vars;
+        row.strides = natural_strides(bk.out_vars, ce);
+        drows.push_back(row);
+        View mv = B.view(t);
+        int bi = B.first_bucket(mv.vars, i + 1);
+        if (bi >= 0) buckets[bi].push_back(mv);
+        else result.push_back(mv);
+    }
+    if (!result.empty()) {
+        p.result_table = B.emit(result, -1, false);         // canonical: (B), or a scalar
+        p.result_vars = p.msgs[p.result_table - p.n_src].vars;
+    }
+    BucketSpec dec;
+    dec.decode_batch = true;
+    dec.decode_batch_rows = rows;
+    dec.decode_rows.assign(drows.rbegin(), drows.rend());   // roots first
+    for (const BucketSpec::DecodeRow &r : dec.decode_rows) {
+        View v;
+        v.table = r.arg_table;
+        dec.in.push_back(v);
+    }
+    if (p.batch_ev_table >= 0) {
+        View v;
+        v.table = p.batch_ev_table;
+        dec.in.push_back(v);
+    }
+    const int64_t xbytes = std::max<int64_t>(sat_mul((int64_t)nv, rows), 8);
+    dec.out_table = B.new_raw((xbytes + elem_bytes - 1) / elem_bytes);
+    dec.level = B.last_level + 1;
+    B.last_level = dec.level;
+    B.level[dec.out_table] = dec.level;
+    p.buckets.push_back(dec);
+    p.results = {p.result_table, dec.out_table};
+    p.results_vars = {p.result_vars, {}};
     B.finish();
     return true;
 }
@@ -3107,7 +3255,8 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
                 mix((uint64_t)(uint32_t)b.elim_var);
                 mix((uint64_t)b.level);
                 mix((uint64_t)(b.xchg * 16 + b.xchg_mode));
-                mix((b.divide ? 1 : 0) + (b.max_out ? 2 : 0) + (b.decode ? 4 : 0) + (b.sample ? 8 : 0) + (b.cond_batch ? 16 : 0));
+                mix((b.divide ? 1 : 0) + (b.max_out ? 2 : 0) + (b.decode ? 4 : 0) + (b.sample ? 8 : 0) + (b.cond_batch ? 16 : 0) +
+                    (b.decode_batch ? 32 : 0));
                 mix(b.out_vars.size());
                 for (int v : b.out_vars) mix((uint64_t)v);
                 mix(b.chain_x.size() * 131 + b.chain_n.size() * 7 + (uint64_t)b.chain_gmask);
@@ -3380,7 +3529,7 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
         Item &it = items[idx];
         BucketSpec b = *it.b;
         b.simple = simplify && lvl_n[it.level] > 1 && b.chain_x.empty() && !b.divide && !b.xchg &&
-                   !b.decode && !b.sample && !b.cond_batch && !b.counts &&
+                   !b.decode && !b.decode_batch && !b.sample && !b.cond_batch && !b.counts &&
                    plans[it.plan]->msgs[b.out_table - s.n_src].size <= simple_max;
         for (View &v : b.in) v.table = remap(it.plan, v.table);
         b.out_table = remap(it.plan, b.out_table);
@@ -3390,6 +3539,13 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
             for (BucketSpec::DecodeRow &r : b.decode_rows) r.arg_table = remap(it.plan, r.arg_table);
             it.ok = build_desc(b, cards, max_vec, it.d, it.pool, &it.msg);
             it.key = kMpeDecodeKey;
+            return;
+        }
+        if (b.decode_batch) {                // the batched MPE traceback: the executor's, its rows in the pool
+            for (BucketSpec::DecodeRow &r : b.decode_rows) r.arg_table = remap(it.plan, r.arg_table);
+            it.ok = build_desc(b, plans[it.plan]->cards_ext.empty() ? cards : plans[it.plan]->cards_ext, max_vec, it.d,
+                               it.pool, &it.msg);
+            it.key = kMpeDecodeBatchKey;
             return;
         }
         if (b.sample) {                      // the sampling step: the executor's, its rows in the pool

@@ -182,6 +182,15 @@ struct BucketSpec {
     // counts_acc_off the factor's first entry in the accumulator buffer.
     // out_table is a one-entry placeholder: the step writes the accumulators,
     // which live outside the arena
+    // the traceback that ends a batched MPE plan (plan_mpe_batch, maxbatch.cuh):
+    // decode_rows in REVERSE elimination order (a bucket after the buckets that
+    // maximise its separator), each row's vars the bucket's output scope -- the
+    // row variable B last where the arg table carries it; `in` lists every arg
+    // table and the evidence table, so that all of them live to this step;
+    // out_table holds x = uint8[n_vars][decode_batch_rows], variable-major,
+    // of which the step writes the rows of the maximised variables only
+    bool decode_batch = false;
+    int64_t decode_batch_rows = 0;
     bool counts = false;
     int counts_factor = -1;
     std::vector<int> counts_scope, counts_rows;
@@ -201,6 +210,9 @@ constexpr int kSampleKey = kXchgKeyBase + 8192;
 constexpr int kCondBatchKey = kXchgKeyBase + 12288;
 // ... of an accumulate step of a counts plan (BucketSpec::counts): the executor's, one group per step
 constexpr int kCountsKey = kXchgKeyBase + 16384;
+// ... of the traceback of a batched MPE plan (BucketSpec::decode_batch): the executor's
+constexpr int kMpeDecodeBatchKey = kXchgKeyBase + 20480;
+constexpr int kDecodeBatchPoolHead = 4;   // words before the rows of a batched traceback's pool
 constexpr int kCountsMaxDims = 32;  // evidence variables, and other variables, in one factor scope of an accumulate step
 constexpr int kCountsPoolHead = 12; // words before the per-variable rows of an accumulate step's pool
 constexpr int kCondMaxRest = 8;     // rest dims of a gather step after merging adjacent ones
@@ -253,6 +265,10 @@ struct VEPlan {
     int n_slices = 1, slice_rank = 0;
     std::vector<int> results_slice_bit;
     int64_t arg_bytes = 0;              // plan_mpe: bytes of all arg tables (resident to the traceback)
+    // plan_mpe_batch: max buckets; arg tables that carry B and their entries per row; ... that do not, and
+    // their entries (arg_bytes = arg_b_entries * rows + arg_nob_entries, the tables' bytes before alignment)
+    int n_max_buckets = 0, n_arg_b = 0, n_arg_nob = 0;
+    int64_t arg_b_entries = 0, arg_nob_entries = 0;
     int64_t sample_bytes = 0;           // plan_sample: bytes of the sample state x (n_vars * n_samples)
     int batch_ev_table = -1;            // plan_batch: the evidence table (-1: no gather step)
     // plan_counts: the per-launch weights (double[rows]) and the first
@@ -317,6 +333,18 @@ bool plan_sample(const std::vector<int> &cards, const std::vector<View> &sources
 bool plan_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                 const std::vector<int> &ev_vars, int64_t rows, int target, int elem_bytes, VEPlan &out,
                 std::string *msg);
+
+// Batched MPE: plan_batch's gather steps (level 0), evidence table and cards_ext
+// = cards + {rows}, then plan_mpe's elimination over them: every eliminating
+// bucket maximises (max_out) and records its argmax in a table over its output
+// scope -- B the fastest dimension exactly where the message has it; a bucket
+// that no evidence reaches has neither.  No fused chain runs; pure-product
+// prefixes stay products.  Then one traceback step (BucketSpec::decode_batch)
+// over R rows at once.  results = {the maxima, a table over (B) or a scalar
+// when no evidence reaches it; x = uint8[n_vars][rows]}.  `order` covers every
+// non-evidence variable.  Returns false (msg) as plan_batch and plan_mpe do.
+bool plan_mpe_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
+                    const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg);
 
 // Expected sufficient statistics: a batched bucket tree.  plan_batch's gather
 // steps (level 0) and forward pass -- the same buckets in the same order, the

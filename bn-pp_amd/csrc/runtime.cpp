@@ -333,6 +333,11 @@ int launch(Context &ctx, Executable &ex, hipStream_t stream, const XchgHooks *ho
             const BucketDesc &d = sc.descs[g.begin];
             err = launch_mpe_decode(ex.d_pool + d.dim_off, ex.d_meta, static_cast<int32_t *>(ex.h_meta[d.out_table].ptr), st);
             if (err != hipSuccess) return fail(ctx, err, "launch_mpe_decode");
+        } else if (g.variant == kMpeDecodeBatchKey) {        // the batched MPE traceback (maxbatch.cuh): a lane per row
+            const BucketDesc &d = sc.descs[g.begin];
+            err = launch_mpe_decode_batch(ex.d_pool + d.dim_off, ex.d_meta, static_cast<uint8_t *>(ex.h_meta[d.out_table].ptr),
+                                          d.n_tiles, ctx.max_grid, st);
+            if (err != hipSuccess) return fail(ctx, err, "launch_mpe_decode_batch");
         } else if (g.variant == kSampleKey) {                // the sampling step (sample.cuh): all rows, one launch
             const BucketDesc &d = sc.descs[g.begin];
             uint8_t *x = static_cast<uint8_t *>(ex.h_meta[d.out_table].ptr);

@@ -58,6 +58,10 @@ inline SingleKey max_single_key(int is_f32, const SingleArgs &a) {
 hipError_t launch_max_single(int is_f32, const SingleArgs &a, int max_grid, hipStream_t stream);
 // the traceback of a max-product run (maxout.cuh mpe_decode_kernel): one workgroup
 hipError_t launch_mpe_decode(const int64_t *pool, const TableMeta *meta, int32_t *x, hipStream_t stream);
+// the traceback of a batched MPE plan (maxbatch.cuh): pool the step's words in
+// the dims pool, x = uint8[n_vars][n_rows], a lane per row, the grid capped at max_grid
+hipError_t launch_mpe_decode_batch(const int64_t *pool, const TableMeta *meta, uint8_t *x, int64_t n_rows, int max_grid,
+                                   hipStream_t stream);
 // posterior sampling (sample.cuh): all rows of a sampling step (pool: the
 // step's words in the dims pool) for samples [0, n) of x = uint8[n_vars][n],
 // global sample index first + s.  seed and first are launch arguments, not

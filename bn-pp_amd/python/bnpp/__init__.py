@@ -105,6 +105,8 @@ _SIGS = {
     "bnpp_partition_batch": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _I, _IP, _I, _I, C.c_int64, _DP, _DP, _DP]),
     "bnpp_posterior_batch": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _I, _I, _I, C.c_int64, _DP, _DP]),
     "bnpp_plan_batch": (_I, [_P, _I, _IP, _I, _IP, _I, _I, _I, C.c_int64, _DP, _I, _LP, _I, _IP, _IP, _IP]),
+    "bnpp_mpe_batch": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _I, _IP, _I, _I, C.c_int64, _DP, _IP, _DP]),
+    "bnpp_plan_mpe_batch": (_I, [_P, _I, _IP, _I, _IP, _I, _I, C.c_int64, _DP, _I, _LP, _I, _IP]),
     "bnpp_counts_size": (_I, [_P, _LP]),
     "bnpp_expected_counts": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _DP, _I, _IP, _I, _I, C.c_int64, _DP, _DP, _LP, _DP]),
     "bnpp_plan_counts": (_I, [_P, _I, _IP, _I, _IP, _I, _I, C.c_int64, _DP, _I, _LP, _I, _IP, _IP, _IP, _I, _IP, _IP]),
@@ -576,6 +578,54 @@ def posterior_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, ta
                                      int(rows_per_launch), out.ctypes.data_as(_DP), C.byref(up)), "bnpp_posterior_batch")
     del keep
     return out[:n, :k], up.value
+
+
+MPE_DECODE_BATCH_KEY = (1 << 24) + 20480   # the launch-group key of the batched traceback (plan.hpp kMpeDecodeBatchKey)
+PLAN_MPE_BATCH_STATS = PLAN_BATCH_STATS + ("arg_bytes", "max_buckets", "arg_tables_b", "arg_tables_no_b",
+                                           "arg_entries_per_row", "arg_entries_no_b")
+
+
+def plan_mpe_batch(model: Model, ev_vars: Sequence[int], heuristic: str = "mf", dtype: int = F64,
+                   rows_per_launch: int = 0, order: Optional[Sequence[int]] = None):
+    """Host-only planning of mpe_batch (bnpp_plan_mpe_batch) -> (stats, groups):
+    stats a dict of PLAN_MPE_BATCH_STATS (arg_bytes = arg_entries_per_row *
+    rows_per_launch + arg_entries_no_b), groups one dict of PLAN_GROUP_FIELDS per
+    launch group: the gather steps (level 0, COND_BATCH_KEY), max and product
+    buckets, and the traceback step last (MPE_DECODE_BATCH_KEY)."""
+    ev_vars = [int(v) for v in ev_vars]
+    oa = _ints(order) if order is not None else None
+    h = ORDER_GIVEN if order is not None else HEURISTICS[heuristic]
+    no = len(order) if order is not None else 0
+    nf = len(PLAN_GROUP_FIELDS)
+    st = (C.c_double * len(PLAN_MPE_BATCH_STATS))()
+    cnt = C.c_int()
+    args = (model.handle, len(ev_vars), _ints(ev_vars), h, oa, no, dtype, int(rows_per_launch), st,
+            len(PLAN_MPE_BATCH_STATS))
+    _check(_lib.bnpp_plan_mpe_batch(*args, None, 0, C.byref(cnt)), "bnpp_plan_mpe_batch")
+    rows = (C.c_int64 * max(cnt.value * nf, 1))()
+    _check(_lib.bnpp_plan_mpe_batch(*args, rows, cnt.value, C.byref(cnt)), "bnpp_plan_mpe_batch")
+    return (dict(zip(PLAN_MPE_BATCH_STATS, list(st))),
+            [dict(zip(PLAN_GROUP_FIELDS, rows[i * nf:(i + 1) * nf])) for i in range(cnt.value)])
+
+
+def mpe_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, heuristic: str = "mf", dtype: int = F64,
+              order: Optional[Sequence[int]] = None, rows_per_launch: int = 0):
+    """The most probable completion of every evidence row from one plan
+    (bnpp_mpe_batch) -> (log10_value float64[n], assignment int32 (n, n_vars),
+    uptime_ms).  rows: an (n, len(ev_vars)) integer array, rows[r][j] the value
+    of ev_vars[j]; row r's answer is mpe()'s for that evidence."""
+    import numpy as np
+    ne, ev_v, n, keep, ev_x = _ev_rows(ev_vars, rows)
+    oa = _ints(order) if order is not None else None
+    h = ORDER_GIVEN if order is not None else HEURISTICS[heuristic]
+    lv = np.zeros(max(n, 1))
+    x = np.zeros((max(n, 1), max(model.n_vars, 1)), dtype=np.intc)
+    up = C.c_double()
+    _check(_lib.bnpp_mpe_batch(ctx.handle, model.handle, ne, ev_v, n, ev_x, h, oa,
+                               len(order) if order is not None else 0, dtype, int(rows_per_launch),
+                               lv.ctypes.data_as(_DP), x.ctypes.data_as(_IP), C.byref(up)), "bnpp_mpe_batch")
+    del keep
+    return lv[:n], x[:n, :model.n_vars].astype(np.int32, copy=False), up.value
 
 
 COUNTS_KEY = (1 << 24) + 16384       # the launch-group key of an accumulate step (plan.hpp kCountsKey)

@@ -384,6 +384,51 @@ int bnpp_posterior_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int
                          const int *ev_vals /* [n_rows][n_ev] */, int heuristic, int target, int dtype,
                          int64_t rows_per_launch, double *out /* [n_rows][card(target)] */, double *uptime_ms);
 
+/* Batched MPE (no reference counterpart): the most probable joint completion
+ * of n_rows evidence assignments over ONE evidence variable set, from one plan.
+ * Row b: log10_value[b] and assignment[b * n_vars ..] are what bnpp_mpe returns
+ * for evidence row b under the same elimination order, which depends on the
+ * evidence VARIABLES only (as in bnpp_partition_batch).  Evidence variables keep
+ * their value in the assignment; a variable in no factor reads 0.
+ * Plan: bnpp_partition_batch's gather steps, evidence table and row variable B
+ * (card = R rows per launch), then bnpp_mpe's elimination over them: every
+ * eliminating bucket maximises and records its argmax (one byte per entry) in a
+ * table over its output scope -- B the fastest dimension exactly where the
+ * message has it; a bucket no evidence reaches has neither and runs once per
+ * launch.  No fused chain runs; pure-product prefixes stay products.  One
+ * traceback step then decodes R assignments at once, a lane per row.
+ * Same assignment, entry for entry: bucket assignment, chain order and the
+ * strict-> tie rule (a tie keeps the lowest value) are the single call's; the
+ * rows of a launch share each message's power-of-two scale, and multiplying
+ * both sides of p > best by the same exact power of two changes no comparison.
+ * So every arg byte, hence assignment[b], equals bnpp_mpe's in every entry, ties
+ * included, in fp64 and in fp32, as long as nothing goes subnormal.
+ * log10_value[b] is taken of the split of the maximum that frexp gives (as
+ * log10_z in bnpp_partition_batch), so it depends on rows_per_launch no more
+ * than the maximum does; it lies within 4 ulp of max(1, |log10_value|) of
+ * bnpp_mpe's.  A row whose maximum is 0: log10_value = -inf and the assignment
+ * bnpp_mpe returns for it (all-zero entries take arg 0); its neighbours are
+ * not affected.  The shared-scale limit of bnpp_partition_batch applies.
+ * rows_per_launch: chosen exactly as in bnpp_partition_batch; the arena now
+ * also holds every arg table, resident up to the traceback, and the assignment
+ * state (n_vars bytes per row).  No checkpointing: BNPP_ERR_OOM names the
+ * message bytes and the arg bytes.  Results do not depend on R (assignments
+ * equal, log10_value bit for bit in fp64).  The last launch is padded by
+ * repeating its last row.
+ * Limits and errors: bnpp_mpe's plus bnpp_partition_batch's.  A maximised
+ * variable has at most 256 values (BNPP_ERR_UNSUPPORTED before any launch); an
+ * explicit order covers every non-evidence variable; the BNPP_ERR_INVALID cases
+ * and messages (naming row and variable) are bnpp_partition_batch's.  The
+ * arguments are checked before the context is looked at; a NULL context then
+ * gives BNPP_ERR_NO_DEVICE where no device is visible, else BNPP_ERR_INVALID.
+ * Evidence values are int, so assignment is int.  Either output may be NULL.
+ * The planned job stays with the context under a job kind of its own; the
+ * cache key holds the kind, the evidence variable set and R, never the values. */
+int bnpp_mpe_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                   const int *ev_vals /* [n_rows][n_ev] */, int heuristic, const int *order, int n_order, int dtype,
+                   int64_t rows_per_launch, double *log10_value /* [n_rows] */,
+                   int *assignment /* [n_rows][n_vars], row-major */, double *uptime_ms);
+
 /* Expected sufficient statistics (no reference counterpart): for every factor f
  * with scope S_f, N_f(x_S) = sum_b w_b P(x_S | evidence row b) -- what EM's E
  * step and the gradient of sum_b w_b log Z_b need (N_f = theta_f * d/d theta_f).
@@ -623,6 +668,19 @@ int bnpp_plan_sample(const bnpp_model *m, int n_ev, const int *ev_vars, const in
 int bnpp_plan_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
                     int target, int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows,
                     int cap_rows, int *n_rows, int *result_scope, int *n_result_scope);
+
+/* Host-only planning of bnpp_mpe_batch, modelled on bnpp_plan_batch:
+ * stats[0..10) as bnpp_plan_batch's ([8] the rows per launch R, [9] the gather
+ * steps), then [10] arg_bytes, the bytes of all arg tables before alignment,
+ * [11] the max buckets, [12] the arg tables that carry B and [13] those that do
+ * not, [14] the entries per row of the former (summed) and [15] the entries of
+ * the latter: arg_bytes = [14] * R + [15].  rows as bnpp_plan_groups's: the
+ * gather steps at level 0 (key 2^24 + 12288), max-family keys and product keys,
+ * and the traceback step as the last group, key 2^24 + 20480. */
+#define BNPP_PLAN_MPE_BATCH_STATS 16
+int bnpp_plan_mpe_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
+                        int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows, int cap_rows,
+                        int *n_rows);
 
 /* Host-only planning of bnpp_expected_counts, modelled on bnpp_plan_batch:
  * stats[0..10) as bnpp_plan_batch's, then [10] the accumulate steps (one per

@@ -162,6 +162,14 @@ public:
                                                      const std::vector<std::vector<unsigned>> &rows, unsigned target,
                                                      std::unordered_map<std::string, bool> &options,
                                                      double *uptime = nullptr) const;
+    // EXTENSION: batched MPE (bnpp_mpe_batch).  Row r of the result is mpe()'s
+    // assignment for evidence row r, entry for entry (ties included), from one
+    // plan; log10_value (optional) per row, -inf for an impossible row.
+    std::vector<std::vector<unsigned>> mpe_batch(const std::vector<unsigned> &ev_vars,
+                                                 const std::vector<std::vector<unsigned>> &rows,
+                                                 std::unordered_map<std::string, bool> &options,
+                                                 std::vector<double> *log10_value = nullptr,
+                                                 double *uptime = nullptr) const;
     // EXTENSION: expected sufficient statistics (bnpp_expected_counts).  Per
     // factor, in model order, N_f(x_S) = sum_r w_r P(x_S | row r) in the
     // factor's own layout over its whole scope; weights empty: all 1.
