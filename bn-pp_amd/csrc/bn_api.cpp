@@ -591,6 +591,31 @@ std::vector<std::vector<unsigned char>> Model::sample(const std::unordered_map<u
     return out;
 }
 
+std::vector<std::vector<unsigned char>> Model::sample_batch(const std::vector<unsigned> &ev_vars,
+                                                            const std::vector<std::vector<unsigned>> &rows,
+                                                            std::unordered_map<std::string, bool> &options, size_t k,
+                                                            unsigned long long seed, std::vector<double> *log10_z,
+                                                            double *uptime) const {
+    auto t0 = std::chrono::steady_clock::now();
+    ModelGuard g{to_engine(_variables, std::vector<const Factor *>(_factors.begin(), _factors.end()))};
+    const std::vector<int> vars(ev_vars.begin(), ev_vars.end()), flat = flatten_rows(ev_vars, rows);
+    const size_t nv = _variables.size(), n = rows.size() * k;
+    std::vector<double> lz(rows.size() ? rows.size() : 1, 0.0);
+    std::vector<unsigned char> x(std::max<size_t>(n * nv, 1), 0);
+    double up = 0;
+    int dt = options["fp32"] ? BNPP_F32 : BNPP_F64;
+    check(bnpp_sample_batch(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(),
+                            heuristic_of(options), nullptr, 0, dt, 0, (int64_t)k, 0, (int64_t)k, seed, x.data(), lz.data(),
+                            nullptr, &up),
+          "sample_batch");
+    lz.resize(rows.size());
+    if (log10_z) *log10_z = lz;
+    std::vector<std::vector<unsigned char>> out(n);
+    for (size_t i = 0; i < n; ++i) out[i].assign(x.begin() + i * nv, x.begin() + (i + 1) * nv);
+    if (uptime) *uptime = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return out;
+}
+
 std::vector<const Factor *> Model::marginals(const std::unordered_map<unsigned, unsigned> &evidence,
                                              std::unordered_map<std::string, bool> &options, double &uptime) const {
     auto t0 = std::chrono::steady_clock::now();

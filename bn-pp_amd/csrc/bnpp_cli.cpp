@@ -16,6 +16,11 @@
 // -mpe-batch (no reference counterpart): the most probable completion of every
 // sample of the evidence file (bnpp_mpe_batch), one line per sample; with -uai,
 // <base>.MPE ("MPE", the sample count, then per sample "N x_0 .. x_{N-1}").
+// -sample-batch K [-seed S] (no reference counterpart): K exact joint samples of
+// the posterior of every sample of the evidence file (bnpp_sample_batch), row r
+// drawing at the global indices r * K .. r * K + K - 1; with -uai,
+// <base>.SAMPLES ("SAMPLES", then "n_rows K n_vars", then one line of n_vars
+// values per sample, rows outermost).
 // -counts (no reference counterpart): the expected sufficient statistics of the
 // evidence file's samples (bnpp_expected_counts); prints the total log10-
 // likelihood of the possible samples and n_impossible; with -uai, <base>.COUNTS
@@ -40,7 +45,7 @@ int main(int argc, char **argv) {
     std::unordered_map<std::string, bool> options;
     std::vector<std::string> positional;
     std::string uai_out;
-    unsigned long long n_samples = 0, seed = 0;
+    unsigned long long n_samples = 0, n_per_row = 0, seed = 0;
     unsigned post_target = 0;
     for (int i = 1; i < argc; ++i) {
         std::string p(argv[i]);
@@ -53,6 +58,7 @@ int main(int argc, char **argv) {
         else if (p == "-counts") options["counts"] = true;
         else if (p == "-post-batch" && i + 1 < argc) { options["posterior-batch"] = true; post_target = (unsigned)std::strtoul(argv[++i], nullptr, 10); }
         else if (p == "-sample" && i + 1 < argc) { options["sample"] = true; n_samples = std::strtoull(argv[++i], nullptr, 10); }
+        else if (p == "-sample-batch" && i + 1 < argc) { options["sample-batch"] = true; n_per_row = std::strtoull(argv[++i], nullptr, 10); }
         else if (p == "-seed" && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
         else if (p == "-mar-tree") { options["marginals"] = true; options["bucket-tree"] = true; }
         else if (p == "-ve") options["variable-elimination"] = true;
@@ -67,7 +73,7 @@ int main(int argc, char **argv) {
         else positional.push_back(p);
     }
     if (positional.empty() || options["help"]) {
-        std::cout << "usage: " << argv[0] << " /path/to/model.uai [/path/to/evidence.uai.evid] -pr|-mar|-mar-tree|-mpe|-sample N [-seed S]|-pr-batch|-post-batch T|-mpe-batch|-counts [-sp] [-mf|-wmf|-md] [-f32] [-uai base]" << std::endl;
+        std::cout << "usage: " << argv[0] << " /path/to/model.uai [/path/to/evidence.uai.evid] -pr|-mar|-mar-tree|-mpe|-sample N [-seed S]|-pr-batch|-post-batch T|-mpe-batch|-sample-batch K [-seed S]|-counts [-sp] [-mf|-wmf|-md] [-f32] [-uai base]" << std::endl;
         return positional.empty() ? 1 : 0;
     }
     bnpp_model *probe = nullptr;
@@ -169,9 +175,10 @@ int main(int argc, char **argv) {
                 std::fclose(f);
             }
         }
-        if (options["partition-batch"] || options["posterior-batch"] || options["counts"] || options["mpe-batch"]) {
+        if (options["partition-batch"] || options["posterior-batch"] || options["counts"] || options["mpe-batch"] ||
+            options["sample-batch"]) {
             if (positional.size() < 2)
-                throw std::runtime_error("-pr-batch / -post-batch / -mpe-batch / -counts need an evidence file");
+                throw std::runtime_error("-pr-batch / -post-batch / -mpe-batch / -sample-batch / -counts need an evidence file");
             int n_ev = 0;
             int64_t n_rows = 0;
             bnpp_evidence_load_batch(positional[1].c_str(), 0, 0, &n_ev, nullptr, &n_rows, nullptr);   // the sizes
@@ -210,6 +217,27 @@ int main(int argc, char **argv) {
                     for (const auto &x : xs) {
                         std::fprintf(f, "%zu", x.size());
                         for (unsigned v : x) std::fprintf(f, " %u", v);
+                        std::fprintf(f, "\n");
+                    }
+                    std::fclose(f);
+                }
+            }
+            if (options["sample-batch"]) {
+                std::vector<double> lz;
+                const std::vector<std::vector<unsigned char>> xs =
+                    model->sample_batch(vars, rows, options, n_per_row, seed, &lz, &uptime);
+                std::cout << ">> " << n_per_row << " samples for each of " << rows.size() << " evidence rows; log10 Z:";
+                for (size_t r = 0; r < lz.size() && r < 8; ++r) std::cout << " " << lz[r];
+                std::cout << (lz.size() > 8 ? " ..." : "") << std::endl << ">> First sample:";
+                if (!xs.empty())
+                    for (unsigned char v : xs[0]) std::cout << " " << (unsigned)v;
+                std::cout << std::endl << ">> Executed in " << uptime << "ms." << std::endl << std::endl;
+                if (!uai_out.empty()) {
+                    FILE *f = std::fopen((uai_out + ".SAMPLES").c_str(), "w");
+                    if (!f) throw std::runtime_error("cannot write " + uai_out + ".SAMPLES");
+                    std::fprintf(f, "SAMPLES\n%zu %llu %zu\n", rows.size(), n_per_row, model->variables().size());
+                    for (const auto &x : xs) {
+                        for (size_t v = 0; v < x.size(); ++v) std::fprintf(f, v ? " %u" : "%u", (unsigned)x[v]);
                         std::fprintf(f, "\n");
                     }
                     std::fclose(f);

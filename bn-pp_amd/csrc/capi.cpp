@@ -1146,8 +1146,9 @@ int batch_check_vars(const ModelData &d, int n_ev, const int *ev_vars, int targe
     return BNPP_OK;
 }
 
-// what plan_batch_schedule plans: plan_batch, plan_counts (the batched bucket tree) or plan_mpe_batch
-enum BatchMode { kBatchSum = 0, kBatchCounts = 1, kBatchMpe = 2 };
+// what plan_batch_schedule plans: plan_batch, plan_counts (the batched bucket tree), plan_mpe_batch or
+// plan_sample_batch (n_per_row draws per row)
+enum BatchMode { kBatchSum = 0, kBatchCounts = 1, kBatchMpe = 2, kBatchSample = 3 };
 
 // Plan one launch: the elimination order the single call uses for this
 // evidence variable set, then plan_batch for R rows.  rows_per_launch 0: the
@@ -1156,8 +1157,8 @@ enum BatchMode { kBatchSum = 0, kBatchCounts = 1, kBatchMpe = 2 };
 int plan_batch_schedule(const ModelData &d, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
                         int target, int dtype, int64_t budget, int64_t rows_per_launch, Schedule &out, double *stats,
                         int64_t &R, int &width, int64_t auto_cap = kBatchAutoRows, int mode = kBatchSum,
-                        VEPlan *plan_out = nullptr) {
-    const bool counts = mode == kBatchCounts, mpe = mode == kBatchMpe;
+                        VEPlan *plan_out = nullptr, int64_t n_per_row = 1) {
+    const bool counts = mode == kBatchCounts, mpe = mode == kBatchMpe, smp = mode == kBatchSample;
     const int nv = (int)d.cards.size();
     const int eb = dtype == BNPP_F32 ? 4 : 8;
     if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
@@ -1176,7 +1177,7 @@ int plan_batch_schedule(const ModelData &d, int n_ev, const int *ev_vars, int he
             seen[v] = 1;
             if (ev[v] < 0) vars.push_back(v);
         }
-        if (mpe)                                            // as build_plans, kind 4
+        if (mpe || smp)                                     // as build_plans, kind 4 and sampling
             for (int v = 0; v < nv; ++v)
                 if (!seen[v] && ev[v] < 0)
                     return set_err(BNPP_ERR_INVALID, "explicit order must cover every non-evidence variable");
@@ -1187,6 +1188,12 @@ int plan_batch_schedule(const ModelData &d, int n_ev, const int *ev_vars, int he
             if (v != target && ev[v] < 0) vars.push_back(v);
         width = elimination_order(nv, d.cards, scopes, vars, (Heuristic)heuristic, ord);
     }
+    if (smp)                                                // `out` holds one byte per variable, evidence included
+        for (int v : evv)
+            if (d.cards[v] > 256)
+                return set_err(BNPP_ERR_UNSUPPORTED, "sampling: evidence variable " + std::to_string(v) + " has " +
+                                                         std::to_string(d.cards[v]) +
+                                                         " values; the samples hold one byte per variable (at most 256)");
     std::vector<View> views;
     for (size_t f = 0; f < d.scopes.size(); ++f) views.push_back(natural_view((int)f, d.scopes[f], d.cards));
     VEPlan plan;
@@ -1197,6 +1204,7 @@ int plan_batch_schedule(const ModelData &d, int n_ev, const int *ev_vars, int he
     auto make = [&](int64_t rows) {
         return counts ? plan_counts(d.cards, views, ord, evv, rows, eb, plan, &msg)
                : mpe  ? plan_mpe_batch(d.cards, views, ord, evv, rows, eb, plan, &msg)
+               : smp  ? plan_sample_batch(d.cards, views, ord, evv, rows, n_per_row, eb, plan, &msg)
                       : plan_batch(d.cards, views, ord, evv, rows, target, eb, plan, &msg);
     };
     if (rows_per_launch > 0) {
@@ -1217,6 +1225,15 @@ int plan_batch_schedule(const ModelData &d, int n_ev, const int *ev_vars, int he
                       "until the traceback) for %lld row%s per launch, budget %.6f GB", need / 1e9,
                       (long long)std::max<int64_t>(need - plan.arg_bytes, 0), (long long)plan.arg_bytes, (long long)R,
                       R == 1 ? "" : "s", budget / 1e9);
+        return set_err(BNPP_ERR_OOM, m);
+    }
+    if (need > budget && smp) {
+        // every message stays resident until the draws (no checkpointing), beside the state
+        char m[320];
+        std::snprintf(m, sizeof m, "batched sampling needs %.6f GB (messages %lld bytes + state %lld bytes, all resident "
+                      "until the draws) for %lld row%s per launch of %lld draw%s each, budget %.6f GB", need / 1e9,
+                      (long long)std::max<int64_t>(need - plan.sample_bytes, 0), (long long)plan.sample_bytes, (long long)R,
+                      R == 1 ? "" : "s", (long long)n_per_row, n_per_row == 1 ? "" : "s", budget / 1e9);
         return set_err(BNPP_ERR_OOM, m);
     }
     if (need > budget) {
@@ -1598,6 +1615,224 @@ int run_mpe_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_va
     record_call_timing(t0, t1, t1 + launch_ms, t3);
     g_timing[4] = fetch_ms;
     if (rc) return rc;
+    if (uptime_ms) *uptime_ms = now_ms() - t0;
+    return BNPP_OK;
+}
+
+// ---- batched sampling (bnpp_sample_batch, bnpp_plan_sample_batch) ----
+// job kind 9 (internal): one plan_sample_batch plan of R rows per launch, K draws per row
+constexpr int kKindSampleBatch = 9;
+
+int run_sample_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const int *ev_vals,
+                     int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch, int64_t n_per_row,
+                     int64_t first_sample, int64_t row_stride, uint64_t seed, uint8_t *out, double *log10_z,
+                     int64_t *n_degenerate, double *uptime_ms) {
+    const double t0 = now_ms();
+    if (!m) return set_err(BNPP_ERR_INVALID, "null context or model");
+    const ModelData &d = m->d;
+    if (int rc = batch_check_rows(d, n_ev, ev_vars, n_rows, ev_vals)) return rc;
+    if (n_per_row < 1) return set_err(BNPP_ERR_INVALID, "n_per_row must be at least 1");
+    if (row_stride < 0 || first_sample < 0)
+        return set_err(BNPP_ERR_INVALID, "row_stride and first_sample must be at least 0");
+    {
+        int64_t g = 0;                                     // one past the last global sample index
+        if (__builtin_mul_overflow(n_rows - 1, row_stride, &g) || __builtin_add_overflow(g, first_sample, &g) ||
+            __builtin_add_overflow(g, n_per_row, &g))
+            return set_err(BNPP_ERR_INVALID, "first_sample + (n_rows - 1) * row_stride + n_per_row overflows int64");
+    }
+    if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
+    if (!ctx) {                                            // no context can exist without a device: say which it is
+        int c = 0;
+        if (hipGetDeviceCount(&c) != hipSuccess || c <= 0)
+            return set_err(BNPP_ERR_NO_DEVICE, "no HIP device visible (the engine has no CPU fallback)");
+        return set_err(BNPP_ERR_INVALID, "null context or model");
+    }
+    const int64_t nv = (int64_t)d.cards.size(), K = n_per_row;
+    bnpp_job *job = nullptr;
+    std::unique_lock<std::mutex> lk(ctx->cache_mu, std::try_to_lock);
+    const bool cache_ok = lk.owns_lock();
+    const int64_t budget = memory_budget(ctx, true);
+    const int64_t auto_cap = batch_auto_cap(n_rows);
+    // keyed like a batch job (the evidence variable set and R, never the values) under a kind of its own, with K;
+    // seed, first_sample and row_stride are launch data: other ones relaunch the cached job
+    uint64_t key = cache_ok ? batch_call_key(m, n_ev, ev_vars, heuristic, order, n_order, -1, dtype,
+                                             rows_per_launch > 0 ? rows_per_launch : -auto_cap) : 0;
+    if (key) {
+        key = (key ^ (uint64_t)kKindSampleBatch) * 1099511628211ull;
+        key = (key ^ (uint64_t)K) * 1099511628211ull;
+        key = key ? key : 1;
+    }
+    int rc = oneshot_job(ctx, cache_ok, key, budget, [&](std::unique_ptr<bnpp_job> &j) {
+        j.reset(new bnpp_job);
+        j->ctx = ctx;
+        j->kind = kKindSampleBatch;
+        j->model_uid = m->uid;
+        j->cards = d.cards;
+        if (cache_ok) evict_cached_job(ctx);       // it runs in the arena this job may replace
+        const double tp = now_ms();
+        std::vector<Schedule> batches(1);
+        int width = 0;
+        int rc2 = plan_batch_schedule(d, n_ev, ev_vars, heuristic, order, n_order, -1, dtype, budget, rows_per_launch,
+                                      batches[0], j->stats, j->batch_rows, width, auto_cap, kBatchSample, nullptr, K);
+        if (rc2) return rc2;
+        const double ta = now_ms();
+        rc2 = cached_sources(ctx, m, dtype, j->src);
+        if (rc2) return rc2;
+        const double tb = now_ms();
+        rc2 = from_ctx(ctx, make_program(ctx->c, *j->src, std::move(batches), j->pg, cache_ok));
+        if (rc2) return rc2;
+        g_timing[0] = ta - tp;
+        g_timing[1] = tb - ta;
+        g_timing[2] = now_ms() - tb;
+        g_timing[7] = j->pg.arena_reused ? 1.0 : 0.0;
+        g_timing[8] = j->pg.arena_alloc_ms;
+        return (int)BNPP_OK;
+    }, job);
+    const double t1 = now_ms();
+    double launch_ms = 0, fetch_ms = 0;
+    double stage_ms = 0, wait_ms = 0, copy_ms = 0, transpose_ms = 0;   // the host's share, printed under BNPP_TIMING
+    const BucketDesc *sd = nullptr;
+    if (rc == BNPP_OK) {
+        const Program &pg = job->pg;
+        if (pg.parts.size() == 1 && job->batch_rows >= 1 && !pg.parts[0].sched.groups.empty() &&
+            pg.parts[0].sched.groups.back().variant == kSampleBatchKey && pg.res_off.size() == 1 &&
+            pg.res_off[0].size() == 2 && pg.res_off[0][1] >= 0)
+            sd = &pg.parts[0].sched.descs[pg.parts[0].sched.groups.back().begin];
+        else
+            rc = set_err(BNPP_ERR_INVALID, "batched sampling job without a draw step");
+    }
+    if (rc == BNPP_OK) {
+        Program &pg = job->pg;
+        Executable &ex = pg.parts[0];
+        const Schedule &sc = ex.sched;
+        const int64_t R = job->batch_rows, n_launch = (n_rows + R - 1) / R, lanes = R * K;
+        const int64_t eb = dtype == BNPP_F32 ? 4 : 8;
+        if (sc.pool[sd->dim_off + 2] != R || sc.pool[sd->dim_off + 3] != K)
+            rc = set_err(BNPP_ERR_INVALID, "batched sampling job of another shape");
+        int32_t *d_ev = nullptr;
+        for (const Schedule::Group &g : sc.groups)
+            if (g.variant == kCondBatchKey && sc.descs[g.begin].in_table[1] >= 0)
+                d_ev = static_cast<int32_t *>(ex.h_meta[sc.descs[g.begin].in_table[1]].ptr);
+        // every launch's rows, variable-major, the last launch padded with its last row;
+        // kept to the end of the call (the copies are enqueued)
+        std::vector<int32_t> hev;
+        const double ts = now_ms();
+        if (d_ev) {
+            hev.resize((size_t)(n_launch * n_ev * R));
+            for (int64_t L = 0; L < n_launch; ++L)
+                for (int j = 0; j < n_ev; ++j)
+                    for (int64_t b = 0; b < R; ++b)
+                        hev[(size_t)((L * n_ev + j) * R + b)] = ev_vals[std::min(L * R + b, n_rows - 1) * n_ev + j];
+        }
+        stage_ms = now_ms() - ts;
+        // the variables the draw step writes (the rest are evidence variables: the host fills them in)
+        std::vector<int> ev_col((size_t)nv, -1);
+        for (int j = 0; j < n_ev; ++j) ev_col[(size_t)ev_vars[j]] = j;
+        const int rt = sc.plan_result_table[0];
+        const std::vector<int> &rv = sc.plan_result_vars[0];
+        const bool has_b = std::find(rv.begin(), rv.end(), (int)nv) != rv.end();
+        const int64_t nb = rt < 0 ? 1 : pg.res_size[0][0];
+        if (rc == BNPP_OK && nb != (has_b ? R : 1))
+            rc = set_err(BNPP_ERR_INVALID, "batched sampling result table of an unexpected size");
+        std::vector<unsigned char> raw((size_t)std::max<int64_t>(pg.results_bytes, 1));
+        std::vector<char> impossible;                      // per row of the launch: Z == 0 (or NaN)
+        hipError_t e = hipSetDevice(ctx->c.device);
+        if (e != hipSuccess) rc = set_err(BNPP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+        ex.sample_seed = seed;
+        ex.sample_first = first_sample;
+        ex.sample_row_stride = row_stride;
+        for (int64_t L = 0; L < n_launch && rc == BNPP_OK; ++L) {
+            const double ta = now_ms();
+            const int64_t rows = std::min(R, n_rows - L * R);
+            if (d_ev) {
+                e = hipMemcpyAsync(d_ev, hev.data() + (size_t)(L * n_ev * R), (size_t)(n_ev * R) * sizeof(int32_t),
+                                   hipMemcpyHostToDevice, ctx->c.stream);
+                if (e != hipSuccess) {
+                    rc = set_err(BNPP_ERR_HIP, std::string("hipMemcpyAsync(evidence): ") + hipGetErrorString(e));
+                    break;
+                }
+            }
+            ex.sample_row0 = L * R;
+            ex.sample_n_valid = rows;
+            rc = from_ctx(ctx, launch_program(ctx->c, pg, ctx->c.stream));
+            const double tb = now_ms();
+            launch_ms += tb - ta;
+            if (rc) break;
+            // the table over (B), the state and the per-row counts in one copy of the results buffer, and the table's scale
+            TableMeta tm{};
+            e = hipStreamSynchronize(ctx->c.stream);
+            const double tw = now_ms();
+            wait_ms += tw - tb;
+            if (e != hipSuccess ||
+                (e = hipMemcpy(raw.data(), pg.results, (size_t)pg.results_bytes, hipMemcpyDeviceToHost)) != hipSuccess ||
+                (rt >= 0 && (e = hipMemcpy(&tm, ex.d_meta + rt, sizeof tm, hipMemcpyDeviceToHost)) != hipSuccess)) {
+                rc = set_err(BNPP_ERR_HIP, std::string("batched sampling fetch: ") + hipGetErrorString(e));
+                break;
+            }
+            const unsigned char *vals = rt >= 0 ? raw.data() + pg.res_off[0][0] : nullptr;
+            const uint8_t *x = raw.data() + pg.res_off[0][1];
+            const unsigned char *deg = x + sample_counter_offset(nv, lanes);
+            impossible.assign((size_t)rows, 0);
+            for (int64_t b = 0; b < rows; ++b) {
+                const int64_t row = L * R + b, c = has_b ? b : 0;
+                double p = 1.0;                                 // no factor at all: the empty product
+                if (vals && eb == 4) {
+                    float f;
+                    std::memcpy(&f, vals + c * 4, 4);
+                    p = f;
+                } else if (vals) {
+                    std::memcpy(&p, vals + c * 8, 8);
+                }
+                if (log10_z) {
+                    // as run_batch: the logarithm of the split frexp gives, which Z alone decides
+                    int pe = 0;
+                    const double pm = std::frexp(p, &pe);
+                    log10_z[row] = p > 0 ? std::log10(pm) + (double)(tm.exp2 + pe) * std::log10(2.0) : -INFINITY;
+                }
+                // an impossible row, as the single call: every draw degenerate, every sampled value 0
+                impossible[(size_t)b] = !(p > 0);
+                if (n_degenerate) {
+                    if (impossible[(size_t)b]) n_degenerate[row] = K * (int64_t)sd->k;
+                    else std::memcpy(&n_degenerate[row], deg + b * 8, 8);
+                }
+            }
+            const double tc = now_ms();
+            copy_ms += tc - tw;
+            // x = uint8[n_vars][K][R] to out = [row][s][n_vars], evidence values from the row: per s a byte
+            // in chunks of 256 rows, whose samples stay in cache while every variable's runs of the chunk
+            // (contiguous in b) are read.  (Walking 64 rows at a time per draw measured slower: 9.8 ms
+            // against 3.7 ms on ising12x12 at 2^16 rows with K = 1)
+            constexpr int64_t kChunk = 256;
+            for (int64_t b0 = 0; out && b0 < rows; b0 += kChunk) {
+                const int64_t b1 = std::min(b0 + kChunk, rows);
+                for (int64_t v = 0; v < nv; ++v) {
+                    const int col = ev_col[(size_t)v];
+                    uint8_t *o = out + (L * R * K) * nv + v;
+                    if (col >= 0) {
+                        for (int64_t b = b0; b < b1; ++b) {
+                            const uint8_t val = (uint8_t)ev_vals[(L * R + b) * n_ev + col];
+                            for (int64_t s = 0; s < K; ++s) o[(b * K + s) * nv] = val;
+                        }
+                    } else {
+                        for (int64_t s = 0; s < K; ++s) {
+                            const uint8_t *xs = x + v * lanes + s * R;
+                            for (int64_t b = b0; b < b1; ++b) o[(b * K + s) * nv] = impossible[(size_t)b] ? (uint8_t)0 : xs[b];
+                        }
+                    }
+                }
+            }
+            transpose_ms += now_ms() - tc;
+            fetch_ms += now_ms() - tb;
+        }
+    }
+    const double t3 = now_ms();
+    oneshot_done(ctx, cache_ok, key, budget, job, rc);
+    record_call_timing(t0, t1, t1 + launch_ms, t3);
+    g_timing[4] = fetch_ms;
+    if (rc) return rc;
+    if (std::getenv("BNPP_TIMING"))
+        std::fprintf(stderr, "[bnpp] sample_batch: stage %.3f ms, enqueue %.3f ms, wait %.3f ms, copy %.3f ms, transpose %.3f ms\n",
+                     stage_ms, launch_ms, wait_ms, copy_ms, transpose_ms);
     if (uptime_ms) *uptime_ms = now_ms() - t0;
     return BNPP_OK;
 }
@@ -2847,6 +3082,7 @@ int bnpp_sample(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars
     if (rc == BNPP_OK) rc = from_ctx(ctx, launch_program(ctx->c, job->pg, ctx->c.stream));
     const double t2 = now_ms();
     double lz = 0;
+    bool impossible = false;                               // Z == 0 (or NaN): there is no posterior to draw from
     if (rc == BNPP_OK) {
         std::vector<std::vector<double>> vals;
         std::vector<int64_t> exp2;
@@ -2855,6 +3091,7 @@ int bnpp_sample(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars
             double p = 0;
             for (double v : vals[0]) p += v;
             lz = p > 0 ? std::log10(p) + (double)exp2[0] * std::log10(2.0) : -INFINITY;
+            impossible = !(p > 0);
         }
     }
     if (rc == BNPP_OK) {
@@ -2866,7 +3103,17 @@ int bnpp_sample(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars
         if (e == hipSuccess)
             e = hipMemcpy(&cnt, x + sample_counter_offset((int64_t)m->d.cards.size(), n_samples), sizeof cnt, hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = set_err(BNPP_ERR_HIP, std::string("hipMemcpy(samples): ") + hipGetErrorString(e));
-        else if (n_degenerate) *n_degenerate = cnt;
+        if (rc == BNPP_OK && impossible) {
+            // impossible evidence: every draw counts as degenerate and every sampled value is 0, also where the
+            // zero reached the result without passing through the bucket of a draw (evidence rows keep their values)
+            std::vector<char> is_ev(m->d.cards.size(), 0);
+            for (int j = 0; j < n_ev; ++j)
+                if (ev_vars[j] >= 0 && (size_t)ev_vars[j] < is_ev.size()) is_ev[(size_t)ev_vars[j]] = 1;
+            for (size_t v = 0; out && v < is_ev.size(); ++v)
+                if (!is_ev[v]) std::memset(out + v * (size_t)n_samples, 0, (size_t)n_samples);
+            cnt = n_samples * (int64_t)sd->k;
+        }
+        if (rc == BNPP_OK && n_degenerate) *n_degenerate = cnt;
     }
     const double t3 = now_ms();
     oneshot_done(ctx, cache_ok, key, budget, job, rc);
@@ -2926,6 +3173,50 @@ int bnpp_plan_mpe_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int h
     st[14] = (double)plan.arg_b_entries;
     st[15] = (double)plan.arg_nob_entries;
     for (int i = 0; i < n_stats && i < BNPP_PLAN_MPE_BATCH_STATS; ++i) stats[i] = st[i];
+    int64_t n = 0;
+    for (const Schedule::Group &g : s.groups) {
+        if (n < cap_rows) {
+            const int64_t v[BNPP_PLAN_GROUP_FIELDS] = {0, g.level, g.variant, g.end - g.begin, g.vblocks, g.lane};
+            std::copy(v, v + BNPP_PLAN_GROUP_FIELDS, rows + n * BNPP_PLAN_GROUP_FIELDS);
+        }
+        ++n;
+    }
+    *n_rows = (int)n;
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+int bnpp_sample_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const int *ev_vals,
+                      int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch, int64_t n_per_row,
+                      int64_t first_sample, int64_t row_stride, uint64_t seed, uint8_t *out, double *log10_z,
+                      int64_t *n_degenerate, double *uptime_ms) {
+    BNPP_GUARD_BEGIN
+    return run_sample_batch(ctx, m, n_ev, ev_vars, n_rows, ev_vals, heuristic, order, n_order, dtype, rows_per_launch,
+                            n_per_row, first_sample, row_stride, seed, out, log10_z, n_degenerate, uptime_ms);
+    BNPP_GUARD_END
+}
+
+int bnpp_plan_sample_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
+                           int dtype, int64_t rows_per_launch, int64_t n_per_row, double *stats, int n_stats,
+                           int64_t *rows, int cap_rows, int *n_rows) {
+    BNPP_GUARD_BEGIN
+    if (!m || !n_rows || (cap_rows > 0 && !rows) || (n_stats > 0 && !stats)) return set_err(BNPP_ERR_INVALID, "null argument");
+    if (int rc = batch_check_vars(m->d, n_ev, ev_vars, -1, false)) return rc;
+    if (n_per_row < 1) return set_err(BNPP_ERR_INVALID, "n_per_row must be at least 1");
+    Schedule s;
+    VEPlan plan;
+    double st[BNPP_PLAN_SAMPLE_BATCH_STATS] = {0};
+    int64_t R = 0;
+    int width = 0;
+    int rc = plan_batch_schedule(m->d, n_ev, ev_vars, heuristic, order, n_order, -1, dtype, memory_budget(nullptr),
+                                 rows_per_launch, s, st, R, width, kBatchAutoRows, kBatchSample, &plan, n_per_row);
+    if (rc) return rc;
+    st[10] = (double)n_per_row;
+    st[11] = (double)plan.sample_bytes;
+    st[12] = plan.n_draw_b + plan.n_draw_nob;
+    st[13] = plan.n_draw_b;
+    st[14] = plan.n_draw_nob;
+    for (int i = 0; i < n_stats && i < BNPP_PLAN_SAMPLE_BATCH_STATS; ++i) stats[i] = st[i];
     int64_t n = 0;
     for (const Schedule::Group &g : s.groups) {
         if (n < cap_rows) {

@@ -8,6 +8,10 @@ hipError_t dispatch_sample_rows_f64(const int64_t *pool, const TableMeta *meta, 
                                     uint64_t seed, unsigned long long *n_degenerate, int max_grid, hipStream_t stream) {
     return go_sample_rows<double>(pool, meta, x, n, first, seed, n_degenerate, max_grid, stream);
 }
+hipError_t dispatch_sample_rows_batch_f64(const int64_t *pool, const TableMeta *meta, uint8_t *x, unsigned long long *deg_rows,
+                                          int64_t lanes, const SampleBatchLaunch &a, int max_grid, hipStream_t stream) {
+    return go_sample_rows_batch<double>(pool, meta, x, deg_rows, lanes, a, max_grid, stream);
+}
 hipError_t dispatch_sample_single_f64(const SampleSingleArgs &a, int max_grid, hipStream_t stream) {
     return go_sample_single<double>(a, max_grid, stream);
 }

@@ -33,6 +33,10 @@ hipError_t dispatch_sample_rows_f32(const int64_t *pool, const TableMeta *meta, 
                                     uint64_t seed, unsigned long long *n_degenerate, int max_grid, hipStream_t stream);
 hipError_t dispatch_sample_rows_f64(const int64_t *pool, const TableMeta *meta, uint8_t *x, int64_t n, int64_t first,
                                     uint64_t seed, unsigned long long *n_degenerate, int max_grid, hipStream_t stream);
+hipError_t dispatch_sample_rows_batch_f32(const int64_t *pool, const TableMeta *meta, uint8_t *x, unsigned long long *deg_rows,
+                                          int64_t lanes, const SampleBatchLaunch &a, int max_grid, hipStream_t stream);
+hipError_t dispatch_sample_rows_batch_f64(const int64_t *pool, const TableMeta *meta, uint8_t *x, unsigned long long *deg_rows,
+                                          int64_t lanes, const SampleBatchLaunch &a, int max_grid, hipStream_t stream);
 hipError_t dispatch_sample_single_f32(const SampleSingleArgs &a, int max_grid, hipStream_t stream);
 hipError_t dispatch_sample_single_f64(const SampleSingleArgs &a, int max_grid, hipStream_t stream);
 
@@ -118,6 +122,14 @@ hipError_t launch_sample_rows(int is_f32, const int64_t *pool, const TableMeta *
     if (n <= 0) return hipSuccess;
     return is_f32 ? dispatch_sample_rows_f32(pool, meta, x, n, first, seed, n_degenerate, max_grid, stream)
                   : dispatch_sample_rows_f64(pool, meta, x, n, first, seed, n_degenerate, max_grid, stream);
+}
+
+hipError_t launch_sample_rows_batch(int is_f32, const int64_t *pool, const TableMeta *meta, uint8_t *x,
+                                    unsigned long long *deg_rows, int64_t lanes, const SampleBatchLaunch &a, int max_grid,
+                                    hipStream_t stream) {
+    if (lanes <= 0 || a.n_valid <= 0) return hipSuccess;
+    return is_f32 ? dispatch_sample_rows_batch_f32(pool, meta, x, deg_rows, lanes, a, max_grid, stream)
+                  : dispatch_sample_rows_batch_f64(pool, meta, x, deg_rows, lanes, a, max_grid, stream);
 }
 
 hipError_t launch_sample_single(int is_f32, const SampleSingleArgs &a, int max_grid, hipStream_t stream) {

@@ -649,6 +649,69 @@ static bool build_sample_desc(const BucketSpec &b, const std::vector<int> &cards
     return true;
 }
 
+// The draw step of a batched sampling plan: build_sample_desc's layout with R,
+// K and, per input, the stride of the row variable B (the layout
+// sample_rows_batch reads, sample.cuh):
+//   [0] n_vars  [1] n_rows  [2] R  [3] K
+//   per row: X, k, n_in, then per input: table, base offset, stride of X (0:
+//   absent), stride of B (0: absent), n, n x (variable, stride) -- without X and B
+// d.k rows, d.out_size variables, d.n_tiles = R * K lanes.  cards: the plan's (B last).
+static bool build_sample_batch_desc(const BucketSpec &b, const std::vector<int> &cards, BucketDesc &d,
+                                    std::vector<int64_t> &pool, std::string *msg) {
+    d = BucketDesc{};
+    d.out_table = b.out_table;
+    d.big = -1;
+    d.dim_off = (int64_t)pool.size();
+    const int Bv = (int)cards.size() - 1, n_vars = Bv;
+    if (Bv < 0 || b.sample_batch_rows < 1 || cards[Bv] != b.sample_batch_rows || b.sample_batch_k < 1) {
+        if (msg) *msg = "batched draws: the plan's last variable must be the row variable, K at least 1";
+        return false;
+    }
+    pool.push_back(n_vars);
+    pool.push_back((int64_t)b.sample_rows.size());
+    pool.push_back(b.sample_batch_rows);
+    pool.push_back(b.sample_batch_k);
+    std::vector<char> done(n_vars, 0);
+    for (const BucketSpec::SampleRow &row : b.sample_rows) {
+        if (row.var < 0 || row.var >= n_vars || cards[row.var] > kMaxOutCard || (int)row.in.size() > kMaxIn) {
+            if (msg) *msg = "sampling row: variable " + std::to_string(row.var) + " needs at most " +
+                            std::to_string(kMaxOutCard) + " values and " + std::to_string(kMaxIn) + " inputs";
+            return false;
+        }
+        pool.push_back(row.var);
+        pool.push_back(cards[row.var]);
+        pool.push_back((int64_t)row.in.size());
+        for (const View &v : row.in) {
+            int64_t es = 0, bs = 0, n = 0;
+            for (size_t j = 0; j < v.vars.size(); ++j) {
+                if (v.vars[j] == row.var) es = v.strides[j];
+                else if (v.vars[j] == Bv) bs = v.strides[j];
+                else if (v.vars[j] >= 0 && v.vars[j] < n_vars && done[v.vars[j]]) ++n;
+                else {
+                    // a separator variable is one an earlier row drew: a lane reads only what it wrote
+                    if (msg) *msg = "batched draws: a row must follow the rows that draw its separator";
+                    return false;
+                }
+            }
+            pool.push_back(v.table);
+            pool.push_back(v.base);
+            pool.push_back(es);
+            pool.push_back(bs);
+            pool.push_back(n);
+            for (size_t j = 0; j < v.vars.size(); ++j)
+                if (v.vars[j] != row.var && v.vars[j] != Bv) {
+                    pool.push_back(v.vars[j]);
+                    pool.push_back(v.strides[j]);
+                }
+        }
+        done[row.var] = 1;
+    }
+    d.k = (int32_t)b.sample_rows.size();
+    d.out_size = n_vars;
+    d.n_tiles = b.sample_batch_rows * b.sample_batch_k;
+    return true;
+}
+
 // A gather step of a batch plan: no kernel descriptor, its words in the dims
 // pool (the layout cond_batch reads, condbatch.cuh).  in_table[0] the source,
 // in_table[1] the evidence table (-1: a single-op call), out_size the output's
@@ -797,6 +860,7 @@ bool build_desc(const BucketSpec &b, const std::vector<int> &cards, int max_vec,
     if (b.decode) return build_decode_desc(b, d, pool, msg);
     if (b.decode_batch) return build_decode_batch_desc(b, cards, d, pool, msg);
     if (b.sample) return build_sample_desc(b, cards, d, pool, msg);
+    if (b.sample_batch) return build_sample_batch_desc(b, cards, d, pool, msg);
     if (b.cond_batch) return build_condb_desc(b, cards, d, pool, msg);
     const int n = (int)b.in.size();
     if (n < 1 || n > kMaxIn) {
@@ -2045,6 +2109,93 @@ bool plan_mpe_batch(const std::vector<int> &cards, const std::vector<View> &sour
     return true;
 }
 
+bool plan_sample_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
+                       const std::vector<int> &ev_vars, int64_t rows, int64_t n_per_row, int elem_bytes, VEPlan &out,
+                       std::string *msg) {
+    out = VEPlan{};
+    VEPlan &p = out;
+    if (rows < 1 || rows > (int64_t)INT32_MAX) {
+        if (msg) *msg = "rows per launch must be in [1, 2^31)";
+        return false;
+    }
+    if (n_per_row < 1) {
+        if (msg) *msg = "n_per_row must be at least 1";
+        return false;
+    }
+    const int nv = (int)cards.size(), Bv = nv;
+    std::vector<int> ce = cards;
+    ce.push_back((int)rows);
+    PlanBuilder B(ce, p, sources, order, true);             // chain_eb stays 0: no fused runs
+    B.n_real = nv;
+    std::vector<View> placed;
+    if (!gather_steps(B, p, ce, sources, ev_vars, rows, elem_bytes, placed, msg)) return false;
+    const int nord = (int)order.size();
+    std::vector<std::vector<View>> buckets(nord);
+    std::vector<View> result;
+    for (const View &s : placed) {
+        int bi = B.first_bucket(s.vars, 0);
+        if (bi >= 0) buckets[bi].push_back(s);
+        else result.push_back(s);
+    }
+    std::vector<BucketSpec::SampleRow> rws(nord);
+    for (int i = 0; i < nord; ++i) {
+        if (cards[order[i]] > kMaxOutCard) {
+            if (msg) *msg = "sampling: variable " + std::to_string(order[i]) + " has " + std::to_string(cards[order[i]]) +
+                            " values; the samples hold one byte per variable (at most " + std::to_string(kMaxOutCard) + ")";
+            return false;
+        }
+        rws[i].var = order[i];
+        if (buckets[i].empty()) {           // a variable in no remaining factor: an input-less row, a uniform draw
+            ++p.n_draw_nob;
+            continue;
+        }
+        const int t = B.emit(buckets[i], order[i], false);
+        rws[i].in = p.buckets.back().in;    // the eliminating bucket's own views (pure-product prefixes precede it)
+        bool has_b = false;
+        for (const View &v : rws[i].in) has_b = has_b || std::find(v.vars.begin(), v.vars.end(), Bv) != v.vars.end();
+        ++(has_b ? p.n_draw_b : p.n_draw_nob);
+        View mv = B.view(t);
+        int bi = B.first_bucket(mv.vars, i + 1);
+        if (bi >= 0) buckets[bi].push_back(mv);
+        else result.push_back(mv);
+    }
+    if (!result.empty()) {
+        p.result_table = B.emit(result, -1, false);         // canonical: (B), or a scalar
+        p.result_vars = p.msgs[p.result_table - p.n_src].vars;
+    }
+    BucketSpec smp;
+    smp.sample_batch = true;
+    smp.sample_batch_rows = rows;
+    smp.sample_batch_k = n_per_row;
+    std::vector<char> listed(p.n_src + p.msgs.size(), 0);
+    for (const BucketSpec::SampleRow &r : rws)
+        for (const View &v : r.in)
+            if (!listed[v.table]) {
+                listed[v.table] = 1;
+                View t;
+                t.table = v.table;
+                smp.in.push_back(t);
+            }
+    if (p.batch_ev_table >= 0) {
+        View v;
+        v.table = p.batch_ev_table;
+        smp.in.push_back(v);
+    }
+    smp.sample_rows.assign(rws.rbegin(), rws.rend());
+    p.sample_bytes = sat_mul(sat_mul((int64_t)nv, rows), n_per_row);
+    // x, then int64[rows] degenerate draws per row
+    const int64_t xbytes = sat_add(sample_counter_offset(1, p.sample_bytes), sat_mul(rows, 8));
+    smp.out_table = B.new_raw((xbytes + elem_bytes - 1) / elem_bytes);
+    smp.level = B.last_level + 1;
+    B.last_level = smp.level;
+    B.level[smp.out_table] = smp.level;
+    p.buckets.push_back(smp);
+    p.results = {p.result_table, smp.out_table};
+    p.results_vars = {p.result_vars, {}};
+    B.finish();
+    return true;
+}
+
 bool plan_counts(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                  const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg) {
     out = VEPlan{};
@@ -3256,7 +3407,7 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
                 mix((uint64_t)b.level);
                 mix((uint64_t)(b.xchg * 16 + b.xchg_mode));
                 mix((b.divide ? 1 : 0) + (b.max_out ? 2 : 0) + (b.decode ? 4 : 0) + (b.sample ? 8 : 0) + (b.cond_batch ? 16 : 0) +
-                    (b.decode_batch ? 32 : 0));
+                    (b.decode_batch ? 32 : 0) + (b.sample_batch ? 64 : 0));
                 mix(b.out_vars.size());
                 for (int v : b.out_vars) mix((uint64_t)v);
                 mix(b.chain_x.size() * 131 + b.chain_n.size() * 7 + (uint64_t)b.chain_gmask);
@@ -3529,7 +3680,7 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
         Item &it = items[idx];
         BucketSpec b = *it.b;
         b.simple = simplify && lvl_n[it.level] > 1 && b.chain_x.empty() && !b.divide && !b.xchg &&
-                   !b.decode && !b.decode_batch && !b.sample && !b.cond_batch && !b.counts &&
+                   !b.decode && !b.decode_batch && !b.sample && !b.sample_batch && !b.cond_batch && !b.counts &&
                    plans[it.plan]->msgs[b.out_table - s.n_src].size <= simple_max;
         for (View &v : b.in) v.table = remap(it.plan, v.table);
         b.out_table = remap(it.plan, b.out_table);
@@ -3553,6 +3704,14 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
                 for (View &v : r.in) v.table = remap(it.plan, v.table);
             it.ok = build_desc(b, cards, max_vec, it.d, it.pool, &it.msg);
             it.key = kSampleKey;
+            return;
+        }
+        if (b.sample_batch) {                // the batched draw step: the executor's, its rows in the pool
+            for (BucketSpec::SampleRow &r : b.sample_rows)
+                for (View &v : r.in) v.table = remap(it.plan, v.table);
+            it.ok = build_desc(b, plans[it.plan]->cards_ext.empty() ? cards : plans[it.plan]->cards_ext, max_vec, it.d,
+                               it.pool, &it.msg);
+            it.key = kSampleBatchKey;
             return;
         }
         if (b.cond_batch) {                  // a gather step of a batch plan: the executor's, its words in the pool

@@ -191,6 +191,16 @@ struct BucketSpec {
     // of which the step writes the rows of the maximised variables only
     bool decode_batch = false;
     int64_t decode_batch_rows = 0;
+    // the draw step that ends a batched sampling plan (plan_sample_batch,
+    // sample.cuh): sample_rows as in a sampling step, over views that carry the
+    // row variable B (the plan's last variable) exactly where evidence reaches
+    // them; sample_batch_rows = R rows per launch, sample_batch_k = K draws per
+    // row; `in` lists every table the rows read and the evidence table;
+    // out_table holds x = uint8[n_vars][K][R] (of which the step writes the
+    // rows of the sampled variables only) and, behind it at the next multiple
+    // of 8 bytes, int64[R] degenerate draws per row
+    bool sample_batch = false;
+    int64_t sample_batch_rows = 0, sample_batch_k = 0;
     bool counts = false;
     int counts_factor = -1;
     std::vector<int> counts_scope, counts_rows;
@@ -213,6 +223,9 @@ constexpr int kCountsKey = kXchgKeyBase + 16384;
 // ... of the traceback of a batched MPE plan (BucketSpec::decode_batch): the executor's
 constexpr int kMpeDecodeBatchKey = kXchgKeyBase + 20480;
 constexpr int kDecodeBatchPoolHead = 4;   // words before the rows of a batched traceback's pool
+// ... of the draw step of a batched sampling plan (BucketSpec::sample_batch): the executor's
+constexpr int kSampleBatchKey = kXchgKeyBase + 24576;
+constexpr int kSampleBatchPoolHead = 4;   // words before the rows of a batched draw step's pool
 constexpr int kCountsMaxDims = 32;  // evidence variables, and other variables, in one factor scope of an accumulate step
 constexpr int kCountsPoolHead = 12; // words before the per-variable rows of an accumulate step's pool
 constexpr int kCondMaxRest = 8;     // rest dims of a gather step after merging adjacent ones
@@ -270,6 +283,8 @@ struct VEPlan {
     int n_max_buckets = 0, n_arg_b = 0, n_arg_nob = 0;
     int64_t arg_b_entries = 0, arg_nob_entries = 0;
     int64_t sample_bytes = 0;           // plan_sample: bytes of the sample state x (n_vars * n_samples)
+    // plan_sample_batch: sample_bytes = n_vars * rows * K; draw rows with an input that carries B, and without
+    int n_draw_b = 0, n_draw_nob = 0;
     int batch_ev_table = -1;            // plan_batch: the evidence table (-1: no gather step)
     // plan_counts: the per-launch weights (double[rows]) and the first
     // accumulate step's scratch (3 x 8 bytes per row; one per step), raw tables; per factor the
@@ -345,6 +360,21 @@ bool plan_batch(const std::vector<int> &cards, const std::vector<View> &sources,
 // non-evidence variable.  Returns false (msg) as plan_batch and plan_mpe do.
 bool plan_mpe_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                     const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg);
+
+// Batched sampling: plan_batch's gather steps (level 0), evidence table and
+// cards_ext = cards + {rows}, then plan_sample's loop over the placed views: no
+// fused chain runs, one SampleRow per variable of `order` in reverse
+// elimination order with the eliminating bucket's own views as emitted (B among
+// them exactly where evidence reaches the view), an input-less row for a
+// variable in no remaining factor.  The result is plan_batch's, a table over
+// (B) or a scalar.  One draw step (BucketSpec::sample_batch) of K = n_per_row
+// draws for each of `rows` rows ends the plan; it names every table its rows
+// read.  results = {the partition function per row; x and the per-row
+// degenerate counts}.  `order` covers every non-evidence variable.  Returns
+// false (msg) as plan_batch and plan_sample do.
+bool plan_sample_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
+                       const std::vector<int> &ev_vars, int64_t rows, int64_t n_per_row, int elem_bytes, VEPlan &out,
+                       std::string *msg);
 
 // Expected sufficient statistics: a batched bucket tree.  plan_batch's gather
 // steps (level 0) and forward pass -- the same buckets in the same order, the

@@ -347,6 +347,23 @@ int launch(Context &ctx, Executable &ex, hipStream_t stream, const XchgHooks *ho
             err = launch_sample_rows(ex.dtype == kF32, ex.d_pool + d.dim_off, ex.d_meta, x, d.n_tiles, ex.sample_first,
                                      ex.sample_seed, cnt, ctx.max_grid, st);
             if (err != hipSuccess) return fail(ctx, err, "launch_sample_rows");
+        } else if (g.variant == kSampleBatchKey) {           // the batched draw step (sample.cuh): R * K lanes, one launch
+            const BucketDesc &d = sc.descs[g.begin];
+            const int64_t R = sc.pool[d.dim_off + 2];
+            uint8_t *x = static_cast<uint8_t *>(ex.h_meta[d.out_table].ptr);
+            unsigned long long *deg =
+                reinterpret_cast<unsigned long long *>(x + sample_counter_offset(d.out_size, d.n_tiles));
+            if ((err = hipMemsetAsync(deg, 0, sizeof *deg * (size_t)R, st)) != hipSuccess)
+                return fail(ctx, err, "hipMemsetAsync(n_degenerate per row)");
+            SampleBatchLaunch a;
+            a.seed = ex.sample_seed;
+            a.first = ex.sample_first;
+            a.row_stride = ex.sample_row_stride;
+            a.row0 = ex.sample_row0;
+            a.n_valid = std::min(ex.sample_n_valid, R);
+            err = launch_sample_rows_batch(ex.dtype == kF32, ex.d_pool + d.dim_off, ex.d_meta, x, deg, d.n_tiles, a,
+                                           ctx.max_grid, st);
+            if (err != hipSuccess) return fail(ctx, err, "launch_sample_rows_batch");
         } else if (g.variant == kCondBatchKey) {             // a gather step of a batch plan (condbatch.cuh)
             const BucketDesc &d = sc.descs[g.begin];
             if (d.in_table[1] < 0) return fail(ctx, hipErrorInvalidValue, "gather step without an evidence table");

@@ -79,6 +79,19 @@ struct SampleSingleArgs {
     unsigned long long *n_degenerate;
 };
 hipError_t launch_sample_single(int is_f32, const SampleSingleArgs &a, int max_grid, hipStream_t stream);
+// batched draws (sample.cuh sample_rows_batch_kernel): the draw step of a
+// batched sampling plan (pool: its words in the dims pool) for `lanes` = R * K
+// lanes of x = uint8[n_vars][K][R]; deg_rows = int64[R] (device), added to,
+// never cleared.  What varies per launch is launch data, not plan data: sample
+// (b, s) draws at global index first + (row0 + b) * row_stride + s, and rows
+// b >= n_valid are padding
+struct SampleBatchLaunch {
+    uint64_t seed;
+    int64_t first, row_stride, row0, n_valid;
+};
+hipError_t launch_sample_rows_batch(int is_f32, const int64_t *pool, const TableMeta *meta, uint8_t *x,
+                                    unsigned long long *deg_rows, int64_t lanes, const SampleBatchLaunch &a, int max_grid,
+                                    hipStream_t stream);
 // batched conditioning (condbatch.cuh): one gather step of a batch plan (pool:
 // the step's words in the dims pool, rest: its rest entries) into table
 // out_table (at out_ptr) for the n_rows rows of ev = int32[.][n_rows]
@@ -238,6 +251,8 @@ struct Executable {
     // a sampling step (kSampleKey) draws with these at the next launch (bnpp_sample sets them per call)
     uint64_t sample_seed = 0;
     int64_t sample_first = 0;
+    // ... and a batched draw step (kSampleBatchKey) with these too (run_sample_batch sets them per launch)
+    int64_t sample_row_stride = 0, sample_row0 = 0, sample_n_valid = 0;
     // the accumulate steps (kCountsKey) add into counts_acc for the first counts_rows rows of the next launch
     double *counts_acc = nullptr;
     int64_t counts_rows = 0;

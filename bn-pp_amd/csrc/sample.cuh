@@ -57,9 +57,13 @@ __device__ __forceinline__ double philox_u01(uint64_t seed, uint64_t g, uint32_t
 
 // One row for one sample: NIN input slots (n_in <= NIN, uniform), VB values of
 // X per batch of loads.  w: the row's first input; returns past the row.
-template <typename T, int NIN, int VB>
+// BATCH: an input has one more word, the stride of the row variable B, and the
+// lane's row b enters its offset (sample_rows_batch_kernel below).
+template <typename T, int NIN, int VB, bool BATCH = false>
 __device__ __forceinline__ cst_t<int64_t> *draw_row(cst_t<int64_t> *w, cst_t<TableMeta> *meta, const gbl_t<uint8_t> *x,
-                                                    int64_t n, int64_t s, int k, int n_in, double u, int &val) {
+                                                    int64_t n, int64_t s, int k, int n_in, double u, int &val,
+                                                    int64_t b = 0) {
+    constexpr int H = BATCH ? 5 : 4;                       // words before an input's (variable, stride) pairs
     const T *ptr[NIN];
     int64_t es[NIN], pos[NIN];
 #pragma unroll
@@ -70,9 +74,10 @@ __device__ __forceinline__ cst_t<int64_t> *draw_row(cst_t<int64_t> *w, cst_t<Tab
         if (i < n_in) {                                    // uniform
             ptr[i] = static_cast<const T *>(meta[w[0]].ptr);
             es[i] = w[2];
-            const int nd = (int)w[3];
+            const int nd = (int)w[H - 1];
             int64_t off = w[1];
-            w += 4;
+            if (BATCH) off += b * w[3];
+            w += H;
 #pragma unroll 4
             for (int j = 0; j < nd; ++j) off += (int64_t)x[w[2 * j] * n + s] * w[2 * j + 1];
             w += 2 * nd;
@@ -165,6 +170,62 @@ __global__ __launch_bounds__(kBlock) void sample_rows_kernel(const int64_t *pool
     sample_rows<T>(as_const(pool), as_const(meta), x, n, first, seed, n_degenerate);
 }
 
+// ---- batched draws (bnpp_sample_batch): K samples for each of R evidence rows ----
+// The messages of a batched plan carry the row variable B as their fastest
+// dimension exactly where evidence reaches them.  Lane t in [0, R*K) owns
+// (b, s) = (t % R, t / R): b fastest, as in the messages, so a wave reads 64
+// consecutive B entries of a message wherever its separator values agree, and
+// index t of each variable's row of x = uint8[n_vars][K][R] (64 contiguous
+// bytes per wave).  The draw is draw_row's with b * (stride of B) added to each
+// input's offset; u = philox_u01(seed, first + (row0 + b) * row_stride + s, X),
+// so sample (b, s) has the bytes the single call draws for row b at that global
+// index.  A lane of a padding row (b >= n_valid) reads and writes nothing.
+// Degenerate draws are counted per row: one atomicAdd per lane that saw any,
+// into deg_rows = int64[R], cleared by the launch.  No barrier, no LDS: a lane
+// reads only what it wrote.  The kernel writes the sampled variables only
+// (evidence variables never appear in a separator; the host fills them in).
+// t % R is computed once per lane and pass of the persistent loop, one 64-bit
+// division beside tens of draws; a 2-D loop over (s, b) would leave lanes idle
+// whenever R is no multiple of the block, so it was not built.
+// pool (plan.cpp build_sample_batch_desc):
+//   [0] n_vars  [1] n_rows  [2] R  [3] K
+//   per row: X, k, n_in, then per input: table, base offset, stride of X (0:
+//   absent), stride of B (0: absent), n, n x (variable, stride)
+template <typename T>
+__global__ __launch_bounds__(kBlock) void sample_rows_batch_kernel(const int64_t *pool_, const TableMeta *meta_, uint8_t *x_,
+                                                                   unsigned long long *deg_rows,
+                                                                   const SampleBatchLaunch a) {
+    cst_t<int64_t> *pool = as_const(pool_);
+    cst_t<TableMeta> *meta = as_const(meta_);
+    gbl_t<uint8_t> *x = (gbl_t<uint8_t> *)x_;
+    const int n_rows = (int)pool[1];
+    const int64_t R = pool[2], n = R * pool[3];
+    for (int64_t t0 = (int64_t)blockIdx.x * kBlock; t0 < n; t0 += (int64_t)gridDim.x * kBlock) {
+        const int64_t t = t0 + threadIdx.x;
+        if (t >= n) continue;
+        const int64_t s = t / R, b = t - s * R;
+        if (b >= a.n_valid) continue;                      // a padding row
+        const uint64_t g = (uint64_t)(a.first + (a.row0 + b) * a.row_stride + s);
+        unsigned deg = 0;
+        cst_t<int64_t> *w = pool + 4;
+        for (int r = 0; r < n_rows; ++r) {
+            const int64_t X = w[0];
+            const int k = (int)w[1], n_in = (int)w[2];
+            w += 3;
+            const double u = philox_u01(a.seed, g, (uint32_t)X);
+            int val;
+            if (n_in <= 2) w = draw_row<T, 2, 8, true>(w, meta, x, n, t, k, n_in, u, val, b);   // uniform
+            else w = draw_row<T, kMaxIn, 2, true>(w, meta, x, n, t, k, n_in, u, val, b);
+            if (val < 0) {                                 // c_{k-1} == 0 or NaN
+                val = 0;
+                ++deg;
+            }
+            x[X * n + t] = (uint8_t)val;
+        }
+        if (deg) atomicAdd(deg_rows + b, (unsigned long long)deg);
+    }
+}
+
 // One row with its metadata in the kernel-argument segment (bnpp_bucket_sample).
 template <typename T>
 __global__ __launch_bounds__(kBlock) void sample_single_kernel(const SampleSingleArgs args) {
@@ -185,6 +246,15 @@ static hipError_t go_sample_rows(const int64_t *pool, const TableMeta *meta, uin
     const int64_t grid = blocks < max_grid ? blocks : max_grid;
     hipLaunchKernelGGL((sample_rows_kernel<T>), dim3((unsigned)grid), dim3(kBlock), 0, stream, pool, meta, x, n, first,
                        seed, n_degenerate);
+    return hipGetLastError();
+}
+template <typename T>
+static hipError_t go_sample_rows_batch(const int64_t *pool, const TableMeta *meta, uint8_t *x, unsigned long long *deg_rows,
+                                       int64_t lanes, const SampleBatchLaunch &a, int max_grid, hipStream_t stream) {
+    const int64_t blocks = (lanes + kBlock - 1) / kBlock;
+    const int64_t grid = blocks < 1 ? 1 : blocks < max_grid ? blocks : max_grid;
+    hipLaunchKernelGGL((sample_rows_batch_kernel<T>), dim3((unsigned)grid), dim3(kBlock), 0, stream, pool, meta, x, deg_rows,
+                       a);
     return hipGetLastError();
 }
 template <typename T>

@@ -107,6 +107,9 @@ _SIGS = {
     "bnpp_plan_batch": (_I, [_P, _I, _IP, _I, _IP, _I, _I, _I, C.c_int64, _DP, _I, _LP, _I, _IP, _IP, _IP]),
     "bnpp_mpe_batch": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _I, _IP, _I, _I, C.c_int64, _DP, _IP, _DP]),
     "bnpp_plan_mpe_batch": (_I, [_P, _I, _IP, _I, _IP, _I, _I, C.c_int64, _DP, _I, _LP, _I, _IP]),
+    "bnpp_sample_batch": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _I, _IP, _I, _I, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                               C.c_uint64, _P, _DP, _LP, _DP]),
+    "bnpp_plan_sample_batch": (_I, [_P, _I, _IP, _I, _IP, _I, _I, C.c_int64, C.c_int64, _DP, _I, _LP, _I, _IP]),
     "bnpp_counts_size": (_I, [_P, _LP]),
     "bnpp_expected_counts": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _DP, _I, _IP, _I, _I, C.c_int64, _DP, _DP, _LP, _DP]),
     "bnpp_plan_counts": (_I, [_P, _I, _IP, _I, _IP, _I, _I, C.c_int64, _DP, _I, _LP, _I, _IP, _IP, _IP, _I, _IP, _IP]),
@@ -628,7 +631,64 @@ def mpe_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, heuristi
     return lv[:n], x[:n, :model.n_vars].astype(np.int32, copy=False), up.value
 
 
-COUNTS_KEY = (1 << 24) + 16384       # the launch-group key of an accumulate step (plan.hpp kCountsKey)
+SAMPLE_BATCH_KEY = (1 << 24) + 24576   # the launch-group key of the batched draw step (plan.hpp kSampleBatchKey)
+PLAN_SAMPLE_BATCH_STATS = PLAN_BATCH_STATS + ("n_per_row", "state_bytes", "draw_rows", "draw_rows_b", "draw_rows_no_b")
+
+
+def plan_sample_batch(model: Model, ev_vars: Sequence[int], n_per_row: int = 1, heuristic: str = "mf", dtype: int = F64,
+                      rows_per_launch: int = 0, order: Optional[Sequence[int]] = None):
+    """Host-only planning of sample_batch (bnpp_plan_sample_batch) -> (stats,
+    groups): stats a dict of PLAN_SAMPLE_BATCH_STATS (state_bytes = n_vars *
+    rows_per_launch * n_per_row; draw_rows = draw_rows_b + draw_rows_no_b, with
+    and without an input that carries the row variable), groups one dict of
+    PLAN_GROUP_FIELDS per launch group: the gather steps (level 0,
+    COND_BATCH_KEY), sum and product buckets, and the draw step last
+    (SAMPLE_BATCH_KEY)."""
+    ev_vars = [int(v) for v in ev_vars]
+    oa = _ints(order) if order is not None else None
+    h = ORDER_GIVEN if order is not None else HEURISTICS[heuristic]
+    no = len(order) if order is not None else 0
+    nf = len(PLAN_GROUP_FIELDS)
+    st = (C.c_double * len(PLAN_SAMPLE_BATCH_STATS))()
+    cnt = C.c_int()
+    args = (model.handle, len(ev_vars), _ints(ev_vars), h, oa, no, dtype, int(rows_per_launch), int(n_per_row), st,
+            len(PLAN_SAMPLE_BATCH_STATS))
+    _check(_lib.bnpp_plan_sample_batch(*args, None, 0, C.byref(cnt)), "bnpp_plan_sample_batch")
+    rows = (C.c_int64 * max(cnt.value * nf, 1))()
+    _check(_lib.bnpp_plan_sample_batch(*args, rows, cnt.value, C.byref(cnt)), "bnpp_plan_sample_batch")
+    return (dict(zip(PLAN_SAMPLE_BATCH_STATS, list(st))),
+            [dict(zip(PLAN_GROUP_FIELDS, rows[i * nf:(i + 1) * nf])) for i in range(cnt.value)])
+
+
+def sample_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, n_per_row: int, seed: int = 0,
+                 first_sample: int = 0, row_stride: Optional[int] = None, heuristic: str = "mf", dtype: int = F64,
+                 order: Optional[Sequence[int]] = None, rows_per_launch: int = 0):
+    """n_per_row exact joint samples of P(x | evidence row) for every evidence
+    row from one plan (bnpp_sample_batch) -> (samples uint8 (n, n_per_row,
+    n_vars), log10_z float64[n], n_degenerate int64[n]).  rows: an (n,
+    len(ev_vars)) integer array.  samples[b, s] is sample()'s draw for evidence
+    row b with the same seed at the global index first_sample + b * row_stride
+    + s, byte for byte.  row_stride None: n_per_row (disjoint streams, rows
+    independent); 0: every row sees the same random numbers."""
+    import numpy as np
+    ne, ev_v, n, keep, ev_x = _ev_rows(ev_vars, rows)
+    oa = _ints(order) if order is not None else None
+    h = ORDER_GIVEN if order is not None else HEURISTICS[heuristic]
+    k = int(n_per_row)
+    stride = k if row_stride is None else int(row_stride)
+    out = np.zeros((max(n, 1), max(k, 1), max(model.n_vars, 1)), dtype=np.uint8)
+    lz = np.zeros(max(n, 1))
+    deg = np.zeros(max(n, 1), dtype=np.int64)
+    up = C.c_double()
+    _check(_lib.bnpp_sample_batch(ctx.handle, model.handle, ne, ev_v, n, ev_x, h, oa,
+                                  len(order) if order is not None else 0, dtype, int(rows_per_launch), k,
+                                  int(first_sample), stride, int(seed) & 0xFFFFFFFFFFFFFFFF, _P(out.ctypes.data),
+                                  lz.ctypes.data_as(_DP), deg.ctypes.data_as(_LP), C.byref(up)), "bnpp_sample_batch")
+    del keep
+    return out[:n, :k, :model.n_vars], lz[:n], deg[:n]
+
+
+COUNTS_KEY = (1 << 24) + 16384      # the launch-group key of an accumulate step (plan.hpp kCountsKey)
 PLAN_COUNTS_STATS = PLAN_BATCH_STATS + ("count_steps", "forward_levels")
 
 

@@ -10,7 +10,7 @@ from typing import List, Sequence, Tuple
 
 import numpy as np
 
-from . import F64, Context, Model, expected_counts, split_counts
+from . import F64, Context, Model, expected_counts, sample_batch, split_counts
 
 
 def m_step(model_dict: dict, counts, prior: float = 0.0) -> dict:
@@ -59,3 +59,12 @@ def em(ctx: Context, model_dict: dict, ev_vars: Sequence[int], rows, iters: int,
         lls.append(float(np.sum((lz if w is None else w * np.where(ok, lz, 0.0))[ok])))
         cur = m_step(cur, counts, prior)
     return cur, lls
+
+
+def impute(ctx: Context, model: Model, ev_vars: Sequence[int], rows, k: int = 1, seed: int = 0, dtype: int = F64):
+    """k completions of every row, drawn from P(x | the row) (sample_batch with
+    disjoint streams) -> uint8 (n, k, n_vars): the observed variables keep
+    their values, the others are one exact joint draw.  Multiple imputation,
+    the E step of a stochastic EM, posterior-predictive checks.  An impossible
+    row (Z = 0) comes back with its observed values and zeros elsewhere."""
+    return sample_batch(ctx, model, ev_vars, rows, int(k), seed=seed, dtype=dtype)[0]

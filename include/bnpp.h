@@ -317,7 +317,10 @@ int bnpp_mpe(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, c
  * so a range of g may be split over calls (or devices) in any way.
  * out: HOST array uint8[n_vars][n_samples], variable-major.  *n_degenerate:
  * draws whose weights summed to 0 or NaN (value 0 taken); 0 on a consistent
- * model with possible evidence.
+ * model with possible evidence.  Impossible evidence (Z = 0 or NaN, *log10_z =
+ * -inf) has no posterior to draw from: every sampled value is 0 and every draw
+ * counts as degenerate (n_samples x the non-evidence variables), also where the
+ * zero reached Z without passing through the bucket of a draw.
  * Limits: every sampled variable has at most 256 values (BNPP_ERR_UNSUPPORTED
  * otherwise, before anything is launched); all messages stay resident until
  * the draws, beside n_vars * n_samples bytes of samples: BNPP_ERR_OOM, naming
@@ -428,6 +431,57 @@ int bnpp_mpe_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_v
                    const int *ev_vals /* [n_rows][n_ev] */, int heuristic, const int *order, int n_order, int dtype,
                    int64_t rows_per_launch, double *log10_value /* [n_rows] */,
                    int *assignment /* [n_rows][n_vars], row-major */, double *uptime_ms);
+
+/* Batched posterior sampling (no reference counterpart): K = n_per_row exact
+ * joint samples of P(x | evidence row b) for each of n_rows evidence
+ * assignments over ONE evidence variable set, from one plan.
+ * Same bytes as the single call: sample (b, s) is the sample bnpp_sample draws
+ * for evidence row b with the same seed at the global index
+ *   g = first_sample + b * row_stride + s        (b: the row's index in the call)
+ * in every byte, in fp64 and in fp32, as long as nothing goes subnormal.  The
+ * elimination order depends on the evidence VARIABLES only, bucket assignment
+ * and chain order are the single call's, and the draw c_v > u * c_{k-1} does
+ * not see the power-of-two scale the rows of a launch share (exp2 is never
+ * read).  The Philox counter stays (g lo, g hi, variable, 0).
+ * row_stride = 0 gives every row the same random numbers (common random
+ * numbers: equal rows give equal samples); row_stride >= K gives the rows
+ * disjoint streams, hence independent draws.  A range of rows may be split over
+ * calls: the call that starts at row b0 passes first_sample + b0 * row_stride.
+ * Plan: bnpp_partition_batch's gather steps, evidence table and row variable B
+ * (card = R rows per launch), then bnpp_sample's unfused forward pass over
+ * them; a view carries B exactly where evidence reaches it, a bucket that no
+ * evidence reaches runs once per launch.  One draw step ends the plan: lane t
+ * of R * K owns (b, s) = (t % R, t / R), state uint8[n_vars][K][R].
+ * out: HOST array uint8[n_rows][K][n_vars], row-major; evidence variables hold
+ * their row's value.  log10_z[b] has bnpp_partition_batch's bits.
+ * n_degenerate[b] is the single call's count for row b: an impossible row has
+ * log10_z = -inf, every draw degenerate and every sampled value 0, as the
+ * single call gives, and leaves its neighbours alone.  Results do not depend on rows_per_launch,
+ * the grid cap or how rows are split over calls, byte for byte; the padding
+ * rows of the last launch are neither written out nor counted.
+ * Limits: bnpp_sample's plus bnpp_partition_batch's.  A sampled variable, or
+ * an evidence variable (out holds bytes), of more than 256 values is
+ * BNPP_ERR_UNSUPPORTED before any launch; an explicit order covers every
+ * non-evidence variable; the shared-scale limit of bnpp_partition_batch
+ * applies.  All forward messages (times R where they carry B) and the n_vars
+ * * R * K state bytes stay resident until the draws (no checkpointing):
+ * BNPP_ERR_OOM names both sizes.  rows_per_launch 0: chosen as in
+ * bnpp_partition_batch, the state counted in the arena.
+ * Errors: the BNPP_ERR_INVALID cases and messages (naming row and variable)
+ * are bnpp_partition_batch's; also n_per_row < 1, row_stride < 0,
+ * first_sample < 0, or first_sample + (n_rows - 1) * row_stride + n_per_row
+ * overflowing int64.  The arguments are checked before the context is looked
+ * at; a NULL context then gives BNPP_ERR_NO_DEVICE where no device is visible,
+ * else BNPP_ERR_INVALID.  Any output may be NULL.
+ * The planned job stays with the context under a job kind of its own; the
+ * cache key holds the kind, the evidence variable set, R and K, never the
+ * values, seed, first_sample or row_stride. */
+int bnpp_sample_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                      const int *ev_vals /* [n_rows][n_ev] */, int heuristic, const int *order, int n_order, int dtype,
+                      int64_t rows_per_launch, int64_t n_per_row /* K >= 1 */, int64_t first_sample,
+                      int64_t row_stride /* >= 0 */, uint64_t seed,
+                      uint8_t *out /* host [n_rows][K][n_vars], row-major */, double *log10_z /* [n_rows], may be NULL */,
+                      int64_t *n_degenerate /* [n_rows], may be NULL */, double *uptime_ms);
 
 /* Expected sufficient statistics (no reference counterpart): for every factor f
  * with scope S_f, N_f(x_S) = sum_b w_b P(x_S | evidence row b) -- what EM's E
@@ -681,6 +735,19 @@ int bnpp_plan_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuri
 int bnpp_plan_mpe_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
                         int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows, int cap_rows,
                         int *n_rows);
+
+/* Host-only planning of bnpp_sample_batch, modelled on bnpp_plan_mpe_batch:
+ * stats[0..10) as bnpp_plan_batch's ([1] the arena bytes, the state included,
+ * [8] the rows per launch R, [9] the gather steps), then [10] K = n_per_row,
+ * [11] the state bytes n_vars * R * K, [12] the draw rows (one per
+ * non-evidence variable), [13] those with an input that carries B and [14]
+ * those without.  rows as bnpp_plan_groups's: the gather steps at level 0 (key
+ * 2^24 + 12288), ordinary sum-plan keys (no chain key), and the draw step as
+ * the last group, key 2^24 + 24576. */
+#define BNPP_PLAN_SAMPLE_BATCH_STATS 15
+int bnpp_plan_sample_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
+                           int dtype, int64_t rows_per_launch, int64_t n_per_row, double *stats, int n_stats,
+                           int64_t *rows, int cap_rows, int *n_rows);
 
 /* Host-only planning of bnpp_expected_counts, modelled on bnpp_plan_batch:
  * stats[0..10) as bnpp_plan_batch's, then [10] the accumulate steps (one per

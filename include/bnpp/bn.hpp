@@ -170,6 +170,17 @@ public:
                                                  std::unordered_map<std::string, bool> &options,
                                                  std::vector<double> *log10_value = nullptr,
                                                  double *uptime = nullptr) const;
+    // EXTENSION: batched posterior sampling (bnpp_sample_batch).  k exact joint
+    // samples of P(x | row r) for every evidence row from one plan, rows
+    // outermost: sample s of row r is entry r * k + s, and it is sample()'s
+    // draw for that evidence at the global index r * k + s (disjoint streams);
+    // log10_z (optional) per row, -inf for an impossible row.
+    std::vector<std::vector<unsigned char>> sample_batch(const std::vector<unsigned> &ev_vars,
+                                                         const std::vector<std::vector<unsigned>> &rows,
+                                                         std::unordered_map<std::string, bool> &options, size_t k,
+                                                         unsigned long long seed = 0,
+                                                         std::vector<double> *log10_z = nullptr,
+                                                         double *uptime = nullptr) const;
     // EXTENSION: expected sufficient statistics (bnpp_expected_counts).  Per
     // factor, in model order, N_f(x_S) = sum_r w_r P(x_S | row r) in the
     // factor's own layout over its whole scope; weights empty: all 1.
