@@ -1123,10 +1123,30 @@ void record_call_timing(double t0, double t1, double t2, double t3) {
     g_timing[6] = now_ms() - t0;
 }
 
-// ---- batched evidence (bnpp_partition_batch, bnpp_posterior_batch, bnpp_plan_batch) ----
-// job kind 6 (internal, like kKindSample): one plan_batch plan of R rows per launch
-constexpr int kKindBatch = 6;
+// ---- batched calls: batched evidence (bnpp_partition_batch, bnpp_posterior_batch), expected counts
+// (bnpp_expected_counts), batched MPE (bnpp_mpe_batch), batched sampling (bnpp_sample_batch) ----
+// Each plans once for R rows per launch, stages the evidence variable-major, runs ceil(n_rows / R) launches and
+// reads a table over the row variable B back per launch.  The job kinds (internal, like kKindSample) name the
+// planner: plan_batch, plan_counts (the batched bucket tree), plan_mpe_batch, plan_sample_batch (K draws per row)
+enum BatchKind { kKindBatch = 6, kKindCounts = 7, kKindMpeBatch = 8, kKindSampleBatch = 9 };
 constexpr int64_t kBatchAutoRows = (int64_t)1 << 16;   // the automatic R's cap
+
+// what a batched call asks for (the plan entry points: no rows)
+struct BatchCall {
+    const bnpp_model *m;
+    int kind;                                           // BatchKind
+    int n_ev;
+    const int *ev_vars;
+    int heuristic;
+    const int *order;
+    int n_order;
+    int dtype;
+    int64_t rows_per_launch;
+    int target = -1;                                    // kKindBatch: the posterior's variable, or -1 for Z
+    int64_t K = 1;                                      // kKindSampleBatch: draws per row
+    int64_t n_rows = 0;
+    const int *ev_vals = nullptr;
+};
 
 // the evidence variable set (no values) and the target: ids in range, no duplicates
 int batch_check_vars(const ModelData &d, int n_ev, const int *ev_vars, int target, bool posterior) {
@@ -1146,33 +1166,55 @@ int batch_check_vars(const ModelData &d, int n_ev, const int *ev_vars, int targe
     return BNPP_OK;
 }
 
-// what plan_batch_schedule plans: plan_batch, plan_counts (the batched bucket tree), plan_mpe_batch or
-// plan_sample_batch (n_per_row draws per row)
-enum BatchMode { kBatchSum = 0, kBatchCounts = 1, kBatchMpe = 2, kBatchSample = 3 };
+// the rows of a batched call, checked before the context is looked at: a bad row fails the same with or without a device
+int batch_check_rows(const BatchCall &c, bool posterior = false) {
+    const ModelData &d = c.m->d;
+    if (c.n_rows < 1) return set_err(BNPP_ERR_INVALID, "n_rows must be at least 1");
+    if (int rc = batch_check_vars(d, c.n_ev, c.ev_vars, c.target, posterior)) return rc;
+    if (c.n_ev > 0 && !c.ev_vals) return set_err(BNPP_ERR_INVALID, "bad evidence arrays");
+    for (int64_t r = 0; r < c.n_rows; ++r)
+        for (int j = 0; j < c.n_ev; ++j) {
+            const int x = c.ev_vals[r * c.n_ev + j];
+            if (x < 0 || x >= d.cards[c.ev_vars[j]])
+                return set_err(BNPP_ERR_INVALID, "evidence row " + std::to_string(r) + ": value " + std::to_string(x) +
+                                                     " of variable " + std::to_string(c.ev_vars[j]) + " is outside [0, " +
+                                                     std::to_string(d.cards[c.ev_vars[j]]) + ")");
+        }
+    return BNPP_OK;
+}
+
+// a null context.  say_no_device (batched MPE and sampling): no context can exist without a device, so say which it is
+int batch_null_ctx(bool say_no_device) {
+    int c = 0;
+    if (say_no_device && (hipGetDeviceCount(&c) != hipSuccess || c <= 0))
+        return set_err(BNPP_ERR_NO_DEVICE, "no HIP device visible (the engine has no CPU fallback)");
+    return set_err(BNPP_ERR_INVALID, "null context or model");
+}
 
 // Plan one launch: the elimination order the single call uses for this
-// evidence variable set, then plan_batch for R rows.  rows_per_launch 0: the
-// largest power of two <= auto_cap (kBatchAutoRows, or less for a call of
-// fewer rows: batch_auto_cap) whose arena fits `budget`.
-int plan_batch_schedule(const ModelData &d, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
-                        int target, int dtype, int64_t budget, int64_t rows_per_launch, Schedule &out, double *stats,
-                        int64_t &R, int &width, int64_t auto_cap = kBatchAutoRows, int mode = kBatchSum,
-                        VEPlan *plan_out = nullptr, int64_t n_per_row = 1) {
-    const bool counts = mode == kBatchCounts, mpe = mode == kBatchMpe, smp = mode == kBatchSample;
+// evidence variable set, then the kind's planner for R rows.  rows_per_launch 0:
+// the largest power of two <= auto_cap (kBatchAutoRows, or less for a call of
+// fewer rows: batch_auto_cap) whose arena fits `budget`.  plan_out: where the VEPlan goes, or null
+int plan_batch_schedule(const BatchCall &c, int64_t budget, int64_t auto_cap, Schedule &out, double *stats, int64_t &R,
+                        VEPlan *plan_out) {
+    const ModelData &d = c.m->d;
+    const int target = c.target, dtype = c.dtype, heuristic = c.heuristic;
+    const bool counts = c.kind == kKindCounts, mpe = c.kind == kKindMpeBatch, smp = c.kind == kKindSampleBatch;
     const int nv = (int)d.cards.size();
     const int eb = dtype == BNPP_F32 ? 4 : 8;
+    int width = 0;
     if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
     if (heuristic < BNPP_ORDER_GIVEN || heuristic > BNPP_MIN_DEGREE) return set_err(BNPP_ERR_INVALID, "unknown heuristic");
-    if (rows_per_launch < 0 || rows_per_launch > (int64_t)INT32_MAX)
+    if (c.rows_per_launch < 0 || c.rows_per_launch > (int64_t)INT32_MAX)
         return set_err(BNPP_ERR_INVALID, "rows_per_launch must be 0 (automatic) or in [1, 2^31)");
-    std::vector<int> ev(nv, -1), evv(ev_vars, ev_vars + n_ev);
+    std::vector<int> ev(nv, -1), evv(c.ev_vars, c.ev_vars + c.n_ev);
     for (int v : evv) ev[v] = 0;                            // the order depends on which variables are observed only
     auto scopes = conditioned_scopes(d, ev);
     std::vector<int> vars, ord;
-    if (target < 0 && order) {                              // as build_plans, kind 0
+    if (target < 0 && c.order) {                            // as build_plans, kind 0
         std::vector<char> seen(nv, 0);
-        for (int i = 0; i < n_order; ++i) {
-            int v = order[i];
+        for (int i = 0; i < c.n_order; ++i) {
+            int v = c.order[i];
             if (v < 0 || v >= nv || seen[v]) return set_err(BNPP_ERR_INVALID, "bad explicit order");
             seen[v] = 1;
             if (ev[v] < 0) vars.push_back(v);
@@ -1204,11 +1246,11 @@ int plan_batch_schedule(const ModelData &d, int n_ev, const int *ev_vars, int he
     auto make = [&](int64_t rows) {
         return counts ? plan_counts(d.cards, views, ord, evv, rows, eb, plan, &msg)
                : mpe  ? plan_mpe_batch(d.cards, views, ord, evv, rows, eb, plan, &msg)
-               : smp  ? plan_sample_batch(d.cards, views, ord, evv, rows, n_per_row, eb, plan, &msg)
+               : smp  ? plan_sample_batch(d.cards, views, ord, evv, rows, c.K, eb, plan, &msg)
                       : plan_batch(d.cards, views, ord, evv, rows, target, eb, plan, &msg);
     };
-    if (rows_per_launch > 0) {
-        R = rows_per_launch;
+    if (c.rows_per_launch > 0) {
+        R = c.rows_per_launch;
         if (!make(R)) return set_err(BNPP_ERR_UNSUPPORTED, msg);
         need = need_of(plan);
     } else {
@@ -1233,7 +1275,7 @@ int plan_batch_schedule(const ModelData &d, int n_ev, const int *ev_vars, int he
         std::snprintf(m, sizeof m, "batched sampling needs %.6f GB (messages %lld bytes + state %lld bytes, all resident "
                       "until the draws) for %lld row%s per launch of %lld draw%s each, budget %.6f GB", need / 1e9,
                       (long long)std::max<int64_t>(need - plan.sample_bytes, 0), (long long)plan.sample_bytes, (long long)R,
-                      R == 1 ? "" : "s", (long long)n_per_row, n_per_row == 1 ? "" : "s", budget / 1e9);
+                      R == 1 ? "" : "s", (long long)c.K, c.K == 1 ? "" : "s", budget / 1e9);
         return set_err(BNPP_ERR_OOM, m);
     }
     if (need > budget) {
@@ -1271,71 +1313,68 @@ int64_t batch_auto_cap(int64_t n_rows) {
     return c;
 }
 
-uint64_t batch_call_key(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
-                        int target, int dtype, int64_t rows_per_launch) {
+// what decides a batched call's plan: the evidence variable set and its column order (never the values), R or,
+// for an automatic R, minus its cap (so calls of 2^16 rows or more, or of one size, share a job), the kind and K.
+// Seed, first_sample and row_stride are launch data: other ones relaunch the cached job
+uint64_t batch_call_key(const BatchCall &c, int64_t auto_cap) {
     if (std::getenv("BNPP_NO_JOB_CACHE")) return 0;
     uint64_t h = 1469598103934665603ull;
     auto mix = [&](uint64_t x) { h = (h ^ x) * 1099511628211ull; };
-    mix(m->uid);
-    mix((uint64_t)kKindBatch);
-    mix((uint64_t)n_ev);
-    for (int i = 0; i < n_ev; ++i) mix((uint32_t)ev_vars[i]);   // the set and its column order; never the values
-    mix((uint64_t)heuristic);
-    mix((uint64_t)n_order);
-    for (int i = 0; i < n_order && order; ++i) mix((uint32_t)order[i]);
-    mix((uint64_t)(int64_t)target);
-    mix((uint64_t)dtype);
-    mix((uint64_t)rows_per_launch);
+    mix(c.m->uid);
+    mix((uint64_t)c.kind);
+    mix((uint64_t)c.n_ev);
+    for (int i = 0; i < c.n_ev; ++i) mix((uint32_t)c.ev_vars[i]);
+    mix((uint64_t)c.heuristic);
+    mix((uint64_t)c.n_order);
+    for (int i = 0; i < c.n_order && c.order; ++i) mix((uint32_t)c.order[i]);
+    mix((uint64_t)(int64_t)c.target);
+    mix((uint64_t)c.dtype);
+    mix((uint64_t)(c.rows_per_launch > 0 ? c.rows_per_launch : -auto_cap));
+    mix((uint64_t)c.K);
     mix_plan_knobs(mix);
     return h ? h : 1;
 }
 
-// target < 0: log10 Z and Z per row; else the posterior of target per row
-int run_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const int *ev_vals,
-              int heuristic, const int *order, int n_order, int target, bool posterior, int dtype,
-              int64_t rows_per_launch, double *log10_z, double *z, double *post, double *uptime_ms) {
-    const double t0 = now_ms();
-    // the arguments are checked before the context is looked at: a bad row fails the same with or without a device
-    if (!m) return set_err(BNPP_ERR_INVALID, "null context or model");
-    const ModelData &d = m->d;
-    if (n_rows < 1) return set_err(BNPP_ERR_INVALID, "n_rows must be at least 1");
-    if (posterior ? !post : !log10_z) return set_err(BNPP_ERR_INVALID, "null output");
-    if (int rc = batch_check_vars(d, n_ev, ev_vars, target, posterior)) return rc;
-    if (n_ev > 0 && !ev_vals) return set_err(BNPP_ERR_INVALID, "bad evidence arrays");
-    for (int64_t r = 0; r < n_rows; ++r)
-        for (int j = 0; j < n_ev; ++j) {
-            const int x = ev_vals[r * n_ev + j];
-            if (x < 0 || x >= d.cards[ev_vars[j]])
-                return set_err(BNPP_ERR_INVALID, "evidence row " + std::to_string(r) + ": value " + std::to_string(x) +
-                                                     " of variable " + std::to_string(ev_vars[j]) + " is outside [0, " +
-                                                     std::to_string(d.cards[ev_vars[j]]) + ")");
-        }
-    if (!posterior) target = -1;
-    if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
-    if (!ctx) return set_err(BNPP_ERR_INVALID, "null context or model");
+// a batched call from its job to its epilogue: batch_open, batch_stage, batch_launches, batch_close
+struct BatchRun {
+    bnpp_ctx *ctx;
+    const BatchCall &c;
+    const double t0;                                    // the call's start
+    std::unique_lock<std::mutex> lk;                    // cache_mu, where nobody else holds it
+    bool cache_ok = false;
+    int64_t budget = 0;
+    uint64_t key = 0;
     bnpp_job *job = nullptr;
-    std::unique_lock<std::mutex> lk(ctx->cache_mu, std::try_to_lock);
-    const bool cache_ok = lk.owns_lock();
-    const int64_t budget = memory_budget(ctx, true);
-    // an automatic R is keyed by its cap, so calls of 2^16 rows or more, or of one size, share a job
-    const int64_t auto_cap = batch_auto_cap(n_rows);
-    const uint64_t key = cache_ok ? batch_call_key(m, n_ev, ev_vars, heuristic, order, n_order, target, dtype,
-                                                   rows_per_launch > 0 ? rows_per_launch : -auto_cap) : 0;
-    int rc = oneshot_job(ctx, cache_ok, key, budget, [&](std::unique_ptr<bnpp_job> &j) {
+    double t1 = 0, launch_ms = 0, fetch_ms = 0;
+    int64_t R = 0, n_launch = 0;
+    int32_t *d_ev = nullptr;                            // the evidence table of the gather steps
+    std::vector<int32_t> hev;
+    bool has_b = false;                                 // the result table is over B (else: one value for every row)
+    BatchRun(bnpp_ctx *x, const BatchCall &call, double start) : ctx(x), c(call), t0(start) {}
+};
+
+// the context's cached job when the call is identical, else a new one: plan, sources, program
+int batch_open(BatchRun &run) {
+    bnpp_ctx *ctx = run.ctx;
+    const BatchCall &c = run.c;
+    run.lk = std::unique_lock<std::mutex>(ctx->cache_mu, std::try_to_lock);
+    const bool cache_ok = run.cache_ok = run.lk.owns_lock();
+    const int64_t budget = run.budget = memory_budget(ctx, true);
+    const int64_t auto_cap = batch_auto_cap(c.n_rows);
+    run.key = cache_ok ? batch_call_key(c, auto_cap) : 0;
+    const int rc = oneshot_job(ctx, cache_ok, run.key, budget, [&](std::unique_ptr<bnpp_job> &j) {
         j.reset(new bnpp_job);
         j->ctx = ctx;
-        j->kind = kKindBatch;
-        j->model_uid = m->uid;
-        j->cards = d.cards;
+        j->kind = c.kind;
+        j->model_uid = c.m->uid;
+        j->cards = c.m->d.cards;
         if (cache_ok) evict_cached_job(ctx);       // it runs in the arena this job may replace
         const double tp = now_ms();
         std::vector<Schedule> batches(1);
-        int width = 0;
-        int rc2 = plan_batch_schedule(d, n_ev, ev_vars, heuristic, order, n_order, target, dtype, budget, rows_per_launch,
-                                      batches[0], j->stats, j->batch_rows, width, auto_cap);
+        int rc2 = plan_batch_schedule(c, budget, auto_cap, batches[0], j->stats, j->batch_rows, nullptr);
         if (rc2) return rc2;
         const double ta = now_ms();
-        rc2 = cached_sources(ctx, m, dtype, j->src);
+        rc2 = cached_sources(ctx, c.m, c.dtype, j->src);
         if (rc2) return rc2;
         const double tb = now_ms();
         rc2 = from_ctx(ctx, make_program(ctx->c, *j->src, std::move(batches), j->pg, cache_ok));
@@ -1346,199 +1385,218 @@ int run_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, 
         g_timing[7] = j->pg.arena_reused ? 1.0 : 0.0;
         g_timing[8] = j->pg.arena_alloc_ms;
         return (int)BNPP_OK;
-    }, job);
-    const double t1 = now_ms();
-    double launch_ms = 0, fetch_ms = 0;
-    if (rc == BNPP_OK && (job->pg.parts.size() != 1 || job->batch_rows < 1))
+    }, run.job);
+    run.t1 = now_ms();
+    return rc;
+}
+
+// every launch's rows, variable-major, the last launch padded with its last row; kept to the end of
+// the call (the copies are enqueued).  No evidence table: no factor mentions an evidence variable
+void batch_stage(BatchRun &run) {
+    const BatchCall &c = run.c;
+    Executable &ex = run.job->pg.parts[0];
+    const Schedule &sc = ex.sched;
+    const int64_t R = run.R = run.job->batch_rows, n_launch = run.n_launch = (c.n_rows + R - 1) / R;
+    for (const Schedule::Group &g : sc.groups)
+        if (g.variant == kCondBatchKey && sc.descs[g.begin].in_table[1] >= 0)
+            run.d_ev = static_cast<int32_t *>(ex.h_meta[sc.descs[g.begin].in_table[1]].ptr);
+    if (run.d_ev) {
+        const int n_ev = c.n_ev;                        // locals: the stores below could alias the call's fields
+        const int64_t n_rows = c.n_rows;
+        const int *ev_vals = c.ev_vals;
+        run.hev.resize((size_t)(n_launch * n_ev * R));
+        int32_t *hev = run.hev.data();
+        for (int64_t L = 0; L < n_launch; ++L)
+            for (int j = 0; j < n_ev; ++j)
+                for (int64_t b = 0; b < R; ++b)
+                    hev[(size_t)((L * n_ev + j) * R + b)] = ev_vals[std::min(L * R + b, n_rows - 1) * n_ev + j];
+    }
+    const std::vector<int> &rv = sc.plan_result_vars[0];
+    run.has_b = std::find(rv.begin(), rv.end(), (int)c.m->d.cards.size()) != rv.end();
+}
+
+int no_hook(int64_t, int64_t) { return BNPP_OK; }
+
+// The launches: per launch the evidence copy, before(L, rows) (what else the launch reads), the launch, and
+// after(L, rows) (the fetch and the rows' unpacking); rows: the launch's rows that are the call's (the rest
+// is padding).  Stops at the first error, and starts nothing on the device after it
+template <typename Before, typename After>
+int batch_launches(BatchRun &run, Before &&before, After &&after) {
+    bnpp_ctx *ctx = run.ctx;
+    const int64_t R = run.R, per = run.c.n_ev * R;
+    hipError_t e = hipSetDevice(ctx->c.device);
+    if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    for (int64_t L = 0; L < run.n_launch; ++L) {
+        const double ta = now_ms();
+        const int64_t rows = std::min(R, run.c.n_rows - L * R);
+        if (run.d_ev) {
+            e = hipMemcpyAsync(run.d_ev, run.hev.data() + (size_t)(L * per), (size_t)per * sizeof(int32_t),
+                               hipMemcpyHostToDevice, ctx->c.stream);
+            if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("hipMemcpyAsync(evidence): ") + hipGetErrorString(e));
+        }
+        int rc = before(L, rows);
+        if (rc) return rc;
+        rc = from_ctx(ctx, launch_program(ctx->c, run.job->pg, ctx->c.stream));
+        const double tb = now_ms();
+        run.launch_ms += tb - ta;
+        if (rc) return rc;
+        rc = after(L, rows);
+        if (rc) return rc;
+        run.fetch_ms += now_ms() - tb;
+    }
+    return BNPP_OK;
+}
+
+// a launch's result table as doubles and its scale (batched evidence, counts); waits for the stream
+int batch_fetch_doubles(BatchRun &run, std::vector<double> &r, int64_t &exp2) {
+    std::vector<std::vector<double>> vals;
+    std::vector<int64_t> e2;
+    if (int rc = from_ctx(run.ctx, fetch_program(run.ctx->c, run.job->pg, run.ctx->c.stream, vals, e2))) return rc;
+    r = std::move(vals[0]);
+    exp2 = e2[0];
+    return BNPP_OK;
+}
+
+// a launch's results buffer (the result table, then what the last step wrote) in one copy, and the result
+// table's scale (batched MPE, sampling); synced_at: when the wait for the stream ended
+int batch_fetch_raw(BatchRun &run, const char *what, std::vector<unsigned char> &raw, TableMeta &tm,
+                    double *synced_at = nullptr) {
+    const Program &pg = run.job->pg;
+    const int rt = pg.parts[0].sched.plan_result_table[0];
+    hipError_t e = hipStreamSynchronize(run.ctx->c.stream);
+    if (synced_at) *synced_at = now_ms();
+    if (e != hipSuccess ||
+        (e = hipMemcpy(raw.data(), pg.results, (size_t)pg.results_bytes, hipMemcpyDeviceToHost)) != hipSuccess ||
+        (rt >= 0 && (e = hipMemcpy(&tm, pg.parts[0].d_meta + rt, sizeof tm, hipMemcpyDeviceToHost)) != hipSuccess))
+        return set_err(BNPP_ERR_HIP, std::string(what) + " fetch: " + hipGetErrorString(e));
+    return BNPP_OK;
+}
+
+// element c of a raw table of floats (eb 4) or doubles; no table (no factor at all): the empty product
+double raw_elem(const unsigned char *vals, int64_t c, int64_t eb) {
+    double p = 1.0;
+    if (vals && eb == 4) {
+        float f;
+        std::memcpy(&f, vals + c * 4, 4);
+        p = f;
+    } else if (vals) {
+        std::memcpy(&p, vals + c * 8, 8);
+    }
+    return p;
+}
+
+// log10(p * 2^exp2).  The table's scale is shared by the rows of a launch, so p * 2^exp2 splits the same value
+// differently at another R: take the logarithm of the split frexp gives, which the value alone decides
+double log10_scaled(double p, int64_t exp2) {
+    int pe = 0;
+    const double pm = std::frexp(p, &pe);
+    return p > 0 ? std::log10(pm) + (double)(exp2 + pe) * std::log10(2.0) : -INFINITY;
+}
+
+// after the call: keep a good job for the next identical call, and the call's phases
+int batch_close(BatchRun &run, int rc, double *uptime_ms) {
+    const double t3 = now_ms();
+    oneshot_done(run.ctx, run.cache_ok, run.key, run.budget, run.job, rc);
+    record_call_timing(run.t0, run.t1, run.t1 + run.launch_ms, t3);
+    g_timing[4] = run.fetch_ms;
+    if (rc) return rc;
+    if (uptime_ms) *uptime_ms = now_ms() - run.t0;
+    return BNPP_OK;
+}
+
+BatchCall batch_call(const bnpp_model *m, int kind, int n_ev, const int *ev_vars, int heuristic, const int *order,
+                     int n_order, int dtype, int64_t rows_per_launch) {
+    BatchCall c{};
+    c.m = m;
+    c.kind = kind;
+    c.n_ev = n_ev;
+    c.ev_vars = ev_vars;
+    c.heuristic = heuristic;
+    c.order = order;
+    c.n_order = n_order;
+    c.dtype = dtype;
+    c.rows_per_launch = rows_per_launch;
+    return c;
+}
+
+// target < 0: log10 Z and Z per row; else the posterior of target per row
+int run_batch(bnpp_ctx *ctx, BatchCall &c, bool posterior, double *log10_z, double *z, double *post, double *uptime_ms) {
+    const double t0 = now_ms();
+    if (!c.m) return set_err(BNPP_ERR_INVALID, "null context or model");
+    const ModelData &d = c.m->d;
+    if (c.n_rows < 1) return set_err(BNPP_ERR_INVALID, "n_rows must be at least 1");
+    if (posterior ? !post : !log10_z) return set_err(BNPP_ERR_INVALID, "null output");
+    if (int rc = batch_check_rows(c, posterior)) return rc;
+    if (!posterior) c.target = -1;
+    if (c.dtype != BNPP_F32 && c.dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
+    if (!ctx) return batch_null_ctx(false);
+    BatchRun run(ctx, c, t0);
+    int rc = batch_open(run);
+    if (rc == BNPP_OK && (run.job->pg.parts.size() != 1 || run.job->batch_rows < 1))
         rc = set_err(BNPP_ERR_INVALID, "batch job without a plan");
     if (rc == BNPP_OK) {
-        Executable &ex = job->pg.parts[0];
-        const Schedule &sc = ex.sched;
-        const int64_t R = job->batch_rows, n_launch = (n_rows + R - 1) / R;
-        // the evidence table of the gather steps (none: no factor mentions an evidence variable)
-        int32_t *d_ev = nullptr;
-        for (const Schedule::Group &g : sc.groups)
-            if (g.variant == kCondBatchKey && sc.descs[g.begin].in_table[1] >= 0)
-                d_ev = static_cast<int32_t *>(ex.h_meta[sc.descs[g.begin].in_table[1]].ptr);
-        // every launch's rows, variable-major, the last launch padded with its last row;
-        // kept to the end of the call (the copies are enqueued)
-        std::vector<int32_t> hev;
-        if (d_ev) {
-            hev.resize((size_t)(n_launch * n_ev * R));
-            for (int64_t L = 0; L < n_launch; ++L)
-                for (int j = 0; j < n_ev; ++j)
-                    for (int64_t b = 0; b < R; ++b)
-                        hev[(size_t)((L * n_ev + j) * R + b)] = ev_vals[std::min(L * R + b, n_rows - 1) * n_ev + j];
-        }
-        const std::vector<int> &rv = sc.plan_result_vars[0];
-        const int Bv = (int)d.cards.size();
-        const bool has_b = std::find(rv.begin(), rv.end(), Bv) != rv.end();
-        const bool has_t = posterior && std::find(rv.begin(), rv.end(), target) != rv.end();
-        const int k = posterior ? d.cards[target] : 1;
-        const int64_t nb = has_b ? R : 1;
-        hipError_t e = hipSetDevice(ctx->c.device);
-        if (e != hipSuccess) rc = set_err(BNPP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-        for (int64_t L = 0; L < n_launch && rc == BNPP_OK; ++L) {
-            const double ta = now_ms();
-            if (d_ev) {
-                e = hipMemcpyAsync(d_ev, hev.data() + (size_t)(L * n_ev * R), (size_t)(n_ev * R) * sizeof(int32_t),
-                                   hipMemcpyHostToDevice, ctx->c.stream);
-                if (e != hipSuccess) {
-                    rc = set_err(BNPP_ERR_HIP, std::string("hipMemcpyAsync(evidence): ") + hipGetErrorString(e));
-                    break;
-                }
-            }
-            rc = from_ctx(ctx, launch_program(ctx->c, job->pg, ctx->c.stream));
-            const double tb = now_ms();
-            launch_ms += tb - ta;
-            if (rc) break;
-            std::vector<std::vector<double>> vals;
-            std::vector<int64_t> exp2;
-            rc = from_ctx(ctx, fetch_program(ctx->c, job->pg, ctx->c.stream, vals, exp2));   // waits for the stream
-            if (rc) break;
-            const std::vector<double> &r = vals[0];
-            const int64_t rows = std::min(R, n_rows - L * R);
-            if ((int64_t)r.size() != nb * (has_t ? k : 1)) {
-                rc = set_err(BNPP_ERR_INVALID, "batch result table of an unexpected size");
-                break;
-            }
+        batch_stage(run);
+        const std::vector<int> &rv = run.job->pg.parts[0].sched.plan_result_vars[0];
+        const bool has_b = run.has_b, has_t = posterior && std::find(rv.begin(), rv.end(), c.target) != rv.end();
+        const int k = posterior ? d.cards[c.target] : 1;
+        const int64_t R = run.R, nb = has_b ? R : 1;
+        std::vector<double> r;
+        int64_t exp2 = 0;
+        rc = batch_launches(run, no_hook, [&](int64_t L, int64_t rows) {
+            if (int rc2 = batch_fetch_doubles(run, r, exp2)) return rc2;
+            if ((int64_t)r.size() != nb * (has_t ? k : 1))
+                return set_err(BNPP_ERR_INVALID, "batch result table of an unexpected size");
             for (int64_t b = 0; b < rows; ++b) {
-                const int64_t row = L * R + b, c = has_b ? b : 0;
+                const int64_t row = L * R + b, cb = has_b ? b : 0;
                 if (!posterior) {                           // job_results, kind 0
                     double p = 0;
-                    p += r[c];
-                    // the table's scale is shared by the rows of a launch, so p * 2^exp2 splits the same Z
-                    // differently at another R: take the logarithm of the split frexp gives, which Z alone decides
-                    int pe = 0;
-                    const double pm = std::frexp(p, &pe);
-                    log10_z[row] = p > 0 ? std::log10(pm) + (double)(exp2[0] + pe) * std::log10(2.0) : -INFINITY;
-                    if (z) z[row] = std::ldexp(p, (int)std::max<int64_t>(std::min<int64_t>(exp2[0], 1 << 20), -(1 << 20)));
+                    p += r[cb];
+                    log10_z[row] = log10_scaled(p, exp2);
+                    if (z) z[row] = std::ldexp(p, (int)std::max<int64_t>(std::min<int64_t>(exp2, 1 << 20), -(1 << 20)));
                 } else if (has_t && k > 0) {                // Factor::normalize (factor.cpp:244-255), as job_results
                     double part = 0;
-                    for (int s = 0; s < k; ++s) part += r[s * nb + c];
-                    for (int s = 0; s < k; ++s) post[row * k + s] = r[s * nb + c] / part;
+                    for (int s = 0; s < k; ++s) part += r[s * nb + cb];
+                    for (int s = 0; s < k; ++s) post[row * k + s] = r[s * nb + cb] / part;
                 } else {                                    // variable in no factor
                     for (int s = 0; s < k; ++s) post[row * k + s] = 1.0 / k;
                 }
             }
-            fetch_ms += now_ms() - tb;
-        }
+            return (int)BNPP_OK;
+        });
     }
-    const double t3 = now_ms();
-    oneshot_done(ctx, cache_ok, key, budget, job, rc);
-    record_call_timing(t0, t1, t1 + launch_ms, t3);
-    g_timing[4] = fetch_ms;
-    if (rc) return rc;
-    if (uptime_ms) *uptime_ms = now_ms() - t0;
-    return BNPP_OK;
+    return batch_close(run, rc, uptime_ms);
 }
 
-// ---- batched MPE (bnpp_mpe_batch, bnpp_plan_mpe_batch) ----
-// job kind 8 (internal): one plan_mpe_batch plan of R rows per launch
-constexpr int kKindMpeBatch = 8;
-
-// the arguments of a batched call, checked before the context is looked at (run_batch's checks and messages)
-int batch_check_rows(const ModelData &d, int n_ev, const int *ev_vars, int64_t n_rows, const int *ev_vals) {
-    if (n_rows < 1) return set_err(BNPP_ERR_INVALID, "n_rows must be at least 1");
-    if (int rc = batch_check_vars(d, n_ev, ev_vars, -1, false)) return rc;
-    if (n_ev > 0 && !ev_vals) return set_err(BNPP_ERR_INVALID, "bad evidence arrays");
-    for (int64_t r = 0; r < n_rows; ++r)
-        for (int j = 0; j < n_ev; ++j) {
-            const int x = ev_vals[r * n_ev + j];
-            if (x < 0 || x >= d.cards[ev_vars[j]])
-                return set_err(BNPP_ERR_INVALID, "evidence row " + std::to_string(r) + ": value " + std::to_string(x) +
-                                                     " of variable " + std::to_string(ev_vars[j]) + " is outside [0, " +
-                                                     std::to_string(d.cards[ev_vars[j]]) + ")");
-        }
-    return BNPP_OK;
+// the last step of a batched MPE or sampling job (the traceback, the draws), or null: not such a job
+const BucketDesc *batch_last_step(const bnpp_job *job, int32_t variant) {
+    const Program &pg = job->pg;
+    if (pg.parts.size() == 1 && job->batch_rows >= 1 && !pg.parts[0].sched.groups.empty() &&
+        pg.parts[0].sched.groups.back().variant == variant && pg.res_off.size() == 1 && pg.res_off[0].size() == 2 &&
+        pg.res_off[0][1] >= 0)
+        return &pg.parts[0].sched.descs[pg.parts[0].sched.groups.back().begin];
+    return nullptr;
 }
 
-int run_mpe_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const int *ev_vals,
-                  int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch, double *log10_value,
-                  int *assignment, double *uptime_ms) {
+int run_mpe_batch(bnpp_ctx *ctx, const BatchCall &c, double *log10_value, int *assignment, double *uptime_ms) {
     const double t0 = now_ms();
-    if (!m) return set_err(BNPP_ERR_INVALID, "null context or model");
-    const ModelData &d = m->d;
-    if (int rc = batch_check_rows(d, n_ev, ev_vars, n_rows, ev_vals)) return rc;
+    if (!c.m) return set_err(BNPP_ERR_INVALID, "null context or model");
+    const ModelData &d = c.m->d;
+    if (int rc = batch_check_rows(c)) return rc;
     if (!log10_value && !assignment) return set_err(BNPP_ERR_INVALID, "null output");
-    if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
-    if (!ctx) {                                            // no context can exist without a device: say which it is
-        int c = 0;
-        if (hipGetDeviceCount(&c) != hipSuccess || c <= 0)
-            return set_err(BNPP_ERR_NO_DEVICE, "no HIP device visible (the engine has no CPU fallback)");
-        return set_err(BNPP_ERR_INVALID, "null context or model");
-    }
-    const int64_t nv = (int64_t)d.cards.size();
-    bnpp_job *job = nullptr;
-    std::unique_lock<std::mutex> lk(ctx->cache_mu, std::try_to_lock);
-    const bool cache_ok = lk.owns_lock();
-    const int64_t budget = memory_budget(ctx, true);
-    const int64_t auto_cap = batch_auto_cap(n_rows);
-    // keyed like a batch job (the evidence variable set and R, never the values) under a kind of its own
-    uint64_t key = cache_ok ? batch_call_key(m, n_ev, ev_vars, heuristic, order, n_order, -1, dtype,
-                                             rows_per_launch > 0 ? rows_per_launch : -auto_cap) : 0;
-    if (key) {
-        key = (key ^ (uint64_t)kKindMpeBatch) * 1099511628211ull;
-        key = key ? key : 1;
-    }
-    int rc = oneshot_job(ctx, cache_ok, key, budget, [&](std::unique_ptr<bnpp_job> &j) {
-        j.reset(new bnpp_job);
-        j->ctx = ctx;
-        j->kind = kKindMpeBatch;
-        j->model_uid = m->uid;
-        j->cards = d.cards;
-        if (cache_ok) evict_cached_job(ctx);       // it runs in the arena this job may replace
-        const double tp = now_ms();
-        std::vector<Schedule> batches(1);
-        int width = 0;
-        int rc2 = plan_batch_schedule(d, n_ev, ev_vars, heuristic, order, n_order, -1, dtype, budget, rows_per_launch,
-                                      batches[0], j->stats, j->batch_rows, width, auto_cap, kBatchMpe);
-        if (rc2) return rc2;
-        const double ta = now_ms();
-        rc2 = cached_sources(ctx, m, dtype, j->src);
-        if (rc2) return rc2;
-        const double tb = now_ms();
-        rc2 = from_ctx(ctx, make_program(ctx->c, *j->src, std::move(batches), j->pg, cache_ok));
-        if (rc2) return rc2;
-        g_timing[0] = ta - tp;
-        g_timing[1] = tb - ta;
-        g_timing[2] = now_ms() - tb;
-        g_timing[7] = j->pg.arena_reused ? 1.0 : 0.0;
-        g_timing[8] = j->pg.arena_alloc_ms;
-        return (int)BNPP_OK;
-    }, job);
-    const double t1 = now_ms();
-    double launch_ms = 0, fetch_ms = 0;
+    if (c.dtype != BNPP_F32 && c.dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
+    if (!ctx) return batch_null_ctx(true);
+    const int64_t nv = (int64_t)d.cards.size(), n_ev = c.n_ev;
+    const int *ev_vals = c.ev_vals;
+    BatchRun run(ctx, c, t0);
+    int rc = batch_open(run);
     const BucketDesc *dd = nullptr;
+    if (rc == BNPP_OK && !(dd = batch_last_step(run.job, kMpeDecodeBatchKey)))
+        rc = set_err(BNPP_ERR_INVALID, "batched MPE job without a traceback step");
     if (rc == BNPP_OK) {
-        const Program &pg = job->pg;
-        if (pg.parts.size() == 1 && job->batch_rows >= 1 && !pg.parts[0].sched.groups.empty() &&
-            pg.parts[0].sched.groups.back().variant == kMpeDecodeBatchKey && pg.res_off.size() == 1 &&
-            pg.res_off[0].size() == 2 && pg.res_off[0][1] >= 0)
-            dd = &pg.parts[0].sched.descs[pg.parts[0].sched.groups.back().begin];
-        else
-            rc = set_err(BNPP_ERR_INVALID, "batched MPE job without a traceback step");
-    }
-    if (rc == BNPP_OK) {
-        Program &pg = job->pg;
-        Executable &ex = pg.parts[0];
-        const Schedule &sc = ex.sched;
-        const int64_t R = job->batch_rows, n_launch = (n_rows + R - 1) / R;
-        const int64_t eb = dtype == BNPP_F32 ? 4 : 8;
-        int32_t *d_ev = nullptr;
-        for (const Schedule::Group &g : sc.groups)
-            if (g.variant == kCondBatchKey && sc.descs[g.begin].in_table[1] >= 0)
-                d_ev = static_cast<int32_t *>(ex.h_meta[sc.descs[g.begin].in_table[1]].ptr);
-        // every launch's rows, variable-major, the last launch padded with its last row;
-        // kept to the end of the call (the copies are enqueued)
-        std::vector<int32_t> hev;
-        if (d_ev) {
-            hev.resize((size_t)(n_launch * n_ev * R));
-            for (int64_t L = 0; L < n_launch; ++L)
-                for (int j = 0; j < n_ev; ++j)
-                    for (int64_t b = 0; b < R; ++b)
-                        hev[(size_t)((L * n_ev + j) * R + b)] = ev_vals[std::min(L * R + b, n_rows - 1) * n_ev + j];
-        }
+        batch_stage(run);
+        const Program &pg = run.job->pg;
+        const Schedule &sc = pg.parts[0].sched;
+        const int64_t R = run.R, eb = c.dtype == BNPP_F32 ? 4 : 8;
         // the variables the traceback writes (the rest: evidence values, 0 for a variable in no factor)
         std::vector<char> decoded((size_t)nv, 0);
         {
@@ -1550,245 +1608,101 @@ int run_mpe_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_va
             }
         }
         std::vector<int> ev_col((size_t)nv, -1);
-        for (int j = 0; j < n_ev; ++j) ev_col[(size_t)ev_vars[j]] = j;
+        for (int j = 0; j < c.n_ev; ++j) ev_col[(size_t)c.ev_vars[j]] = j;
         const int rt = sc.plan_result_table[0];
-        const std::vector<int> &rv = sc.plan_result_vars[0];
-        const bool has_b = std::find(rv.begin(), rv.end(), (int)nv) != rv.end();
-        const int64_t nb = rt < 0 ? 1 : pg.res_size[0][0];
-        if (nb != (has_b ? R : 1)) rc = set_err(BNPP_ERR_INVALID, "batched MPE result table of an unexpected size");
+        const bool has_b = run.has_b;
+        if ((rt < 0 ? 1 : pg.res_size[0][0]) != (has_b ? R : 1))
+            rc = set_err(BNPP_ERR_INVALID, "batched MPE result table of an unexpected size");
         std::vector<unsigned char> raw((size_t)std::max<int64_t>(pg.results_bytes, 1));
-        hipError_t e = hipSetDevice(ctx->c.device);
-        if (e != hipSuccess) rc = set_err(BNPP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-        for (int64_t L = 0; L < n_launch && rc == BNPP_OK; ++L) {
-            const double ta = now_ms();
-            if (d_ev) {
-                e = hipMemcpyAsync(d_ev, hev.data() + (size_t)(L * n_ev * R), (size_t)(n_ev * R) * sizeof(int32_t),
-                                   hipMemcpyHostToDevice, ctx->c.stream);
-                if (e != hipSuccess) {
-                    rc = set_err(BNPP_ERR_HIP, std::string("hipMemcpyAsync(evidence): ") + hipGetErrorString(e));
-                    break;
-                }
-            }
-            rc = from_ctx(ctx, launch_program(ctx->c, pg, ctx->c.stream));
-            const double tb = now_ms();
-            launch_ms += tb - ta;
-            if (rc) break;
-            // the maxima table and x in one copy of the results buffer, and the maxima table's scale
+        if (rc == BNPP_OK) rc = batch_launches(run, no_hook, [&](int64_t L, int64_t rows) {
+            // the maxima table and x, and the maxima table's scale
             TableMeta tm{};
-            if ((e = hipStreamSynchronize(ctx->c.stream)) != hipSuccess ||
-                (e = hipMemcpy(raw.data(), pg.results, (size_t)pg.results_bytes, hipMemcpyDeviceToHost)) != hipSuccess ||
-                (rt >= 0 && (e = hipMemcpy(&tm, ex.d_meta + rt, sizeof tm, hipMemcpyDeviceToHost)) != hipSuccess)) {
-                rc = set_err(BNPP_ERR_HIP, std::string("batched MPE fetch: ") + hipGetErrorString(e));
-                break;
-            }
+            if (int rc2 = batch_fetch_raw(run, "batched MPE", raw, tm)) return rc2;
             const unsigned char *vals = rt >= 0 ? raw.data() + pg.res_off[0][0] : nullptr;
             const uint8_t *x = raw.data() + pg.res_off[0][1];
-            const int64_t rows = std::min(R, n_rows - L * R);
             for (int64_t b = 0; b < rows; ++b) {
-                const int64_t row = L * R + b, c = has_b ? b : 0;
-                if (log10_value) {
-                    double p = 1.0;                             // no factor at all: the empty product
-                    if (vals && eb == 4) {
-                        float f;
-                        std::memcpy(&f, vals + c * 4, 4);
-                        p = f;
-                    } else if (vals) {
-                        std::memcpy(&p, vals + c * 8, 8);
-                    }
-                    // as run_batch: the launch's rows share the table's scale, so take the logarithm of the
-                    // split frexp gives, which the maximum alone decides
-                    int pe = 0;
-                    const double pm = std::frexp(p, &pe);
-                    log10_value[row] = p > 0 ? std::log10(pm) + (double)(tm.exp2 + pe) * std::log10(2.0) : -INFINITY;
-                }
+                const int64_t row = L * R + b;
+                if (log10_value) log10_value[row] = log10_scaled(raw_elem(vals, has_b ? b : 0, eb), tm.exp2);
                 if (assignment)
                     for (int64_t v = 0; v < nv; ++v)
                         assignment[row * nv + v] = decoded[(size_t)v]        ? (int)x[v * R + b]
                                                    : ev_col[(size_t)v] >= 0 ? ev_vals[row * n_ev + ev_col[(size_t)v]]
                                                                             : 0;
             }
-            fetch_ms += now_ms() - tb;
-        }
+            return (int)BNPP_OK;
+        });
     }
-    const double t3 = now_ms();
-    oneshot_done(ctx, cache_ok, key, budget, job, rc);
-    record_call_timing(t0, t1, t1 + launch_ms, t3);
-    g_timing[4] = fetch_ms;
-    if (rc) return rc;
-    if (uptime_ms) *uptime_ms = now_ms() - t0;
-    return BNPP_OK;
+    return batch_close(run, rc, uptime_ms);
 }
 
-// ---- batched sampling (bnpp_sample_batch, bnpp_plan_sample_batch) ----
-// job kind 9 (internal): one plan_sample_batch plan of R rows per launch, K draws per row
-constexpr int kKindSampleBatch = 9;
-
-int run_sample_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const int *ev_vals,
-                     int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch, int64_t n_per_row,
-                     int64_t first_sample, int64_t row_stride, uint64_t seed, uint8_t *out, double *log10_z,
-                     int64_t *n_degenerate, double *uptime_ms) {
+int run_sample_batch(bnpp_ctx *ctx, const BatchCall &c, int64_t first_sample, int64_t row_stride, uint64_t seed,
+                     uint8_t *out, double *log10_z, int64_t *n_degenerate, double *uptime_ms) {
     const double t0 = now_ms();
-    if (!m) return set_err(BNPP_ERR_INVALID, "null context or model");
-    const ModelData &d = m->d;
-    if (int rc = batch_check_rows(d, n_ev, ev_vars, n_rows, ev_vals)) return rc;
-    if (n_per_row < 1) return set_err(BNPP_ERR_INVALID, "n_per_row must be at least 1");
+    if (!c.m) return set_err(BNPP_ERR_INVALID, "null context or model");
+    const ModelData &d = c.m->d;
+    if (int rc = batch_check_rows(c)) return rc;
+    if (c.K < 1) return set_err(BNPP_ERR_INVALID, "n_per_row must be at least 1");
     if (row_stride < 0 || first_sample < 0)
         return set_err(BNPP_ERR_INVALID, "row_stride and first_sample must be at least 0");
     {
         int64_t g = 0;                                     // one past the last global sample index
-        if (__builtin_mul_overflow(n_rows - 1, row_stride, &g) || __builtin_add_overflow(g, first_sample, &g) ||
-            __builtin_add_overflow(g, n_per_row, &g))
+        if (__builtin_mul_overflow(c.n_rows - 1, row_stride, &g) || __builtin_add_overflow(g, first_sample, &g) ||
+            __builtin_add_overflow(g, c.K, &g))
             return set_err(BNPP_ERR_INVALID, "first_sample + (n_rows - 1) * row_stride + n_per_row overflows int64");
     }
-    if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
-    if (!ctx) {                                            // no context can exist without a device: say which it is
-        int c = 0;
-        if (hipGetDeviceCount(&c) != hipSuccess || c <= 0)
-            return set_err(BNPP_ERR_NO_DEVICE, "no HIP device visible (the engine has no CPU fallback)");
-        return set_err(BNPP_ERR_INVALID, "null context or model");
-    }
-    const int64_t nv = (int64_t)d.cards.size(), K = n_per_row;
-    bnpp_job *job = nullptr;
-    std::unique_lock<std::mutex> lk(ctx->cache_mu, std::try_to_lock);
-    const bool cache_ok = lk.owns_lock();
-    const int64_t budget = memory_budget(ctx, true);
-    const int64_t auto_cap = batch_auto_cap(n_rows);
-    // keyed like a batch job (the evidence variable set and R, never the values) under a kind of its own, with K;
-    // seed, first_sample and row_stride are launch data: other ones relaunch the cached job
-    uint64_t key = cache_ok ? batch_call_key(m, n_ev, ev_vars, heuristic, order, n_order, -1, dtype,
-                                             rows_per_launch > 0 ? rows_per_launch : -auto_cap) : 0;
-    if (key) {
-        key = (key ^ (uint64_t)kKindSampleBatch) * 1099511628211ull;
-        key = (key ^ (uint64_t)K) * 1099511628211ull;
-        key = key ? key : 1;
-    }
-    int rc = oneshot_job(ctx, cache_ok, key, budget, [&](std::unique_ptr<bnpp_job> &j) {
-        j.reset(new bnpp_job);
-        j->ctx = ctx;
-        j->kind = kKindSampleBatch;
-        j->model_uid = m->uid;
-        j->cards = d.cards;
-        if (cache_ok) evict_cached_job(ctx);       // it runs in the arena this job may replace
-        const double tp = now_ms();
-        std::vector<Schedule> batches(1);
-        int width = 0;
-        int rc2 = plan_batch_schedule(d, n_ev, ev_vars, heuristic, order, n_order, -1, dtype, budget, rows_per_launch,
-                                      batches[0], j->stats, j->batch_rows, width, auto_cap, kBatchSample, nullptr, K);
-        if (rc2) return rc2;
-        const double ta = now_ms();
-        rc2 = cached_sources(ctx, m, dtype, j->src);
-        if (rc2) return rc2;
-        const double tb = now_ms();
-        rc2 = from_ctx(ctx, make_program(ctx->c, *j->src, std::move(batches), j->pg, cache_ok));
-        if (rc2) return rc2;
-        g_timing[0] = ta - tp;
-        g_timing[1] = tb - ta;
-        g_timing[2] = now_ms() - tb;
-        g_timing[7] = j->pg.arena_reused ? 1.0 : 0.0;
-        g_timing[8] = j->pg.arena_alloc_ms;
-        return (int)BNPP_OK;
-    }, job);
-    const double t1 = now_ms();
-    double launch_ms = 0, fetch_ms = 0;
+    if (c.dtype != BNPP_F32 && c.dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
+    if (!ctx) return batch_null_ctx(true);
+    const int64_t nv = (int64_t)d.cards.size(), K = c.K, n_ev = c.n_ev;
+    const int *ev_vals = c.ev_vals;
+    BatchRun run(ctx, c, t0);
+    int rc = batch_open(run);
     double stage_ms = 0, wait_ms = 0, copy_ms = 0, transpose_ms = 0;   // the host's share, printed under BNPP_TIMING
     const BucketDesc *sd = nullptr;
+    if (rc == BNPP_OK && !(sd = batch_last_step(run.job, kSampleBatchKey)))
+        rc = set_err(BNPP_ERR_INVALID, "batched sampling job without a draw step");
     if (rc == BNPP_OK) {
-        const Program &pg = job->pg;
-        if (pg.parts.size() == 1 && job->batch_rows >= 1 && !pg.parts[0].sched.groups.empty() &&
-            pg.parts[0].sched.groups.back().variant == kSampleBatchKey && pg.res_off.size() == 1 &&
-            pg.res_off[0].size() == 2 && pg.res_off[0][1] >= 0)
-            sd = &pg.parts[0].sched.descs[pg.parts[0].sched.groups.back().begin];
-        else
-            rc = set_err(BNPP_ERR_INVALID, "batched sampling job without a draw step");
-    }
-    if (rc == BNPP_OK) {
-        Program &pg = job->pg;
-        Executable &ex = pg.parts[0];
+        const double ts = now_ms();
+        batch_stage(run);
+        stage_ms = now_ms() - ts;
+        const Program &pg = run.job->pg;
+        Executable &ex = run.job->pg.parts[0];
         const Schedule &sc = ex.sched;
-        const int64_t R = job->batch_rows, n_launch = (n_rows + R - 1) / R, lanes = R * K;
-        const int64_t eb = dtype == BNPP_F32 ? 4 : 8;
+        const int64_t R = run.R, lanes = R * K, eb = c.dtype == BNPP_F32 ? 4 : 8;
         if (sc.pool[sd->dim_off + 2] != R || sc.pool[sd->dim_off + 3] != K)
             rc = set_err(BNPP_ERR_INVALID, "batched sampling job of another shape");
-        int32_t *d_ev = nullptr;
-        for (const Schedule::Group &g : sc.groups)
-            if (g.variant == kCondBatchKey && sc.descs[g.begin].in_table[1] >= 0)
-                d_ev = static_cast<int32_t *>(ex.h_meta[sc.descs[g.begin].in_table[1]].ptr);
-        // every launch's rows, variable-major, the last launch padded with its last row;
-        // kept to the end of the call (the copies are enqueued)
-        std::vector<int32_t> hev;
-        const double ts = now_ms();
-        if (d_ev) {
-            hev.resize((size_t)(n_launch * n_ev * R));
-            for (int64_t L = 0; L < n_launch; ++L)
-                for (int j = 0; j < n_ev; ++j)
-                    for (int64_t b = 0; b < R; ++b)
-                        hev[(size_t)((L * n_ev + j) * R + b)] = ev_vals[std::min(L * R + b, n_rows - 1) * n_ev + j];
-        }
-        stage_ms = now_ms() - ts;
         // the variables the draw step writes (the rest are evidence variables: the host fills them in)
         std::vector<int> ev_col((size_t)nv, -1);
-        for (int j = 0; j < n_ev; ++j) ev_col[(size_t)ev_vars[j]] = j;
+        for (int j = 0; j < c.n_ev; ++j) ev_col[(size_t)c.ev_vars[j]] = j;
         const int rt = sc.plan_result_table[0];
-        const std::vector<int> &rv = sc.plan_result_vars[0];
-        const bool has_b = std::find(rv.begin(), rv.end(), (int)nv) != rv.end();
-        const int64_t nb = rt < 0 ? 1 : pg.res_size[0][0];
-        if (rc == BNPP_OK && nb != (has_b ? R : 1))
+        const bool has_b = run.has_b;
+        if (rc == BNPP_OK && (rt < 0 ? 1 : pg.res_size[0][0]) != (has_b ? R : 1))
             rc = set_err(BNPP_ERR_INVALID, "batched sampling result table of an unexpected size");
         std::vector<unsigned char> raw((size_t)std::max<int64_t>(pg.results_bytes, 1));
         std::vector<char> impossible;                      // per row of the launch: Z == 0 (or NaN)
-        hipError_t e = hipSetDevice(ctx->c.device);
-        if (e != hipSuccess) rc = set_err(BNPP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
         ex.sample_seed = seed;
         ex.sample_first = first_sample;
         ex.sample_row_stride = row_stride;
-        for (int64_t L = 0; L < n_launch && rc == BNPP_OK; ++L) {
-            const double ta = now_ms();
-            const int64_t rows = std::min(R, n_rows - L * R);
-            if (d_ev) {
-                e = hipMemcpyAsync(d_ev, hev.data() + (size_t)(L * n_ev * R), (size_t)(n_ev * R) * sizeof(int32_t),
-                                   hipMemcpyHostToDevice, ctx->c.stream);
-                if (e != hipSuccess) {
-                    rc = set_err(BNPP_ERR_HIP, std::string("hipMemcpyAsync(evidence): ") + hipGetErrorString(e));
-                    break;
-                }
-            }
+        auto before = [&](int64_t L, int64_t rows) {
             ex.sample_row0 = L * R;
             ex.sample_n_valid = rows;
-            rc = from_ctx(ctx, launch_program(ctx->c, pg, ctx->c.stream));
-            const double tb = now_ms();
-            launch_ms += tb - ta;
-            if (rc) break;
-            // the table over (B), the state and the per-row counts in one copy of the results buffer, and the table's scale
+            return (int)BNPP_OK;
+        };
+        if (rc == BNPP_OK) rc = batch_launches(run, before, [&](int64_t L, int64_t rows) {
+            // the table over (B), the state and the per-row counts, and the table's scale
             TableMeta tm{};
-            e = hipStreamSynchronize(ctx->c.stream);
-            const double tw = now_ms();
+            const double tb = now_ms();
+            double tw = tb;
+            const int rc2 = batch_fetch_raw(run, "batched sampling", raw, tm, &tw);
             wait_ms += tw - tb;
-            if (e != hipSuccess ||
-                (e = hipMemcpy(raw.data(), pg.results, (size_t)pg.results_bytes, hipMemcpyDeviceToHost)) != hipSuccess ||
-                (rt >= 0 && (e = hipMemcpy(&tm, ex.d_meta + rt, sizeof tm, hipMemcpyDeviceToHost)) != hipSuccess)) {
-                rc = set_err(BNPP_ERR_HIP, std::string("batched sampling fetch: ") + hipGetErrorString(e));
-                break;
-            }
+            if (rc2) return rc2;
             const unsigned char *vals = rt >= 0 ? raw.data() + pg.res_off[0][0] : nullptr;
             const uint8_t *x = raw.data() + pg.res_off[0][1];
             const unsigned char *deg = x + sample_counter_offset(nv, lanes);
             impossible.assign((size_t)rows, 0);
             for (int64_t b = 0; b < rows; ++b) {
-                const int64_t row = L * R + b, c = has_b ? b : 0;
-                double p = 1.0;                                 // no factor at all: the empty product
-                if (vals && eb == 4) {
-                    float f;
-                    std::memcpy(&f, vals + c * 4, 4);
-                    p = f;
-                } else if (vals) {
-                    std::memcpy(&p, vals + c * 8, 8);
-                }
-                if (log10_z) {
-                    // as run_batch: the logarithm of the split frexp gives, which Z alone decides
-                    int pe = 0;
-                    const double pm = std::frexp(p, &pe);
-                    log10_z[row] = p > 0 ? std::log10(pm) + (double)(tm.exp2 + pe) * std::log10(2.0) : -INFINITY;
-                }
+                const int64_t row = L * R + b;
+                const double p = raw_elem(vals, has_b ? b : 0, eb);
+                if (log10_z) log10_z[row] = log10_scaled(p, tm.exp2);
                 // an impossible row, as the single call: every draw degenerate, every sampled value 0
                 impossible[(size_t)b] = !(p > 0);
                 if (n_degenerate) {
@@ -1822,119 +1736,51 @@ int run_sample_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev
                 }
             }
             transpose_ms += now_ms() - tc;
-            fetch_ms += now_ms() - tb;
-        }
+            return (int)BNPP_OK;
+        });
     }
-    const double t3 = now_ms();
-    oneshot_done(ctx, cache_ok, key, budget, job, rc);
-    record_call_timing(t0, t1, t1 + launch_ms, t3);
-    g_timing[4] = fetch_ms;
-    if (rc) return rc;
-    if (std::getenv("BNPP_TIMING"))
+    const double launch_ms = run.launch_ms;
+    rc = batch_close(run, rc, uptime_ms);
+    if (rc == BNPP_OK && std::getenv("BNPP_TIMING"))
         std::fprintf(stderr, "[bnpp] sample_batch: stage %.3f ms, enqueue %.3f ms, wait %.3f ms, copy %.3f ms, transpose %.3f ms\n",
                      stage_ms, launch_ms, wait_ms, copy_ms, transpose_ms);
-    if (uptime_ms) *uptime_ms = now_ms() - t0;
-    return BNPP_OK;
+    return rc;
 }
 
-// ---- expected counts (bnpp_expected_counts, bnpp_plan_counts) ----
-// job kind 7 (internal): one plan_counts plan of R rows per launch
-constexpr int kKindCounts = 7;
-
-int run_counts(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const int *ev_vals,
-               const double *weights, int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch,
-               double *counts, double *log10_z, int64_t *n_impossible, double *uptime_ms) {
+int run_counts(bnpp_ctx *ctx, const BatchCall &c, const double *weights, double *counts, double *log10_z,
+               int64_t *n_impossible, double *uptime_ms) {
     const double t0 = now_ms();
-    // the arguments are checked before the context is looked at, as run_batch does
-    if (!m) return set_err(BNPP_ERR_INVALID, "null context or model");
-    const ModelData &d = m->d;
+    if (!c.m) return set_err(BNPP_ERR_INVALID, "null context or model");
+    const ModelData &d = c.m->d;
+    const int64_t n_rows = c.n_rows;
     if (n_rows < 1) return set_err(BNPP_ERR_INVALID, "n_rows must be at least 1");
     if (!counts) return set_err(BNPP_ERR_INVALID, "null output");
-    if (int rc = batch_check_vars(d, n_ev, ev_vars, -1, false)) return rc;
-    if (n_ev > 0 && !ev_vals) return set_err(BNPP_ERR_INVALID, "bad evidence arrays");
-    for (int64_t r = 0; r < n_rows; ++r)
-        for (int j = 0; j < n_ev; ++j) {
-            const int x = ev_vals[r * n_ev + j];
-            if (x < 0 || x >= d.cards[ev_vars[j]])
-                return set_err(BNPP_ERR_INVALID, "evidence row " + std::to_string(r) + ": value " + std::to_string(x) +
-                                                     " of variable " + std::to_string(ev_vars[j]) + " is outside [0, " +
-                                                     std::to_string(d.cards[ev_vars[j]]) + ")");
-        }
+    if (int rc = batch_check_rows(c)) return rc;
     for (int64_t r = 0; weights && r < n_rows; ++r)
         if (!(weights[r] >= 0) || !std::isfinite(weights[r]))
             return set_err(BNPP_ERR_INVALID, "evidence row " + std::to_string(r) + ": the weight must be finite and not negative");
-    if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
-    if (!ctx) return set_err(BNPP_ERR_INVALID, "null context or model");
+    if (c.dtype != BNPP_F32 && c.dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
+    if (!ctx) return batch_null_ctx(false);
     int64_t total = 0;
     for (const auto &v : d.values) total += (int64_t)v.size();
-    bnpp_job *job = nullptr;
-    std::unique_lock<std::mutex> lk(ctx->cache_mu, std::try_to_lock);
-    const bool cache_ok = lk.owns_lock();
-    const int64_t budget = memory_budget(ctx, true);
-    const int64_t auto_cap = batch_auto_cap(n_rows);
-    const uint64_t key = cache_ok ? batch_call_key(m, n_ev, ev_vars, heuristic, order, n_order, -1 - kKindCounts, dtype,
-                                                   rows_per_launch > 0 ? rows_per_launch : -auto_cap) : 0;
-    int rc = oneshot_job(ctx, cache_ok, key, budget, [&](std::unique_ptr<bnpp_job> &j) {
-        j.reset(new bnpp_job);
-        j->ctx = ctx;
-        j->kind = kKindCounts;
-        j->model_uid = m->uid;
-        j->cards = d.cards;
-        if (cache_ok) evict_cached_job(ctx);       // it runs in the arena this job may replace
-        const double tp = now_ms();
-        std::vector<Schedule> batches(1);
-        int width = 0;
-        int rc2 = plan_batch_schedule(d, n_ev, ev_vars, heuristic, order, n_order, -1, dtype, budget, rows_per_launch,
-                                      batches[0], j->stats, j->batch_rows, width, auto_cap, kBatchCounts);
-        if (rc2) return rc2;
-        const double ta = now_ms();
-        rc2 = cached_sources(ctx, m, dtype, j->src);
-        if (rc2) return rc2;
-        const double tb = now_ms();
-        rc2 = from_ctx(ctx, make_program(ctx->c, *j->src, std::move(batches), j->pg, cache_ok));
-        if (rc2) return rc2;
-        g_timing[0] = ta - tp;
-        g_timing[1] = tb - ta;
-        g_timing[2] = now_ms() - tb;
-        g_timing[7] = j->pg.arena_reused ? 1.0 : 0.0;
-        g_timing[8] = j->pg.arena_alloc_ms;
-        return (int)BNPP_OK;
-    }, job);
-    const double t1 = now_ms();
-    double launch_ms = 0, fetch_ms = 0;
-    if (rc == BNPP_OK && (job->pg.parts.size() != 1 || job->batch_rows < 1))
+    BatchRun run(ctx, c, t0);
+    int rc = batch_open(run);
+    if (rc == BNPP_OK && (run.job->pg.parts.size() != 1 || run.job->batch_rows < 1))
         rc = set_err(BNPP_ERR_INVALID, "counts job without a plan");
     void *d_acc = nullptr;
     size_t acc_cap = 0;
     if (rc == BNPP_OK) {
-        Executable &ex = job->pg.parts[0];
+        batch_stage(run);
+        Executable &ex = run.job->pg.parts[0];
         const Schedule &sc = ex.sched;
-        const int64_t R = job->batch_rows, n_launch = (n_rows + R - 1) / R;
-        // the evidence table of the gather steps and the weights table of the accumulate steps
-        int32_t *d_ev = nullptr;
+        const int64_t R = run.R, nb = run.has_b ? R : 1;
+        // the weights table of the accumulate steps, and every launch's weights (padding: 0)
         double *d_w = nullptr;
-        for (const Schedule::Group &g : sc.groups) {
-            const BucketDesc &bd = sc.descs[g.begin];
-            if (g.variant == kCondBatchKey && bd.in_table[1] >= 0) d_ev = static_cast<int32_t *>(ex.h_meta[bd.in_table[1]].ptr);
-            if (g.variant == kCountsKey && sc.pool[bd.dim_off + 8] >= 0)
-                d_w = static_cast<double *>(ex.h_meta[sc.pool[bd.dim_off + 8]].ptr);
-        }
-        // every launch's rows, variable-major, the last launch padded with its last row, and its
-        // weights; kept to the end of the call (the copies are enqueued)
-        std::vector<int32_t> hev;
-        if (d_ev) {
-            hev.resize((size_t)(n_launch * n_ev * R));
-            for (int64_t L = 0; L < n_launch; ++L)
-                for (int j = 0; j < n_ev; ++j)
-                    for (int64_t b = 0; b < R; ++b)
-                        hev[(size_t)((L * n_ev + j) * R + b)] = ev_vals[std::min(L * R + b, n_rows - 1) * n_ev + j];
-        }
-        std::vector<double> hw((size_t)(n_launch * R), 0.0);
+        for (const Schedule::Group &g : sc.groups)
+            if (g.variant == kCountsKey && sc.pool[sc.descs[g.begin].dim_off + 8] >= 0)
+                d_w = static_cast<double *>(ex.h_meta[sc.pool[sc.descs[g.begin].dim_off + 8]].ptr);
+        std::vector<double> hw((size_t)(run.n_launch * R), 0.0);
         for (int64_t r = 0; r < n_rows; ++r) hw[(size_t)r] = weights ? weights[r] : 1.0;
-        const std::vector<int> &rv = sc.plan_result_vars[0];
-        const int Bv = (int)d.cards.size();
-        const bool has_b = std::find(rv.begin(), rv.end(), Bv) != rv.end();
-        const int64_t nb = has_b ? R : 1;
         if (n_impossible) *n_impossible = 0;
         hipError_t e = hipSetDevice(ctx->c.device);
         if (e == hipSuccess) e = get_buffer(ctx->c, (size_t)std::max<int64_t>(total, 1) * sizeof(double), &d_acc, &acc_cap);
@@ -1942,42 +1788,28 @@ int run_counts(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars,
         if (e != hipSuccess) rc = set_err(e == hipErrorOutOfMemory ? BNPP_ERR_OOM : BNPP_ERR_HIP,
                                           std::string("accumulators: ") + hipGetErrorString(e));
         ex.counts_acc = static_cast<double *>(d_acc);
-        for (int64_t L = 0; L < n_launch && rc == BNPP_OK; ++L) {
-            const double ta = now_ms();
-            if (d_ev) e = hipMemcpyAsync(d_ev, hev.data() + (size_t)(L * n_ev * R), (size_t)(n_ev * R) * sizeof(int32_t),
-                                         hipMemcpyHostToDevice, ctx->c.stream);
-            if (e == hipSuccess && d_w)
+        auto before = [&](int64_t L, int64_t rows) {
+            if (d_w) {
                 e = hipMemcpyAsync(d_w, hw.data() + (size_t)(L * R), (size_t)R * sizeof(double), hipMemcpyHostToDevice,
                                    ctx->c.stream);
-            if (e != hipSuccess) {
-                rc = set_err(BNPP_ERR_HIP, std::string("hipMemcpyAsync(evidence): ") + hipGetErrorString(e));
-                break;
+                if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("hipMemcpyAsync(evidence): ") + hipGetErrorString(e));
             }
-            const int64_t rows = std::min(R, n_rows - L * R);
             ex.counts_rows = rows;
-            rc = from_ctx(ctx, launch_program(ctx->c, job->pg, ctx->c.stream));
-            const double tb = now_ms();
-            launch_ms += tb - ta;
-            if (rc) break;
-            std::vector<std::vector<double>> vals;
-            std::vector<int64_t> exp2;
-            rc = from_ctx(ctx, fetch_program(ctx->c, job->pg, ctx->c.stream, vals, exp2));   // waits for the stream
-            if (rc) break;
-            const std::vector<double> &r = vals[0];
-            if ((int64_t)r.size() != nb) {
-                rc = set_err(BNPP_ERR_INVALID, "counts result table of an unexpected size");
-                break;
-            }
-            for (int64_t b = 0; b < rows; ++b) {            // as run_batch
+            return (int)BNPP_OK;
+        };
+        std::vector<double> r;
+        int64_t exp2 = 0;
+        if (rc == BNPP_OK) rc = batch_launches(run, before, [&](int64_t L, int64_t rows) {
+            if (int rc2 = batch_fetch_doubles(run, r, exp2)) return rc2;
+            if ((int64_t)r.size() != nb) return set_err(BNPP_ERR_INVALID, "counts result table of an unexpected size");
+            for (int64_t b = 0; b < rows; ++b) {
                 double p = 0;
-                p += r[has_b ? b : 0];
-                int pe = 0;
-                const double pm = std::frexp(p, &pe);
-                if (log10_z) log10_z[L * R + b] = p > 0 ? std::log10(pm) + (double)(exp2[0] + pe) * std::log10(2.0) : -INFINITY;
+                p += r[run.has_b ? b : 0];
+                if (log10_z) log10_z[L * R + b] = log10_scaled(p, exp2);
                 if (n_impossible && !(p > 0)) ++*n_impossible;
             }
-            fetch_ms += now_ms() - tb;
-        }
+            return (int)BNPP_OK;
+        });
         ex.counts_acc = nullptr;
         if (rc == BNPP_OK && total > 0) {
             e = hipMemcpy(counts, d_acc, (size_t)total * sizeof(double), hipMemcpyDeviceToHost);
@@ -1988,12 +1820,31 @@ int run_counts(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars,
         (void)hipStreamSynchronize(ctx->c.stream);
         put_buffer(ctx->c, d_acc, acc_cap);
     }
-    const double t3 = now_ms();
-    oneshot_done(ctx, cache_ok, key, budget, job, rc);
-    record_call_timing(t0, t1, t1 + launch_ms, t3);
-    g_timing[4] = fetch_ms;
-    if (rc) return rc;
-    if (uptime_ms) *uptime_ms = now_ms() - t0;
+    return batch_close(run, rc, uptime_ms);
+}
+
+// the launch groups of schedule `batch`, from row n of the caller's rows on: the rows after them
+int64_t copy_group_rows(const Schedule &s, int64_t batch, int64_t *rows, int64_t cap_rows, int64_t n) {
+    for (const Schedule::Group &g : s.groups) {
+        if (n < cap_rows) {
+            const int64_t v[BNPP_PLAN_GROUP_FIELDS] = {batch, g.level, g.variant, g.end - g.begin, g.vblocks, g.lane};
+            std::copy(v, v + BNPP_PLAN_GROUP_FIELDS, rows + n * BNPP_PLAN_GROUP_FIELDS);
+        }
+        ++n;
+    }
+    return n;
+}
+
+// a batched plan entry point: the null checks, the variable set, the schedule (and its plan), the
+// group rows.  st: at least 10 stats, which plan_batch_schedule fills
+int plan_batch_entry(const BatchCall &c, bool posterior, double *stats, int n_stats, int64_t *rows, int cap_rows,
+                     int *n_rows, Schedule &s, VEPlan &plan, double *st) {
+    if (!c.m || !n_rows || (cap_rows > 0 && !rows) || (n_stats > 0 && !stats)) return set_err(BNPP_ERR_INVALID, "null argument");
+    if (int rc = batch_check_vars(c.m->d, c.n_ev, c.ev_vars, c.target, posterior)) return rc;
+    if (c.K < 1) return set_err(BNPP_ERR_INVALID, "n_per_row must be at least 1");
+    int64_t R = 0;
+    if (int rc = plan_batch_schedule(c, memory_budget(nullptr), kBatchAutoRows, s, st, R, &plan)) return rc;
+    *n_rows = (int)copy_group_rows(s, 0, rows, cap_rows, 0);
     return BNPP_OK;
 }
 
@@ -2013,8 +1864,10 @@ int bnpp_expected_counts(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int
                          int dtype, int64_t rows_per_launch, double *counts, double *log10_z, int64_t *n_impossible,
                          double *uptime_ms) {
     BNPP_GUARD_BEGIN
-    return run_counts(ctx, m, n_ev, ev_vars, n_rows, ev_vals, weights, heuristic, order, n_order, dtype, rows_per_launch,
-                      counts, log10_z, n_impossible, uptime_ms);
+    BatchCall c = batch_call(m, kKindCounts, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
+    c.n_rows = n_rows;
+    c.ev_vals = ev_vals;
+    return run_counts(ctx, c, weights, counts, log10_z, n_impossible, uptime_ms);
     BNPP_GUARD_END
 }
 
@@ -2022,28 +1875,14 @@ int bnpp_plan_counts(const bnpp_model *m, int n_ev, const int *ev_vars, int heur
                      int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows, int cap_rows,
                      int *n_rows, int *belief_off, int *belief_vars, int cap_belief, int *n_belief, int *no_b_elim) {
     BNPP_GUARD_BEGIN
-    if (!m || !n_rows || (cap_rows > 0 && !rows) || (n_stats > 0 && !stats)) return set_err(BNPP_ERR_INVALID, "null argument");
-    if (int rc = batch_check_vars(m->d, n_ev, ev_vars, -1, false)) return rc;
     Schedule s;
     VEPlan plan;
     double st[12] = {0};
-    int64_t R = 0;
-    int width = 0;
-    int rc = plan_batch_schedule(m->d, n_ev, ev_vars, heuristic, order, n_order, -1, dtype, memory_budget(nullptr),
-                                 rows_per_launch, s, st, R, width, kBatchAutoRows, kBatchCounts, &plan);
-    if (rc) return rc;
-    int64_t n = 0;
-    for (const Schedule::Group &g : s.groups) {
-        if (n < cap_rows) {
-            const int64_t v[BNPP_PLAN_GROUP_FIELDS] = {0, g.level, g.variant, g.end - g.begin, g.vblocks, g.lane};
-            std::copy(v, v + BNPP_PLAN_GROUP_FIELDS, rows + n * BNPP_PLAN_GROUP_FIELDS);
-        }
-        st[10] += g.variant == kCountsKey;
-        ++n;
-    }
+    const BatchCall c = batch_call(m, kKindCounts, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
+    if (int rc = plan_batch_entry(c, false, stats, n_stats, rows, cap_rows, n_rows, s, plan, st)) return rc;
+    for (const Schedule::Group &g : s.groups) st[10] += g.variant == kCountsKey;
     st[11] = plan.counts_fwd_levels;
     for (int i = 0; i < n_stats && i < 12; ++i) stats[i] = st[i];
-    *n_rows = (int)n;
     const int Bv = (int)m->d.cards.size();
     int nb = 0;
     for (size_t f = 0; f < plan.counts_belief_vars.size(); ++f) {
@@ -2795,14 +2634,7 @@ static int plan_groups_rows(const bnpp_model *m, int kind, int n_ev, const int *
                             part, n_parts);
     if (rc) return rc;
     int64_t n = 0;
-    for (size_t b = 0; b < batches.size(); ++b)
-        for (const Schedule::Group &g : batches[b].groups) {
-            if (n < cap_rows) {
-                const int64_t v[BNPP_PLAN_GROUP_FIELDS] = {(int64_t)b, g.level, g.variant, g.end - g.begin, g.vblocks, g.lane};
-                std::copy(v, v + BNPP_PLAN_GROUP_FIELDS, rows + n * BNPP_PLAN_GROUP_FIELDS);
-            }
-            ++n;
-        }
+    for (size_t b = 0; b < batches.size(); ++b) n = copy_group_rows(batches[b], (int64_t)b, rows, cap_rows, n);
     if (n > INT32_MAX) return set_err(BNPP_ERR_UNSUPPORTED, "more launch groups than the count can hold");
     *n_rows = (int)n;
     return BNPP_OK;
@@ -2841,14 +2673,7 @@ int bnpp_plan_sample(const bnpp_model *m, int n_ev, const int *ev_vars, const in
     st[9] = st[11];                                  // bytes of x
     for (int i = 0; i < n_stats && i < 10; ++i) stats[i] = st[i];
     int64_t n = 0;
-    for (size_t b = 0; b < batches.size(); ++b)
-        for (const Schedule::Group &g : batches[b].groups) {
-            if (n < cap_rows) {
-                const int64_t v[BNPP_PLAN_GROUP_FIELDS] = {(int64_t)b, g.level, g.variant, g.end - g.begin, g.vblocks, g.lane};
-                std::copy(v, v + BNPP_PLAN_GROUP_FIELDS, rows + n * BNPP_PLAN_GROUP_FIELDS);
-            }
-            ++n;
-        }
+    for (size_t b = 0; b < batches.size(); ++b) n = copy_group_rows(batches[b], (int64_t)b, rows, cap_rows, n);
     if (n > INT32_MAX) return set_err(BNPP_ERR_UNSUPPORTED, "more launch groups than the count can hold");
     *n_rows = (int)n;
     return BNPP_OK;
@@ -3129,8 +2954,10 @@ int bnpp_partition_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int
                          const int *ev_vals, int heuristic, const int *order, int n_order, int dtype,
                          int64_t rows_per_launch, double *log10_z, double *z, double *uptime_ms) {
     BNPP_GUARD_BEGIN
-    return run_batch(ctx, m, n_ev, ev_vars, n_rows, ev_vals, heuristic, order, n_order, -1, false, dtype, rows_per_launch,
-                     log10_z, z, nullptr, uptime_ms);
+    BatchCall c = batch_call(m, kKindBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
+    c.n_rows = n_rows;
+    c.ev_vals = ev_vals;
+    return run_batch(ctx, c, false, log10_z, z, nullptr, uptime_ms);
     BNPP_GUARD_END
 }
 
@@ -3138,8 +2965,11 @@ int bnpp_posterior_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int
                          const int *ev_vals, int heuristic, int target, int dtype, int64_t rows_per_launch, double *out,
                          double *uptime_ms) {
     BNPP_GUARD_BEGIN
-    return run_batch(ctx, m, n_ev, ev_vars, n_rows, ev_vals, heuristic, nullptr, 0, target, true, dtype, rows_per_launch,
-                     nullptr, nullptr, out, uptime_ms);
+    BatchCall c = batch_call(m, kKindBatch, n_ev, ev_vars, heuristic, nullptr, 0, dtype, rows_per_launch);
+    c.target = target;
+    c.n_rows = n_rows;
+    c.ev_vals = ev_vals;
+    return run_batch(ctx, c, true, nullptr, nullptr, out, uptime_ms);
     BNPP_GUARD_END
 }
 
@@ -3147,8 +2977,10 @@ int bnpp_mpe_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_v
                    int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch, double *log10_value,
                    int *assignment, double *uptime_ms) {
     BNPP_GUARD_BEGIN
-    return run_mpe_batch(ctx, m, n_ev, ev_vars, n_rows, ev_vals, heuristic, order, n_order, dtype, rows_per_launch,
-                         log10_value, assignment, uptime_ms);
+    BatchCall c = batch_call(m, kKindMpeBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
+    c.n_rows = n_rows;
+    c.ev_vals = ev_vals;
+    return run_mpe_batch(ctx, c, log10_value, assignment, uptime_ms);
     BNPP_GUARD_END
 }
 
@@ -3156,16 +2988,11 @@ int bnpp_plan_mpe_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int h
                         int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows, int cap_rows,
                         int *n_rows) {
     BNPP_GUARD_BEGIN
-    if (!m || !n_rows || (cap_rows > 0 && !rows) || (n_stats > 0 && !stats)) return set_err(BNPP_ERR_INVALID, "null argument");
-    if (int rc = batch_check_vars(m->d, n_ev, ev_vars, -1, false)) return rc;
     Schedule s;
     VEPlan plan;
     double st[BNPP_PLAN_MPE_BATCH_STATS] = {0};
-    int64_t R = 0;
-    int width = 0;
-    int rc = plan_batch_schedule(m->d, n_ev, ev_vars, heuristic, order, n_order, -1, dtype, memory_budget(nullptr),
-                                 rows_per_launch, s, st, R, width, kBatchAutoRows, kBatchMpe, &plan);
-    if (rc) return rc;
+    const BatchCall c = batch_call(m, kKindMpeBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
+    if (int rc = plan_batch_entry(c, false, stats, n_stats, rows, cap_rows, n_rows, s, plan, st)) return rc;
     st[10] = (double)plan.arg_bytes;
     st[11] = plan.n_max_buckets;
     st[12] = plan.n_arg_b;
@@ -3173,15 +3000,6 @@ int bnpp_plan_mpe_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int h
     st[14] = (double)plan.arg_b_entries;
     st[15] = (double)plan.arg_nob_entries;
     for (int i = 0; i < n_stats && i < BNPP_PLAN_MPE_BATCH_STATS; ++i) stats[i] = st[i];
-    int64_t n = 0;
-    for (const Schedule::Group &g : s.groups) {
-        if (n < cap_rows) {
-            const int64_t v[BNPP_PLAN_GROUP_FIELDS] = {0, g.level, g.variant, g.end - g.begin, g.vblocks, g.lane};
-            std::copy(v, v + BNPP_PLAN_GROUP_FIELDS, rows + n * BNPP_PLAN_GROUP_FIELDS);
-        }
-        ++n;
-    }
-    *n_rows = (int)n;
     return BNPP_OK;
     BNPP_GUARD_END
 }
@@ -3191,8 +3009,11 @@ int bnpp_sample_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *e
                       int64_t first_sample, int64_t row_stride, uint64_t seed, uint8_t *out, double *log10_z,
                       int64_t *n_degenerate, double *uptime_ms) {
     BNPP_GUARD_BEGIN
-    return run_sample_batch(ctx, m, n_ev, ev_vars, n_rows, ev_vals, heuristic, order, n_order, dtype, rows_per_launch,
-                            n_per_row, first_sample, row_stride, seed, out, log10_z, n_degenerate, uptime_ms);
+    BatchCall c = batch_call(m, kKindSampleBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
+    c.K = n_per_row;
+    c.n_rows = n_rows;
+    c.ev_vals = ev_vals;
+    return run_sample_batch(ctx, c, first_sample, row_stride, seed, out, log10_z, n_degenerate, uptime_ms);
     BNPP_GUARD_END
 }
 
@@ -3200,32 +3021,18 @@ int bnpp_plan_sample_batch(const bnpp_model *m, int n_ev, const int *ev_vars, in
                            int dtype, int64_t rows_per_launch, int64_t n_per_row, double *stats, int n_stats,
                            int64_t *rows, int cap_rows, int *n_rows) {
     BNPP_GUARD_BEGIN
-    if (!m || !n_rows || (cap_rows > 0 && !rows) || (n_stats > 0 && !stats)) return set_err(BNPP_ERR_INVALID, "null argument");
-    if (int rc = batch_check_vars(m->d, n_ev, ev_vars, -1, false)) return rc;
-    if (n_per_row < 1) return set_err(BNPP_ERR_INVALID, "n_per_row must be at least 1");
     Schedule s;
     VEPlan plan;
     double st[BNPP_PLAN_SAMPLE_BATCH_STATS] = {0};
-    int64_t R = 0;
-    int width = 0;
-    int rc = plan_batch_schedule(m->d, n_ev, ev_vars, heuristic, order, n_order, -1, dtype, memory_budget(nullptr),
-                                 rows_per_launch, s, st, R, width, kBatchAutoRows, kBatchSample, &plan, n_per_row);
-    if (rc) return rc;
+    BatchCall c = batch_call(m, kKindSampleBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
+    c.K = n_per_row;
+    if (int rc = plan_batch_entry(c, false, stats, n_stats, rows, cap_rows, n_rows, s, plan, st)) return rc;
     st[10] = (double)n_per_row;
     st[11] = (double)plan.sample_bytes;
     st[12] = plan.n_draw_b + plan.n_draw_nob;
     st[13] = plan.n_draw_b;
     st[14] = plan.n_draw_nob;
     for (int i = 0; i < n_stats && i < BNPP_PLAN_SAMPLE_BATCH_STATS; ++i) stats[i] = st[i];
-    int64_t n = 0;
-    for (const Schedule::Group &g : s.groups) {
-        if (n < cap_rows) {
-            const int64_t v[BNPP_PLAN_GROUP_FIELDS] = {0, g.level, g.variant, g.end - g.begin, g.vblocks, g.lane};
-            std::copy(v, v + BNPP_PLAN_GROUP_FIELDS, rows + n * BNPP_PLAN_GROUP_FIELDS);
-        }
-        ++n;
-    }
-    *n_rows = (int)n;
     return BNPP_OK;
     BNPP_GUARD_END
 }
@@ -3234,25 +3041,14 @@ int bnpp_plan_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuri
                     int target, int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows,
                     int cap_rows, int *n_rows, int *result_scope, int *n_result_scope) {
     BNPP_GUARD_BEGIN
-    if (!m || !n_rows || (cap_rows > 0 && !rows) || (n_stats > 0 && !stats)) return set_err(BNPP_ERR_INVALID, "null argument");
-    if (int rc = batch_check_vars(m->d, n_ev, ev_vars, target, target >= 0)) return rc;
     Schedule s;
+    VEPlan plan;
     double st[10] = {0};
-    int64_t R = 0;
-    int width = 0;
-    int rc = plan_batch_schedule(m->d, n_ev, ev_vars, heuristic, target >= 0 ? nullptr : order, target >= 0 ? 0 : n_order,
-                                 target >= 0 ? target : -1, dtype, memory_budget(nullptr), rows_per_launch, s, st, R, width);
-    if (rc) return rc;
+    BatchCall c = batch_call(m, kKindBatch, n_ev, ev_vars, heuristic, target >= 0 ? nullptr : order,
+                             target >= 0 ? 0 : n_order, dtype, rows_per_launch);
+    c.target = target >= 0 ? target : -1;
+    if (int rc = plan_batch_entry(c, target >= 0, stats, n_stats, rows, cap_rows, n_rows, s, plan, st)) return rc;
     for (int i = 0; i < n_stats && i < 10; ++i) stats[i] = st[i];
-    int64_t n = 0;
-    for (const Schedule::Group &g : s.groups) {
-        if (n < cap_rows) {
-            const int64_t v[BNPP_PLAN_GROUP_FIELDS] = {0, g.level, g.variant, g.end - g.begin, g.vblocks, g.lane};
-            std::copy(v, v + BNPP_PLAN_GROUP_FIELDS, rows + n * BNPP_PLAN_GROUP_FIELDS);
-        }
-        ++n;
-    }
-    *n_rows = (int)n;
     const std::vector<int> &rv = s.plan_result_vars[0];
     if (n_result_scope) *n_result_scope = (int)rv.size();
     if (result_scope)

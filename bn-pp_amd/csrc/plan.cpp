@@ -1980,44 +1980,136 @@ static bool gather_steps(PlanBuilder &B, VEPlan &p, const std::vector<int> &ce, 
     return true;
 }
 
+static bool batch_rows_ok(int64_t rows, std::string *msg) {
+    if (rows >= 1 && rows <= (int64_t)INT32_MAX) return true;
+    if (msg) *msg = "rows per launch must be in [1, 2^31)";
+    return false;
+}
+
+namespace {
+// What the batched planners share: the cards extended by the row variable B
+// (it follows the model's), the builder, level 0 (the gather steps) with each
+// gathered view in its first bucket, the bucket step and the result table
+struct BatchPlan {
+    VEPlan &p;
+    const std::vector<int> &order;
+    const int Bv;
+    std::vector<int> ce;                        // the model's cards, then the rows
+    PlanBuilder B;
+    std::vector<View> placed;                   // per source: itself, or the view of its gather step
+    std::vector<std::vector<View>> buckets;     // per place in the order: the bucket's inputs so far
+    std::vector<View> result;                   // what no bucket takes
+
+    static std::vector<int> with_rows(std::vector<int> c, int64_t rows) {
+        c.push_back((int)rows);
+        return c;
+    }
+    BatchPlan(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &ord, int64_t rows,
+              VEPlan &plan)
+        : p(plan), order(ord), Bv((int)cards.size()), ce(with_rows(cards, rows)),
+          B(ce, p, sources, ord, true),         // chain_eb stays 0: no fused runs
+          buckets(ord.size()) {
+        B.n_real = Bv;                          // finish() records cards_ext
+    }
+    // to the first bucket from `from` on that holds one of the view's variables, else to the result
+    void pass(const View &v, int from) {
+        const int bi = B.first_bucket(v.vars, from);
+        (bi >= 0 ? buckets[bi] : result).push_back(v);
+    }
+    bool gather(const std::vector<View> &sources, const std::vector<int> &ev_vars, int elem_bytes, std::string *msg) {
+        if (!gather_steps(B, p, ce, sources, ev_vars, ce.back(), elem_bytes, placed, msg)) return false;
+        for (const View &s : placed) pass(s, 0);
+        return true;
+    }
+    // emit bucket i and pass its message on: the message's table (the
+    // eliminating bucket is p.buckets.back(), prefix products precede it)
+    int emit_bucket(int i) {
+        const int t = B.emit(buckets[i], order[i], false);
+        pass(B.view(t), i + 1);
+        return t;
+    }
+    void emit_result() {                        // canonical: (target, B), (B) or a scalar
+        if (result.empty()) return;
+        p.result_table = B.emit(result, -1, false);
+        p.result_vars = p.msgs[p.result_table - p.n_src].vars;
+    }
+    // the table a trailing step (traceback, draws) writes, `bytes` in whole elements, and its level: the last
+    void add_last_step(BucketSpec &s, int64_t bytes, int elem_bytes) {
+        s.out_table = B.new_raw((bytes + elem_bytes - 1) / elem_bytes);
+        s.level = B.last_level + 1;
+        B.last_level = s.level;
+        B.level[s.out_table] = s.level;
+        p.buckets.push_back(s);
+        p.results = {p.result_table, s.out_table};
+        p.results_vars = {p.result_vars, {}};
+    }
+};
+
+// The bucket tree of an elimination order (plan_bucket_tree, plan_counts):
+// the collect pass emits the VE buckets and remembers which bucket takes each
+// message, the distribute pass sends a message down every edge
+struct BucketTree {
+    PlanBuilder &B;
+    std::vector<std::vector<View>> src_in;      // per bucket: the sources placed in it
+    std::vector<std::vector<int>> children;
+    std::vector<int> lam;                       // per bucket: its message's table, -1 for an empty bucket
+    std::vector<View> pi;
+    std::vector<char> has_pi;
+
+    BucketTree(PlanBuilder &b, int nord)
+        : B(b), src_in(nord), children(nord), lam(nord, -1), pi(nord), has_pi(nord, 0) {}
+    View lam_view(int c) const { return B.view(lam[c]); }
+    // forward (collect) pass: exactly the VE buckets of plan_ve, remembering
+    // the tree; a message no bucket takes goes to `result` where one is given
+    void collect(const std::vector<int> &order, std::vector<View> *result) {
+        for (int i = 0; i < (int)order.size(); ++i) {
+            std::vector<View> in = src_in[i];
+            for (int c : children[i]) in.push_back(lam_view(c));
+            if (in.empty()) continue;
+            lam[i] = B.emit(in, order[i], false);
+            const int par = B.first_bucket(B.p.msgs[lam[i] - B.p.n_src].vars, i + 1);
+            if (par >= 0) children[par].push_back(i);
+            else if (result) result->push_back(lam_view(i));
+        }
+    }
+    // what bucket q multiplies, but for the message of its child `skip` (-1: the whole belief)
+    std::vector<View> inputs(int q, int skip) const {
+        std::vector<View> in = src_in[q];
+        if (has_pi[q]) in.push_back(pi[q]);
+        for (int c : children[q])
+            if (c != skip) in.push_back(lam_view(c));
+        return in;
+    }
+    // backward (distribute) pass, parents before children:
+    // pi_i = sum_{scope(p) \ sep_i} F_p * pi_p * prod_{c != i} lam_c,
+    // where reduce(in, sep_i) sums the product of `in` down to the separator
+    template <typename Reduce>
+    void distribute(Reduce &&reduce) {
+        for (int q = (int)lam.size() - 1; q >= 0; --q) {
+            if (lam[q] < 0) continue;
+            for (int i : children[q]) {
+                const std::vector<View> in = inputs(q, i);
+                if (in.empty()) continue;                    // constant 1
+                pi[i] = reduce(in, B.p.msgs[lam[i] - B.p.n_src].vars);
+                has_pi[i] = 1;
+            }
+        }
+    }
+};
+}  // namespace
+
 bool plan_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                 const std::vector<int> &ev_vars, int64_t rows, int target, int elem_bytes, VEPlan &out,
                 std::string *msg) {
     out = VEPlan{};
-    VEPlan &p = out;
-    if (rows < 1 || rows > (int64_t)INT32_MAX) {
-        if (msg) *msg = "rows per launch must be in [1, 2^31)";
-        return false;
-    }
-    const int nv = (int)cards.size();
-    std::vector<int> ce = cards;
-    ce.push_back((int)rows);                                // the row variable follows the model's
-    PlanBuilder B(ce, p, sources, order, true);             // chain_eb stays 0: no fused runs
-    B.n_real = nv;                                          // finish() records cards_ext
+    if (!batch_rows_ok(rows, msg)) return false;
     (void)target;                                           // kept: it is not in `order`, canon() lays it before B
-    std::vector<View> placed;
-    if (!gather_steps(B, p, ce, sources, ev_vars, rows, elem_bytes, placed, msg)) return false;
-    const int nord = (int)order.size();
-    std::vector<std::vector<View>> buckets(nord);
-    std::vector<View> result;
-    for (const View &s : placed) {
-        int bi = B.first_bucket(s.vars, 0);
-        if (bi >= 0) buckets[bi].push_back(s);
-        else result.push_back(s);
-    }
-    for (int i = 0; i < nord; ++i) {
-        if (buckets[i].empty()) continue;
-        const int t = B.emit(buckets[i], order[i], false);
-        View mv = B.view(t);
-        int bi = B.first_bucket(mv.vars, i + 1);
-        if (bi >= 0) buckets[bi].push_back(mv);
-        else result.push_back(mv);
-    }
-    if (!result.empty()) {
-        p.result_table = B.emit(result, -1, false);         // canonical: (target, B)
-        p.result_vars = p.msgs[p.result_table - p.n_src].vars;
-    }
-    B.finish();
+    BatchPlan S(cards, sources, order, rows, out);
+    if (!S.gather(sources, ev_vars, elem_bytes, msg)) return false;
+    for (size_t i = 0; i < order.size(); ++i)
+        if (!S.buckets[i].empty()) S.emit_bucket((int)i);
+    S.emit_result();
+    S.B.finish();
     return true;
 }
 
@@ -2025,42 +2117,26 @@ bool plan_mpe_batch(const std::vector<int> &cards, const std::vector<View> &sour
                     const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg) {
     out = VEPlan{};
     VEPlan &p = out;
-    if (rows < 1 || rows > (int64_t)INT32_MAX) {
-        if (msg) *msg = "rows per launch must be in [1, 2^31)";
-        return false;
-    }
-    const int nv = (int)cards.size(), Bv = nv;
-    std::vector<int> ce = cards;
-    ce.push_back((int)rows);
-    PlanBuilder B(ce, p, sources, order, true);             // chain_eb stays 0: no fused runs
-    B.n_real = nv;
-    std::vector<View> placed;
-    if (!gather_steps(B, p, ce, sources, ev_vars, rows, elem_bytes, placed, msg)) return false;
-    const int nord = (int)order.size();
-    std::vector<std::vector<View>> buckets(nord);
-    std::vector<View> result;
-    for (const View &s : placed) {
-        int bi = B.first_bucket(s.vars, 0);
-        if (bi >= 0) buckets[bi].push_back(s);
-        else result.push_back(s);
-    }
+    if (!batch_rows_ok(rows, msg)) return false;
+    BatchPlan S(cards, sources, order, rows, p);
+    if (!S.gather(sources, ev_vars, elem_bytes, msg)) return false;
     std::vector<BucketSpec::DecodeRow> drows;
-    for (int i = 0; i < nord; ++i) {
-        if (buckets[i].empty()) continue;   // a variable in no remaining factor: the assignment keeps 0
+    for (int i = 0; i < (int)order.size(); ++i) {
+        if (S.buckets[i].empty()) continue;   // a variable in no remaining factor: the assignment keeps 0
         if (cards[order[i]] > kMaxOutCard) {
             if (msg) *msg = "MPE: variable " + std::to_string(order[i]) + " has " + std::to_string(cards[order[i]]) +
                             " values; the arg tables hold one byte per entry (at most " + std::to_string(kMaxOutCard) + ")";
             return false;
         }
-        const int t = B.emit(buckets[i], order[i], false);
-        BucketSpec &bk = p.buckets.back();              // the eliminating bucket (prefix products precede it)
+        const int t = S.emit_bucket(i);
+        BucketSpec &bk = p.buckets.back();
         const int64_t entries = p.msgs[t - p.n_src].size;
         bk.max_out = true;
-        bk.arg_table = B.new_raw((entries + elem_bytes - 1) / elem_bytes);   // bytes, in whole elements
-        B.level[bk.arg_table] = bk.level;
+        bk.arg_table = S.B.new_raw((entries + elem_bytes - 1) / elem_bytes);   // bytes, in whole elements
+        S.B.level[bk.arg_table] = bk.level;
         p.arg_bytes = sat_add(p.arg_bytes, entries);
         ++p.n_max_buckets;
-        if (!bk.out_vars.empty() && bk.out_vars.back() == Bv) {
+        if (!bk.out_vars.empty() && bk.out_vars.back() == S.Bv) {
             ++p.n_arg_b;
             p.arg_b_entries = sat_add(p.arg_b_entries, entries / rows);
         } else {
@@ -2072,17 +2148,10 @@ bool plan_mpe_batch(const std::vector<int> &cards, const std::vector<View> &sour
         row.elim_var = order[i];
         row.depth = 0;
         row.vars = bk.out_vars;
-        row.strides = natural_strides(bk.out_vars, ce);
+        row.strides = natural_strides(bk.out_vars, S.ce);
         drows.push_back(row);
-        View mv = B.view(t);
-        int bi = B.first_bucket(mv.vars, i + 1);
-        if (bi >= 0) buckets[bi].push_back(mv);
-        else result.push_back(mv);
     }
-    if (!result.empty()) {
-        p.result_table = B.emit(result, -1, false);         // canonical: (B), or a scalar
-        p.result_vars = p.msgs[p.result_table - p.n_src].vars;
-    }
+    S.emit_result();
     BucketSpec dec;
     dec.decode_batch = true;
     dec.decode_batch_rows = rows;
@@ -2097,15 +2166,8 @@ bool plan_mpe_batch(const std::vector<int> &cards, const std::vector<View> &sour
         v.table = p.batch_ev_table;
         dec.in.push_back(v);
     }
-    const int64_t xbytes = std::max<int64_t>(sat_mul((int64_t)nv, rows), 8);
-    dec.out_table = B.new_raw((xbytes + elem_bytes - 1) / elem_bytes);
-    dec.level = B.last_level + 1;
-    B.last_level = dec.level;
-    B.level[dec.out_table] = dec.level;
-    p.buckets.push_back(dec);
-    p.results = {p.result_table, dec.out_table};
-    p.results_vars = {p.result_vars, {}};
-    B.finish();
+    S.add_last_step(dec, std::max<int64_t>(sat_mul((int64_t)cards.size(), rows), 8), elem_bytes);
+    S.B.finish();
     return true;
 }
 
@@ -2114,55 +2176,32 @@ bool plan_sample_batch(const std::vector<int> &cards, const std::vector<View> &s
                        std::string *msg) {
     out = VEPlan{};
     VEPlan &p = out;
-    if (rows < 1 || rows > (int64_t)INT32_MAX) {
-        if (msg) *msg = "rows per launch must be in [1, 2^31)";
-        return false;
-    }
+    if (!batch_rows_ok(rows, msg)) return false;
     if (n_per_row < 1) {
         if (msg) *msg = "n_per_row must be at least 1";
         return false;
     }
-    const int nv = (int)cards.size(), Bv = nv;
-    std::vector<int> ce = cards;
-    ce.push_back((int)rows);
-    PlanBuilder B(ce, p, sources, order, true);             // chain_eb stays 0: no fused runs
-    B.n_real = nv;
-    std::vector<View> placed;
-    if (!gather_steps(B, p, ce, sources, ev_vars, rows, elem_bytes, placed, msg)) return false;
-    const int nord = (int)order.size();
-    std::vector<std::vector<View>> buckets(nord);
-    std::vector<View> result;
-    for (const View &s : placed) {
-        int bi = B.first_bucket(s.vars, 0);
-        if (bi >= 0) buckets[bi].push_back(s);
-        else result.push_back(s);
-    }
-    std::vector<BucketSpec::SampleRow> rws(nord);
-    for (int i = 0; i < nord; ++i) {
+    BatchPlan S(cards, sources, order, rows, p);
+    if (!S.gather(sources, ev_vars, elem_bytes, msg)) return false;
+    std::vector<BucketSpec::SampleRow> rws(order.size());
+    for (int i = 0; i < (int)order.size(); ++i) {
         if (cards[order[i]] > kMaxOutCard) {
             if (msg) *msg = "sampling: variable " + std::to_string(order[i]) + " has " + std::to_string(cards[order[i]]) +
                             " values; the samples hold one byte per variable (at most " + std::to_string(kMaxOutCard) + ")";
             return false;
         }
         rws[i].var = order[i];
-        if (buckets[i].empty()) {           // a variable in no remaining factor: an input-less row, a uniform draw
+        if (S.buckets[i].empty()) {         // a variable in no remaining factor: an input-less row, a uniform draw
             ++p.n_draw_nob;
             continue;
         }
-        const int t = B.emit(buckets[i], order[i], false);
-        rws[i].in = p.buckets.back().in;    // the eliminating bucket's own views (pure-product prefixes precede it)
+        S.emit_bucket(i);
+        rws[i].in = p.buckets.back().in;    // the eliminating bucket's own views
         bool has_b = false;
-        for (const View &v : rws[i].in) has_b = has_b || std::find(v.vars.begin(), v.vars.end(), Bv) != v.vars.end();
+        for (const View &v : rws[i].in) has_b = has_b || contains(v.vars, S.Bv);
         ++(has_b ? p.n_draw_b : p.n_draw_nob);
-        View mv = B.view(t);
-        int bi = B.first_bucket(mv.vars, i + 1);
-        if (bi >= 0) buckets[bi].push_back(mv);
-        else result.push_back(mv);
     }
-    if (!result.empty()) {
-        p.result_table = B.emit(result, -1, false);         // canonical: (B), or a scalar
-        p.result_vars = p.msgs[p.result_table - p.n_src].vars;
-    }
+    S.emit_result();
     BucketSpec smp;
     smp.sample_batch = true;
     smp.sample_batch_rows = rows;
@@ -2182,17 +2221,10 @@ bool plan_sample_batch(const std::vector<int> &cards, const std::vector<View> &s
         smp.in.push_back(v);
     }
     smp.sample_rows.assign(rws.rbegin(), rws.rend());
-    p.sample_bytes = sat_mul(sat_mul((int64_t)nv, rows), n_per_row);
+    p.sample_bytes = sat_mul(sat_mul((int64_t)cards.size(), rows), n_per_row);
     // x, then int64[rows] degenerate draws per row
-    const int64_t xbytes = sat_add(sample_counter_offset(1, p.sample_bytes), sat_mul(rows, 8));
-    smp.out_table = B.new_raw((xbytes + elem_bytes - 1) / elem_bytes);
-    smp.level = B.last_level + 1;
-    B.last_level = smp.level;
-    B.level[smp.out_table] = smp.level;
-    p.buckets.push_back(smp);
-    p.results = {p.result_table, smp.out_table};
-    p.results_vars = {p.result_vars, {}};
-    B.finish();
+    S.add_last_step(smp, sat_add(sample_counter_offset(1, p.sample_bytes), sat_mul(rows, 8)), elem_bytes);
+    S.B.finish();
     return true;
 }
 
@@ -2200,110 +2232,41 @@ bool plan_counts(const std::vector<int> &cards, const std::vector<View> &sources
                  const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg) {
     out = VEPlan{};
     VEPlan &p = out;
-    if (rows < 1 || rows > (int64_t)INT32_MAX) {
-        if (msg) *msg = "rows per launch must be in [1, 2^31)";
-        return false;
-    }
-    const int nv = (int)cards.size(), Bv = nv;              // the row variable follows the model's
-    std::vector<int> ce = cards;
-    ce.push_back((int)rows);
-    PlanBuilder B(ce, p, sources, order, true);             // chain_eb stays 0: no fused runs
-    B.n_real = nv;                                          // finish() records cards_ext
-    std::vector<int> row_of(nv, -1);
+    if (!batch_rows_ok(rows, msg)) return false;
+    BatchPlan S(cards, sources, order, rows, p);
+    PlanBuilder &B = S.B;
+    const int Bv = S.Bv;
+    // level 0: plan_batch's gather steps, in its order
+    if (!S.gather(sources, ev_vars, elem_bytes, msg)) return false;
+    std::vector<int> row_of(cards.size(), -1), bucket_of(S.placed.size(), -1);
     for (size_t i = 0; i < ev_vars.size(); ++i) row_of[ev_vars[i]] = (int)i;
+    for (size_t f = 0; f < S.placed.size(); ++f) {
+        for (int v : S.placed[f].vars)
+            if (v != Bv && B.rank[v] < 0) {
+                if (msg) *msg = "the order leaves out variable " + std::to_string(v) + ", which is no evidence variable";
+                return false;
+            }
+        bucket_of[f] = B.first_bucket(S.placed[f].vars, 0);
+    }
+    // forward (collect) pass: plan_batch's buckets, remembering the tree
+    BucketTree T(B, (int)order.size());
+    T.src_in = S.buckets;
+    T.collect(order, &S.result);
+    S.emit_result();
+    p.counts_fwd_levels = B.last_level;
+    B.floor_level = B.last_level;                           // the backward pass and the beliefs: levels of their own
+    // a reduction keeps `keep` and, when any input carries it, B
+    auto reduce = [&](const std::vector<View> &in, std::vector<int> keep) {
+        for (const View &v : in)
+            if (contains(v.vars, Bv) && !contains(keep, Bv)) keep.push_back(Bv);
+        return B.view(B.reduce_keep(in, keep));
+    };
+    T.distribute(reduce);
     auto raw_bytes = [&](int64_t bytes) {
         const int t = B.new_raw((bytes + elem_bytes - 1) / elem_bytes);
         B.level[t] = 0;
         return t;
     };
-    // level 0: plan_batch's gather steps, in its order
-    std::vector<View> placed;
-    for (const View &s : sources) {
-        bool any = false;
-        for (int v : s.vars) any = any || row_of[v] >= 0;
-        if (!any) {
-            placed.push_back(s);
-            continue;
-        }
-        if (p.batch_ev_table < 0) p.batch_ev_table = raw_bytes(sat_mul(sat_mul((int64_t)ev_vars.size(), rows), 4));
-        BucketSpec g;
-        g.cond_batch = true;
-        g.in.push_back(s);
-        View evt;
-        evt.table = p.batch_ev_table;
-        g.in.push_back(evt);
-        for (int v : s.vars) {
-            g.cond_rows.push_back(row_of[v]);
-            if (row_of[v] < 0) g.out_vars.push_back(v);
-        }
-        g.out_vars.push_back(Bv);
-        {
-            BucketDesc d;
-            std::vector<int64_t> pool;
-            if (!build_desc(g, ce, 1, d, pool, msg)) return false;
-        }
-        g.out_table = B.new_msg(g.out_vars);
-        g.level = 0;
-        B.level[g.out_table] = 0;
-        p.elems_moved += 2.0 * (double)p.msgs[g.out_table - p.n_src].size;
-        p.buckets.push_back(g);
-        placed.push_back(B.view(g.out_table));
-    }
-    // forward (collect) pass: plan_batch's buckets, remembering the tree
-    const int nord = (int)order.size();
-    std::vector<std::vector<View>> src_in(nord);
-    std::vector<std::vector<int>> children(nord);
-    std::vector<int> lam(nord, -1), bucket_of(placed.size(), -1);
-    std::vector<View> result;
-    for (size_t f = 0; f < placed.size(); ++f) {
-        const View &s = placed[f];
-        for (int v : s.vars)
-            if (v != Bv && B.rank[v] < 0) {
-                if (msg) *msg = "the order leaves out variable " + std::to_string(v) + ", which is no evidence variable";
-                return false;
-            }
-        const int bi = B.first_bucket(s.vars, 0);
-        bucket_of[f] = bi;
-        if (bi >= 0) src_in[bi].push_back(s);
-        else result.push_back(s);
-    }
-    auto lam_view = [&](int c) { return B.view(lam[c]); };
-    for (int i = 0; i < nord; ++i) {
-        std::vector<View> in = src_in[i];
-        for (int c : children[i]) in.push_back(lam_view(c));
-        if (in.empty()) continue;
-        lam[i] = B.emit(in, order[i], false);
-        const int par = B.first_bucket(p.msgs[lam[i] - p.n_src].vars, i + 1);
-        if (par >= 0) children[par].push_back(i);
-        else result.push_back(lam_view(i));
-    }
-    if (!result.empty()) {
-        p.result_table = B.emit(result, -1, false);         // over (B), or a scalar
-        p.result_vars = p.msgs[p.result_table - p.n_src].vars;
-    }
-    p.counts_fwd_levels = B.last_level;
-    B.floor_level = B.last_level;                           // the backward pass and the beliefs: levels of their own
-    // what a reduction keeps: `keep` and, when any input carries it, B
-    auto with_b = [&](const std::vector<View> &in, std::vector<int> keep) {
-        for (const View &v : in)
-            if (contains(v.vars, Bv) && !contains(keep, Bv)) keep.push_back(Bv);
-        return keep;
-    };
-    // backward (distribute) pass, parents before children (plan_bucket_tree)
-    std::vector<View> pi(nord);
-    std::vector<char> has_pi(nord, 0);
-    for (int q = nord - 1; q >= 0; --q) {
-        if (lam[q] < 0) continue;
-        for (int i : children[q]) {
-            std::vector<View> in = src_in[q];
-            if (has_pi[q]) in.push_back(pi[q]);
-            for (int c : children[q])
-                if (c != i) in.push_back(lam_view(c));
-            if (in.empty()) continue;                        // constant 1
-            pi[i] = B.view(B.reduce_keep(in, with_b(in, p.msgs[lam[i] - p.n_src].vars)));
-            has_pi[i] = 1;
-        }
-    }
     // per factor: the belief of its bucket summed down to (scope minus evidence, B), then its accumulate step
     p.counts_w_table = raw_bytes(sat_mul(rows, 8));
     const bool valid_b = contains(p.result_vars, Bv);
@@ -2311,15 +2274,12 @@ bool plan_counts(const std::vector<int> &cards, const std::vector<View> &sources
     std::vector<BucketSpec> steps;
     for (size_t f = 0; f < sources.size(); ++f) {
         const int i = bucket_of[f];
-        View belief = placed[f];                            // no variable left: the factor is its own belief
+        View belief = S.placed[f];                          // no variable left: the factor is its own belief
         if (i >= 0) {
-            std::vector<View> in = src_in[i];
-            if (has_pi[i]) in.push_back(pi[i]);
-            for (int c : children[i]) in.push_back(lam_view(c));
             std::vector<int> keep;
             for (int v : sources[f].vars)
                 if (row_of[v] < 0) keep.push_back(v);
-            belief = B.view(B.reduce_keep(in, with_b(in, keep)));
+            belief = reduce(T.inputs(i, -1), keep);
         }
         BucketSpec c;
         c.counts = true;
@@ -2345,10 +2305,10 @@ bool plan_counts(const std::vector<int> &cards, const std::vector<View> &sources
         {
             BucketDesc d;
             std::vector<int64_t> pool;
-            if (!build_desc(c, ce, 1, d, pool, msg)) return false;
+            if (!build_desc(c, S.ce, 1, d, pool, msg)) return false;
         }
         c.out_table = B.new_raw(1);
-        p.elems_moved += (double)table_size(belief.vars, ce);
+        p.elems_moved += (double)table_size(belief.vars, S.ce);
         steps.push_back(c);
         p.counts_belief_vars.push_back(belief.vars);
     }
@@ -2368,55 +2328,24 @@ VEPlan plan_bucket_tree(const std::vector<int> &cards, const std::vector<View> &
                         const std::vector<int> &order, const std::vector<int> &targets, int part, int n_parts) {
     VEPlan p;
     PlanBuilder B(cards, p, sources, order, true);
-    const int nord = (int)order.size();
-    // forward (collect) pass: exactly the VE buckets of plan_ve, remembering the tree
-    std::vector<std::vector<View>> src_in(nord);
-    std::vector<std::vector<int>> children(nord);
-    std::vector<int> lam(nord, -1);
+    BucketTree T(B, (int)order.size());
     for (const View &s : sources) {
         int bi = B.first_bucket(s.vars, 0);
-        if (bi >= 0) src_in[bi].push_back(s);   // else: a constant, cancels in every marginal
+        if (bi >= 0) T.src_in[bi].push_back(s);   // else: a constant, cancels in every marginal
     }
-    auto lam_view = [&](int c) { return B.view(lam[c]); };
-    for (int i = 0; i < nord; ++i) {
-        std::vector<View> in = src_in[i];
-        for (int c : children[i]) in.push_back(lam_view(c));
-        if (in.empty()) continue;
-        lam[i] = B.emit(in, order[i], false);
-        int par = B.first_bucket(p.msgs[lam[i] - p.n_src].vars, i + 1);
-        if (par >= 0) children[par].push_back(i);
-    }
+    T.collect(order, nullptr);
     // sum everything in `in` except `keep` (elimination-rank order): one fused
     // bucket for the first variable, then single-input sums
-    auto reduce = [&](const std::vector<View> &in, const std::vector<int> &keep, bool materialise) -> View {
+    T.distribute([&](const std::vector<View> &in, const std::vector<int> &keep) -> View {
         std::vector<int> y;
         for (int v : chain_scope(in))
             if (std::find(keep.begin(), keep.end(), v) == keep.end()) y.push_back(v);
         std::sort(y.begin(), y.end(), [&](int a, int b) { return B.rank[a] < B.rank[b]; });
-        if (y.empty()) {
-            if (in.size() == 1 && !(materialise && (in[0].table < p.n_src || in[0].base != 0))) return in[0];
-            return B.view(B.emit(in, -1, false));
-        }
+        if (y.empty()) return in.size() == 1 ? in[0] : B.view(B.emit(in, -1, false));
         int t = B.emit(in, y[0], false);
         for (size_t j = 1; j < y.size(); ++j) t = B.emit({B.view(t)}, y[j], false);
         return B.view(t);
-    };
-    // backward (distribute) pass, parents before children:
-    // pi_i = sum_{scope(p) \ sep_i} F_p * pi_p * prod_{c != i} lam_c
-    std::vector<View> pi(nord);
-    std::vector<char> has_pi(nord, 0);
-    for (int q = nord - 1; q >= 0; --q) {
-        if (lam[q] < 0) continue;
-        for (int i : children[q]) {
-            std::vector<View> in = src_in[q];
-            if (has_pi[q]) in.push_back(pi[q]);
-            for (int c : children[q])
-                if (c != i) in.push_back(lam_view(c));
-            if (in.empty()) continue;                    // constant 1
-            pi[i] = reduce(in, p.msgs[lam[i] - p.n_src].vars, false);
-            has_pi[i] = 1;
-        }
-    }
+    });
     // marginals: the belief of the target's bucket, or of the smallest
     // separator below it (lam_c * pi_c), summed down to the target
     for (size_t ti = 0; ti < targets.size(); ++ti) {
@@ -2424,20 +2353,18 @@ VEPlan plan_bucket_tree(const std::vector<int> &cards, const std::vector<View> &
         const bool mine = (int)(ti % (size_t)n_parts) == part;
         p.results_owned.push_back(mine);
         int i = t >= 0 && t < (int)cards.size() ? B.rank[t] : -1;
-        if (!mine || i < 0 || lam[i] < 0) {              // other part / evidence / in no factor
+        if (!mine || i < 0 || T.lam[i] < 0) {            // other part / evidence / in no factor
             p.results.push_back(-1);
             p.results_vars.push_back({});
             continue;
         }
-        std::vector<View> best = src_in[i];
-        if (has_pi[i]) best.push_back(pi[i]);
-        for (int c : children[i]) best.push_back(lam_view(c));
+        std::vector<View> best = T.inputs(i, -1);
         double best_size = (double)table_size(chain_scope(best), cards);
-        for (int c : children[i]) {
-            double sz = (double)p.msgs[lam[c] - p.n_src].size;
+        for (int c : T.children[i]) {
+            double sz = (double)p.msgs[T.lam[c] - p.n_src].size;
             if (sz < best_size) {
-                best = {lam_view(c)};
-                if (has_pi[c]) best.push_back(pi[c]);
+                best = {T.lam_view(c)};
+                if (T.has_pi[c]) best.push_back(T.pi[c]);
                 best_size = sz;
             }
         }

@@ -509,6 +509,28 @@ def _ev_rows(ev_vars: Sequence[int], rows):
     return len(ev_vars), _ints(ev_vars), a32.shape[0], a32, a32.ctypes.data_as(_IP)
 
 
+def _order_args(order, heuristic):
+    """(heuristic, order, n_order) as the C ABI takes them: an explicit order wins over the heuristic's name."""
+    if order is None:
+        return HEURISTICS[heuristic], None, 0
+    return ORDER_GIVEN, _ints(order), len(order)
+
+
+def _plan_call(fn, name, stat_names, head, tail=lambda: ()):
+    """A batched plan entry point called twice, for the number of launch groups
+    and then for the groups -> (stats dict, one dict of PLAN_GROUP_FIELDS per
+    group).  head: the arguments before the stats; tail(): those after n_rows,
+    asked for before either call."""
+    nf = len(PLAN_GROUP_FIELDS)
+    st = (C.c_double * len(stat_names))()
+    cnt = C.c_int()
+    _check(fn(*head, st, len(stat_names), None, 0, C.byref(cnt), *tail()), name)
+    rows = (C.c_int64 * max(cnt.value * nf, 1))()
+    _check(fn(*head, st, len(stat_names), rows, cnt.value, C.byref(cnt), *tail()), name)
+    return (dict(zip(stat_names, list(st))),
+            [dict(zip(PLAN_GROUP_FIELDS, rows[i * nf:(i + 1) * nf])) for i in range(cnt.value)])
+
+
 def load_evidence_batch(path: str):
     """An .evid file of any number of samples over one variable set
     (bnpp_evidence_load_batch) -> (ev_vars ascending, rows as an (n, n_ev) numpy int array)."""
@@ -532,21 +554,13 @@ def plan_batch(model: Model, ev_vars: Sequence[int], target: Optional[int] = Non
     gather steps: level 0, key COND_BATCH_KEY), result_scope the result
     table's variables with the row variable B reported as model.n_vars."""
     ev_vars = [int(v) for v in ev_vars]
-    oa = _ints(order) if order is not None else None
-    h = ORDER_GIVEN if order is not None else HEURISTICS[heuristic]
-    no = len(order) if order is not None else 0
-    nf = len(PLAN_GROUP_FIELDS)
-    st = (C.c_double * len(PLAN_BATCH_STATS))()
-    cnt, nrs = C.c_int(), C.c_int()
+    nrs = C.c_int()
     rs = (C.c_int * 2)()
     t = -1 if target is None else int(target)
-    args = (model.handle, len(ev_vars), _ints(ev_vars), h, oa, no, t, dtype, int(rows_per_launch), st, len(PLAN_BATCH_STATS))
-    _check(_lib.bnpp_plan_batch(*args, None, 0, C.byref(cnt), rs, C.byref(nrs)), "bnpp_plan_batch")
-    rows = (C.c_int64 * max(cnt.value * nf, 1))()
-    _check(_lib.bnpp_plan_batch(*args, rows, cnt.value, C.byref(cnt), rs, C.byref(nrs)), "bnpp_plan_batch")
-    return (dict(zip(PLAN_BATCH_STATS, list(st))),
-            [dict(zip(PLAN_GROUP_FIELDS, rows[i * nf:(i + 1) * nf])) for i in range(cnt.value)],
-            [rs[i] for i in range(min(nrs.value, 2))])
+    st, groups = _plan_call(_lib.bnpp_plan_batch, "bnpp_plan_batch", PLAN_BATCH_STATS,
+                            (model.handle, len(ev_vars), _ints(ev_vars), *_order_args(order, heuristic), t, dtype,
+                             int(rows_per_launch)), lambda: (rs, C.byref(nrs)))
+    return st, groups, [rs[i] for i in range(min(nrs.value, 2))]
 
 
 def partition_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, heuristic: str = "mf", dtype: int = F64,
@@ -556,12 +570,10 @@ def partition_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, he
     (n, len(ev_vars)) integer array, rows[r][j] the value of ev_vars[j]."""
     import numpy as np
     ne, ev_v, n, keep, ev_x = _ev_rows(ev_vars, rows)
-    oa = _ints(order) if order is not None else None
-    h = ORDER_GIVEN if order is not None else HEURISTICS[heuristic]
+    h, oa, no = _order_args(order, heuristic)
     lz, z = np.zeros(max(n, 1)), np.zeros(max(n, 1))
     up = C.c_double()
-    _check(_lib.bnpp_partition_batch(ctx.handle, model.handle, ne, ev_v, n, ev_x, h, oa,
-                                     len(order) if order is not None else 0, dtype, int(rows_per_launch),
+    _check(_lib.bnpp_partition_batch(ctx.handle, model.handle, ne, ev_v, n, ev_x, h, oa, no, dtype, int(rows_per_launch),
                                      lz.ctypes.data_as(_DP), z.ctypes.data_as(_DP), C.byref(up)), "bnpp_partition_batch")
     del keep
     return lz[:n], z[:n], up.value
@@ -596,19 +608,9 @@ def plan_mpe_batch(model: Model, ev_vars: Sequence[int], heuristic: str = "mf", 
     launch group: the gather steps (level 0, COND_BATCH_KEY), max and product
     buckets, and the traceback step last (MPE_DECODE_BATCH_KEY)."""
     ev_vars = [int(v) for v in ev_vars]
-    oa = _ints(order) if order is not None else None
-    h = ORDER_GIVEN if order is not None else HEURISTICS[heuristic]
-    no = len(order) if order is not None else 0
-    nf = len(PLAN_GROUP_FIELDS)
-    st = (C.c_double * len(PLAN_MPE_BATCH_STATS))()
-    cnt = C.c_int()
-    args = (model.handle, len(ev_vars), _ints(ev_vars), h, oa, no, dtype, int(rows_per_launch), st,
-            len(PLAN_MPE_BATCH_STATS))
-    _check(_lib.bnpp_plan_mpe_batch(*args, None, 0, C.byref(cnt)), "bnpp_plan_mpe_batch")
-    rows = (C.c_int64 * max(cnt.value * nf, 1))()
-    _check(_lib.bnpp_plan_mpe_batch(*args, rows, cnt.value, C.byref(cnt)), "bnpp_plan_mpe_batch")
-    return (dict(zip(PLAN_MPE_BATCH_STATS, list(st))),
-            [dict(zip(PLAN_GROUP_FIELDS, rows[i * nf:(i + 1) * nf])) for i in range(cnt.value)])
+    return _plan_call(_lib.bnpp_plan_mpe_batch, "bnpp_plan_mpe_batch", PLAN_MPE_BATCH_STATS,
+                      (model.handle, len(ev_vars), _ints(ev_vars), *_order_args(order, heuristic), dtype,
+                       int(rows_per_launch)))
 
 
 def mpe_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, heuristic: str = "mf", dtype: int = F64,
@@ -619,13 +621,11 @@ def mpe_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, heuristi
     of ev_vars[j]; row r's answer is mpe()'s for that evidence."""
     import numpy as np
     ne, ev_v, n, keep, ev_x = _ev_rows(ev_vars, rows)
-    oa = _ints(order) if order is not None else None
-    h = ORDER_GIVEN if order is not None else HEURISTICS[heuristic]
+    h, oa, no = _order_args(order, heuristic)
     lv = np.zeros(max(n, 1))
     x = np.zeros((max(n, 1), max(model.n_vars, 1)), dtype=np.intc)
     up = C.c_double()
-    _check(_lib.bnpp_mpe_batch(ctx.handle, model.handle, ne, ev_v, n, ev_x, h, oa,
-                               len(order) if order is not None else 0, dtype, int(rows_per_launch),
+    _check(_lib.bnpp_mpe_batch(ctx.handle, model.handle, ne, ev_v, n, ev_x, h, oa, no, dtype, int(rows_per_launch),
                                lv.ctypes.data_as(_DP), x.ctypes.data_as(_IP), C.byref(up)), "bnpp_mpe_batch")
     del keep
     return lv[:n], x[:n, :model.n_vars].astype(np.int32, copy=False), up.value
@@ -645,19 +645,9 @@ def plan_sample_batch(model: Model, ev_vars: Sequence[int], n_per_row: int = 1, 
     COND_BATCH_KEY), sum and product buckets, and the draw step last
     (SAMPLE_BATCH_KEY)."""
     ev_vars = [int(v) for v in ev_vars]
-    oa = _ints(order) if order is not None else None
-    h = ORDER_GIVEN if order is not None else HEURISTICS[heuristic]
-    no = len(order) if order is not None else 0
-    nf = len(PLAN_GROUP_FIELDS)
-    st = (C.c_double * len(PLAN_SAMPLE_BATCH_STATS))()
-    cnt = C.c_int()
-    args = (model.handle, len(ev_vars), _ints(ev_vars), h, oa, no, dtype, int(rows_per_launch), int(n_per_row), st,
-            len(PLAN_SAMPLE_BATCH_STATS))
-    _check(_lib.bnpp_plan_sample_batch(*args, None, 0, C.byref(cnt)), "bnpp_plan_sample_batch")
-    rows = (C.c_int64 * max(cnt.value * nf, 1))()
-    _check(_lib.bnpp_plan_sample_batch(*args, rows, cnt.value, C.byref(cnt)), "bnpp_plan_sample_batch")
-    return (dict(zip(PLAN_SAMPLE_BATCH_STATS, list(st))),
-            [dict(zip(PLAN_GROUP_FIELDS, rows[i * nf:(i + 1) * nf])) for i in range(cnt.value)])
+    return _plan_call(_lib.bnpp_plan_sample_batch, "bnpp_plan_sample_batch", PLAN_SAMPLE_BATCH_STATS,
+                      (model.handle, len(ev_vars), _ints(ev_vars), *_order_args(order, heuristic), dtype,
+                       int(rows_per_launch), int(n_per_row)))
 
 
 def sample_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, n_per_row: int, seed: int = 0,
@@ -672,16 +662,14 @@ def sample_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, n_per
     independent); 0: every row sees the same random numbers."""
     import numpy as np
     ne, ev_v, n, keep, ev_x = _ev_rows(ev_vars, rows)
-    oa = _ints(order) if order is not None else None
-    h = ORDER_GIVEN if order is not None else HEURISTICS[heuristic]
+    h, oa, no = _order_args(order, heuristic)
     k = int(n_per_row)
     stride = k if row_stride is None else int(row_stride)
     out = np.zeros((max(n, 1), max(k, 1), max(model.n_vars, 1)), dtype=np.uint8)
     lz = np.zeros(max(n, 1))
     deg = np.zeros(max(n, 1), dtype=np.int64)
     up = C.c_double()
-    _check(_lib.bnpp_sample_batch(ctx.handle, model.handle, ne, ev_v, n, ev_x, h, oa,
-                                  len(order) if order is not None else 0, dtype, int(rows_per_launch), k,
+    _check(_lib.bnpp_sample_batch(ctx.handle, model.handle, ne, ev_v, n, ev_x, h, oa, no, dtype, int(rows_per_launch), k,
                                   int(first_sample), stride, int(seed) & 0xFFFFFFFFFFFFFFFF, _P(out.ctypes.data),
                                   lz.ctypes.data_as(_DP), deg.ctypes.data_as(_LP), C.byref(up)), "bnpp_sample_batch")
     del keep
@@ -702,23 +690,19 @@ def plan_counts(model: Model, ev_vars: Sequence[int], heuristic: str = "mf", dty
     of the belief table its accumulate step reads (B reported as model.n_vars),
     no_b_elim whether no bucket sums B or merges it into a composite."""
     ev_vars = [int(v) for v in ev_vars]
-    oa = _ints(order) if order is not None else None
-    h = ORDER_GIVEN if order is not None else HEURISTICS[heuristic]
-    no = len(order) if order is not None else 0
-    nf = len(PLAN_GROUP_FIELDS)
-    st = (C.c_double * len(PLAN_COUNTS_STATS))()
-    cnt, nb, flag = C.c_int(), C.c_int(), C.c_int()
+    nb, flag = C.c_int(), C.c_int()
     off = (C.c_int * (model.n_factors + 1))()
-    args = (model.handle, len(ev_vars), _ints(ev_vars), h, oa, no, dtype, int(rows_per_launch), st, len(PLAN_COUNTS_STATS))
-    _check(_lib.bnpp_plan_counts(*args, None, 0, C.byref(cnt), off, None, 0, C.byref(nb), C.byref(flag)), "bnpp_plan_counts")
-    rows = (C.c_int64 * max(cnt.value * nf, 1))()
-    bv = (C.c_int * max(nb.value, 1))()
-    _check(_lib.bnpp_plan_counts(*args, rows, cnt.value, C.byref(cnt), off, bv, nb.value, C.byref(nb), C.byref(flag)),
-           "bnpp_plan_counts")
-    return (dict(zip(PLAN_COUNTS_STATS, list(st))),
-            [dict(zip(PLAN_GROUP_FIELDS, rows[i * nf:(i + 1) * nf])) for i in range(cnt.value)],
-            [[bv[j] for j in range(off[f], off[f + 1])] for f in range(model.n_factors)],
-            bool(flag.value))
+    bvs = []
+
+    def beliefs():                  # room for the belief variables the call before counted (at first: none)
+        bvs.append((C.c_int * max(nb.value, 1))())
+        return off, bvs[-1], nb.value, C.byref(nb), C.byref(flag)
+
+    st, groups = _plan_call(_lib.bnpp_plan_counts, "bnpp_plan_counts", PLAN_COUNTS_STATS,
+                            (model.handle, len(ev_vars), _ints(ev_vars), *_order_args(order, heuristic), dtype,
+                             int(rows_per_launch)), beliefs)
+    bv = bvs[-1]
+    return st, groups, [[bv[j] for j in range(off[f], off[f + 1])] for f in range(model.n_factors)], bool(flag.value)
 
 
 def expected_counts(ctx: Context, model: Model, ev_vars: Sequence[int], rows, weights=None, heuristic: str = "mf",
@@ -733,8 +717,7 @@ def expected_counts(ctx: Context, model: Model, ev_vars: Sequence[int], rows, we
     patterns by pattern, call once per pattern and add the counts."""
     import numpy as np
     ne, ev_v, n, keep, ev_x = _ev_rows(ev_vars, rows)
-    oa = _ints(order) if order is not None else None
-    h = ORDER_GIVEN if order is not None else HEURISTICS[heuristic]
+    h, oa, no = _order_args(order, heuristic)
     total = C.c_int64()
     _check(_lib.bnpp_counts_size(model.handle, C.byref(total)), "bnpp_counts_size")
     counts, lz = np.zeros(max(total.value, 1)), np.zeros(max(n, 1))
@@ -746,8 +729,7 @@ def expected_counts(ctx: Context, model: Model, ev_vars: Sequence[int], rows, we
     ni = C.c_int64()
     up = C.c_double()
     _check(_lib.bnpp_expected_counts(ctx.handle if ctx is not None else None, model.handle, ne, ev_v, n, ev_x,
-                                     w.ctypes.data_as(_DP) if w is not None else None, h, oa,
-                                     len(order) if order is not None else 0, dtype, int(rows_per_launch),
+                                     w.ctypes.data_as(_DP) if w is not None else None, h, oa, no, dtype, int(rows_per_launch),
                                      counts.ctypes.data_as(_DP), lz.ctypes.data_as(_DP), C.byref(ni), C.byref(up)),
            "bnpp_expected_counts")
     del keep
