@@ -569,6 +569,37 @@ std::vector<std::vector<double>> Model::expected_counts(const std::vector<unsign
     return out;
 }
 
+std::vector<std::vector<double>> Model::marginals_batch(const std::vector<unsigned> &ev_vars,
+                                                        const std::vector<std::vector<unsigned>> &rows,
+                                                        const std::vector<unsigned> &targets,
+                                                        std::unordered_map<std::string, bool> &options,
+                                                        std::vector<double> *log10_z, double *uptime) const {
+    auto t0 = std::chrono::steady_clock::now();
+    ModelGuard g{to_engine(_variables, std::vector<const Factor *>(_factors.begin(), _factors.end()))};
+    const std::vector<int> vars(ev_vars.begin(), ev_vars.end()), flat = flatten_rows(ev_vars, rows);
+    const std::vector<int> ts(targets.begin(), targets.end());
+    size_t w = 0;
+    if (ts.empty())
+        for (const Variable *v : _variables) w += v->size();
+    for (unsigned t : targets) {
+        if (t >= _variables.size()) throw std::runtime_error("marginals_batch: bad target");
+        w += _variables[t]->size();
+    }
+    std::vector<double> flat_out(std::max<size_t>(rows.size() * w, 1), 0.0), lz(rows.size() ? rows.size() : 1, 0.0);
+    double up = 0;
+    int dt = options["fp32"] ? BNPP_F32 : BNPP_F64;
+    check(bnpp_marginals_batch(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(),
+                               heuristic_of(options), nullptr, 0, (int)ts.size(), ts.empty() ? nullptr : ts.data(), dt, 0,
+                               flat_out.data(), lz.data(), &up),
+          "marginals_batch");
+    lz.resize(rows.size());
+    if (log10_z) *log10_z = lz;
+    std::vector<std::vector<double>> out(rows.size());
+    for (size_t r = 0; r < rows.size(); ++r) out[r].assign(flat_out.begin() + r * w, flat_out.begin() + (r + 1) * w);
+    if (uptime) *uptime = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return out;
+}
+
 std::vector<std::vector<unsigned char>> Model::sample(const std::unordered_map<unsigned, unsigned> &evidence,
                                                       std::unordered_map<std::string, bool> &options, size_t n,
                                                       unsigned long long seed, double *log10_z, double *uptime) const {

@@ -25,6 +25,10 @@
 // evidence file's samples (bnpp_expected_counts); prints the total log10-
 // likelihood of the possible samples and n_impossible; with -uai, <base>.COUNTS
 // ("COUNTS", the factor count, then per factor "size v_0 .. v_{size-1}", %.17g).
+// -mar-batch (no reference counterpart): every posterior marginal of every
+// sample of the evidence file (bnpp_marginals_batch), one line per sample; with
+// -uai, <base>.MAR ("MAR", the sample count, then per sample the UAI MAR line
+// "n_vars card_0 p.. card_1 p.. ...", %.17g, evidence variables one-hot).
 // BAYES files print like `bn` (raw Z), MARKOV files like `mn` (log10 Z).
 // -ve is accepted and, as in the reference, changes nothing here: bn reads it
 // only for REPL queries (bn.cpp:346); partition / marginals always run VE
@@ -56,6 +60,7 @@ int main(int argc, char **argv) {
         else if (p == "-pr-batch") options["partition-batch"] = true;
         else if (p == "-mpe-batch") options["mpe-batch"] = true;
         else if (p == "-counts") options["counts"] = true;
+        else if (p == "-mar-batch") options["marginals-batch"] = true;
         else if (p == "-post-batch" && i + 1 < argc) { options["posterior-batch"] = true; post_target = (unsigned)std::strtoul(argv[++i], nullptr, 10); }
         else if (p == "-sample" && i + 1 < argc) { options["sample"] = true; n_samples = std::strtoull(argv[++i], nullptr, 10); }
         else if (p == "-sample-batch" && i + 1 < argc) { options["sample-batch"] = true; n_per_row = std::strtoull(argv[++i], nullptr, 10); }
@@ -73,7 +78,7 @@ int main(int argc, char **argv) {
         else positional.push_back(p);
     }
     if (positional.empty() || options["help"]) {
-        std::cout << "usage: " << argv[0] << " /path/to/model.uai [/path/to/evidence.uai.evid] -pr|-mar|-mar-tree|-mpe|-sample N [-seed S]|-pr-batch|-post-batch T|-mpe-batch|-sample-batch K [-seed S]|-counts [-sp] [-mf|-wmf|-md] [-f32] [-uai base]" << std::endl;
+        std::cout << "usage: " << argv[0] << " /path/to/model.uai [/path/to/evidence.uai.evid] -pr|-mar|-mar-tree|-mpe|-sample N [-seed S]|-pr-batch|-post-batch T|-mpe-batch|-sample-batch K [-seed S]|-counts|-mar-batch [-sp] [-mf|-wmf|-md] [-f32] [-uai base]" << std::endl;
         return positional.empty() ? 1 : 0;
     }
     bnpp_model *probe = nullptr;
@@ -176,9 +181,9 @@ int main(int argc, char **argv) {
             }
         }
         if (options["partition-batch"] || options["posterior-batch"] || options["counts"] || options["mpe-batch"] ||
-            options["sample-batch"]) {
+            options["sample-batch"] || options["marginals-batch"]) {
             if (positional.size() < 2)
-                throw std::runtime_error("-pr-batch / -post-batch / -mpe-batch / -sample-batch / -counts need an evidence file");
+                throw std::runtime_error("-pr-batch / -post-batch / -mpe-batch / -sample-batch / -counts / -mar-batch need an evidence file");
             int n_ev = 0;
             int64_t n_rows = 0;
             bnpp_evidence_load_batch(positional[1].c_str(), 0, 0, &n_ev, nullptr, &n_rows, nullptr);   // the sizes
@@ -260,6 +265,32 @@ int main(int argc, char **argv) {
                     for (const auto &t : counts) {
                         std::fprintf(f, "%zu", t.size());
                         for (double v : t) std::fprintf(f, " %.17g", v);
+                        std::fprintf(f, "\n");
+                    }
+                    std::fclose(f);
+                }
+            }
+            if (options["marginals-batch"]) {
+                std::vector<double> lz;
+                const std::vector<std::vector<double>> marg = model->marginals_batch(vars, rows, {}, options, &lz, &uptime);
+                const std::vector<bn::Variable *> &mv = model->variables();
+                for (size_t r = 0; r < marg.size(); ++r) {
+                    std::cout << ">> MAR row " << r << " log10 Z = " << lz[r] << " marginals:";
+                    for (double v : marg[r]) std::cout << " " << v;
+                    std::cout << std::endl;
+                }
+                std::cout << ">> Executed in " << uptime << "ms." << std::endl << std::endl;
+                if (!uai_out.empty()) {
+                    FILE *f = std::fopen((uai_out + ".MAR").c_str(), "w");
+                    if (!f) throw std::runtime_error("cannot write " + uai_out + ".MAR");
+                    std::fprintf(f, "MAR\n%zu\n", marg.size());
+                    for (const auto &row : marg) {
+                        std::fprintf(f, "%zu", mv.size());
+                        size_t at = 0;
+                        for (const bn::Variable *v : mv) {
+                            std::fprintf(f, " %u", (unsigned)v->size());
+                            for (unsigned x = 0; x < v->size(); ++x) std::fprintf(f, " %.17g", row[at++]);
+                        }
                         std::fprintf(f, "\n");
                     }
                     std::fclose(f);

@@ -1124,11 +1124,13 @@ void record_call_timing(double t0, double t1, double t2, double t3) {
 }
 
 // ---- batched calls: batched evidence (bnpp_partition_batch, bnpp_posterior_batch), expected counts
-// (bnpp_expected_counts), batched MPE (bnpp_mpe_batch), batched sampling (bnpp_sample_batch) ----
+// (bnpp_expected_counts), batched MPE (bnpp_mpe_batch), batched sampling (bnpp_sample_batch), batched marginals
+// (bnpp_marginals_batch) ----
 // Each plans once for R rows per launch, stages the evidence variable-major, runs ceil(n_rows / R) launches and
 // reads a table over the row variable B back per launch.  The job kinds (internal, like kKindSample) name the
-// planner: plan_batch, plan_counts (the batched bucket tree), plan_mpe_batch, plan_sample_batch (K draws per row)
-enum BatchKind { kKindBatch = 6, kKindCounts = 7, kKindMpeBatch = 8, kKindSampleBatch = 9 };
+// planner: plan_batch, plan_counts (the batched bucket tree), plan_mpe_batch, plan_sample_batch (K draws per row),
+// plan_marginals_batch (the batched bucket tree handed out per row)
+enum BatchKind { kKindBatch = 6, kKindCounts = 7, kKindMpeBatch = 8, kKindSampleBatch = 9, kKindMarginalsBatch = 10 };
 constexpr int64_t kBatchAutoRows = (int64_t)1 << 16;   // the automatic R's cap
 
 // what a batched call asks for (the plan entry points: no rows)
@@ -1144,6 +1146,7 @@ struct BatchCall {
     int64_t rows_per_launch;
     int target = -1;                                    // kKindBatch: the posterior's variable, or -1 for Z
     int64_t K = 1;                                      // kKindSampleBatch: draws per row
+    std::vector<int> targets;                           // kKindMarginalsBatch: the column blocks' variables, in order
     int64_t n_rows = 0;
     const int *ev_vals = nullptr;
 };
@@ -1200,6 +1203,7 @@ int plan_batch_schedule(const BatchCall &c, int64_t budget, int64_t auto_cap, Sc
     const ModelData &d = c.m->d;
     const int target = c.target, dtype = c.dtype, heuristic = c.heuristic;
     const bool counts = c.kind == kKindCounts, mpe = c.kind == kKindMpeBatch, smp = c.kind == kKindSampleBatch;
+    const bool mar = c.kind == kKindMarginalsBatch;
     const int nv = (int)d.cards.size();
     const int eb = dtype == BNPP_F32 ? 4 : 8;
     int width = 0;
@@ -1219,7 +1223,7 @@ int plan_batch_schedule(const BatchCall &c, int64_t budget, int64_t auto_cap, Sc
             seen[v] = 1;
             if (ev[v] < 0) vars.push_back(v);
         }
-        if (mpe || smp)                                     // as build_plans, kind 4 and sampling
+        if (mpe || smp || mar)                              // as build_plans, kind 4 and sampling
             for (int v = 0; v < nv; ++v)
                 if (!seen[v] && ev[v] < 0)
                     return set_err(BNPP_ERR_INVALID, "explicit order must cover every non-evidence variable");
@@ -1247,6 +1251,7 @@ int plan_batch_schedule(const BatchCall &c, int64_t budget, int64_t auto_cap, Sc
         return counts ? plan_counts(d.cards, views, ord, evv, rows, eb, plan, &msg)
                : mpe  ? plan_mpe_batch(d.cards, views, ord, evv, rows, eb, plan, &msg)
                : smp  ? plan_sample_batch(d.cards, views, ord, evv, rows, c.K, eb, plan, &msg)
+               : mar  ? plan_marginals_batch(d.cards, views, ord, evv, rows, c.targets, eb, plan, &msg)
                       : plan_batch(d.cards, views, ord, evv, rows, target, eb, plan, &msg);
     };
     if (c.rows_per_launch > 0) {
@@ -1276,6 +1281,15 @@ int plan_batch_schedule(const BatchCall &c, int64_t budget, int64_t auto_cap, Sc
                       "until the draws) for %lld row%s per launch of %lld draw%s each, budget %.6f GB", need / 1e9,
                       (long long)std::max<int64_t>(need - plan.sample_bytes, 0), (long long)plan.sample_bytes, (long long)R,
                       R == 1 ? "" : "s", (long long)c.K, c.K == 1 ? "" : "s", budget / 1e9);
+        return set_err(BNPP_ERR_OOM, m);
+    }
+    if (need > budget && mar) {
+        // every forward message stays resident through the backward pass, beside the output table
+        char m[320];
+        std::snprintf(m, sizeof m, "batched marginals need %.6f GB (messages %lld bytes + output %lld bytes) for %lld "
+                      "row%s per launch, budget %.6f GB", need / 1e9,
+                      (long long)std::max<int64_t>(need - plan.marg_out_bytes, 0), (long long)plan.marg_out_bytes,
+                      (long long)R, R == 1 ? "" : "s", budget / 1e9);
         return set_err(BNPP_ERR_OOM, m);
     }
     if (need > budget) {
@@ -1331,6 +1345,8 @@ uint64_t batch_call_key(const BatchCall &c, int64_t auto_cap) {
     mix((uint64_t)c.dtype);
     mix((uint64_t)(c.rows_per_launch > 0 ? c.rows_per_launch : -auto_cap));
     mix((uint64_t)c.K);
+    mix((uint64_t)c.targets.size());
+    for (int t : c.targets) mix((uint32_t)t);
     mix_plan_knobs(mix);
     return h ? h : 1;
 }
@@ -1400,6 +1416,8 @@ void batch_stage(BatchRun &run) {
     for (const Schedule::Group &g : sc.groups)
         if (g.variant == kCondBatchKey && sc.descs[g.begin].in_table[1] >= 0)
             run.d_ev = static_cast<int32_t *>(ex.h_meta[sc.descs[g.begin].in_table[1]].ptr);
+        else if (g.variant == kMargRowsKey && sc.pool[sc.descs[g.begin].dim_off + 3] >= 0)   // an evidence block's, gather step or not
+            run.d_ev = static_cast<int32_t *>(ex.h_meta[sc.pool[sc.descs[g.begin].dim_off + 3]].ptr);
     if (run.d_ev) {
         const int n_ev = c.n_ev;                        // locals: the stores below could alias the call's fields
         const int64_t n_rows = c.n_rows;
@@ -1823,6 +1841,110 @@ int run_counts(bnpp_ctx *ctx, const BatchCall &c, const double *weights, double 
     return batch_close(run, rc, uptime_ms);
 }
 
+// the targets of a batched-marginals call (null: all variables): in range, none twice
+int marginals_targets(const ModelData &d, int n_targets, const int *targets, std::vector<int> &out) {
+    const int nv = (int)d.cards.size();
+    out.clear();
+    if (!targets) {
+        for (int v = 0; v < nv; ++v) out.push_back(v);
+        if (out.empty()) return set_err(BNPP_ERR_INVALID, "the model has no variable");
+        return BNPP_OK;
+    }
+    if (n_targets < 1) return set_err(BNPP_ERR_INVALID, "n_targets must be at least 1");
+    std::vector<char> seen(nv, 0);
+    for (int i = 0; i < n_targets; ++i) {
+        const int t = targets[i];
+        if (t < 0 || t >= nv) return set_err(BNPP_ERR_INVALID, "target " + std::to_string(t) + " out of range");
+        if (seen[t]) return set_err(BNPP_ERR_INVALID, "target " + std::to_string(t) + " is listed twice");
+        seen[t] = 1;
+        out.push_back(t);
+    }
+    return BNPP_OK;
+}
+
+// an explicit order of a batched-marginals call covers every non-evidence variable (n_ev and ev_vars are checked)
+int marginals_order_covers(const BatchCall &c) {
+    if (!c.order) return BNPP_OK;
+    const int nv = (int)c.m->d.cards.size();
+    std::vector<char> seen(nv, 0);
+    for (int i = 0; i < c.n_order; ++i) {
+        const int v = c.order[i];
+        if (v < 0 || v >= nv || seen[v]) return set_err(BNPP_ERR_INVALID, "bad explicit order");
+        seen[v] = 1;
+    }
+    for (int j = 0; j < c.n_ev; ++j) seen[c.ev_vars[j]] = 1;
+    for (int v = 0; v < nv; ++v)
+        if (!seen[v]) return set_err(BNPP_ERR_INVALID, "explicit order must cover every non-evidence variable");
+    return BNPP_OK;
+}
+
+int run_marginals_batch(bnpp_ctx *ctx, const BatchCall &c, double *out, double *log10_z, double *uptime_ms) {
+    const double t0 = now_ms();
+    if (!c.m) return set_err(BNPP_ERR_INVALID, "null context or model");
+    if (c.n_rows < 1) return set_err(BNPP_ERR_INVALID, "n_rows must be at least 1");
+    if (!out) return set_err(BNPP_ERR_INVALID, "null output");
+    if (int rc = batch_check_rows(c)) return rc;
+    if (int rc = marginals_order_covers(c)) return rc;
+    if (c.dtype != BNPP_F32 && c.dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
+    if (!ctx) return batch_null_ctx(false);
+    BatchRun run(ctx, c, t0);
+    int rc = batch_open(run);
+    double stage_ms = 0, wait_ms = 0, copy_ms = 0;         // the host's share, printed under BNPP_TIMING
+    const BucketDesc *ed = nullptr;
+    if (rc == BNPP_OK && !(ed = batch_last_step(run.job, kMargRowsKey)))
+        rc = set_err(BNPP_ERR_INVALID, "batched marginals job without an emit step");
+    if (rc == BNPP_OK) {
+        const double ts = now_ms();
+        batch_stage(run);
+        stage_ms = now_ms() - ts;
+        const Program &pg = run.job->pg;
+        Executable &ex = run.job->pg.parts[0];
+        const Schedule &sc = ex.sched;
+        const int64_t R = run.R, eb = c.dtype == BNPP_F32 ? 4 : 8, W = ed->out_size;
+        int64_t w_call = 0;
+        for (int t : c.targets) w_call += c.m->d.cards[t];
+        if (sc.pool[ed->dim_off + 1] != R || W != w_call || pg.res_size[0][1] * eb < R * W * 8)
+            rc = set_err(BNPP_ERR_INVALID, "batched marginals job of another shape");
+        const int rt = sc.plan_result_table[0];
+        const bool has_b = run.has_b;
+        const int64_t nb = has_b ? R : 1;
+        if (rc == BNPP_OK && (rt < 0 ? 1 : pg.res_size[0][0]) != nb)
+            rc = set_err(BNPP_ERR_INVALID, "batched marginals result table of an unexpected size");
+        std::vector<unsigned char> zr((size_t)(nb * eb));
+        const unsigned char *res = static_cast<const unsigned char *>(pg.results);
+        auto before = [&](int64_t, int64_t rows) {
+            ex.marg_rows_live = rows;
+            return (int)BNPP_OK;
+        };
+        if (rc == BNPP_OK) rc = batch_launches(run, before, [&](int64_t L, int64_t rows) {
+            const double tb = now_ms();
+            hipError_t e = hipStreamSynchronize(ctx->c.stream);
+            const double tw = now_ms();
+            wait_ms += tw - tb;
+            // the launch's rows are contiguous in the caller's array: one copy, no host loop over entries
+            if (e == hipSuccess)
+                e = hipMemcpy(out + L * R * W, res + pg.res_off[0][1], (size_t)(rows * W * 8), hipMemcpyDeviceToHost);
+            TableMeta tm{};
+            if (e == hipSuccess && rt >= 0) e = hipMemcpy(zr.data(), res + pg.res_off[0][0], zr.size(), hipMemcpyDeviceToHost);
+            if (e == hipSuccess && rt >= 0) e = hipMemcpy(&tm, ex.d_meta + rt, sizeof tm, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("batched marginals fetch: ") + hipGetErrorString(e));
+            for (int64_t b = 0; log10_z && b < rows; ++b) {
+                double p = 0;                                   // as run_batch
+                p += raw_elem(rt >= 0 ? zr.data() : nullptr, has_b ? b : 0, eb);
+                log10_z[L * R + b] = log10_scaled(p, tm.exp2);
+            }
+            copy_ms += now_ms() - tw;
+            return (int)BNPP_OK;
+        });
+    }
+    const double launch_ms = run.launch_ms;
+    rc = batch_close(run, rc, uptime_ms);
+    if (rc == BNPP_OK && std::getenv("BNPP_TIMING"))
+        std::fprintf(stderr, "[bnpp] marginals_batch: stage %.3f ms, enqueue %.3f ms, wait %.3f ms, copy %.3f ms\n", stage_ms,
+                     launch_ms, wait_ms, copy_ms);
+    return rc;
+}
+
 // the launch groups of schedule `batch`, from row n of the caller's rows on: the rows after them
 int64_t copy_group_rows(const Schedule &s, int64_t batch, int64_t *rows, int64_t cap_rows, int64_t n) {
     for (const Schedule::Group &g : s.groups) {
@@ -1963,6 +2085,94 @@ int bnpp_bucket_counts(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, cons
     if (!counts_args(pool.data(), n_rows, rows_live, table, ev, weights, valid, acc, ctx->c.counts_scratch, a))
         return set_err(BNPP_ERR_INVALID, "bad accumulate step");
     e = launch_counts(dtype == BNPP_F32, a, ctx->c.max_grid, pick_stream(ctx, stream));
+    if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+int bnpp_marginals_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                         const int *ev_vals, int heuristic, const int *order, int n_order, int n_targets,
+                         const int *targets, int dtype, int64_t rows_per_launch, double *out, double *log10_z,
+                         double *uptime_ms) {
+    BNPP_GUARD_BEGIN
+    BatchCall c = batch_call(m, kKindMarginalsBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
+    c.n_rows = n_rows;
+    c.ev_vals = ev_vals;
+    if (!m) return set_err(BNPP_ERR_INVALID, "null context or model");
+    if (int rc = marginals_targets(m->d, n_targets, targets, c.targets)) return rc;
+    return run_marginals_batch(ctx, c, out, log10_z, uptime_ms);
+    BNPP_GUARD_END
+}
+
+int bnpp_plan_marginals_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order,
+                              int n_order, int n_targets, const int *targets, int dtype, int64_t rows_per_launch,
+                              double *stats, int n_stats, int64_t *rows, int cap_rows, int *n_rows, int *col_kind) {
+    BNPP_GUARD_BEGIN
+    Schedule s;
+    VEPlan plan;
+    double st[BNPP_PLAN_MARGINALS_BATCH_STATS] = {0};
+    BatchCall c = batch_call(m, kKindMarginalsBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
+    if (!m) return set_err(BNPP_ERR_INVALID, "null argument");
+    if (int rc = marginals_targets(m->d, n_targets, targets, c.targets)) return rc;
+    if (int rc = plan_batch_entry(c, false, stats, n_stats, rows, cap_rows, n_rows, s, plan, st)) return rc;
+    for (const Schedule::Group &g : s.groups) st[10] += g.variant == kMargRowsKey;
+    st[11] = plan.counts_fwd_levels;
+    st[12] = plan.n_marg_belief;
+    st[13] = plan.n_marg_ev;
+    st[14] = plan.n_marg_free;
+    st[15] = (double)plan.marg_width;
+    st[16] = (double)plan.marg_out_bytes;
+    st[17] = plan.n_marg_belief_b;
+    for (int i = 0; i < n_stats && i < BNPP_PLAN_MARGINALS_BATCH_STATS; ++i) stats[i] = st[i];
+    if (col_kind)
+        for (const BucketSpec &b : plan.buckets)
+            for (size_t j = 0; b.marg_rows && j < b.marg_cols.size(); ++j)
+                col_kind[j] = b.marg_cols[j].table >= 0 ? (b.marg_cols[j].has_b ? 1 : 0) : b.marg_cols[j].ev_row >= 0 ? -1 : -2;
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+int bnpp_bucket_marginal_rows(bnpp_ctx *ctx, void *stream, int dtype, int n_targets, const int *cards,
+                              const void *const *tables, const int *has_b, const int *ev_row, int64_t n_rows,
+                              int64_t rows_live, const int32_t *ev, double *out) {
+    BNPP_GUARD_BEGIN
+    // the shape is checked before the context is looked at
+    if (!cards || !tables || !has_b || !ev_row || !out) return set_err(BNPP_ERR_INVALID, "null argument");
+    if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "dtype must be BNPP_F64 or BNPP_F32");
+    if (n_targets < 1) return set_err(BNPP_ERR_INVALID, "n_targets must be at least 1");
+    if (n_rows < 1 || n_rows > (int64_t)INT32_MAX) return set_err(BNPP_ERR_INVALID, "n_rows must be in [1, 2^31)");
+    if (rows_live < 0 || rows_live > n_rows) return set_err(BNPP_ERR_INVALID, "rows_live must be in [0, n_rows]");
+    for (int j = 0; j < n_targets; ++j) {
+        if (cards[j] < 1) return set_err(BNPP_ERR_INVALID, "target " + std::to_string(j) + ": the card must be at least 1");
+        if (!tables[j] && ev_row[j] < 0 && has_b[j])
+            return set_err(BNPP_ERR_INVALID, "target " + std::to_string(j) + ": has_b without a table");
+        if (!tables[j] && ev_row[j] >= 0 && !ev)
+            return set_err(BNPP_ERR_INVALID, "target " + std::to_string(j) + ": an evidence row without the evidence table");
+    }
+    if (n_targets > kMargRowsSingleMax)
+        return set_err(BNPP_ERR_UNSUPPORTED, "at most " + std::to_string(kMargRowsSingleMax) + " targets per call");
+    if (!ctx) return set_err(BNPP_ERR_INVALID, "null context");
+    MargRowsSingleArgs a;
+    std::memset(&a, 0, sizeof a);
+    int64_t W = 0;
+    for (int j = 0; j < n_targets; ++j) {
+        int64_t *w = a.words + kMargRowsPoolHead + kMargRowsColWords * j;
+        w[0] = (int64_t)reinterpret_cast<uintptr_t>(tables[j]);
+        w[1] = cards[j];
+        w[2] = tables[j] && has_b[j] ? 1 : 0;
+        w[3] = tables[j] ? -1 : ev_row[j] >= 0 ? ev_row[j] : -1;
+        w[4] = W;
+        W += cards[j];
+    }
+    a.words[0] = n_targets;
+    a.words[1] = n_rows;
+    a.words[2] = W;
+    a.words[3] = -1;
+    a.ev = ev;
+    a.out = out;
+    a.rows_live = rows_live;
+    hipError_t e = hipSetDevice(ctx->c.device);
+    if (e == hipSuccess) e = launch_marg_rows_single(dtype == BNPP_F32, a, ctx->c.max_grid, pick_stream(ctx, stream));
     if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return BNPP_OK;
     BNPP_GUARD_END

@@ -1,6 +1,7 @@
 // Host-side launchers: route a descriptor to the translation unit that holds
 // its kernel instantiation (k_generic_f32/f64, k_stream_f32/f64, k_slab_f32/f64,
-// k_chain_f32/f64, k_max_f32/f64, k_sample_f32/f64, k_condb_f32/f64).
+// k_chain_f32/f64, k_max_f32/f64, k_sample_f32/f64, k_condb_f32/f64,
+// k_counts_f32/f64, k_margrows_f32/f64).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -53,6 +54,13 @@ hipError_t dispatch_counts_list_f32(const CountsArgs *list, int n, int64_t rows_
                                     hipStream_t stream);
 hipError_t dispatch_counts_list_f64(const CountsArgs *list, int n, int64_t rows_max, int64_t rest_max, int max_grid,
                                     hipStream_t stream);
+
+hipError_t dispatch_marg_rows_f32(const int64_t *pool, const TableMeta *meta, const int32_t *ev, double *out,
+                                  int64_t rows_live, int max_grid, hipStream_t stream);
+hipError_t dispatch_marg_rows_f64(const int64_t *pool, const TableMeta *meta, const int32_t *ev, double *out,
+                                  int64_t rows_live, int max_grid, hipStream_t stream);
+hipError_t dispatch_marg_rows_single_f32(const MargRowsSingleArgs &a, int max_grid, hipStream_t stream);
+hipError_t dispatch_marg_rows_single_f64(const MargRowsSingleArgs &a, int max_grid, hipStream_t stream);
 
 hipError_t dispatch_slab_single_f32(int key, const SingleArgs &a, hipStream_t stream);
 hipError_t dispatch_slab_single_f64(int key, const SingleArgs &a, hipStream_t stream);
@@ -159,6 +167,18 @@ hipError_t launch_counts_list(int is_f32, const CountsArgs *list, int n, int64_t
     if (n <= 0 || rows_max <= 0 || rest_max <= 0) return hipSuccess;
     return is_f32 ? dispatch_counts_list_f32(list, n, rows_max, rest_max, max_grid, stream)
                   : dispatch_counts_list_f64(list, n, rows_max, rest_max, max_grid, stream);
+}
+
+hipError_t launch_marg_rows(int is_f32, const int64_t *pool, const TableMeta *meta, const int32_t *ev, double *out,
+                            int64_t rows_live, int max_grid, hipStream_t stream) {
+    if (rows_live <= 0) return hipSuccess;
+    return is_f32 ? dispatch_marg_rows_f32(pool, meta, ev, out, rows_live, max_grid, stream)
+                  : dispatch_marg_rows_f64(pool, meta, ev, out, rows_live, max_grid, stream);
+}
+
+hipError_t launch_marg_rows_single(int is_f32, const MargRowsSingleArgs &a, int max_grid, hipStream_t stream) {
+    if (a.rows_live <= 0) return hipSuccess;
+    return is_f32 ? dispatch_marg_rows_single_f32(a, max_grid, stream) : dispatch_marg_rows_single_f64(a, max_grid, stream);
 }
 
 void kernel_keys(int is_f32, int level, int family, std::vector<int> &keys) {

@@ -853,8 +853,50 @@ static bool build_counts_desc(const BucketSpec &b, const std::vector<int> &cards
     return true;
 }
 
+// The emit step of a batched-marginals plan: no kernel descriptor, its words
+// in the dims pool (the layout marg_rows reads, margrows.cuh):
+//   [0] n_targets  [1] R  [2] W  [3] evidence table (-1: none)
+//   per column block: table (-1: evidence or free), card, carries B (0 / 1),
+//   row of the evidence table (-1: none), first column
+// d.k blocks, d.out_size = W, d.n_tiles = R.  out_vars = {B}.
+static bool build_marg_rows_desc(const BucketSpec &b, const std::vector<int> &cards, BucketDesc &d,
+                                 std::vector<int64_t> &pool, std::string *msg) {
+    d = BucketDesc{};
+    d.out_table = b.out_table;
+    d.big = -1;
+    d.dim_off = (int64_t)pool.size();
+    const int Bv = b.out_vars.empty() ? -1 : b.out_vars.back();       // the row variable (out_vars = {B})
+    if (Bv < 0 || Bv >= (int)cards.size() || b.marg_n_rows < 1 || cards[Bv] != b.marg_n_rows || b.marg_cols.empty()) {
+        if (msg) *msg = "emit step: at least one target, and out_vars must name the row variable";
+        return false;
+    }
+    pool.push_back((int64_t)b.marg_cols.size());
+    pool.push_back(b.marg_n_rows);
+    pool.push_back(0);
+    pool.push_back(b.marg_ev_table);
+    int64_t W = 0;
+    for (const BucketSpec::MargCol &c : b.marg_cols) {
+        if (c.card < 1 || (c.table < 0 && c.has_b) || (c.ev_row >= 0 && (c.table >= 0 || b.marg_ev_table < 0))) {
+            if (msg) *msg = "emit step: a column block is a belief table, an evidence row or free, of at least one value";
+            return false;
+        }
+        pool.push_back(c.table);
+        pool.push_back(c.card);
+        pool.push_back(c.has_b ? 1 : 0);
+        pool.push_back(c.ev_row);
+        pool.push_back(W);
+        W = sat_add(W, c.card);
+    }
+    pool[(size_t)d.dim_off + 2] = W;
+    d.k = (int32_t)b.marg_cols.size();
+    d.out_size = W;
+    d.n_tiles = b.marg_n_rows;
+    return true;
+}
+
 bool build_desc(const BucketSpec &b, const std::vector<int> &cards, int max_vec, BucketDesc &d,
                 std::vector<int64_t> &pool, std::string *msg, bool slab_outer) {
+    if (b.marg_rows) return build_marg_rows_desc(b, cards, d, pool, msg);
     if (b.counts) return build_counts_desc(b, cards, d, pool, msg);
     if (!b.chain_x.empty()) return build_chain_desc(b, cards, max_vec, d, pool, msg);
     if (b.decode) return build_decode_desc(b, d, pool, msg);
@@ -2228,40 +2270,65 @@ bool plan_sample_batch(const std::vector<int> &cards, const std::vector<View> &s
     return true;
 }
 
+namespace {
+// The batched bucket tree plan_counts and plan_marginals_batch share: level 0
+// (plan_batch's gather steps, in its order), the forward (collect) pass --
+// plan_batch's buckets and result table -- and the backward (distribute) pass
+// at levels of its own, B kept by every reduction one of whose inputs carries it
+struct BatchBucketTree {
+    BatchPlan S;
+    BucketTree T;
+    std::vector<int> row_of, bucket_of;     // per variable: its row of the evidence table; per source: its bucket
+    int fwd_levels = 0;                     // the last level of the forward pass
+
+    BatchBucketTree(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
+                    int64_t rows, VEPlan &p)
+        : S(cards, sources, order, rows, p), T(S.B, (int)order.size()), row_of(cards.size(), -1) {}
+    // a reduction keeps `keep` and, when any input carries it, B
+    View reduce(const std::vector<View> &in, std::vector<int> keep) {
+        for (const View &v : in)
+            if (contains(v.vars, S.Bv) && !contains(keep, S.Bv)) keep.push_back(S.Bv);
+        return S.B.view(S.B.reduce_keep(in, keep));
+    }
+    bool build(const std::vector<View> &sources, const std::vector<int> &ev_vars, int elem_bytes, std::string *msg) {
+        PlanBuilder &B = S.B;
+        if (!S.gather(sources, ev_vars, elem_bytes, msg)) return false;
+        bucket_of.assign(S.placed.size(), -1);
+        for (size_t i = 0; i < ev_vars.size(); ++i) row_of[ev_vars[i]] = (int)i;
+        for (size_t f = 0; f < S.placed.size(); ++f) {
+            for (int v : S.placed[f].vars)
+                if (v != S.Bv && B.rank[v] < 0) {
+                    if (msg) *msg = "the order leaves out variable " + std::to_string(v) + ", which is no evidence variable";
+                    return false;
+                }
+            bucket_of[f] = B.first_bucket(S.placed[f].vars, 0);
+        }
+        // forward (collect) pass: plan_batch's buckets, remembering the tree
+        T.src_in = S.buckets;
+        T.collect(S.order, &S.result);
+        S.emit_result();
+        fwd_levels = B.last_level;
+        B.floor_level = B.last_level;                       // the backward pass and the beliefs: levels of their own
+        T.distribute([&](const std::vector<View> &in, const std::vector<int> &keep) { return reduce(in, keep); });
+        return true;
+    }
+};
+}  // namespace
+
 bool plan_counts(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                  const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg) {
     out = VEPlan{};
     VEPlan &p = out;
     if (!batch_rows_ok(rows, msg)) return false;
-    BatchPlan S(cards, sources, order, rows, p);
+    BatchBucketTree W(cards, sources, order, rows, p);
+    if (!W.build(sources, ev_vars, elem_bytes, msg)) return false;
+    BatchPlan &S = W.S;
+    BucketTree &T = W.T;
     PlanBuilder &B = S.B;
     const int Bv = S.Bv;
-    // level 0: plan_batch's gather steps, in its order
-    if (!S.gather(sources, ev_vars, elem_bytes, msg)) return false;
-    std::vector<int> row_of(cards.size(), -1), bucket_of(S.placed.size(), -1);
-    for (size_t i = 0; i < ev_vars.size(); ++i) row_of[ev_vars[i]] = (int)i;
-    for (size_t f = 0; f < S.placed.size(); ++f) {
-        for (int v : S.placed[f].vars)
-            if (v != Bv && B.rank[v] < 0) {
-                if (msg) *msg = "the order leaves out variable " + std::to_string(v) + ", which is no evidence variable";
-                return false;
-            }
-        bucket_of[f] = B.first_bucket(S.placed[f].vars, 0);
-    }
-    // forward (collect) pass: plan_batch's buckets, remembering the tree
-    BucketTree T(B, (int)order.size());
-    T.src_in = S.buckets;
-    T.collect(order, &S.result);
-    S.emit_result();
-    p.counts_fwd_levels = B.last_level;
-    B.floor_level = B.last_level;                           // the backward pass and the beliefs: levels of their own
-    // a reduction keeps `keep` and, when any input carries it, B
-    auto reduce = [&](const std::vector<View> &in, std::vector<int> keep) {
-        for (const View &v : in)
-            if (contains(v.vars, Bv) && !contains(keep, Bv)) keep.push_back(Bv);
-        return B.view(B.reduce_keep(in, keep));
-    };
-    T.distribute(reduce);
+    const std::vector<int> &row_of = W.row_of, &bucket_of = W.bucket_of;
+    p.counts_fwd_levels = W.fwd_levels;
+    auto reduce = [&](const std::vector<View> &in, const std::vector<int> &keep) { return W.reduce(in, keep); };
     auto raw_bytes = [&](int64_t bytes) {
         const int t = B.new_raw((bytes + elem_bytes - 1) / elem_bytes);
         B.level[t] = 0;
@@ -2320,6 +2387,126 @@ bool plan_counts(const std::vector<int> &cards, const std::vector<View> &sources
         p.buckets.push_back(c);
     }
     B.last_level = last;
+    B.finish();
+    return true;
+}
+
+bool plan_marginals_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
+                          const std::vector<int> &ev_vars, int64_t rows, const std::vector<int> &targets, int elem_bytes,
+                          VEPlan &out, std::string *msg) {
+    out = VEPlan{};
+    VEPlan &p = out;
+    if (!batch_rows_ok(rows, msg)) return false;
+    {
+        std::vector<char> seen(cards.size(), 0);
+        for (int t : targets) {
+            if (t < 0 || t >= (int)cards.size() || seen[t]) {
+                if (msg) *msg = "target " + std::to_string(t) + (t < 0 || t >= (int)cards.size() ? " out of range" : " is listed twice");
+                return false;
+            }
+            seen[t] = 1;
+        }
+    }
+    BatchBucketTree W(cards, sources, order, rows, p);
+    if (!W.build(sources, ev_vars, elem_bytes, msg)) return false;
+    BatchPlan &S = W.S;
+    BucketTree &T = W.T;
+    PlanBuilder &B = S.B;
+    const int Bv = S.Bv;
+    p.counts_fwd_levels = W.fwd_levels;
+    BucketSpec em;
+    em.marg_rows = true;
+    em.marg_n_rows = rows;
+    std::vector<int> parent(order.size(), -1);
+    for (size_t q = 0; q < order.size(); ++q)
+        for (int c : T.children[q]) parent[c] = (int)q;
+    auto size_no_b = [&](const std::vector<int> &vars) {
+        double e = 1;
+        for (int v : vars)
+            if (v != Bv) e *= S.ce[v];
+        return e;
+    };
+    std::vector<char> listed;
+    auto name = [&](int table) {                            // the step keeps `table` alive
+        if ((int)listed.size() < p.n_src + (int)p.msgs.size()) listed.resize(p.n_src + p.msgs.size(), 0);
+        if (listed[table]) return;
+        listed[table] = 1;
+        View v;
+        v.table = table;
+        em.in.push_back(v);
+    };
+    for (int t : targets) {
+        BucketSpec::MargCol col;
+        col.var = t;
+        col.card = cards[t];
+        const int i = B.rank[t];
+        if (W.row_of[t] >= 0) {                             // an evidence variable: one-hot of the row's value
+            col.ev_row = W.row_of[t];
+            ++p.n_marg_ev;
+        } else if (i < 0 || T.lam[i] < 0) {                 // in no remaining factor: 1 / card
+            ++p.n_marg_free;
+        } else {
+            // the belief of the target's bucket, or of the smallest separator below it (lam_c * pi_c); sizes
+            // without B, so that the choice -- and with it the order of the sums -- does not depend on R
+            std::vector<View> best = T.inputs(i, -1);
+            double best_size = size_no_b(chain_scope(best));
+            for (int c : T.children[i]) {
+                const double sz = size_no_b(p.msgs[T.lam[c] - p.n_src].vars);
+                if (sz < best_size) {
+                    best = {T.lam_view(c)};
+                    if (T.has_pi[c]) best.push_back(T.pi[c]);
+                    best_size = sz;
+                }
+            }
+            // what never enters the target's tree -- a factor over evidence variables only, the root message of
+            // another component -- scales its belief row by row: a row one of them makes impossible reads 0 / 0
+            int root = i;
+            while (parent[root] >= 0) root = parent[root];
+            bool scaled = false;
+            for (const View &r : S.result)
+                if (r.table != T.lam[root]) {
+                    best.push_back(r);
+                    scaled = true;
+                }
+            // a single table already over (t, B) or (t) is the target's table as it is
+            const std::vector<int> tb = {t, Bv}, tt = {t};
+            View bel = !scaled && best.size() == 1 && best[0].base == 0 && best[0].table >= p.n_src &&
+                               (best[0].vars == tb || best[0].vars == tt) &&
+                               best[0].strides == natural_strides(best[0].vars, S.ce)
+                           ? best[0]
+                           : W.reduce(best, {t});
+            col.table = bel.table;
+            col.has_b = !bel.vars.empty() && bel.vars.back() == Bv;
+            if (bel.vars.empty() || bel.vars[0] != t || bel.vars.size() != (col.has_b ? 2u : 1u)) {
+                if (msg) *msg = "batched marginals: the table of target " + std::to_string(t) + " is not over (target, B)";
+                return false;
+            }
+            name(bel.table);
+            ++p.n_marg_belief;
+            p.n_marg_belief_b += col.has_b;
+            p.elems_moved += (double)table_size(bel.vars, S.ce);
+        }
+        p.marg_width = sat_add(p.marg_width, col.card);
+        em.marg_cols.push_back(col);
+    }
+    if (p.n_marg_ev > 0 && p.batch_ev_table < 0) {          // no gather step made the evidence table
+        const int64_t bytes = sat_mul(sat_mul((int64_t)ev_vars.size(), rows), 4);
+        p.batch_ev_table = B.new_raw((bytes + elem_bytes - 1) / elem_bytes);
+        B.level[p.batch_ev_table] = 0;
+    }
+    if (p.batch_ev_table >= 0) {
+        em.marg_ev_table = p.batch_ev_table;
+        name(p.batch_ev_table);
+    }
+    em.out_vars = {Bv};
+    p.marg_out_bytes = sat_mul(sat_mul(rows, std::max<int64_t>(p.marg_width, 1)), 8);
+    p.elems_moved += (double)p.marg_out_bytes / elem_bytes;
+    {
+        BucketDesc d;
+        std::vector<int64_t> pool;
+        if (!build_desc(em, S.ce, 1, d, pool, msg)) return false;
+    }
+    S.add_last_step(em, p.marg_out_bytes, elem_bytes);
     B.finish();
     return true;
 }
@@ -3334,7 +3521,7 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
                 mix((uint64_t)b.level);
                 mix((uint64_t)(b.xchg * 16 + b.xchg_mode));
                 mix((b.divide ? 1 : 0) + (b.max_out ? 2 : 0) + (b.decode ? 4 : 0) + (b.sample ? 8 : 0) + (b.cond_batch ? 16 : 0) +
-                    (b.decode_batch ? 32 : 0) + (b.sample_batch ? 64 : 0));
+                    (b.decode_batch ? 32 : 0) + (b.sample_batch ? 64 : 0) + (b.marg_rows ? 128 : 0));
                 mix(b.out_vars.size());
                 for (int v : b.out_vars) mix((uint64_t)v);
                 mix(b.chain_x.size() * 131 + b.chain_n.size() * 7 + (uint64_t)b.chain_gmask);
@@ -3607,7 +3794,7 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
         Item &it = items[idx];
         BucketSpec b = *it.b;
         b.simple = simplify && lvl_n[it.level] > 1 && b.chain_x.empty() && !b.divide && !b.xchg &&
-                   !b.decode && !b.decode_batch && !b.sample && !b.sample_batch && !b.cond_batch && !b.counts &&
+                   !b.decode && !b.decode_batch && !b.sample && !b.sample_batch && !b.cond_batch && !b.counts && !b.marg_rows &&
                    plans[it.plan]->msgs[b.out_table - s.n_src].size <= simple_max;
         for (View &v : b.in) v.table = remap(it.plan, v.table);
         b.out_table = remap(it.plan, b.out_table);
@@ -3653,6 +3840,15 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
             it.ok = build_desc(b, plans[it.plan]->cards_ext.empty() ? cards : plans[it.plan]->cards_ext, max_vec, it.d,
                                it.pool, &it.msg);
             it.key = kCountsKey;
+            return;
+        }
+        if (b.marg_rows) {                   // the emit step of a batched-marginals plan: the executor's, its words in the pool
+            for (BucketSpec::MargCol &c : b.marg_cols)
+                if (c.table >= 0) c.table = remap(it.plan, c.table);
+            if (b.marg_ev_table >= 0) b.marg_ev_table = remap(it.plan, b.marg_ev_table);
+            it.ok = build_desc(b, plans[it.plan]->cards_ext.empty() ? cards : plans[it.plan]->cards_ext, max_vec, it.d,
+                               it.pool, &it.msg);
+            it.key = kMargRowsKey;
             return;
         }
         if (b.xchg) {                        // an exchange step: the executor's, no kernel descriptor

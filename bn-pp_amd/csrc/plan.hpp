@@ -207,6 +207,25 @@ struct BucketSpec {
     int64_t counts_acc_off = 0;
     int counts_ev_table = -1, counts_w_table = -1, counts_valid_table = -1, counts_scratch_table = -1;
     bool counts_valid_b = false;        // the validity table is over (B) (else one entry)
+    // the emit step that ends a batched-marginals plan (plan_marginals_batch,
+    // margrows.cuh): one column block per target, in the caller's order -- a
+    // belief (the target's table over (target, B), B the fastest dim, or over
+    // (target) alone where no evidence reaches it), an evidence block (one-hot
+    // of the row's value, from row ev_row of the evidence table) or a free
+    // block (a variable in no remaining factor: 1 / card).  `in` lists every
+    // target table and the evidence table, so that all of them live to this
+    // step; out_table holds out = double[marg_n_rows][W], row-major, W the
+    // sum of the blocks' cards
+    struct MargCol {
+        int var = -1, card = 1;
+        int table = -1;                 // the belief's table (-1: evidence or free)
+        bool has_b = false;             // ... carries B
+        int ev_row = -1;                // the evidence table's row (-1: no evidence variable)
+    };
+    bool marg_rows = false;
+    std::vector<MargCol> marg_cols;
+    int marg_ev_table = -1;
+    int64_t marg_n_rows = 0;
 };
 enum XchgKind { kXchgNone = 0, kXchgSync = 1, kXchgPack = 2, kXchgComm = 3, kXchgUnpack = 4 };
 // schedule group variant of an exchange step: kXchgKeyBase + kind * 16 + mode
@@ -226,6 +245,10 @@ constexpr int kDecodeBatchPoolHead = 4;   // words before the rows of a batched 
 // ... of the draw step of a batched sampling plan (BucketSpec::sample_batch): the executor's
 constexpr int kSampleBatchKey = kXchgKeyBase + 24576;
 constexpr int kSampleBatchPoolHead = 4;   // words before the rows of a batched draw step's pool
+// ... of the emit step of a batched-marginals plan (BucketSpec::marg_rows): the executor's
+constexpr int kMargRowsKey = kXchgKeyBase + 28672;
+constexpr int kMargRowsPoolHead = 4;      // words before the column blocks of an emit step's pool
+constexpr int kMargRowsColWords = 5;      // words per column block
 constexpr int kCountsMaxDims = 32;  // evidence variables, and other variables, in one factor scope of an accumulate step
 constexpr int kCountsPoolHead = 12; // words before the per-variable rows of an accumulate step's pool
 constexpr int kCondMaxRest = 8;     // rest dims of a gather step after merging adjacent ones
@@ -293,6 +316,10 @@ struct VEPlan {
     int counts_w_table = -1, counts_scratch_table = -1;
     std::vector<std::vector<int>> counts_belief_vars;
     int counts_fwd_levels = 0;
+    // plan_marginals_batch: belief, evidence and free column blocks of the emit step, of the beliefs those
+    // whose table carries B, W = the columns of a row, and the bytes of the output table (rows * W * 8)
+    int n_marg_belief = 0, n_marg_belief_b = 0, n_marg_ev = 0, n_marg_free = 0;
+    int64_t marg_width = 0, marg_out_bytes = 0;
     int n_xchg = 0;                     // message exchanges (all-to-all / all-gather)
     double xchg_elems = 0;              // entries this rank sends to other ranks
 };
@@ -394,6 +421,24 @@ bool plan_sample_batch(const std::vector<int> &cards, const std::vector<View> &s
 // non-evidence variable of a factor.
 bool plan_counts(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                  const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg);
+
+// Batched marginals: plan_counts's batched bucket tree -- the same gather
+// steps, forward pass (plan_batch's, so the first result is its table over (B))
+// and backward pass with B kept wherever an input carries it -- then, for every
+// target that is no evidence variable and sits in a factor, the smallest of its
+// bucket's belief and the separator beliefs lam_c * pi_c of the bucket's
+// children (plan_bucket_tree's choice, by sizes without B so that it does not
+// depend on `rows`), times what never enters the target's tree (a factor over
+// evidence variables only, the root message of another component: a row one of
+// them makes impossible then has an all-zero column), summed down to
+// (target, B) -- (target) alone where no evidence reaches it -- and one emit step
+// (BucketSpec::marg_rows) at a last level of its own that normalises every
+// target's table row by row into out = double[rows][W].  results =
+// {plan_batch's table; out}.  No fused chain runs, no checkpointing.  Returns
+// false (msg) as plan_counts does, or on a target out of range or listed twice.
+bool plan_marginals_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
+                          const std::vector<int> &ev_vars, int64_t rows, const std::vector<int> &targets, int elem_bytes,
+                          VEPlan &out, std::string *msg);
 
 // All marginals of `targets` from one two-pass bucket tree over `order`
 // (Shafer-Shenoy on the VE bucket tree; replaces the N independent VEs of

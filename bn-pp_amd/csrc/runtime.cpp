@@ -364,6 +364,14 @@ int launch(Context &ctx, Executable &ex, hipStream_t stream, const XchgHooks *ho
             err = launch_sample_rows_batch(ex.dtype == kF32, ex.d_pool + d.dim_off, ex.d_meta, x, deg, d.n_tiles, a,
                                            ctx.max_grid, st);
             if (err != hipSuccess) return fail(ctx, err, "launch_sample_rows_batch");
+        } else if (g.variant == kMargRowsKey) {              // the emit step of a batched-marginals plan (margrows.cuh)
+            const BucketDesc &d = sc.descs[g.begin];
+            const int64_t evt = sc.pool[d.dim_off + 3];
+            err = launch_marg_rows(ex.dtype == kF32, ex.d_pool + d.dim_off, ex.d_meta,
+                                   evt >= 0 ? static_cast<const int32_t *>(ex.h_meta[evt].ptr) : nullptr,
+                                   static_cast<double *>(ex.h_meta[d.out_table].ptr),
+                                   std::min(ex.marg_rows_live, d.n_tiles), ctx.max_grid, st);
+            if (err != hipSuccess) return fail(ctx, err, "launch_marg_rows");
         } else if (g.variant == kCondBatchKey) {             // a gather step of a batch plan (condbatch.cuh)
             const BucketDesc &d = sc.descs[g.begin];
             if (d.in_table[1] < 0) return fail(ctx, hipErrorInvalidValue, "gather step without an evidence table");

@@ -132,6 +132,21 @@ hipError_t launch_counts(int is_f32, const CountsArgs &a, int max_grid, hipStrea
 constexpr int kCountsListMax = 65535;
 hipError_t launch_counts_list(int is_f32, const CountsArgs *list, int n, int64_t rows_max, int64_t rest_max,
                               int max_grid, hipStream_t stream);
+// batched marginals (margrows.cuh): the emit step of a batched-marginals plan
+// (pool: its words in the dims pool) normalises every target's table row by
+// row into out = double[R][W] for rows [0, rows_live) (include/bnpp.h,
+// bnpp_bucket_marginal_rows, states the arithmetic); ev = int32[.][R]
+hipError_t launch_marg_rows(int is_f32, const int64_t *pool, const TableMeta *meta, const int32_t *ev, double *out,
+                            int64_t rows_live, int max_grid, hipStream_t stream);
+// ... and one call with its words (tables by address, 0: none) in the kernel-argument segment
+constexpr int kMargRowsSingleMax = 64;  // targets of a single-op call
+struct MargRowsSingleArgs {
+    int64_t words[kMargRowsPoolHead + kMargRowsColWords * kMargRowsSingleMax];
+    const int32_t *ev;
+    double *out;
+    int64_t rows_live;
+};
+hipError_t launch_marg_rows_single(int is_f32, const MargRowsSingleArgs &a, int max_grid, hipStream_t stream);
 // the keys a family's dispatch switch holds (single-op or level launches),
 // appended to `keys`: generated from the X-macro lists of the switches
 // themselves (kernels.cuh, slab.cuh, chain.cuh, chainsplit.cuh), so the two
@@ -256,6 +271,8 @@ struct Executable {
     // the accumulate steps (kCountsKey) add into counts_acc for the first counts_rows rows of the next launch
     double *counts_acc = nullptr;
     int64_t counts_rows = 0;
+    // the emit step (kMargRowsKey) writes the first marg_rows_live rows of the next launch (run_marginals_batch sets it)
+    int64_t marg_rows_live = 0;
     // their arguments: staged here per launch, copied to d_counts_args (one entry per accumulate step)
     std::vector<CountsArgs> h_counts_args;
     CountsArgs *d_counts_args = nullptr;

@@ -114,6 +114,9 @@ _SIGS = {
     "bnpp_expected_counts": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _DP, _I, _IP, _I, _I, C.c_int64, _DP, _DP, _LP, _DP]),
     "bnpp_plan_counts": (_I, [_P, _I, _IP, _I, _IP, _I, _I, C.c_int64, _DP, _I, _LP, _I, _IP, _IP, _IP, _I, _IP, _IP]),
     "bnpp_bucket_counts": (_I, [_P, _P, _I, _I, _IP, _P, _I, _IP, _I, _IP, C.c_int64, C.c_int64, _P, _P, _P, _I, _P]),
+    "bnpp_marginals_batch": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _I, _IP, _I, _I, _IP, _I, C.c_int64, _DP, _DP, _DP]),
+    "bnpp_plan_marginals_batch": (_I, [_P, _I, _IP, _I, _IP, _I, _I, _IP, _I, C.c_int64, _DP, _I, _LP, _I, _IP, _IP]),
+    "bnpp_bucket_marginal_rows": (_I, [_P, _P, _I, _I, _IP, C.POINTER(_P), _IP, _IP, C.c_int64, C.c_int64, _P, _P]),
     "bnpp_job_create": (_I, [_P, _P, _I, _I, _IP, _IP, _I, _IP, _I, _I, _IP, _I, C.POINTER(_P)]),
     "bnpp_job_stats": (_I, [_P, _DP, _I]),
     "bnpp_job_launch": (_I, [_P, _P]),
@@ -752,6 +755,84 @@ def split_counts(model_dict: dict, counts):
     return out
 
 
+MARG_ROWS_KEY = (1 << 24) + 28672   # the launch-group key of the emit step of batched marginals (plan.hpp kMargRowsKey)
+PLAN_MARGINALS_BATCH_STATS = PLAN_BATCH_STATS + ("emit_steps", "forward_levels", "belief_cols", "evidence_cols",
+                                                 "free_cols", "width", "out_bytes", "belief_cols_b")
+COL_KINDS = {1: "belief_b", 0: "belief", -1: "evidence", -2: "free"}
+
+
+def _targets_arg(model: Model, targets):
+    """(the target list, n_targets, targets as the C ABI takes them); None: all variables."""
+    if targets is None:
+        return list(range(model.n_vars)), 0, None
+    ts = [int(t) for t in targets]
+    return ts, len(ts), _ints(ts) if ts else (C.c_int * 1)()
+
+
+def plan_marginals_batch(model: Model, ev_vars: Sequence[int], targets: Optional[Sequence[int]] = None,
+                         heuristic: str = "mf", dtype: int = F64, rows_per_launch: int = 0,
+                         order: Optional[Sequence[int]] = None):
+    """Host-only planning of marginals_batch (bnpp_plan_marginals_batch) ->
+    (stats, groups, col_kinds): stats a dict of PLAN_MARGINALS_BATCH_STATS,
+    groups one dict of PLAN_GROUP_FIELDS per launch group (the groups up to
+    level stats["forward_levels"] are plan_batch's; the emit step is the last
+    group, key MARG_ROWS_KEY, at a level of its own), col_kinds per target one
+    of COL_KINDS' names: "belief_b" (its table carries the row variable),
+    "belief" (no evidence reaches it), "evidence" or "free"."""
+    ev_vars = [int(v) for v in ev_vars]
+    ts, nt, ta = _targets_arg(model, targets)
+    kinds = (C.c_int * max(len(ts), 1))()
+    st, groups = _plan_call(_lib.bnpp_plan_marginals_batch, "bnpp_plan_marginals_batch", PLAN_MARGINALS_BATCH_STATS,
+                            (model.handle, len(ev_vars), _ints(ev_vars), *_order_args(order, heuristic), nt, ta, dtype,
+                             int(rows_per_launch)), lambda: (kinds,))
+    return st, groups, [COL_KINDS[kinds[j]] for j in range(len(ts))]
+
+
+def marginals_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, targets: Optional[Sequence[int]] = None,
+                    heuristic: str = "mf", dtype: int = F64, rows_per_launch: int = 0,
+                    order: Optional[Sequence[int]] = None, out=None):
+    """Every posterior marginal P(X_t | evidence row) of every row from one
+    plan (bnpp_marginals_batch) -> (out, log10_z): out an (n, W) float64 array,
+    row-major, W = sum of the targets' cards, the targets' blocks in the given
+    order (None: all variables; split_marginals gives per-target views) -- the
+    library writes it directly; log10_z per row as partition_batch's.  A target
+    that is an evidence variable reads one-hot; a row with Z = 0 reads NaN in
+    its other columns.  All rows share the evidence variables ev_vars.
+    out: a C-contiguous (n, W) float64 array to write instead of a new one (a
+    fresh array of 2^16 x 105 doubles costs more in page faults than the
+    device-to-host copy that fills it)."""
+    import numpy as np
+    ne, ev_v, n, keep, ev_x = _ev_rows(ev_vars, rows)
+    h, oa, no = _order_args(order, heuristic)
+    ts, nt, ta = _targets_arg(model, targets)
+    width = sum(model.cards[t] for t in ts if 0 <= t < model.n_vars)
+    if out is None:
+        out = np.empty((max(n, 1), max(width, 1)))
+    elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.flags.writeable
+              and out.shape == (max(n, 1), max(width, 1))):
+        raise ValueError("out must be a writeable C-contiguous float64 array of shape (n, W)")
+    lz = np.zeros(max(n, 1))
+    up = C.c_double()
+    _check(_lib.bnpp_marginals_batch(ctx.handle if ctx is not None else None, model.handle, ne, ev_v, n, ev_x, h, oa, no,
+                                     nt, ta, dtype, int(rows_per_launch), out.ctypes.data_as(_DP), lz.ctypes.data_as(_DP),
+                                     C.byref(up)), "bnpp_marginals_batch")
+    del keep
+    return out[:n], lz[:n]
+
+
+def split_marginals(cards: Sequence[int], targets: Optional[Sequence[int]], out):
+    """The (n, W) array of marginals_batch as one (n, card) view per target, in
+    the targets' order (None: all variables)."""
+    ts = list(range(len(cards))) if targets is None else [int(t) for t in targets]
+    if out.ndim != 2 or out.shape[1] != sum(cards[t] for t in ts):
+        raise ValueError("the array does not match the targets' cards")
+    views, at = [], 0
+    for t in ts:
+        views.append(out[:, at:at + cards[t]])
+        at += cards[t]
+    return views
+
+
 def marginals(ctx: Context, model: Model, evidence=None, heuristic: str = "mf", dtype: int = F64,
               targets: Optional[Sequence[int]] = None):
     """BN::marginals (model.cpp:303-346) -> ({var: [p_0..p_k-1]}, uptime_ms)."""
@@ -1042,6 +1123,22 @@ def bucket_counts(ctx: Context, dtype: int, cards: Sequence[int], table: int, sc
                                    len(scope), _ints(scope), len(ev_vars), _ints(ev_vars), int(n_rows), int(rows_live),
                                    _P(ev) if ev else None, _P(weights) if weights else None,
                                    _P(valid) if valid else None, 1 if has_b else 0, _P(acc)), "bnpp_bucket_counts")
+
+
+def bucket_marginal_rows(ctx: Context, dtype: int, cards: Sequence[int], tables: Sequence[int], has_b: Sequence[bool],
+                         ev_row: Sequence[int], n_rows: int, rows_live: int, ev: int, out: int,
+                         stream: Optional[int] = None) -> None:
+    """The emit step of marginals_batch on caller-owned device buffers
+    (bnpp_bucket_marginal_rows): target j's table tables[j] over (x, b) -- b
+    fastest, n_rows rows; has_b[j] false: no b -- is normalised row by row into
+    columns off_j.. of out, a device float64[n_rows][sum(cards)], row-major.
+    tables[j] 0: an evidence block (ev_row[j] >= 0, the row of ev = device
+    int32[.][n_rows]) or a free block (1 / card).  Only enqueues on `stream`."""
+    tabs = (_P * max(len(cards), 1))(*[_P(t) if t else None for t in tables])
+    _check(_lib.bnpp_bucket_marginal_rows(ctx.handle if ctx is not None else None, _P(stream) if stream else None, dtype,
+                                          len(cards), _ints(cards), tabs, _ints([1 if b else 0 for b in has_b]),
+                                          _ints(ev_row), int(n_rows), int(rows_live), _P(ev) if ev else None, _P(out)),
+           "bnpp_bucket_marginal_rows")
 
 
 def condition(ctx: Context, dtype: int, cards: Sequence[int], table: int, scope: Sequence[int],

@@ -1,5 +1,6 @@
 """Parameter learning on top of expected_counts: the M step of a Bayesian
-network's CPTs and a small EM driver.
+network's CPTs and a small EM driver; imputation (sample_batch) and
+maximum-posterior-marginal decoding (marginals_batch) of the rows.
 
 All rows of one call share their evidence variables.  Rows with different
 missing patterns are the caller's to group by pattern: counts add, so call
@@ -10,7 +11,7 @@ from typing import List, Sequence, Tuple
 
 import numpy as np
 
-from . import F64, Context, Model, expected_counts, sample_batch, split_counts
+from . import F64, Context, Model, expected_counts, marginals_batch, sample_batch, split_counts, split_marginals
 
 
 def m_step(model_dict: dict, counts, prior: float = 0.0) -> dict:
@@ -68,3 +69,24 @@ def impute(ctx: Context, model: Model, ev_vars: Sequence[int], rows, k: int = 1,
     the E step of a stochastic EM, posterior-predictive checks.  An impossible
     row (Z = 0) comes back with its observed values and zeros elsewhere."""
     return sample_batch(ctx, model, ev_vars, rows, int(k), seed=seed, dtype=dtype)[0]
+
+
+def argmax_marginals(cards: Sequence[int], targets, out) -> np.ndarray:
+    """The per-row argmax of every target's block of a marginals_batch array ->
+    an (n, len(targets)) int array; the lowest value wins a tie (and a block of
+    NaN, an impossible row's, reads 0)."""
+    blocks = split_marginals(cards, targets, np.asarray(out))
+    if not blocks:
+        return np.zeros((np.asarray(out).shape[0], 0), dtype=np.int64)
+    return np.stack([np.argmax(b, axis=1) for b in blocks], axis=1).astype(np.int64)
+
+
+def classify(ctx: Context, model: Model, ev_vars: Sequence[int], rows, targets, dtype: int = F64):
+    """Maximum-posterior-marginal decoding: for every row the most probable
+    value of each target on its own, argmax_x P(X_t = x | the row) -> (an
+    (n, len(targets)) int array, lowest value on ties; the (n, W) marginals of
+    marginals_batch).  Unlike the MPE (mpe_batch) the targets are decoded one by
+    one, which minimises the expected number of wrong labels."""
+    targets = [int(t) for t in targets]
+    out, _ = marginals_batch(ctx, model, ev_vars, rows, targets=targets, dtype=dtype)
+    return argmax_marginals(model.cards, targets, out), out

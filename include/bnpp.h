@@ -46,7 +46,8 @@ extern "C" {
                               adds symbols and shifts no argument of an existing one; likewise batched evidence
                               (bnpp_condition_batch, bnpp_partition_batch, bnpp_posterior_batch, bnpp_plan_batch,
                               bnpp_evidence_load_batch) and expected counts (bnpp_bucket_counts,
-                              bnpp_expected_counts, bnpp_plan_counts) */
+                              bnpp_expected_counts, bnpp_plan_counts) and batched marginals
+                              (bnpp_bucket_marginal_rows, bnpp_marginals_batch, bnpp_plan_marginals_batch) */
 
 enum bnpp_status {
     BNPP_OK = 0,
@@ -542,6 +543,70 @@ int bnpp_bucket_counts(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, cons
                        int n_scope, const int *scope, int n_ev, const int *ev_vars, int64_t n_rows, int64_t rows_live,
                        const int32_t *ev, const double *weights, const void *valid, int has_b, double *acc);
 
+/* Batched marginals (no reference counterpart): every single-variable posterior
+ * P(X_t | evidence row b) of every row from ONE plan -- what a loop of
+ * bnpp_posterior_batch over the targets computes with one plan and one forward
+ * elimination per target.  Plan: bnpp_expected_counts's batched bucket tree (the
+ * gather steps, bnpp_partition_batch's forward buckets and result table over
+ * (B), the backward pass with B kept in every message evidence reaches); for
+ * every target the smallest belief that contains it is summed down to
+ * (target, B), and one emit step (below) normalises the tables row by row into
+ * a row-major device array that one copy per launch moves into `out`.
+ * targets NULL: all variables (n_targets is ignored); else n_targets >= 1 ids
+ * in range, none twice.  out: host [n_rows][W], row-major, W = sum of the
+ * targets' cards, the targets in the given order.  A target that is an evidence
+ * variable gets the one-hot of the row's value; a variable in no remaining
+ * factor 1 / card.  Arguments are checked before the context is looked at: the
+ * rows as bnpp_partition_batch (messages naming row and variable), a target
+ * out of range or listed twice, an explicit order that leaves out a
+ * non-evidence variable.
+ * Guarantees: log10_z[b] (may be NULL) has bnpp_partition_batch's bits.  The
+ * fp64 out does not depend on rows_per_launch, the grid cap
+ * (bnpp_ctx_set_max_grid) or how rows split over calls, bit for bit.  Row b is
+ * within 1e-12 (fp64) / 1e-5 (fp32) absolute of bnpp_marginals for that row's
+ * evidence -- not bit-identical to bnpp_posterior_batch: the sums associate
+ * differently.  A row with Z_b == 0 gets log10_z = -inf, NaN in its belief
+ * columns and keeps its one-hot evidence columns; its neighbours are not
+ * touched.  The shared-scale limit of bnpp_partition_batch applies: a row that
+ * flushes to zero beside a much likelier row of its launch reads NaN.  One
+ * evidence variable set per call (group rows by missing pattern); cardinalities
+ * have no limit.  rows_per_launch and BNPP_ERR_OOM as bnpp_expected_counts (every
+ * forward message resident, no checkpointing); the arena also holds the
+ * rows_per_launch * W * 8 bytes of the output table, and the message names the
+ * message bytes and the output bytes.  The planned job stays with the context,
+ * keyed by its kind, the evidence variable set, R and the target list (never
+ * the values). */
+int bnpp_marginals_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                         const int *ev_vals /* [n_rows][n_ev] */, int heuristic, const int *order, int n_order,
+                         int n_targets, const int *targets /* NULL: all variables */, int dtype, int64_t rows_per_launch,
+                         double *out /* host [n_rows][W] */, double *log10_z /* [n_rows] or NULL */, double *uptime_ms);
+
+/* The emit step on caller-owned device buffers (what bnpp_bucket_counts is to
+ * the accumulate step): only enqueues on `stream`.  Target j has cards[j]
+ * values and the table tables[j] of the dtype over (x, b), b fastest, n_rows =
+ * R rows; has_b[j] = 0: no b dimension, read with row stride 0.  tables[j]
+ * NULL: an evidence block when ev_row[j] >= 0 (the row of ev = device
+ * int32[n_ev][R], variable-major, that holds the target's values), else a free
+ * block.  out: device double[R][W], row-major, W = sum of cards, target j's
+ * block at column off_j = cards[0] + .. + cards[j - 1].
+ * Contract -- all arithmetic in fp64 on values converted from the table, every
+ * operation rounded once, no contraction:
+ *   c = sum over x, ascending, sequentially from 0.0, of (double)T_j[x][b];
+ *   out[b][off_j + x] = (double)T_j[x][b] / c      (c == 0: 0/0 = NaN, nothing special-cased);
+ *   evidence block: 1.0 at the row's value (clamped into range), 0.0 elsewhere;
+ *   free block: 1.0 / card;
+ *   rows b >= rows_live are not written.
+ * The result depends on neither the grid (bnpp_ctx_set_max_grid) nor how rows
+ * split over calls; a table's scale cancels in t / c.  BNPP_ERR_INVALID:
+ * n_targets < 1 or a card < 1; rows_live outside [0, R]; a target with no
+ * table, ev_row[j] < 0 and has_b[j] set; ev_row[j] >= 0 with ev == NULL.  At most
+ * 64 targets per call (the descriptors travel in the kernel-argument segment;
+ * BNPP_ERR_UNSUPPORTED beyond): split a longer list by columns. */
+int bnpp_bucket_marginal_rows(bnpp_ctx *ctx, void *stream, int dtype, int n_targets, const int *cards /* per target */,
+                              const void *const *tables /* NULL: evidence or free */, const int *has_b,
+                              const int *ev_row /* -1: none */, int64_t n_rows /* R */, int64_t rows_live,
+                              const int32_t *ev /* device int32[n_ev][R], may be NULL */, double *out /* device double[R][W] */);
+
 /* BN::marginals (model.cpp:303-346), VE branch: one VE per target with every
  * other variable eliminated, then Factor::normalize (factor.cpp:244-255).  All
  * targets run as one batched device schedule.  targets NULL: all variables.
@@ -761,6 +826,21 @@ int bnpp_plan_sample_batch(const bnpp_model *m, int n_ev, const int *ev_vars, in
 int bnpp_plan_counts(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
                      int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows, int cap_rows,
                      int *n_rows, int *belief_off, int *belief_vars, int cap_belief, int *n_belief, int *no_b_elim);
+
+/* Host-only planning of bnpp_marginals_batch, modelled on bnpp_plan_counts:
+ * stats[0..10) as bnpp_plan_batch's ([1] the arena bytes, the output table
+ * included), then [10] the emit steps (1; key 2^24 + 28672, the last group, at
+ * a level of its own), [11] the last level of the forward pass -- the groups up
+ * to that level are bnpp_plan_batch's for the same arguments --, [12] the belief
+ * column blocks, [13] the evidence blocks, [14] the free blocks, [15] W, [16]
+ * the output bytes per launch (R * W * 8) and [17] the belief blocks whose table
+ * carries B; rows as bnpp_plan_groups's.  targets NULL: all variables.
+ * col_kind[n_targets] (may be NULL): per target 1 a belief with B, 0 a belief
+ * without, -1 an evidence block, -2 a free block. */
+#define BNPP_PLAN_MARGINALS_BATCH_STATS 18
+int bnpp_plan_marginals_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order,
+                              int n_order, int n_targets, const int *targets, int dtype, int64_t rows_per_launch,
+                              double *stats, int n_stats, int64_t *rows, int cap_rows, int *n_rows, int *col_kind);
 
 /* Host-only planning of one part of bnpp_marginals_tree_part (all variables
  * as targets): owned[v] = 1 when this part computes v's marginal; stats as

@@ -193,6 +193,17 @@ public:
                                                      std::unordered_map<std::string, bool> &options,
                                                      std::vector<double> *log10_z = nullptr,
                                                      long long *n_impossible = nullptr, double *uptime = nullptr) const;
+    // EXTENSION: batched marginals (bnpp_marginals_batch).  Row r of the result
+    // holds P(X_t | row r) of every target t, one block of card(t) values after
+    // another in the targets' order (targets empty: all variables); a target
+    // that is an evidence variable reads one-hot, an impossible row NaN in its
+    // other blocks.  log10_z (optional) per row, -inf for an impossible row.
+    std::vector<std::vector<double>> marginals_batch(const std::vector<unsigned> &ev_vars,
+                                                     const std::vector<std::vector<unsigned>> &rows,
+                                                     const std::vector<unsigned> &targets,
+                                                     std::unordered_map<std::string, bool> &options,
+                                                     std::vector<double> *log10_z = nullptr,
+                                                     double *uptime = nullptr) const;
     virtual void write(std::ostream &) const {}
 
 protected:
