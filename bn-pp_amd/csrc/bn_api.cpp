@@ -462,28 +462,38 @@ std::vector<unsigned> Model::mpe(const std::unordered_map<unsigned, unsigned> &e
 
 namespace {
 // rows[r][j]: the value of ev_vars[j] in row r, flattened row-major
-std::vector<int> flatten_rows(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<unsigned>> &rows) {
+std::vector<int> flatten_rows(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows) {
     std::vector<int> flat;
     flat.reserve(rows.size() * ev_vars.size());
     for (const auto &r : rows) {
         if (r.size() != ev_vars.size()) throw std::runtime_error("evidence row of another length than the variable set");
-        for (unsigned x : r) flat.push_back((int)x);
+        for (int x : r) flat.push_back(x);
     }
     return flat;
 }
+// the rows of the calls without missing values, as the calls with them take them
+std::vector<std::vector<int>> int_rows(const std::vector<std::vector<unsigned>> &rows) {
+    std::vector<std::vector<int>> out;
+    out.reserve(rows.size());
+    for (const auto &r : rows) out.emplace_back(r.begin(), r.end());
+    return out;
+}
+// partial[j] != 0: ev_vars[j] may be BNPP_MISSING in a row; empty: none (the call without the argument)
+const unsigned char *partial_arg(const std::vector<unsigned> &ev_vars, const std::vector<unsigned char> &partial) {
+    if (partial.empty()) return nullptr;
+    if (partial.size() != ev_vars.size()) throw std::runtime_error("one partial flag per evidence variable is needed");
+    return partial.data();
+}
 }  // namespace
 
-std::vector<double> Model::partition_batch(const std::vector<unsigned> &ev_vars,
-                                           const std::vector<std::vector<unsigned>> &rows,
-                                           std::unordered_map<std::string, bool> &options, std::vector<double> *z,
-                                           double *uptime) const {
+std::vector<double> Model::partition_batch(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, std::unordered_map<std::string, bool> &options, std::vector<double> *z, double *uptime) const {
     auto t0 = std::chrono::steady_clock::now();
     ModelGuard g{to_engine(_variables, std::vector<const Factor *>(_factors.begin(), _factors.end()))};
     const std::vector<int> vars(ev_vars.begin(), ev_vars.end()), flat = flatten_rows(ev_vars, rows);
     std::vector<double> lz(rows.size() ? rows.size() : 1, 0.0), zz(lz.size(), 0.0);
     double up = 0;
     int dt = options["fp32"] ? BNPP_F32 : BNPP_F64;
-    check(bnpp_partition_batch(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(),
+    check(bnpp_partition_batch_mv(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(), partial_arg(ev_vars, partial),
                                heuristic_of(options), nullptr, 0, dt, 0, lz.data(), zz.data(), &up),
           "partition_batch");
     lz.resize(rows.size());
@@ -493,10 +503,14 @@ std::vector<double> Model::partition_batch(const std::vector<unsigned> &ev_vars,
     return lz;
 }
 
-std::vector<std::vector<unsigned>> Model::mpe_batch(const std::vector<unsigned> &ev_vars,
-                                                    const std::vector<std::vector<unsigned>> &rows,
-                                                    std::unordered_map<std::string, bool> &options,
-                                                    std::vector<double> *log10_value, double *uptime) const {
+std::vector<double> Model::partition_batch(const std::vector<unsigned> &ev_vars,
+                                           const std::vector<std::vector<unsigned>> &rows,
+                                           std::unordered_map<std::string, bool> &options, std::vector<double> *z,
+                                           double *uptime) const {
+    return partition_batch(ev_vars, int_rows(rows), std::vector<unsigned char>(), options, z, uptime);
+}
+
+std::vector<std::vector<unsigned>> Model::mpe_batch(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, std::unordered_map<std::string, bool> &options, std::vector<double> *log10_value, double *uptime) const {
     auto t0 = std::chrono::steady_clock::now();
     ModelGuard g{to_engine(_variables, std::vector<const Factor *>(_factors.begin(), _factors.end()))};
     const std::vector<int> vars(ev_vars.begin(), ev_vars.end()), flat = flatten_rows(ev_vars, rows);
@@ -505,7 +519,7 @@ std::vector<std::vector<unsigned>> Model::mpe_batch(const std::vector<unsigned> 
     std::vector<int> x(std::max<size_t>(rows.size() * nv, 1), 0);
     double up = 0;
     int dt = options["fp32"] ? BNPP_F32 : BNPP_F64;
-    check(bnpp_mpe_batch(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(),
+    check(bnpp_mpe_batch_mv(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(), partial_arg(ev_vars, partial),
                          heuristic_of(options), nullptr, 0, dt, 0, lv.data(), x.data(), &up),
           "mpe_batch");
     lv.resize(rows.size());
@@ -516,10 +530,14 @@ std::vector<std::vector<unsigned>> Model::mpe_batch(const std::vector<unsigned> 
     return out;
 }
 
-std::vector<std::vector<double>> Model::posterior_batch(const std::vector<unsigned> &ev_vars,
-                                                        const std::vector<std::vector<unsigned>> &rows, unsigned target,
-                                                        std::unordered_map<std::string, bool> &options,
-                                                        double *uptime) const {
+std::vector<std::vector<unsigned>> Model::mpe_batch(const std::vector<unsigned> &ev_vars,
+                                                    const std::vector<std::vector<unsigned>> &rows,
+                                                    std::unordered_map<std::string, bool> &options,
+                                                    std::vector<double> *log10_value, double *uptime) const {
+    return mpe_batch(ev_vars, int_rows(rows), std::vector<unsigned char>(), options, log10_value, uptime);
+}
+
+std::vector<std::vector<double>> Model::posterior_batch(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, unsigned target, std::unordered_map<std::string, bool> &options, double *uptime) const {
     auto t0 = std::chrono::steady_clock::now();
     ModelGuard g{to_engine(_variables, std::vector<const Factor *>(_factors.begin(), _factors.end()))};
     const std::vector<int> vars(ev_vars.begin(), ev_vars.end()), flat = flatten_rows(ev_vars, rows);
@@ -528,7 +546,7 @@ std::vector<std::vector<double>> Model::posterior_batch(const std::vector<unsign
     std::vector<double> flat_out(std::max<size_t>(rows.size() * k, 1), 0.0);
     double up = 0;
     int dt = options["fp32"] ? BNPP_F32 : BNPP_F64;
-    check(bnpp_posterior_batch(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(),
+    check(bnpp_posterior_batch_mv(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(), partial_arg(ev_vars, partial),
                                heuristic_of(options), (int)target, dt, 0, flat_out.data(), &up),
           "posterior_batch");
     std::vector<std::vector<double>> out(rows.size());
@@ -537,12 +555,14 @@ std::vector<std::vector<double>> Model::posterior_batch(const std::vector<unsign
     return out;
 }
 
-std::vector<std::vector<double>> Model::expected_counts(const std::vector<unsigned> &ev_vars,
-                                                        const std::vector<std::vector<unsigned>> &rows,
-                                                        const std::vector<double> &weights,
+std::vector<std::vector<double>> Model::posterior_batch(const std::vector<unsigned> &ev_vars,
+                                                        const std::vector<std::vector<unsigned>> &rows, unsigned target,
                                                         std::unordered_map<std::string, bool> &options,
-                                                        std::vector<double> *log10_z, long long *n_impossible,
                                                         double *uptime) const {
+    return posterior_batch(ev_vars, int_rows(rows), std::vector<unsigned char>(), target, options, uptime);
+}
+
+std::vector<std::vector<double>> Model::expected_counts(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, const std::vector<double> &weights, std::unordered_map<std::string, bool> &options, std::vector<double> *log10_z, long long *n_impossible, double *uptime) const {
     auto t0 = std::chrono::steady_clock::now();
     ModelGuard g{to_engine(_variables, std::vector<const Factor *>(_factors.begin(), _factors.end()))};
     const std::vector<int> vars(ev_vars.begin(), ev_vars.end()), flat = flatten_rows(ev_vars, rows);
@@ -552,7 +572,7 @@ std::vector<std::vector<double>> Model::expected_counts(const std::vector<unsign
     std::vector<double> flat_out((size_t)std::max<int64_t>(total, 1), 0.0), lz(rows.size() ? rows.size() : 1, 0.0);
     double up = 0;
     int dt = options["fp32"] ? BNPP_F32 : BNPP_F64;
-    check(bnpp_expected_counts(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(),
+    check(bnpp_expected_counts_mv(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(), partial_arg(ev_vars, partial),
                                weights.empty() ? nullptr : weights.data(), heuristic_of(options), nullptr, 0, dt, 0,
                                flat_out.data(), lz.data(), &n_imp, &up),
           "expected_counts");
@@ -569,11 +589,16 @@ std::vector<std::vector<double>> Model::expected_counts(const std::vector<unsign
     return out;
 }
 
-std::vector<std::vector<double>> Model::marginals_batch(const std::vector<unsigned> &ev_vars,
+std::vector<std::vector<double>> Model::expected_counts(const std::vector<unsigned> &ev_vars,
                                                         const std::vector<std::vector<unsigned>> &rows,
-                                                        const std::vector<unsigned> &targets,
+                                                        const std::vector<double> &weights,
                                                         std::unordered_map<std::string, bool> &options,
-                                                        std::vector<double> *log10_z, double *uptime) const {
+                                                        std::vector<double> *log10_z, long long *n_impossible,
+                                                        double *uptime) const {
+    return expected_counts(ev_vars, int_rows(rows), std::vector<unsigned char>(), weights, options, log10_z, n_impossible, uptime);
+}
+
+std::vector<std::vector<double>> Model::marginals_batch(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, const std::vector<unsigned> &targets, std::unordered_map<std::string, bool> &options, std::vector<double> *log10_z, double *uptime) const {
     auto t0 = std::chrono::steady_clock::now();
     ModelGuard g{to_engine(_variables, std::vector<const Factor *>(_factors.begin(), _factors.end()))};
     const std::vector<int> vars(ev_vars.begin(), ev_vars.end()), flat = flatten_rows(ev_vars, rows);
@@ -588,7 +613,7 @@ std::vector<std::vector<double>> Model::marginals_batch(const std::vector<unsign
     std::vector<double> flat_out(std::max<size_t>(rows.size() * w, 1), 0.0), lz(rows.size() ? rows.size() : 1, 0.0);
     double up = 0;
     int dt = options["fp32"] ? BNPP_F32 : BNPP_F64;
-    check(bnpp_marginals_batch(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(),
+    check(bnpp_marginals_batch_mv(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(), partial_arg(ev_vars, partial),
                                heuristic_of(options), nullptr, 0, (int)ts.size(), ts.empty() ? nullptr : ts.data(), dt, 0,
                                flat_out.data(), lz.data(), &up),
           "marginals_batch");
@@ -598,6 +623,14 @@ std::vector<std::vector<double>> Model::marginals_batch(const std::vector<unsign
     for (size_t r = 0; r < rows.size(); ++r) out[r].assign(flat_out.begin() + r * w, flat_out.begin() + (r + 1) * w);
     if (uptime) *uptime = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return out;
+}
+
+std::vector<std::vector<double>> Model::marginals_batch(const std::vector<unsigned> &ev_vars,
+                                                        const std::vector<std::vector<unsigned>> &rows,
+                                                        const std::vector<unsigned> &targets,
+                                                        std::unordered_map<std::string, bool> &options,
+                                                        std::vector<double> *log10_z, double *uptime) const {
+    return marginals_batch(ev_vars, int_rows(rows), std::vector<unsigned char>(), targets, options, log10_z, uptime);
 }
 
 std::vector<std::vector<unsigned char>> Model::sample(const std::unordered_map<unsigned, unsigned> &evidence,
@@ -622,11 +655,7 @@ std::vector<std::vector<unsigned char>> Model::sample(const std::unordered_map<u
     return out;
 }
 
-std::vector<std::vector<unsigned char>> Model::sample_batch(const std::vector<unsigned> &ev_vars,
-                                                            const std::vector<std::vector<unsigned>> &rows,
-                                                            std::unordered_map<std::string, bool> &options, size_t k,
-                                                            unsigned long long seed, std::vector<double> *log10_z,
-                                                            double *uptime) const {
+std::vector<std::vector<unsigned char>> Model::sample_batch(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, std::unordered_map<std::string, bool> &options, size_t k, unsigned long long seed, std::vector<double> *log10_z, double *uptime) const {
     auto t0 = std::chrono::steady_clock::now();
     ModelGuard g{to_engine(_variables, std::vector<const Factor *>(_factors.begin(), _factors.end()))};
     const std::vector<int> vars(ev_vars.begin(), ev_vars.end()), flat = flatten_rows(ev_vars, rows);
@@ -635,7 +664,7 @@ std::vector<std::vector<unsigned char>> Model::sample_batch(const std::vector<un
     std::vector<unsigned char> x(std::max<size_t>(n * nv, 1), 0);
     double up = 0;
     int dt = options["fp32"] ? BNPP_F32 : BNPP_F64;
-    check(bnpp_sample_batch(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(),
+    check(bnpp_sample_batch_mv(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(), partial_arg(ev_vars, partial),
                             heuristic_of(options), nullptr, 0, dt, 0, (int64_t)k, 0, (int64_t)k, seed, x.data(), lz.data(),
                             nullptr, &up),
           "sample_batch");
@@ -645,6 +674,14 @@ std::vector<std::vector<unsigned char>> Model::sample_batch(const std::vector<un
     for (size_t i = 0; i < n; ++i) out[i].assign(x.begin() + i * nv, x.begin() + (i + 1) * nv);
     if (uptime) *uptime = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return out;
+}
+
+std::vector<std::vector<unsigned char>> Model::sample_batch(const std::vector<unsigned> &ev_vars,
+                                                            const std::vector<std::vector<unsigned>> &rows,
+                                                            std::unordered_map<std::string, bool> &options, size_t k,
+                                                            unsigned long long seed, std::vector<double> *log10_z,
+                                                            double *uptime) const {
+    return sample_batch(ev_vars, int_rows(rows), std::vector<unsigned char>(), options, k, seed, log10_z, uptime);
 }
 
 std::vector<const Factor *> Model::marginals(const std::unordered_map<unsigned, unsigned> &evidence,

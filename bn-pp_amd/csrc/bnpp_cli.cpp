@@ -25,6 +25,9 @@
 // evidence file's samples (bnpp_expected_counts); prints the total log10-
 // likelihood of the possible samples and n_impossible; with -uai, <base>.COUNTS
 // ("COUNTS", the factor count, then per factor "size v_0 .. v_{size-1}", %.17g).
+// -missing beside a batch mode: the samples of the evidence file may observe
+// differing variable sets (bnpp_evidence_load_batch_mv); every variable some
+// sample lacks is declared partial and the _mv entries run.  Outputs as without it.
 // -mar-batch (no reference counterpart): every posterior marginal of every
 // sample of the evidence file (bnpp_marginals_batch), one line per sample; with
 // -uai, <base>.MAR ("MAR", the sample count, then per sample the UAI MAR line
@@ -61,6 +64,7 @@ int main(int argc, char **argv) {
         else if (p == "-mpe-batch") options["mpe-batch"] = true;
         else if (p == "-counts") options["counts"] = true;
         else if (p == "-mar-batch") options["marginals-batch"] = true;
+        else if (p == "-missing") options["missing"] = true;
         else if (p == "-post-batch" && i + 1 < argc) { options["posterior-batch"] = true; post_target = (unsigned)std::strtoul(argv[++i], nullptr, 10); }
         else if (p == "-sample" && i + 1 < argc) { options["sample"] = true; n_samples = std::strtoull(argv[++i], nullptr, 10); }
         else if (p == "-sample-batch" && i + 1 < argc) { options["sample-batch"] = true; n_per_row = std::strtoull(argv[++i], nullptr, 10); }
@@ -78,7 +82,7 @@ int main(int argc, char **argv) {
         else positional.push_back(p);
     }
     if (positional.empty() || options["help"]) {
-        std::cout << "usage: " << argv[0] << " /path/to/model.uai [/path/to/evidence.uai.evid] -pr|-mar|-mar-tree|-mpe|-sample N [-seed S]|-pr-batch|-post-batch T|-mpe-batch|-sample-batch K [-seed S]|-counts|-mar-batch [-sp] [-mf|-wmf|-md] [-f32] [-uai base]" << std::endl;
+        std::cout << "usage: " << argv[0] << " /path/to/model.uai [/path/to/evidence.uai.evid] -pr|-mar|-mar-tree|-mpe|-sample N [-seed S]|-pr-batch|-post-batch T|-mpe-batch|-sample-batch K [-seed S]|-counts|-mar-batch [-missing] [-sp] [-mf|-wmf|-md] [-f32] [-uai base]" << std::endl;
         return positional.empty() ? 1 : 0;
     }
     bnpp_model *probe = nullptr;
@@ -186,15 +190,24 @@ int main(int argc, char **argv) {
                 throw std::runtime_error("-pr-batch / -post-batch / -mpe-batch / -sample-batch / -counts / -mar-batch need an evidence file");
             int n_ev = 0;
             int64_t n_rows = 0;
-            bnpp_evidence_load_batch(positional[1].c_str(), 0, 0, &n_ev, nullptr, &n_rows, nullptr);   // the sizes
+            // -missing: the samples may observe differing variable sets; every variable some sample lacks is partial
+            const bool missing = options["missing"];
+            if (missing) bnpp_evidence_load_batch_mv(positional[1].c_str(), 0, 0, &n_ev, nullptr, &n_rows, nullptr, nullptr);
+            else bnpp_evidence_load_batch(positional[1].c_str(), 0, 0, &n_ev, nullptr, &n_rows, nullptr);   // the sizes
             std::vector<int> ev_vars(n_ev > 0 ? n_ev : 1), flat((size_t)(n_ev > 0 ? n_ev : 1) * (size_t)(n_rows > 0 ? n_rows : 1));
-            if (bnpp_evidence_load_batch(positional[1].c_str(), n_ev, n_rows, &n_ev, ev_vars.data(), &n_rows, flat.data()) != BNPP_OK)
+            std::vector<unsigned char> partial;             // empty: the calls without missing values
+            if (missing) partial.assign((size_t)(n_ev > 0 ? n_ev : 1), 0);
+            if ((missing ? bnpp_evidence_load_batch_mv(positional[1].c_str(), n_ev, n_rows, &n_ev, ev_vars.data(), &n_rows,
+                                                       flat.data(), partial.data())
+                         : bnpp_evidence_load_batch(positional[1].c_str(), n_ev, n_rows, &n_ev, ev_vars.data(), &n_rows,
+                                                    flat.data())) != BNPP_OK)
                 throw std::runtime_error(bnpp_last_error());
+            if (missing) partial.resize((size_t)n_ev);
             const std::vector<unsigned> vars(ev_vars.begin(), ev_vars.begin() + n_ev);
-            std::vector<std::vector<unsigned>> rows((size_t)n_rows);
+            std::vector<std::vector<int>> rows((size_t)n_rows);
             for (int64_t r = 0; r < n_rows; ++r) rows[r].assign(flat.begin() + r * n_ev, flat.begin() + (r + 1) * n_ev);
             if (options["partition-batch"]) {
-                const std::vector<double> lz = model->partition_batch(vars, rows, options, nullptr, &uptime);
+                const std::vector<double> lz = model->partition_batch(vars, rows, partial, options, nullptr, &uptime);
                 std::cout << ">> log10 Z of " << lz.size() << " evidence rows:";
                 for (size_t r = 0; r < lz.size() && r < 8; ++r) std::cout << " " << lz[r];
                 std::cout << (lz.size() > 8 ? " ..." : "") << std::endl << ">> Executed in " << uptime << "ms." << std::endl << std::endl;
@@ -208,7 +221,7 @@ int main(int argc, char **argv) {
             }
             if (options["mpe-batch"]) {
                 std::vector<double> lv;
-                const std::vector<std::vector<unsigned>> xs = model->mpe_batch(vars, rows, options, &lv, &uptime);
+                const std::vector<std::vector<unsigned>> xs = model->mpe_batch(vars, rows, partial, options, &lv, &uptime);
                 for (size_t r = 0; r < xs.size(); ++r) {
                     std::cout << ">> MPE row " << r << " log10 value = " << lv[r] << " assignment:";
                     for (unsigned v : xs[r]) std::cout << " " << v;
@@ -230,7 +243,7 @@ int main(int argc, char **argv) {
             if (options["sample-batch"]) {
                 std::vector<double> lz;
                 const std::vector<std::vector<unsigned char>> xs =
-                    model->sample_batch(vars, rows, options, n_per_row, seed, &lz, &uptime);
+                    model->sample_batch(vars, rows, partial, options, n_per_row, seed, &lz, &uptime);
                 std::cout << ">> " << n_per_row << " samples for each of " << rows.size() << " evidence rows; log10 Z:";
                 for (size_t r = 0; r < lz.size() && r < 8; ++r) std::cout << " " << lz[r];
                 std::cout << (lz.size() > 8 ? " ..." : "") << std::endl << ">> First sample:";
@@ -252,7 +265,7 @@ int main(int argc, char **argv) {
                 std::vector<double> lz;
                 long long n_impossible = 0;
                 const std::vector<std::vector<double>> counts =
-                    model->expected_counts(vars, rows, {}, options, &lz, &n_impossible, &uptime);
+                    model->expected_counts(vars, rows, partial, {}, options, &lz, &n_impossible, &uptime);
                 double ll = 0;
                 for (double v : lz)
                     if (std::isfinite(v)) ll += v;
@@ -272,7 +285,7 @@ int main(int argc, char **argv) {
             }
             if (options["marginals-batch"]) {
                 std::vector<double> lz;
-                const std::vector<std::vector<double>> marg = model->marginals_batch(vars, rows, {}, options, &lz, &uptime);
+                const std::vector<std::vector<double>> marg = model->marginals_batch(vars, rows, partial, {}, options, &lz, &uptime);
                 const std::vector<bn::Variable *> &mv = model->variables();
                 for (size_t r = 0; r < marg.size(); ++r) {
                     std::cout << ">> MAR row " << r << " log10 Z = " << lz[r] << " marginals:";
@@ -297,7 +310,7 @@ int main(int argc, char **argv) {
                 }
             }
             if (options["posterior-batch"]) {
-                const std::vector<std::vector<double>> post = model->posterior_batch(vars, rows, post_target, options, &uptime);
+                const std::vector<std::vector<double>> post = model->posterior_batch(vars, rows, partial, post_target, options, &uptime);
                 std::cout << ">> P(" << post_target << " | row) of " << post.size() << " evidence rows; row 0:";
                 if (!post.empty())
                     for (double v : post[0]) std::cout << " " << v;

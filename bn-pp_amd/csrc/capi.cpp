@@ -1149,6 +1149,13 @@ struct BatchCall {
     std::vector<int> targets;                           // kKindMarginalsBatch: the column blocks' variables, in order
     int64_t n_rows = 0;
     const int *ev_vals = nullptr;
+    const unsigned char *partial = nullptr;             // [n_ev] or null: the evidence variables that may be missing (-1)
+    bool is_partial(int j) const { return partial && partial[j]; }
+    bool any_partial() const {
+        for (int j = 0; j < n_ev && partial; ++j)
+            if (partial[j]) return true;
+        return false;
+    }
 };
 
 // the evidence variable set (no values) and the target: ids in range, no duplicates
@@ -1178,6 +1185,7 @@ int batch_check_rows(const BatchCall &c, bool posterior = false) {
     for (int64_t r = 0; r < c.n_rows; ++r)
         for (int j = 0; j < c.n_ev; ++j) {
             const int x = c.ev_vals[r * c.n_ev + j];
+            if (x == BNPP_MISSING && c.is_partial(j)) continue;
             if (x < 0 || x >= d.cards[c.ev_vars[j]])
                 return set_err(BNPP_ERR_INVALID, "evidence row " + std::to_string(r) + ": value " + std::to_string(x) +
                                                      " of variable " + std::to_string(c.ev_vars[j]) + " is outside [0, " +
@@ -1212,7 +1220,11 @@ int plan_batch_schedule(const BatchCall &c, int64_t budget, int64_t auto_cap, Sc
     if (c.rows_per_launch < 0 || c.rows_per_launch > (int64_t)INT32_MAX)
         return set_err(BNPP_ERR_INVALID, "rows_per_launch must be 0 (automatic) or in [1, 2^31)");
     std::vector<int> ev(nv, -1), evv(c.ev_vars, c.ev_vars + c.n_ev);
-    for (int v : evv) ev[v] = 0;                            // the order depends on which variables are observed only
+    std::vector<char> part;                                 // empty: no partial variable, the planners' own default
+    if (c.any_partial()) part.assign(c.partial, c.partial + c.n_ev);
+    // the order depends on which variables are observed in every row only: a partial variable is eliminated
+    for (int j = 0; j < c.n_ev; ++j)
+        if (!c.is_partial(j)) ev[evv[j]] = 0;
     auto scopes = conditioned_scopes(d, ev);
     std::vector<int> vars, ord;
     if (target < 0 && c.order) {                            // as build_plans, kind 0
@@ -1248,11 +1260,11 @@ int plan_batch_schedule(const BatchCall &c, int64_t budget, int64_t auto_cap, Sc
     int64_t need = 0;
     // counts: the batched bucket tree (plan_counts), every forward message resident through the backward pass
     auto make = [&](int64_t rows) {
-        return counts ? plan_counts(d.cards, views, ord, evv, rows, eb, plan, &msg)
-               : mpe  ? plan_mpe_batch(d.cards, views, ord, evv, rows, eb, plan, &msg)
-               : smp  ? plan_sample_batch(d.cards, views, ord, evv, rows, c.K, eb, plan, &msg)
-               : mar  ? plan_marginals_batch(d.cards, views, ord, evv, rows, c.targets, eb, plan, &msg)
-                      : plan_batch(d.cards, views, ord, evv, rows, target, eb, plan, &msg);
+        return counts ? plan_counts(d.cards, views, ord, evv, rows, eb, plan, &msg, part)
+               : mpe  ? plan_mpe_batch(d.cards, views, ord, evv, rows, eb, plan, &msg, part)
+               : smp  ? plan_sample_batch(d.cards, views, ord, evv, rows, c.K, eb, plan, &msg, part)
+               : mar  ? plan_marginals_batch(d.cards, views, ord, evv, rows, c.targets, eb, plan, &msg, part)
+                      : plan_batch(d.cards, views, ord, evv, rows, target, eb, plan, &msg, part);
     };
     if (c.rows_per_launch > 0) {
         R = c.rows_per_launch;
@@ -1304,7 +1316,7 @@ int plan_batch_schedule(const BatchCall &c, int64_t budget, int64_t auto_cap, Sc
     if (!build_schedule({&plan}, d.cards, src_sizes, eb, max_vec_for(dtype), out, &msg, budget))
         return set_err(out.arena_bytes >= kSatMax ? BNPP_ERR_OOM : BNPP_ERR_INVALID, msg);
     int64_t n_gather = 0;
-    for (const Schedule::Group &g : out.groups) n_gather += g.variant == kCondBatchKey;
+    for (const Schedule::Group &g : out.groups) n_gather += g.variant == kCondBatchKey || g.variant == kCondBatchMaskKey;
     stats[0] = out.entries;
     stats[1] = (double)out.arena_bytes;
     stats[2] = out.n_levels;
@@ -1347,6 +1359,8 @@ uint64_t batch_call_key(const BatchCall &c, int64_t auto_cap) {
     mix((uint64_t)c.K);
     mix((uint64_t)c.targets.size());
     for (int t : c.targets) mix((uint32_t)t);
+    if (c.any_partial())                                    // none: the key of the call without the argument
+        for (int i = 0; i < c.n_ev; ++i) mix(0x9e3779b9ull + (c.partial[i] ? 1 : 0));
     mix_plan_knobs(mix);
     return h ? h : 1;
 }
@@ -1414,7 +1428,7 @@ void batch_stage(BatchRun &run) {
     const Schedule &sc = ex.sched;
     const int64_t R = run.R = run.job->batch_rows, n_launch = run.n_launch = (c.n_rows + R - 1) / R;
     for (const Schedule::Group &g : sc.groups)
-        if (g.variant == kCondBatchKey && sc.descs[g.begin].in_table[1] >= 0)
+        if ((g.variant == kCondBatchKey || g.variant == kCondBatchMaskKey) && sc.descs[g.begin].in_table[1] >= 0)
             run.d_ev = static_cast<int32_t *>(ex.h_meta[sc.descs[g.begin].in_table[1]].ptr);
         else if (g.variant == kMargRowsKey && sc.pool[sc.descs[g.begin].dim_off + 3] >= 0)   // an evidence block's, gather step or not
             run.d_ev = static_cast<int32_t *>(ex.h_meta[sc.pool[sc.descs[g.begin].dim_off + 3]].ptr);
@@ -1643,9 +1657,10 @@ int run_mpe_batch(bnpp_ctx *ctx, const BatchCall &c, double *log10_value, int *a
                 if (log10_value) log10_value[row] = log10_scaled(raw_elem(vals, has_b ? b : 0, eb), tm.exp2);
                 if (assignment)
                     for (int64_t v = 0; v < nv; ++v)
-                        assignment[row * nv + v] = decoded[(size_t)v]        ? (int)x[v * R + b]
-                                                   : ev_col[(size_t)v] >= 0 ? ev_vals[row * n_ev + ev_col[(size_t)v]]
-                                                                            : 0;
+                        assignment[row * nv + v] = ev_col[(size_t)v] >= 0 && ev_vals[row * n_ev + ev_col[(size_t)v]] >= 0
+                                                       ? ev_vals[row * n_ev + ev_col[(size_t)v]]   // observed, partial or not
+                                                   : decoded[(size_t)v] ? (int)x[v * R + b]
+                                                                        : 0;
             }
             return (int)BNPP_OK;
         });
@@ -1740,7 +1755,15 @@ int run_sample_batch(bnpp_ctx *ctx, const BatchCall &c, int64_t first_sample, in
                 for (int64_t v = 0; v < nv; ++v) {
                     const int col = ev_col[(size_t)v];
                     uint8_t *o = out + (L * R * K) * nv + v;
-                    if (col >= 0) {
+                    if (col >= 0 && c.is_partial(col)) {    // observed: the row's value; missing: the draws
+                        for (int64_t b = b0; b < b1; ++b) {
+                            const int val = ev_vals[(L * R + b) * n_ev + col];
+                            for (int64_t s = 0; s < K; ++s)
+                                o[(b * K + s) * nv] = val >= 0                  ? (uint8_t)val
+                                                      : impossible[(size_t)b] ? (uint8_t)0
+                                                                              : x[v * lanes + s * R + b];
+                        }
+                    } else if (col >= 0) {
                         for (int64_t b = b0; b < b1; ++b) {
                             const uint8_t val = (uint8_t)ev_vals[(L * R + b) * n_ev + col];
                             for (int64_t s = 0; s < K; ++s) o[(b * K + s) * nv] = val;
@@ -1872,7 +1895,8 @@ int marginals_order_covers(const BatchCall &c) {
         if (v < 0 || v >= nv || seen[v]) return set_err(BNPP_ERR_INVALID, "bad explicit order");
         seen[v] = 1;
     }
-    for (int j = 0; j < c.n_ev; ++j) seen[c.ev_vars[j]] = 1;
+    for (int j = 0; j < c.n_ev; ++j)
+        if (!c.is_partial(j)) seen[c.ev_vars[j]] = 1;
     for (int v = 0; v < nv; ++v)
         if (!seen[v]) return set_err(BNPP_ERR_INVALID, "explicit order must cover every non-evidence variable");
     return BNPP_OK;
@@ -1981,26 +2005,37 @@ int bnpp_counts_size(const bnpp_model *m, int64_t *n) {
     return BNPP_OK;
 }
 
-int bnpp_expected_counts(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
-                         const int *ev_vals, const double *weights, int heuristic, const int *order, int n_order,
-                         int dtype, int64_t rows_per_launch, double *counts, double *log10_z, int64_t *n_impossible,
-                         double *uptime_ms) {
+int bnpp_expected_counts_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                            const int *ev_vals, const unsigned char *partial, const double *weights, int heuristic,
+                            const int *order, int n_order, int dtype, int64_t rows_per_launch, double *counts,
+                            double *log10_z, int64_t *n_impossible, double *uptime_ms) {
     BNPP_GUARD_BEGIN
     BatchCall c = batch_call(m, kKindCounts, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
+    c.partial = partial;
     c.n_rows = n_rows;
     c.ev_vals = ev_vals;
     return run_counts(ctx, c, weights, counts, log10_z, n_impossible, uptime_ms);
     BNPP_GUARD_END
 }
 
-int bnpp_plan_counts(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
-                     int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows, int cap_rows,
-                     int *n_rows, int *belief_off, int *belief_vars, int cap_belief, int *n_belief, int *no_b_elim) {
+int bnpp_expected_counts(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                         const int *ev_vals, const double *weights, int heuristic, const int *order, int n_order,
+                         int dtype, int64_t rows_per_launch, double *counts, double *log10_z, int64_t *n_impossible,
+                         double *uptime_ms) {
+    return bnpp_expected_counts_mv(ctx, m, n_ev, ev_vars, n_rows, ev_vals, nullptr, weights, heuristic, order,
+                                   n_order, dtype, rows_per_launch, counts, log10_z, n_impossible, uptime_ms);
+}
+
+int bnpp_plan_counts_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial,
+                        int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch,
+                        double *stats, int n_stats, int64_t *rows, int cap_rows, int *n_rows, int *belief_off,
+                        int *belief_vars, int cap_belief, int *n_belief, int *no_b_elim, int *mask_factor) {
     BNPP_GUARD_BEGIN
     Schedule s;
     VEPlan plan;
     double st[12] = {0};
-    const BatchCall c = batch_call(m, kKindCounts, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
+    BatchCall c = batch_call(m, kKindCounts, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
+    c.partial = partial;
     if (int rc = plan_batch_entry(c, false, stats, n_stats, rows, cap_rows, n_rows, s, plan, st)) return rc;
     for (const Schedule::Group &g : s.groups) st[10] += g.variant == kCountsKey;
     st[11] = plan.counts_fwd_levels;
@@ -2031,8 +2066,18 @@ int bnpp_plan_counts(const bnpp_model *m, int n_ev, const int *ev_vars, int heur
                 *no_b_elim = 0;
         }
     }
+    for (int j = 0; mask_factor && j < n_ev; ++j)
+        mask_factor[j] = j < (int)plan.batch_mask_factor.size() ? plan.batch_mask_factor[j] : -1;
     return BNPP_OK;
     BNPP_GUARD_END
+}
+
+int bnpp_plan_counts(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
+                     int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows, int cap_rows,
+                     int *n_rows, int *belief_off, int *belief_vars, int cap_belief, int *n_belief, int *no_b_elim) {
+    return bnpp_plan_counts_mv(m, n_ev, ev_vars, nullptr, heuristic, order, n_order, dtype, rows_per_launch, stats,
+                               n_stats, rows, cap_rows, n_rows, belief_off, belief_vars, cap_belief, n_belief,
+                               no_b_elim, nullptr);
 }
 
 int bnpp_bucket_counts(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, const void *table,
@@ -2090,12 +2135,13 @@ int bnpp_bucket_counts(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, cons
     BNPP_GUARD_END
 }
 
-int bnpp_marginals_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
-                         const int *ev_vals, int heuristic, const int *order, int n_order, int n_targets,
-                         const int *targets, int dtype, int64_t rows_per_launch, double *out, double *log10_z,
-                         double *uptime_ms) {
+int bnpp_marginals_batch_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                            const int *ev_vals, const unsigned char *partial, int heuristic, const int *order,
+                            int n_order, int n_targets, const int *targets, int dtype, int64_t rows_per_launch,
+                            double *out, double *log10_z, double *uptime_ms) {
     BNPP_GUARD_BEGIN
     BatchCall c = batch_call(m, kKindMarginalsBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
+    c.partial = partial;
     c.n_rows = n_rows;
     c.ev_vals = ev_vals;
     if (!m) return set_err(BNPP_ERR_INVALID, "null context or model");
@@ -2104,14 +2150,24 @@ int bnpp_marginals_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int
     BNPP_GUARD_END
 }
 
-int bnpp_plan_marginals_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order,
-                              int n_order, int n_targets, const int *targets, int dtype, int64_t rows_per_launch,
-                              double *stats, int n_stats, int64_t *rows, int cap_rows, int *n_rows, int *col_kind) {
+int bnpp_marginals_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                         const int *ev_vals, int heuristic, const int *order, int n_order, int n_targets,
+                         const int *targets, int dtype, int64_t rows_per_launch, double *out, double *log10_z,
+                         double *uptime_ms) {
+    return bnpp_marginals_batch_mv(ctx, m, n_ev, ev_vars, n_rows, ev_vals, nullptr, heuristic, order, n_order,
+                                   n_targets, targets, dtype, rows_per_launch, out, log10_z, uptime_ms);
+}
+
+int bnpp_plan_marginals_batch_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial,
+                                 int heuristic, const int *order, int n_order, int n_targets, const int *targets,
+                                 int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows,
+                                 int cap_rows, int *n_rows, int *col_kind, int *mask_factor) {
     BNPP_GUARD_BEGIN
     Schedule s;
     VEPlan plan;
     double st[BNPP_PLAN_MARGINALS_BATCH_STATS] = {0};
     BatchCall c = batch_call(m, kKindMarginalsBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
+    c.partial = partial;
     if (!m) return set_err(BNPP_ERR_INVALID, "null argument");
     if (int rc = marginals_targets(m->d, n_targets, targets, c.targets)) return rc;
     if (int rc = plan_batch_entry(c, false, stats, n_stats, rows, cap_rows, n_rows, s, plan, st)) return rc;
@@ -2128,8 +2184,18 @@ int bnpp_plan_marginals_batch(const bnpp_model *m, int n_ev, const int *ev_vars,
         for (const BucketSpec &b : plan.buckets)
             for (size_t j = 0; b.marg_rows && j < b.marg_cols.size(); ++j)
                 col_kind[j] = b.marg_cols[j].table >= 0 ? (b.marg_cols[j].has_b ? 1 : 0) : b.marg_cols[j].ev_row >= 0 ? -1 : -2;
+    for (int j = 0; mask_factor && j < n_ev; ++j)
+        mask_factor[j] = j < (int)plan.batch_mask_factor.size() ? plan.batch_mask_factor[j] : -1;
     return BNPP_OK;
     BNPP_GUARD_END
+}
+
+int bnpp_plan_marginals_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order,
+                              int n_order, int n_targets, const int *targets, int dtype, int64_t rows_per_launch,
+                              double *stats, int n_stats, int64_t *rows, int cap_rows, int *n_rows, int *col_kind) {
+    return bnpp_plan_marginals_batch_mv(m, n_ev, ev_vars, nullptr, heuristic, order, n_order, n_targets, targets,
+                                        dtype, rows_per_launch, stats, n_stats, rows, cap_rows, n_rows, col_kind,
+                                        nullptr);
 }
 
 int bnpp_bucket_marginal_rows(bnpp_ctx *ctx, void *stream, int dtype, int n_targets, const int *cards,
@@ -2684,9 +2750,31 @@ int bnpp_evidence_load_batch(const char *path, int cap_vars, int64_t cap_rows, i
     BNPP_GUARD_END
 }
 
-int bnpp_condition_batch(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, const void *in,
-                         int ndims, const int *vars, int n_ev, const int *ev_vars, int64_t n_rows, const int32_t *ev,
-                         void *out) {
+int bnpp_evidence_load_batch_mv(const char *path, int cap_vars, int64_t cap_rows, int *n_ev, int *ev_vars,
+                                int64_t *n_rows, int *ev_vals, unsigned char *partial) {
+    BNPP_GUARD_BEGIN
+    if (!path || !n_ev || !n_rows) return set_err(BNPP_ERR_INVALID, "null argument");
+    std::vector<int> vars, vals;
+    std::vector<unsigned char> part;
+    int64_t rows = 0;
+    std::string msg;
+    const int rc = load_evidence_batch_missing(path, vars, vals, part, rows, &msg);
+    if (rc == -1) return set_err(BNPP_ERR_IO, std::string("couldn't read file ") + path);
+    if (rc) return set_err(BNPP_ERR_IO, msg);
+    *n_ev = (int)vars.size();
+    *n_rows = rows;
+    if ((int)vars.size() > cap_vars || rows > cap_rows) return set_err(BNPP_ERR_INVALID, "evidence larger than cap");
+    if ((!vars.empty() && (!ev_vars || !partial)) || (!vals.empty() && !ev_vals)) return set_err(BNPP_ERR_INVALID, "null argument");
+    std::copy(vars.begin(), vars.end(), ev_vars);
+    std::copy(vals.begin(), vals.end(), ev_vals);
+    std::copy(part.begin(), part.end(), partial);
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+int bnpp_condition_batch_mv(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, const void *in,
+                            int ndims, const int *vars, int n_ev, const int *ev_vars, const unsigned char *partial,
+                            int64_t n_rows, const int32_t *ev, void *out) {
     BNPP_GUARD_BEGIN
     if (!ctx || !cards || !in || !out || (n_ev > 0 && (!ev_vars || !ev))) return set_err(BNPP_ERR_INVALID, "null argument");
     if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "dtype must be BNPP_F64 or BNPP_F32");
@@ -2699,14 +2787,19 @@ int bnpp_condition_batch(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, co
     b.cond_batch = true;
     b.in.push_back(natural_view(0, std::vector<int>(vars, vars + ndims), cv));
     int n_in_scope = 0;
+    bool masked = false;
     for (int j = 0; j < ndims; ++j) {
         int row = -1;
         for (int e = 0; e < n_ev; ++e)
             if (ev_vars[e] == vars[j]) row = e;
-        b.cond_rows.push_back(row);
-        if (row < 0) b.out_vars.push_back(vars[j]);
+        const bool part = row >= 0 && partial && partial[row];     // kept, under the row's mask
+        b.cond_rows.push_back(part ? -1 : row);
+        b.mask_rows.push_back(part ? row : -1);
+        masked = masked || part;
+        if (row < 0 || part) b.out_vars.push_back(vars[j]);
         else ++n_in_scope;
     }
+    if (!masked) b.mask_rows.clear();
     if (n_in_scope > kCondMaxEv) return set_err(BNPP_ERR_UNSUPPORTED, "at most 32 evidence variables in the scope of a single-op call");
     b.out_vars.push_back(n_cards);
     b.out_table = 1;
@@ -2714,19 +2807,40 @@ int bnpp_condition_batch(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, co
     std::vector<int64_t> pool;
     std::string msg;
     if (!build_desc(b, cv, max_vec_for(dtype), d, pool, &msg)) return set_err(BNPP_ERR_UNSUPPORTED, msg);
-    CondBatchSingleArgs a;
-    std::memset(&a, 0, sizeof a);
-    if (pool.size() > sizeof a.pool / sizeof a.pool[0]) return set_err(BNPP_ERR_UNSUPPORTED, "scope too wide for a single-op call");
-    std::copy(pool.begin(), pool.end(), a.pool);
-    a.src = in;
-    a.out = out;
-    a.ev = ev;
-    a.n_rows = n_rows;
-    hipError_t e = hipSetDevice(ctx->c.device);
-    if (e == hipSuccess) e = launch_cond_batch_single(dtype == BNPP_F32, a, ctx->c.max_grid, pick_stream(ctx, stream));
+    hipError_t e = hipSuccess;
+    if (masked) {
+        CondBatchMaskedArgs a;
+        std::memset(&a, 0, sizeof a);
+        if (pool.size() > sizeof a.pool / sizeof a.pool[0]) return set_err(BNPP_ERR_UNSUPPORTED, "scope too wide for a single-op call");
+        std::copy(pool.begin(), pool.end(), a.pool);
+        a.src = in;
+        a.out = out;
+        a.ev = ev;
+        a.n_rows = n_rows;
+        e = hipSetDevice(ctx->c.device);
+        if (e == hipSuccess) e = launch_cond_batch_masked_single(dtype == BNPP_F32, a, ctx->c.max_grid, pick_stream(ctx, stream));
+    } else {
+        CondBatchSingleArgs a;
+        std::memset(&a, 0, sizeof a);
+        if (pool.size() > sizeof a.pool / sizeof a.pool[0]) return set_err(BNPP_ERR_UNSUPPORTED, "scope too wide for a single-op call");
+        std::copy(pool.begin(), pool.end(), a.pool);
+        a.src = in;
+        a.out = out;
+        a.ev = ev;
+        a.n_rows = n_rows;
+        e = hipSetDevice(ctx->c.device);
+        if (e == hipSuccess) e = launch_cond_batch_single(dtype == BNPP_F32, a, ctx->c.max_grid, pick_stream(ctx, stream));
+    }
     if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return BNPP_OK;
     BNPP_GUARD_END
+}
+
+int bnpp_condition_batch(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, const void *in,
+                         int ndims, const int *vars, int n_ev, const int *ev_vars, int64_t n_rows, const int32_t *ev,
+                         void *out) {
+    return bnpp_condition_batch_mv(ctx, stream, dtype, n_cards, cards, in, ndims, vars, n_ev, ev_vars, nullptr, n_rows, ev,
+                                   out);
 }
 
 int bnpp_ordering(const bnpp_model *m, int n_ev, const int *ev_vars, const int *ev_vals, int n_vars,
@@ -3160,22 +3274,32 @@ int bnpp_sample(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars
     BNPP_GUARD_END
 }
 
-int bnpp_partition_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
-                         const int *ev_vals, int heuristic, const int *order, int n_order, int dtype,
-                         int64_t rows_per_launch, double *log10_z, double *z, double *uptime_ms) {
+int bnpp_partition_batch_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                            const int *ev_vals, const unsigned char *partial, int heuristic, const int *order,
+                            int n_order, int dtype, int64_t rows_per_launch, double *log10_z, double *z,
+                            double *uptime_ms) {
     BNPP_GUARD_BEGIN
     BatchCall c = batch_call(m, kKindBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
+    c.partial = partial;
     c.n_rows = n_rows;
     c.ev_vals = ev_vals;
     return run_batch(ctx, c, false, log10_z, z, nullptr, uptime_ms);
     BNPP_GUARD_END
 }
 
-int bnpp_posterior_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
-                         const int *ev_vals, int heuristic, int target, int dtype, int64_t rows_per_launch, double *out,
-                         double *uptime_ms) {
+int bnpp_partition_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                         const int *ev_vals, int heuristic, const int *order, int n_order, int dtype,
+                         int64_t rows_per_launch, double *log10_z, double *z, double *uptime_ms) {
+    return bnpp_partition_batch_mv(ctx, m, n_ev, ev_vars, n_rows, ev_vals, nullptr, heuristic, order, n_order, dtype,
+                                   rows_per_launch, log10_z, z, uptime_ms);
+}
+
+int bnpp_posterior_batch_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                            const int *ev_vals, const unsigned char *partial, int heuristic, int target, int dtype,
+                            int64_t rows_per_launch, double *out, double *uptime_ms) {
     BNPP_GUARD_BEGIN
     BatchCall c = batch_call(m, kKindBatch, n_ev, ev_vars, heuristic, nullptr, 0, dtype, rows_per_launch);
+    c.partial = partial;
     c.target = target;
     c.n_rows = n_rows;
     c.ev_vals = ev_vals;
@@ -3183,25 +3307,41 @@ int bnpp_posterior_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int
     BNPP_GUARD_END
 }
 
-int bnpp_mpe_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const int *ev_vals,
-                   int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch, double *log10_value,
-                   int *assignment, double *uptime_ms) {
+int bnpp_posterior_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                         const int *ev_vals, int heuristic, int target, int dtype, int64_t rows_per_launch, double *out,
+                         double *uptime_ms) {
+    return bnpp_posterior_batch_mv(ctx, m, n_ev, ev_vars, n_rows, ev_vals, nullptr, heuristic, target, dtype,
+                                   rows_per_launch, out, uptime_ms);
+}
+
+int bnpp_mpe_batch_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                      const int *ev_vals, const unsigned char *partial, int heuristic, const int *order, int n_order,
+                      int dtype, int64_t rows_per_launch, double *log10_value, int *assignment, double *uptime_ms) {
     BNPP_GUARD_BEGIN
     BatchCall c = batch_call(m, kKindMpeBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
+    c.partial = partial;
     c.n_rows = n_rows;
     c.ev_vals = ev_vals;
     return run_mpe_batch(ctx, c, log10_value, assignment, uptime_ms);
     BNPP_GUARD_END
 }
 
-int bnpp_plan_mpe_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
-                        int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows, int cap_rows,
-                        int *n_rows) {
+int bnpp_mpe_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const int *ev_vals,
+                   int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch, double *log10_value,
+                   int *assignment, double *uptime_ms) {
+    return bnpp_mpe_batch_mv(ctx, m, n_ev, ev_vars, n_rows, ev_vals, nullptr, heuristic, order, n_order, dtype,
+                             rows_per_launch, log10_value, assignment, uptime_ms);
+}
+
+int bnpp_plan_mpe_batch_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial,
+                           int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch,
+                           double *stats, int n_stats, int64_t *rows, int cap_rows, int *n_rows, int *mask_factor) {
     BNPP_GUARD_BEGIN
     Schedule s;
     VEPlan plan;
     double st[BNPP_PLAN_MPE_BATCH_STATS] = {0};
-    const BatchCall c = batch_call(m, kKindMpeBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
+    BatchCall c = batch_call(m, kKindMpeBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
+    c.partial = partial;
     if (int rc = plan_batch_entry(c, false, stats, n_stats, rows, cap_rows, n_rows, s, plan, st)) return rc;
     st[10] = (double)plan.arg_bytes;
     st[11] = plan.n_max_buckets;
@@ -3210,16 +3350,27 @@ int bnpp_plan_mpe_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int h
     st[14] = (double)plan.arg_b_entries;
     st[15] = (double)plan.arg_nob_entries;
     for (int i = 0; i < n_stats && i < BNPP_PLAN_MPE_BATCH_STATS; ++i) stats[i] = st[i];
+    for (int j = 0; mask_factor && j < n_ev; ++j)
+        mask_factor[j] = j < (int)plan.batch_mask_factor.size() ? plan.batch_mask_factor[j] : -1;
     return BNPP_OK;
     BNPP_GUARD_END
 }
 
-int bnpp_sample_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const int *ev_vals,
-                      int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch, int64_t n_per_row,
-                      int64_t first_sample, int64_t row_stride, uint64_t seed, uint8_t *out, double *log10_z,
-                      int64_t *n_degenerate, double *uptime_ms) {
+int bnpp_plan_mpe_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
+                        int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows, int cap_rows,
+                        int *n_rows) {
+    return bnpp_plan_mpe_batch_mv(m, n_ev, ev_vars, nullptr, heuristic, order, n_order, dtype, rows_per_launch, stats,
+                                  n_stats, rows, cap_rows, n_rows, nullptr);
+}
+
+int bnpp_sample_batch_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                         const int *ev_vals, const unsigned char *partial, int heuristic, const int *order,
+                         int n_order, int dtype, int64_t rows_per_launch, int64_t n_per_row, int64_t first_sample,
+                         int64_t row_stride, uint64_t seed, uint8_t *out, double *log10_z, int64_t *n_degenerate,
+                         double *uptime_ms) {
     BNPP_GUARD_BEGIN
     BatchCall c = batch_call(m, kKindSampleBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
+    c.partial = partial;
     c.K = n_per_row;
     c.n_rows = n_rows;
     c.ev_vals = ev_vals;
@@ -3227,14 +3378,25 @@ int bnpp_sample_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *e
     BNPP_GUARD_END
 }
 
-int bnpp_plan_sample_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
-                           int dtype, int64_t rows_per_launch, int64_t n_per_row, double *stats, int n_stats,
-                           int64_t *rows, int cap_rows, int *n_rows) {
+int bnpp_sample_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const int *ev_vals,
+                      int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch, int64_t n_per_row,
+                      int64_t first_sample, int64_t row_stride, uint64_t seed, uint8_t *out, double *log10_z,
+                      int64_t *n_degenerate, double *uptime_ms) {
+    return bnpp_sample_batch_mv(ctx, m, n_ev, ev_vars, n_rows, ev_vals, nullptr, heuristic, order, n_order, dtype,
+                                rows_per_launch, n_per_row, first_sample, row_stride, seed, out, log10_z,
+                                n_degenerate, uptime_ms);
+}
+
+int bnpp_plan_sample_batch_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial,
+                              int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch,
+                              int64_t n_per_row, double *stats, int n_stats, int64_t *rows, int cap_rows, int *n_rows,
+                              int *mask_factor) {
     BNPP_GUARD_BEGIN
     Schedule s;
     VEPlan plan;
     double st[BNPP_PLAN_SAMPLE_BATCH_STATS] = {0};
     BatchCall c = batch_call(m, kKindSampleBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
+    c.partial = partial;
     c.K = n_per_row;
     if (int rc = plan_batch_entry(c, false, stats, n_stats, rows, cap_rows, n_rows, s, plan, st)) return rc;
     st[10] = (double)n_per_row;
@@ -3243,19 +3405,30 @@ int bnpp_plan_sample_batch(const bnpp_model *m, int n_ev, const int *ev_vars, in
     st[13] = plan.n_draw_b;
     st[14] = plan.n_draw_nob;
     for (int i = 0; i < n_stats && i < BNPP_PLAN_SAMPLE_BATCH_STATS; ++i) stats[i] = st[i];
+    for (int j = 0; mask_factor && j < n_ev; ++j)
+        mask_factor[j] = j < (int)plan.batch_mask_factor.size() ? plan.batch_mask_factor[j] : -1;
     return BNPP_OK;
     BNPP_GUARD_END
 }
 
-int bnpp_plan_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
-                    int target, int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows,
-                    int cap_rows, int *n_rows, int *result_scope, int *n_result_scope) {
+int bnpp_plan_sample_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
+                           int dtype, int64_t rows_per_launch, int64_t n_per_row, double *stats, int n_stats,
+                           int64_t *rows, int cap_rows, int *n_rows) {
+    return bnpp_plan_sample_batch_mv(m, n_ev, ev_vars, nullptr, heuristic, order, n_order, dtype, rows_per_launch,
+                                     n_per_row, stats, n_stats, rows, cap_rows, n_rows, nullptr);
+}
+
+int bnpp_plan_batch_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial, int heuristic,
+                       const int *order, int n_order, int target, int dtype, int64_t rows_per_launch, double *stats,
+                       int n_stats, int64_t *rows, int cap_rows, int *n_rows, int *result_scope, int *n_result_scope,
+                       int *mask_factor) {
     BNPP_GUARD_BEGIN
     Schedule s;
     VEPlan plan;
     double st[10] = {0};
     BatchCall c = batch_call(m, kKindBatch, n_ev, ev_vars, heuristic, target >= 0 ? nullptr : order,
                              target >= 0 ? 0 : n_order, dtype, rows_per_launch);
+    c.partial = partial;
     c.target = target >= 0 ? target : -1;
     if (int rc = plan_batch_entry(c, target >= 0, stats, n_stats, rows, cap_rows, n_rows, s, plan, st)) return rc;
     for (int i = 0; i < n_stats && i < 10; ++i) stats[i] = st[i];
@@ -3263,8 +3436,17 @@ int bnpp_plan_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuri
     if (n_result_scope) *n_result_scope = (int)rv.size();
     if (result_scope)
         for (size_t i = 0; i < rv.size() && i < 2; ++i) result_scope[i] = rv[i];
+    for (int j = 0; mask_factor && j < n_ev; ++j)
+        mask_factor[j] = j < (int)plan.batch_mask_factor.size() ? plan.batch_mask_factor[j] : -1;
     return BNPP_OK;
     BNPP_GUARD_END
+}
+
+int bnpp_plan_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
+                    int target, int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows,
+                    int cap_rows, int *n_rows, int *result_scope, int *n_result_scope) {
+    return bnpp_plan_batch_mv(m, n_ev, ev_vars, nullptr, heuristic, order, n_order, target, dtype, rows_per_launch,
+                              stats, n_stats, rows, cap_rows, n_rows, result_scope, n_result_scope, nullptr);
 }
 
 int bnpp_marginals(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, const int *ev_vals,

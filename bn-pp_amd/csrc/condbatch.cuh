@@ -23,6 +23,19 @@
 //   [0] source table  [1] n_e  [2] n_rest  [3] rest entries
 //   n_e x (row of ev, stride in src, card)     evidence variables in the scope
 //   n_rest x (card, stride in src)             fastest first, at most kCondMaxRest
+//
+// Masked form (Masked = true, missing values): some rest dims are PARTIAL
+// evidence variables.  Row b keeps an entry only where, for every partial dim,
+// its evidence value is negative (missing) or equals the dim's digit:
+//
+//   out[rest][b] = src[...]  if for every partial dim p: ev[row_p][b] < 0 or ev[row_p][b] == digit_p(rest)
+//                  0         otherwise
+//
+// A masked-out entry issues no load; a value >= the card equals no digit.  The
+// digits are the (wave-uniform) odometer's, so the test is one compare of a
+// lane's value against a scalar per partial dim.  A partial dim is never merged
+// with a neighbour.  The pool continues after the rest words:
+//   n_p, then n_p x (row of ev, index of the rest dim)
 #pragma once
 #include "kernels.cuh"
 
@@ -31,7 +44,7 @@ namespace bnpp {
 constexpr int kCondRestChunk = 32;     // rest entries per virtual block
 constexpr int kCondBatchU = 4;         // rest entries whose gathers are in flight together
 
-template <typename T, int V>
+template <typename T, int V, bool Masked = false>
 __device__ __forceinline__ void cond_batch(cst_t<int64_t> *pool, const T *src, T *out, const int32_t *ev, int64_t R) {
     const int n_e = (int)pool[1], n_rest = (int)pool[2];
     const int64_t n_r = pool[3];
@@ -58,6 +71,23 @@ __device__ __forceinline__ void cond_batch(cst_t<int64_t> *pool, const T *src, T
                 }
             }
         }
+        // masked: the lane's values of the partial dims (-1, "missing", for every other dim and a dead lane)
+        int32_t pv[Masked ? kCondMaxRest : 1][V];
+        bool pd[Masked ? kCondMaxRest : 1];
+        if constexpr (Masked) {
+            const int n_p = (int)rw[2 * n_rest];
+            cst_t<int64_t> *pw = rw + 2 * n_rest + 1;
+#pragma unroll
+            for (int d = 0; d < kCondMaxRest; ++d) {
+                int64_t row = -1;
+                for (int k = 0; k < n_p; ++k)
+                    if (pw[2 * k + 1] == d) row = pw[2 * k];
+                pd[d] = row >= 0;
+#pragma unroll
+                for (int j = 0; j < V; ++j) pv[d][j] = -1;
+                if (pd[d] && live) load_n<int32_t, V, false, true>(ev + row * R + b, pv[d]);
+            }
+        }
         // the odometer at the chunk's first rest entry (uniform)
         const int64_t r0 = rc * kCondRestChunk;
         const int64_t r1 = r0 + kCondRestChunk < n_r ? r0 + kCondRestChunk : n_r;
@@ -75,9 +105,21 @@ __device__ __forceinline__ void cond_batch(cst_t<int64_t> *pool, const T *src, T
         }
         for (int64_t r = r0; r < r1; r += kCondBatchU) {
             int64_t offs[kCondBatchU];
+            bool hit[kCondBatchU][V];
 #pragma unroll
             for (int u = 0; u < kCondBatchU; ++u) {
                 offs[u] = off;
+#pragma unroll
+                for (int j = 0; j < V; ++j) hit[u][j] = true;
+                if constexpr (Masked) {
+#pragma unroll
+                    for (int d = 0; d < kCondMaxRest; ++d)
+                        if (pd[d]) {
+                            const int32_t digit = (int32_t)dig[d];
+#pragma unroll
+                            for (int j = 0; j < V; ++j) hit[u][j] = hit[u][j] && (pv[d][j] < 0 || pv[d][j] == digit);
+                        }
+                }
                 bool carry = true;
 #pragma unroll
                 for (int d = 0; d < kCondMaxRest; ++d) {
@@ -99,7 +141,10 @@ __device__ __forceinline__ void cond_batch(cst_t<int64_t> *pool, const T *src, T
             for (int u = 0; u < kCondBatchU; ++u)
                 if (live && r + u < r1) {
 #pragma unroll
-                    for (int j = 0; j < V; ++j) x[u][j] = gload(src + base[j] + offs[u]);
+                    for (int j = 0; j < V; ++j) {
+                        if constexpr (Masked) x[u][j] = hit[u][j] ? gload(src + base[j] + offs[u]) : T(0);
+                        else x[u][j] = gload(src + base[j] + offs[u]);
+                    }
                 }
 #pragma unroll
             for (int u = 0; u < kCondBatchU; ++u)
@@ -134,6 +179,30 @@ __global__ __launch_bounds__(kBlock) void cond_batch_single_kernel(const CondBat
     cst_t<CondBatchSingleArgs> &a = *(cst_t<CondBatchSingleArgs> *)&args;
 #endif
     cond_batch<T, V>(a.pool, static_cast<const T *>(a.src), static_cast<T *>(a.out), a.ev, a.n_rows);
+}
+
+// The masked gather step of a batch plan, and the masked single gather (bnpp_condition_batch_mv)
+template <typename T, int V>
+__global__ __launch_bounds__(kBlock) void cond_batch_masked_kernel(const int64_t *pool_, TableMeta *meta, int out_table,
+                                                                   const int32_t *ev, int64_t R) {
+    cst_t<int64_t> *pool = as_const(pool_);
+    const int src_table = (int)pool[0];
+    cst_t<TableMeta> &ms = *as_const(meta + src_table);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        meta[out_table].exp2 = ms.exp2;
+        meta[out_table].maxbits = ms.maxbits;
+    }
+    cond_batch<T, V, true>(pool, static_cast<const T *>(ms.ptr), static_cast<T *>(as_const(meta + out_table)->ptr), ev, R);
+}
+template <typename T, int V>
+__global__ __launch_bounds__(kBlock) void cond_batch_masked_single_kernel(const CondBatchMaskedArgs args) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    (void)args;
+    cst_t<CondBatchMaskedArgs> &a = *(cst_t<CondBatchMaskedArgs> *)__builtin_amdgcn_kernarg_segment_ptr();
+#else
+    cst_t<CondBatchMaskedArgs> &a = *(cst_t<CondBatchMaskedArgs> *)&args;
+#endif
+    cond_batch<T, V, true>(a.pool, static_cast<const T *>(a.src), static_cast<T *>(a.out), a.ev, a.n_rows);
 }
 
 // persistent: the grid capped like the other persistent launches
@@ -171,6 +240,30 @@ static hipError_t go_cond_batch_single(const CondBatchSingleArgs &a, int max_gri
     else
         hipLaunchKernelGGL((cond_batch_single_kernel<T, 1>), dim3((unsigned)cond_batch_grid<1>(a.pool[3], a.n_rows, max_grid)),
                            dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
+
+template <typename T>
+static hipError_t go_cond_batch_masked(const int64_t *pool, int64_t rest, TableMeta *meta, int out_table, const void *out_ptr,
+                                       const int32_t *ev, int64_t R, int max_grid, hipStream_t stream) {
+    constexpr int V = 16 / (int)sizeof(T);
+    if (cond_batch_wide<T>(R, out_ptr, ev))
+        hipLaunchKernelGGL((cond_batch_masked_kernel<T, V>), dim3((unsigned)cond_batch_grid<V>(rest, R, max_grid)), dim3(kBlock),
+                           0, stream, pool, meta, out_table, ev, R);
+    else
+        hipLaunchKernelGGL((cond_batch_masked_kernel<T, 1>), dim3((unsigned)cond_batch_grid<1>(rest, R, max_grid)), dim3(kBlock),
+                           0, stream, pool, meta, out_table, ev, R);
+    return hipGetLastError();
+}
+template <typename T>
+static hipError_t go_cond_batch_masked_single(const CondBatchMaskedArgs &a, int max_grid, hipStream_t stream) {
+    constexpr int V = 16 / (int)sizeof(T);
+    if (cond_batch_wide<T>(a.n_rows, a.out, a.ev))
+        hipLaunchKernelGGL((cond_batch_masked_single_kernel<T, V>),
+                           dim3((unsigned)cond_batch_grid<V>(a.pool[3], a.n_rows, max_grid)), dim3(kBlock), 0, stream, a);
+    else
+        hipLaunchKernelGGL((cond_batch_masked_single_kernel<T, 1>),
+                           dim3((unsigned)cond_batch_grid<1>(a.pool[3], a.n_rows, max_grid)), dim3(kBlock), 0, stream, a);
     return hipGetLastError();
 }
 

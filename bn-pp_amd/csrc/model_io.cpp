@@ -146,6 +146,55 @@ int load_evidence_batch(const std::string &path, std::vector<int> &vars, std::ve
     return 0;
 }
 
+int load_evidence_batch_missing(const std::string &path, std::vector<int> &vars, std::vector<int> &vals,
+                                std::vector<unsigned char> &partial, int64_t &n_rows, std::string *err) {
+    std::ifstream in(path);
+    if (!in.is_open()) return -1;
+    vars.clear();
+    vals.clear();
+    partial.clear();
+    n_rows = 0;
+    long n;
+    if (!next_long(in, n) || n < 0) {
+        if (err) *err = "malformed evidence file " + path;
+        return -2;
+    }
+    std::vector<std::vector<std::pair<int, int>>> samples((size_t)n);
+    for (long s = 0; s < n; ++s) {
+        long size;
+        if (!next_long(in, size) || size < 0) {
+            if (err) *err = "malformed evidence file " + path + ": sample " + std::to_string(s) + " is missing";
+            return -2;
+        }
+        std::vector<std::pair<int, int>> &ev = samples[(size_t)s];
+        for (long i = 0; i < size; ++i) {
+            long id, val;
+            if (!next_long(in, id) || !next_long(in, val)) {
+                if (err) *err = "malformed evidence file " + path + ": sample " + std::to_string(s) + " is cut short";
+                return -2;
+            }
+            bool found = false;
+            for (auto &p : ev)
+                if (p.first == id) { p.second = (int)val; found = true; }   // a repeated id: the last value
+            if (!found) ev.push_back({(int)id, (int)val});
+        }
+        for (auto &p : ev) vars.push_back(p.first);
+    }
+    std::sort(vars.begin(), vars.end());                    // the union, ascending
+    vars.erase(std::unique(vars.begin(), vars.end()), vars.end());
+    const size_t ne = vars.size();
+    vals.assign((size_t)n * ne, -1);                        // -1 where a sample is silent
+    for (long s = 0; s < n; ++s)
+        for (auto &p : samples[(size_t)s])
+            vals[(size_t)s * ne + (size_t)(std::lower_bound(vars.begin(), vars.end(), p.first) - vars.begin())] = p.second;
+    partial.assign(ne, 0);
+    for (long s = 0; s < n; ++s)
+        for (size_t j = 0; j < ne; ++j)
+            if (vals[(size_t)s * ne + j] < 0) partial[j] = 1;
+    n_rows = n;
+    return 0;
+}
+
 bool validate(const ModelData &m, std::string *err) {
     for (size_t f = 0; f < m.scopes.size(); ++f) {
         long double sz = 1;

@@ -27,6 +27,10 @@ int load_evidence(const std::string &path, std::vector<std::pair<int, int>> &ev)
 // (malformed), -3 (a sample observes another variable set than the first; err names it)
 int load_evidence_batch(const std::string &path, std::vector<int> &vars, std::vector<int> &vals, int64_t &n_rows,
                         std::string *err);
+// ... whose samples may observe differing variable sets (missing values): vars is the union, ascending,
+// vals holds -1 where a sample is silent, partial[j] = 1 for a variable some sample lacks.  Returns 0, -1, -2
+int load_evidence_batch_missing(const std::string &path, std::vector<int> &vars, std::vector<int> &vals,
+                                std::vector<unsigned char> &partial, int64_t &n_rows, std::string *err);
 // validate shapes (scope ids in range, table sizes = prod(card))
 bool validate(const ModelData &m, std::string *err);
 

@@ -730,15 +730,25 @@ static bool build_condb_desc(const BucketSpec &b, const std::vector<int> &cards,
     // rest dims, fastest first; a variable whose stride continues the previous (faster) one's block is merged into it
     std::vector<std::pair<int64_t, int64_t>> rest, evs;     // (card, stride)
     std::vector<int64_t> ev_row;
+    std::vector<std::pair<int64_t, int64_t>> masks;         // (row of ev, rest dim): a partial dim is never merged
+    bool masked = false, last_partial = false;
+    for (int r : b.mask_rows) masked = masked || r >= 0;
+    if (masked && b.mask_rows.size() != v.vars.size()) {
+        if (msg) *msg = "gather step: one mask row per scope variable is needed";
+        return false;
+    }
     for (int j = (int)v.vars.size() - 1; j >= 0; --j) {
         const int64_t c = cards[v.vars[j]], st = v.strides[j];
+        const bool partial = masked && b.mask_rows[j] >= 0 && b.cond_rows[j] < 0;
         if (b.cond_rows[j] >= 0) {
             evs.push_back({c, st});
             ev_row.push_back(b.cond_rows[j]);
-        } else if (!rest.empty() && rest.back().second * rest.back().first == st) {
+        } else if (!partial && !last_partial && !rest.empty() && rest.back().second * rest.back().first == st) {
             rest.back().first *= c;
         } else {
+            if (partial) masks.push_back({b.mask_rows[j], (int64_t)rest.size()});
             rest.push_back({c, st});
+            last_partial = partial;
         }
     }
     if ((int)rest.size() > kCondMaxRest) {
@@ -760,6 +770,13 @@ static bool build_condb_desc(const BucketSpec &b, const std::vector<int> &cards,
     for (const auto &r : rest) {
         pool.push_back(r.first);
         pool.push_back(r.second);
+    }
+    if (masked) {                                           // the masked kernel's words (condbatch.cuh)
+        pool.push_back((int64_t)masks.size());
+        for (const auto &m : masks) {
+            pool.push_back(m.first);
+            pool.push_back(m.second);
+        }
     }
     const int64_t rows = cards[b.out_vars.back()];
     d.n_in = (int)std::min<size_t>(b.in.size(), 2);
@@ -1975,18 +1992,61 @@ bool plan_sample(const std::vector<int> &cards, const std::vector<View> &sources
     return true;
 }
 
-// level 0 of a batch plan: one gather step per source that mentions an
-// evidence variable (`placed`: per source, the view that takes its place);
-// ce: the model's cards, then the rows
+std::vector<int> batch_mask_factors(const std::vector<int> &cards, const std::vector<View> &sources,
+                                    const std::vector<int> &ev_vars, const std::vector<char> &partial) {
+    std::vector<int> mf(ev_vars.size(), -1);
+    std::vector<char> hard(cards.size(), 0);
+    for (size_t i = 0; i < ev_vars.size(); ++i) hard[ev_vars[i]] = !(i < partial.size() && partial[i]);
+    for (size_t i = 0; i < ev_vars.size(); ++i) {
+        if (!(i < partial.size() && partial[i])) continue;
+        bool best_hard = false;
+        double best_size = 0;
+        for (size_t f = 0; f < sources.size(); ++f) {
+            if (!contains(sources[f].vars, ev_vars[i])) continue;
+            bool has_hard = false;
+            double size = 1;
+            for (int v : sources[f].vars) {
+                has_hard = has_hard || hard[v];
+                if (!hard[v]) size *= cards[v];
+            }
+            if (mf[i] < 0 || (has_hard && !best_hard) || (has_hard == best_hard && size < best_size)) {
+                mf[i] = (int)f;
+                best_hard = has_hard;
+                best_size = size;
+            }
+        }
+    }
+    return mf;
+}
+
+// level 0 of a batch plan: one gather step per source that mentions a hard
+// evidence variable or carries a partial one's mask (`placed`: per source, the
+// view that takes its place); ce: the model's cards, then the rows
 static bool gather_steps(PlanBuilder &B, VEPlan &p, const std::vector<int> &ce, const std::vector<View> &sources,
-                         const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, std::vector<View> &placed,
-                         std::string *msg) {
+                         const std::vector<int> &ev_vars, const std::vector<char> &partial, int64_t rows, int elem_bytes,
+                         std::vector<View> &placed, std::string *msg) {
     const int nv = (int)ce.size() - 1, Bv = nv;
-    std::vector<int> row_of(nv, -1);
-    for (size_t i = 0; i < ev_vars.size(); ++i) row_of[ev_vars[i]] = (int)i;
-    for (const View &s : sources) {
+    std::vector<int> row_of(nv, -1);                        // hard evidence variables only
+    bool any_partial = false;
+    for (size_t i = 0; i < ev_vars.size(); ++i) {
+        const bool part = i < partial.size() && partial[i];
+        any_partial = any_partial || part;
+        if (!part) row_of[ev_vars[i]] = (int)i;
+    }
+    if (any_partial)
+        p.batch_mask_factor = batch_mask_factors(std::vector<int>(ce.begin(), ce.begin() + nv), sources, ev_vars, partial);
+    for (size_t f = 0; f < sources.size(); ++f) {
+        const View &s = sources[f];
         bool any = false;
         for (int v : s.vars) any = any || row_of[v] >= 0;
+        std::vector<int> mask_rows;
+        for (size_t i = 0; i < p.batch_mask_factor.size(); ++i)
+            if (p.batch_mask_factor[i] == (int)f) {
+                if (mask_rows.empty()) mask_rows.assign(s.vars.size(), -1);
+                for (size_t j = 0; j < s.vars.size(); ++j)
+                    if (s.vars[j] == ev_vars[i]) mask_rows[j] = (int)i;
+                any = true;
+            }
         if (!any) {
             placed.push_back(s);
             continue;
@@ -1998,6 +2058,7 @@ static bool gather_steps(PlanBuilder &B, VEPlan &p, const std::vector<int> &ce, 
         }
         BucketSpec g;
         g.cond_batch = true;
+        g.mask_rows = mask_rows;
         g.in.push_back(s);
         View evt;
         evt.table = p.batch_ev_table;
@@ -2058,8 +2119,9 @@ struct BatchPlan {
         const int bi = B.first_bucket(v.vars, from);
         (bi >= 0 ? buckets[bi] : result).push_back(v);
     }
-    bool gather(const std::vector<View> &sources, const std::vector<int> &ev_vars, int elem_bytes, std::string *msg) {
-        if (!gather_steps(B, p, ce, sources, ev_vars, ce.back(), elem_bytes, placed, msg)) return false;
+    bool gather(const std::vector<View> &sources, const std::vector<int> &ev_vars, const std::vector<char> &partial,
+                int elem_bytes, std::string *msg) {
+        if (!gather_steps(B, p, ce, sources, ev_vars, partial, ce.back(), elem_bytes, placed, msg)) return false;
         for (const View &s : placed) pass(s, 0);
         return true;
     }
@@ -2142,12 +2204,12 @@ struct BucketTree {
 
 bool plan_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                 const std::vector<int> &ev_vars, int64_t rows, int target, int elem_bytes, VEPlan &out,
-                std::string *msg) {
+                std::string *msg, const std::vector<char> &partial) {
     out = VEPlan{};
     if (!batch_rows_ok(rows, msg)) return false;
     (void)target;                                           // kept: it is not in `order`, canon() lays it before B
     BatchPlan S(cards, sources, order, rows, out);
-    if (!S.gather(sources, ev_vars, elem_bytes, msg)) return false;
+    if (!S.gather(sources, ev_vars, partial, elem_bytes, msg)) return false;
     for (size_t i = 0; i < order.size(); ++i)
         if (!S.buckets[i].empty()) S.emit_bucket((int)i);
     S.emit_result();
@@ -2156,12 +2218,12 @@ bool plan_batch(const std::vector<int> &cards, const std::vector<View> &sources,
 }
 
 bool plan_mpe_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
-                    const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg) {
+                    const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg, const std::vector<char> &partial) {
     out = VEPlan{};
     VEPlan &p = out;
     if (!batch_rows_ok(rows, msg)) return false;
     BatchPlan S(cards, sources, order, rows, p);
-    if (!S.gather(sources, ev_vars, elem_bytes, msg)) return false;
+    if (!S.gather(sources, ev_vars, partial, elem_bytes, msg)) return false;
     std::vector<BucketSpec::DecodeRow> drows;
     for (int i = 0; i < (int)order.size(); ++i) {
         if (S.buckets[i].empty()) continue;   // a variable in no remaining factor: the assignment keeps 0
@@ -2215,7 +2277,7 @@ bool plan_mpe_batch(const std::vector<int> &cards, const std::vector<View> &sour
 
 bool plan_sample_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                        const std::vector<int> &ev_vars, int64_t rows, int64_t n_per_row, int elem_bytes, VEPlan &out,
-                       std::string *msg) {
+                       std::string *msg, const std::vector<char> &partial) {
     out = VEPlan{};
     VEPlan &p = out;
     if (!batch_rows_ok(rows, msg)) return false;
@@ -2224,7 +2286,7 @@ bool plan_sample_batch(const std::vector<int> &cards, const std::vector<View> &s
         return false;
     }
     BatchPlan S(cards, sources, order, rows, p);
-    if (!S.gather(sources, ev_vars, elem_bytes, msg)) return false;
+    if (!S.gather(sources, ev_vars, partial, elem_bytes, msg)) return false;
     std::vector<BucketSpec::SampleRow> rws(order.size());
     for (int i = 0; i < (int)order.size(); ++i) {
         if (cards[order[i]] > kMaxOutCard) {
@@ -2290,11 +2352,13 @@ struct BatchBucketTree {
             if (contains(v.vars, S.Bv) && !contains(keep, S.Bv)) keep.push_back(S.Bv);
         return S.B.view(S.B.reduce_keep(in, keep));
     }
-    bool build(const std::vector<View> &sources, const std::vector<int> &ev_vars, int elem_bytes, std::string *msg) {
+    bool build(const std::vector<View> &sources, const std::vector<int> &ev_vars, const std::vector<char> &partial,
+               int elem_bytes, std::string *msg) {
         PlanBuilder &B = S.B;
-        if (!S.gather(sources, ev_vars, elem_bytes, msg)) return false;
+        if (!S.gather(sources, ev_vars, partial, elem_bytes, msg)) return false;
         bucket_of.assign(S.placed.size(), -1);
-        for (size_t i = 0; i < ev_vars.size(); ++i) row_of[ev_vars[i]] = (int)i;
+        for (size_t i = 0; i < ev_vars.size(); ++i)         // a partial variable is no evidence variable to the tree
+            if (!(i < partial.size() && partial[i])) row_of[ev_vars[i]] = (int)i;
         for (size_t f = 0; f < S.placed.size(); ++f) {
             for (int v : S.placed[f].vars)
                 if (v != S.Bv && B.rank[v] < 0) {
@@ -2316,12 +2380,12 @@ struct BatchBucketTree {
 }  // namespace
 
 bool plan_counts(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
-                 const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg) {
+                 const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg, const std::vector<char> &partial) {
     out = VEPlan{};
     VEPlan &p = out;
     if (!batch_rows_ok(rows, msg)) return false;
     BatchBucketTree W(cards, sources, order, rows, p);
-    if (!W.build(sources, ev_vars, elem_bytes, msg)) return false;
+    if (!W.build(sources, ev_vars, partial, elem_bytes, msg)) return false;
     BatchPlan &S = W.S;
     BucketTree &T = W.T;
     PlanBuilder &B = S.B;
@@ -2393,7 +2457,7 @@ bool plan_counts(const std::vector<int> &cards, const std::vector<View> &sources
 
 bool plan_marginals_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                           const std::vector<int> &ev_vars, int64_t rows, const std::vector<int> &targets, int elem_bytes,
-                          VEPlan &out, std::string *msg) {
+                          VEPlan &out, std::string *msg, const std::vector<char> &partial) {
     out = VEPlan{};
     VEPlan &p = out;
     if (!batch_rows_ok(rows, msg)) return false;
@@ -2408,7 +2472,7 @@ bool plan_marginals_batch(const std::vector<int> &cards, const std::vector<View>
         }
     }
     BatchBucketTree W(cards, sources, order, rows, p);
-    if (!W.build(sources, ev_vars, elem_bytes, msg)) return false;
+    if (!W.build(sources, ev_vars, partial, elem_bytes, msg)) return false;
     BatchPlan &S = W.S;
     BucketTree &T = W.T;
     PlanBuilder &B = S.B;
@@ -3832,6 +3896,8 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
             it.ok = build_desc(b, plans[it.plan]->cards_ext.empty() ? cards : plans[it.plan]->cards_ext, max_vec, it.d,
                                it.pool, &it.msg);
             it.key = kCondBatchKey;
+            for (int r : b.mask_rows)
+                if (r >= 0) it.key = kCondBatchMaskKey;
             return;
         }
         if (b.counts) {                      // an accumulate step of a counts plan: the executor's, its words in the pool
@@ -3910,7 +3976,7 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
         int64_t vb = 0;
         for (; i < ord.size() && items[ord[i]].level == g.level && items[ord[i]].key == g.variant &&
                items[ord[i]].b->lane == g.lane &&
-               !((g.variant == kCondBatchKey || g.variant == kCountsKey) && (int)i > g.begin);   // one launch per gather / accumulate step
+               !((g.variant == kCondBatchKey || g.variant == kCondBatchMaskKey || g.variant == kCountsKey) && (int)i > g.begin);   // one launch per gather / accumulate step
              ++i) {
             const Item &it = items[ord[i]];
             BucketDesc &d = s.descs[i];

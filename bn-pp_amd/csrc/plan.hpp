@@ -173,6 +173,10 @@ struct BucketSpec {
     // holds the values of in[0].vars[j] (-1: not an evidence variable)
     bool cond_batch = false;
     std::vector<int> cond_rows;
+    // missing values: mask_rows[j] >= 0 names the row of the evidence table of a PARTIAL evidence variable
+    // in[0].vars[j] whose mask this step carries (cond_rows[j] is then -1 and the variable stays in out_vars);
+    // empty, or all -1: an unmasked step
+    std::vector<int> mask_rows;
     // an accumulate step of a counts plan (plan_counts, counts.cuh): in[0] is
     // the belief of one factor over (its non-evidence variables, B) -- B the
     // fastest dim, absent when no evidence reaches the belief -- and the other
@@ -247,6 +251,8 @@ constexpr int kSampleBatchKey = kXchgKeyBase + 24576;
 constexpr int kSampleBatchPoolHead = 4;   // words before the rows of a batched draw step's pool
 // ... of the emit step of a batched-marginals plan (BucketSpec::marg_rows): the executor's
 constexpr int kMargRowsKey = kXchgKeyBase + 28672;
+// ... of a masked gather step (BucketSpec::cond_batch with mask_rows: partial evidence variables): the executor's
+constexpr int kCondBatchMaskKey = kXchgKeyBase + 32768;
 constexpr int kMargRowsPoolHead = 4;      // words before the column blocks of an emit step's pool
 constexpr int kMargRowsColWords = 5;      // words per column block
 constexpr int kCountsMaxDims = 32;  // evidence variables, and other variables, in one factor scope of an accumulate step
@@ -309,6 +315,7 @@ struct VEPlan {
     // plan_sample_batch: sample_bytes = n_vars * rows * K; draw rows with an input that carries B, and without
     int n_draw_b = 0, n_draw_nob = 0;
     int batch_ev_table = -1;            // plan_batch: the evidence table (-1: no gather step)
+    std::vector<int> batch_mask_factor; // per evidence variable: the factor whose gather step carries its mask (-1: none)
     // plan_counts: the per-launch weights (double[rows]) and the first
     // accumulate step's scratch (3 x 8 bytes per row; one per step), raw tables; per factor the
     // variables of its belief table (B = cards.size() last when carried);
@@ -355,6 +362,12 @@ bool plan_mpe(const std::vector<int> &cards, const std::vector<View> &sources, c
 bool plan_sample(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                  const std::vector<int> &ev_val, int elem_bytes, int64_t n_samples, VEPlan &out, std::string *msg);
 
+// Missing values (all batched planners): partial[i] != 0 marks ev_vars[i] as
+// PARTIAL -- it may be missing (-1) in any row.  A partial variable is not
+// conditioned away: it is an ordinary variable of `order`, and exactly one
+// gather step that holds it carries its mask (BucketSpec::mask_rows), chosen
+// by batch_mask_factors.  Empty `partial`: none.
+//
 // Batched evidence: one plan for `rows` evidence assignments over the evidence
 // variables ev_vars.  `sources` are the NATURAL views of the model's factors.
 // A virtual variable B (id cards.size(), card = rows) stands for "which row":
@@ -374,7 +387,13 @@ bool plan_sample(const std::vector<int> &cards, const std::vector<View> &sources
 // than kCondMaxRest runs of non-evidence variables between evidence variables.
 bool plan_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                 const std::vector<int> &ev_vars, int64_t rows, int target, int elem_bytes, VEPlan &out,
-                std::string *msg);
+                std::string *msg, const std::vector<char> &partial = std::vector<char>());
+
+// The factor that carries the mask of each evidence variable (-1: hard, or in no factor): 1. a factor that
+// holds a hard evidence variable (it has a gather step anyway); 2. among those, else among all factors that
+// hold it, the fewest entries after conditioning on the hard variables; 3. the lowest factor index
+std::vector<int> batch_mask_factors(const std::vector<int> &cards, const std::vector<View> &sources,
+                                    const std::vector<int> &ev_vars, const std::vector<char> &partial);
 
 // Batched MPE: plan_batch's gather steps (level 0), evidence table and cards_ext
 // = cards + {rows}, then plan_mpe's elimination over them: every eliminating
@@ -386,7 +405,7 @@ bool plan_batch(const std::vector<int> &cards, const std::vector<View> &sources,
 // when no evidence reaches it; x = uint8[n_vars][rows]}.  `order` covers every
 // non-evidence variable.  Returns false (msg) as plan_batch and plan_mpe do.
 bool plan_mpe_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
-                    const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg);
+                    const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg, const std::vector<char> &partial = std::vector<char>());
 
 // Batched sampling: plan_batch's gather steps (level 0), evidence table and
 // cards_ext = cards + {rows}, then plan_sample's loop over the placed views: no
@@ -401,7 +420,7 @@ bool plan_mpe_batch(const std::vector<int> &cards, const std::vector<View> &sour
 // false (msg) as plan_batch and plan_sample do.
 bool plan_sample_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                        const std::vector<int> &ev_vars, int64_t rows, int64_t n_per_row, int elem_bytes, VEPlan &out,
-                       std::string *msg);
+                       std::string *msg, const std::vector<char> &partial = std::vector<char>());
 
 // Expected sufficient statistics: a batched bucket tree.  plan_batch's gather
 // steps (level 0) and forward pass -- the same buckets in the same order, the
@@ -420,7 +439,7 @@ bool plan_sample_batch(const std::vector<int> &cards, const std::vector<View> &s
 // kCountsMaxDims evidence (or other) variables, or when `order` leaves out a
 // non-evidence variable of a factor.
 bool plan_counts(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
-                 const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg);
+                 const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg, const std::vector<char> &partial = std::vector<char>());
 
 // Batched marginals: plan_counts's batched bucket tree -- the same gather
 // steps, forward pass (plan_batch's, so the first result is its table over (B))
@@ -438,7 +457,7 @@ bool plan_counts(const std::vector<int> &cards, const std::vector<View> &sources
 // false (msg) as plan_counts does, or on a target out of range or listed twice.
 bool plan_marginals_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                           const std::vector<int> &ev_vars, int64_t rows, const std::vector<int> &targets, int elem_bytes,
-                          VEPlan &out, std::string *msg);
+                          VEPlan &out, std::string *msg, const std::vector<char> &partial = std::vector<char>());
 
 // All marginals of `targets` from one two-pass bucket tree over `order`
 // (Shafer-Shenoy on the VE bucket tree; replaces the N independent VEs of

@@ -106,6 +106,19 @@ struct CondBatchSingleArgs {
     int64_t n_rows;
 };
 hipError_t launch_cond_batch_single(int is_f32, const CondBatchSingleArgs &a, int max_grid, hipStream_t stream);
+// the masked forms (missing values: partial evidence variables among the rest dims); the pool continues with
+// n_p and n_p x (row of ev, rest dim)
+hipError_t launch_cond_batch_masked(int is_f32, const int64_t *pool, int64_t rest, TableMeta *meta, int out_table,
+                                    const void *out_ptr, const int32_t *ev, int64_t n_rows, int max_grid,
+                                    hipStream_t stream);
+struct CondBatchMaskedArgs {
+    int64_t pool[4 + 3 * kCondMaxEv + 2 * kCondMaxRest + 1 + 2 * kCondMaxRest];
+    const void *src;
+    void *out;
+    const int32_t *ev;
+    int64_t n_rows;
+};
+hipError_t launch_cond_batch_masked_single(int is_f32, const CondBatchMaskedArgs &a, int max_grid, hipStream_t stream);
 // expected counts (counts.cuh): one factor's belief T over (rest, b) folded
 // into its accumulator, normalised row by row (include/bnpp.h,
 // bnpp_bucket_counts, states the arithmetic).  Everything by value in the

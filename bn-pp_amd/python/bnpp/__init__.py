@@ -42,6 +42,7 @@ _I = C.c_int
 _IP = C.POINTER(C.c_int)
 _DP = C.POINTER(C.c_double)
 _LP = C.POINTER(C.c_int64)
+_UBP = C.POINTER(C.c_ubyte)
 # bnpp_collective_fn (include/bnpp.h): (user, op, send, recv, bytes, stream) -> 0 on success
 COLLECTIVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
 COLL_ALLGATHER, COLL_ALLTOALL = 0, 1
@@ -117,6 +118,27 @@ _SIGS = {
     "bnpp_marginals_batch": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _I, _IP, _I, _I, _IP, _I, C.c_int64, _DP, _DP, _DP]),
     "bnpp_plan_marginals_batch": (_I, [_P, _I, _IP, _I, _IP, _I, _I, _IP, _I, C.c_int64, _DP, _I, _LP, _I, _IP, _IP]),
     "bnpp_bucket_marginal_rows": (_I, [_P, _P, _I, _I, _IP, C.POINTER(_P), _IP, _IP, C.c_int64, C.c_int64, _P, _P]),
+    # missing values: the _mv siblings take partial[n_ev] (after ev_vals; the plan entries: after ev_vars, and
+    # return mask_factor[n_ev] last)
+    "bnpp_partition_batch_mv": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _UBP, _I, _IP, _I, _I, C.c_int64, _DP, _DP, _DP]),
+    "bnpp_posterior_batch_mv": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _UBP, _I, _I, _I, C.c_int64, _DP, _DP]),
+    "bnpp_plan_batch_mv": (_I, [_P, _I, _IP, _UBP, _I, _IP, _I, _I, _I, C.c_int64, _DP, _I, _LP, _I, _IP, _IP, _IP, _IP]),
+    "bnpp_mpe_batch_mv": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _UBP, _I, _IP, _I, _I, C.c_int64, _DP, _IP, _DP]),
+    "bnpp_plan_mpe_batch_mv": (_I, [_P, _I, _IP, _UBP, _I, _IP, _I, _I, C.c_int64, _DP, _I, _LP, _I, _IP, _IP]),
+    "bnpp_sample_batch_mv": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _UBP, _I, _IP, _I, _I, C.c_int64, C.c_int64, C.c_int64,
+                                  C.c_int64, C.c_uint64, _P, _DP, _LP, _DP]),
+    "bnpp_plan_sample_batch_mv": (_I, [_P, _I, _IP, _UBP, _I, _IP, _I, _I, C.c_int64, C.c_int64, _DP, _I, _LP, _I, _IP,
+                                       _IP]),
+    "bnpp_expected_counts_mv": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _UBP, _DP, _I, _IP, _I, _I, C.c_int64, _DP, _DP, _LP,
+                                     _DP]),
+    "bnpp_plan_counts_mv": (_I, [_P, _I, _IP, _UBP, _I, _IP, _I, _I, C.c_int64, _DP, _I, _LP, _I, _IP, _IP, _IP, _I, _IP,
+                                 _IP, _IP]),
+    "bnpp_marginals_batch_mv": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _UBP, _I, _IP, _I, _I, _IP, _I, C.c_int64, _DP, _DP,
+                                     _DP]),
+    "bnpp_plan_marginals_batch_mv": (_I, [_P, _I, _IP, _UBP, _I, _IP, _I, _I, _IP, _I, C.c_int64, _DP, _I, _LP, _I, _IP,
+                                          _IP, _IP]),
+    "bnpp_condition_batch_mv": (_I, [_P, _P, _I, _I, _IP, _P, _I, _IP, _I, _IP, _UBP, C.c_int64, _P, _P]),
+    "bnpp_evidence_load_batch_mv": (_I, [C.c_char_p, _I, C.c_int64, _IP, _IP, _LP, _IP, _UBP]),
     "bnpp_job_create": (_I, [_P, _P, _I, _I, _IP, _IP, _I, _IP, _I, _I, _IP, _I, C.POINTER(_P)]),
     "bnpp_job_stats": (_I, [_P, _DP, _I]),
     "bnpp_job_launch": (_I, [_P, _P]),
@@ -512,6 +534,54 @@ def _ev_rows(ev_vars: Sequence[int], rows):
     return len(ev_vars), _ints(ev_vars), a32.shape[0], a32, a32.ctypes.data_as(_IP)
 
 
+MISSING = -1                         # a missing value of a partial evidence variable (include/bnpp.h BNPP_MISSING)
+COND_BATCH_MASK_KEY = (1 << 24) + 32768   # the launch-group key of a masked gather step (plan.hpp kCondBatchMaskKey)
+
+
+def _partial_flags(ev_vars: Sequence[int], partial, rows=None):
+    """partial as the _mv entries take it: None (the call without the argument),
+    else one unsigned byte per evidence variable.  partial: None, "auto" (the
+    columns of `rows` that hold a MISSING) or a sequence of variable ids."""
+    if partial is None:
+        return None
+    ev_vars = [int(v) for v in ev_vars]
+    flags = (C.c_ubyte * max(len(ev_vars), 1))()
+    if isinstance(partial, str):
+        if partial != "auto":
+            raise ValueError('partial must be None, "auto" or a sequence of variable ids')
+        if rows is None:
+            raise ValueError('partial="auto" needs the rows')
+        for j in range(len(ev_vars)):
+            flags[j] = 1 if rows.shape[0] and bool((rows[:, j] == MISSING).any()) else 0
+        return flags
+    ids = [int(v) for v in partial]
+    for v in ids:
+        if v not in ev_vars:
+            raise ValueError("partial variable %d is not an evidence variable" % v)
+    for j, v in enumerate(ev_vars):
+        flags[j] = 1 if v in ids else 0
+    return flags
+
+
+def _mv(name: str, pf):
+    """(the entry point, its name, the partial argument as a tuple to splice in)."""
+    if pf is None:
+        return getattr(_lib, name), name, ()
+    return getattr(_lib, name + "_mv"), name + "_mv", (pf,)
+
+
+def _mask_tail(pf, n_ev, tail=lambda: ()):
+    """The tail of a plan entry with mask_factor appended for the _mv entries; the list that reads it back."""
+    mf = (C.c_int * max(n_ev, 1))()
+    if pf is None:
+        return tail, lambda: None
+    return (lambda: (*tail(), mf)), (lambda: [mf[j] for j in range(n_ev)])
+
+
+def _h(ctx):
+    return ctx.handle if ctx is not None else None
+
+
 def _order_args(order, heuristic):
     """(heuristic, order, n_order) as the C ABI takes them: an explicit order wins over the heuristic's name."""
     if order is None:
@@ -534,11 +604,25 @@ def _plan_call(fn, name, stat_names, head, tail=lambda: ()):
             [dict(zip(PLAN_GROUP_FIELDS, rows[i * nf:(i + 1) * nf])) for i in range(cnt.value)])
 
 
-def load_evidence_batch(path: str):
+def load_evidence_batch(path: str, missing: bool = False):
     """An .evid file of any number of samples over one variable set
-    (bnpp_evidence_load_batch) -> (ev_vars ascending, rows as an (n, n_ev) numpy int array)."""
+    (bnpp_evidence_load_batch) -> (ev_vars ascending, rows as an (n, n_ev) numpy int array).
+    missing=True (bnpp_evidence_load_batch_mv): the samples may observe differing
+    variable sets -> (the union ascending, rows with MISSING where a sample is
+    silent, the variables some sample lacks: what to pass as `partial`)."""
     import numpy as np
     n_ev, n_rows = C.c_int(), C.c_int64()
+    if missing:
+        fn, name = _lib.bnpp_evidence_load_batch_mv, "bnpp_evidence_load_batch_mv"
+        rc = fn(path.encode(), 0, 0, C.byref(n_ev), None, C.byref(n_rows), None, None)
+        if rc != OK and not (rc == ERR_INVALID and (n_ev.value > 0 or n_rows.value > 0)):
+            raise BnppError(rc, name)
+        vs = (C.c_int * max(n_ev.value, 1))()
+        pf = (C.c_ubyte * max(n_ev.value, 1))()
+        rows = np.zeros((n_rows.value, n_ev.value), dtype=np.intc)
+        _check(fn(path.encode(), n_ev.value, n_rows.value, C.byref(n_ev), vs, C.byref(n_rows), rows.ctypes.data_as(_IP), pf),
+               name)
+        return [vs[i] for i in range(n_ev.value)], rows, [vs[i] for i in range(n_ev.value) if pf[i]]
     rc = _lib.bnpp_evidence_load_batch(path.encode(), 0, 0, C.byref(n_ev), None, C.byref(n_rows), None)
     if rc != OK and not (rc == ERR_INVALID and (n_ev.value > 0 or n_rows.value > 0)):
         raise BnppError(rc, "bnpp_evidence_load_batch")
@@ -550,8 +634,14 @@ def load_evidence_batch(path: str):
 
 
 def plan_batch(model: Model, ev_vars: Sequence[int], target: Optional[int] = None, heuristic: str = "mf",
-               dtype: int = F64, rows_per_launch: int = 0, order: Optional[Sequence[int]] = None):
-    """Host-only planning of partition_batch (target None) or posterior_batch
+               dtype: int = F64, rows_per_launch: int = 0, order: Optional[Sequence[int]] = None, partial=None):
+    """partial (here and in every batched call and plan function): None, or the
+    evidence variables that may be MISSING in a row -- a sequence of ids, or
+    "auto" in the run calls for the columns that hold a MISSING (include/bnpp.h,
+    missing values).  A plan function given `partial` also returns mask_factor
+    (per evidence variable the factor that carries its mask, -1: none) last.
+
+    Host-only planning of partition_batch (target None) or posterior_batch
     (bnpp_plan_batch) -> (stats, groups, result_scope): stats a dict of
     PLAN_BATCH_STATS, groups one dict of PLAN_GROUP_FIELDS per launch group (the
     gather steps: level 0, key COND_BATCH_KEY), result_scope the result
@@ -560,14 +650,17 @@ def plan_batch(model: Model, ev_vars: Sequence[int], target: Optional[int] = Non
     nrs = C.c_int()
     rs = (C.c_int * 2)()
     t = -1 if target is None else int(target)
-    st, groups = _plan_call(_lib.bnpp_plan_batch, "bnpp_plan_batch", PLAN_BATCH_STATS,
-                            (model.handle, len(ev_vars), _ints(ev_vars), *_order_args(order, heuristic), t, dtype,
-                             int(rows_per_launch)), lambda: (rs, C.byref(nrs)))
-    return st, groups, [rs[i] for i in range(min(nrs.value, 2))]
+    fn, name, pa = _mv("bnpp_plan_batch", _partial_flags(ev_vars, partial))
+    tail, mask = _mask_tail(pa[0] if pa else None, len(ev_vars), lambda: (rs, C.byref(nrs)))
+    st, groups = _plan_call(fn, name, PLAN_BATCH_STATS,
+                            (model.handle, len(ev_vars), _ints(ev_vars), *pa, *_order_args(order, heuristic), t, dtype,
+                             int(rows_per_launch)), tail)
+    res = st, groups, [rs[i] for i in range(min(nrs.value, 2))]
+    return res + (mask(),) if pa else res
 
 
 def partition_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, heuristic: str = "mf", dtype: int = F64,
-                    rows_per_launch: int = 0, order: Optional[Sequence[int]] = None):
+                    rows_per_launch: int = 0, order: Optional[Sequence[int]] = None, partial=None):
     """log10 Z and Z of every evidence row from one plan (bnpp_partition_batch)
     -> (log10_z, z, uptime_ms), numpy float64 arrays of length n.  rows: an
     (n, len(ev_vars)) integer array, rows[r][j] the value of ev_vars[j]."""
@@ -576,14 +669,15 @@ def partition_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, he
     h, oa, no = _order_args(order, heuristic)
     lz, z = np.zeros(max(n, 1)), np.zeros(max(n, 1))
     up = C.c_double()
-    _check(_lib.bnpp_partition_batch(ctx.handle, model.handle, ne, ev_v, n, ev_x, h, oa, no, dtype, int(rows_per_launch),
-                                     lz.ctypes.data_as(_DP), z.ctypes.data_as(_DP), C.byref(up)), "bnpp_partition_batch")
+    fn, name, pa = _mv("bnpp_partition_batch", _partial_flags(ev_vars, partial, keep))
+    _check(fn(_h(ctx), model.handle, ne, ev_v, n, ev_x, *pa, h, oa, no, dtype, int(rows_per_launch),
+              lz.ctypes.data_as(_DP), z.ctypes.data_as(_DP), C.byref(up)), name)
     del keep
     return lz[:n], z[:n], up.value
 
 
 def posterior_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, target: int, heuristic: str = "mf",
-                    dtype: int = F64, rows_per_launch: int = 0):
+                    dtype: int = F64, rows_per_launch: int = 0, partial=None):
     """P(target | evidence row) for every row from one plan (bnpp_posterior_batch)
     -> (an (n, card(target)) numpy float64 array, uptime_ms)."""
     import numpy as np
@@ -592,8 +686,9 @@ def posterior_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, ta
     k = model.cards[t] if 0 <= t < model.n_vars else 1
     out = np.zeros((max(n, 1), max(k, 1)))
     up = C.c_double()
-    _check(_lib.bnpp_posterior_batch(ctx.handle, model.handle, ne, ev_v, n, ev_x, HEURISTICS[heuristic], t, dtype,
-                                     int(rows_per_launch), out.ctypes.data_as(_DP), C.byref(up)), "bnpp_posterior_batch")
+    fn, name, pa = _mv("bnpp_posterior_batch", _partial_flags(ev_vars, partial, keep))
+    _check(fn(_h(ctx), model.handle, ne, ev_v, n, ev_x, *pa, HEURISTICS[heuristic], t, dtype,
+              int(rows_per_launch), out.ctypes.data_as(_DP), C.byref(up)), name)
     del keep
     return out[:n, :k], up.value
 
@@ -604,20 +699,23 @@ PLAN_MPE_BATCH_STATS = PLAN_BATCH_STATS + ("arg_bytes", "max_buckets", "arg_tabl
 
 
 def plan_mpe_batch(model: Model, ev_vars: Sequence[int], heuristic: str = "mf", dtype: int = F64,
-                   rows_per_launch: int = 0, order: Optional[Sequence[int]] = None):
+                   rows_per_launch: int = 0, order: Optional[Sequence[int]] = None, partial=None):
     """Host-only planning of mpe_batch (bnpp_plan_mpe_batch) -> (stats, groups):
     stats a dict of PLAN_MPE_BATCH_STATS (arg_bytes = arg_entries_per_row *
     rows_per_launch + arg_entries_no_b), groups one dict of PLAN_GROUP_FIELDS per
     launch group: the gather steps (level 0, COND_BATCH_KEY), max and product
     buckets, and the traceback step last (MPE_DECODE_BATCH_KEY)."""
     ev_vars = [int(v) for v in ev_vars]
-    return _plan_call(_lib.bnpp_plan_mpe_batch, "bnpp_plan_mpe_batch", PLAN_MPE_BATCH_STATS,
-                      (model.handle, len(ev_vars), _ints(ev_vars), *_order_args(order, heuristic), dtype,
-                       int(rows_per_launch)))
+    fn, name, pa = _mv("bnpp_plan_mpe_batch", _partial_flags(ev_vars, partial))
+    tail, mask = _mask_tail(pa[0] if pa else None, len(ev_vars))
+    res = _plan_call(fn, name, PLAN_MPE_BATCH_STATS,
+                     (model.handle, len(ev_vars), _ints(ev_vars), *pa, *_order_args(order, heuristic), dtype,
+                      int(rows_per_launch)), tail)
+    return res + (mask(),) if pa else res
 
 
 def mpe_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, heuristic: str = "mf", dtype: int = F64,
-              order: Optional[Sequence[int]] = None, rows_per_launch: int = 0):
+              order: Optional[Sequence[int]] = None, rows_per_launch: int = 0, partial=None):
     """The most probable completion of every evidence row from one plan
     (bnpp_mpe_batch) -> (log10_value float64[n], assignment int32 (n, n_vars),
     uptime_ms).  rows: an (n, len(ev_vars)) integer array, rows[r][j] the value
@@ -628,8 +726,9 @@ def mpe_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, heuristi
     lv = np.zeros(max(n, 1))
     x = np.zeros((max(n, 1), max(model.n_vars, 1)), dtype=np.intc)
     up = C.c_double()
-    _check(_lib.bnpp_mpe_batch(ctx.handle, model.handle, ne, ev_v, n, ev_x, h, oa, no, dtype, int(rows_per_launch),
-                               lv.ctypes.data_as(_DP), x.ctypes.data_as(_IP), C.byref(up)), "bnpp_mpe_batch")
+    fn, name, pa = _mv("bnpp_mpe_batch", _partial_flags(ev_vars, partial, keep))
+    _check(fn(_h(ctx), model.handle, ne, ev_v, n, ev_x, *pa, h, oa, no, dtype, int(rows_per_launch),
+              lv.ctypes.data_as(_DP), x.ctypes.data_as(_IP), C.byref(up)), name)
     del keep
     return lv[:n], x[:n, :model.n_vars].astype(np.int32, copy=False), up.value
 
@@ -639,7 +738,7 @@ PLAN_SAMPLE_BATCH_STATS = PLAN_BATCH_STATS + ("n_per_row", "state_bytes", "draw_
 
 
 def plan_sample_batch(model: Model, ev_vars: Sequence[int], n_per_row: int = 1, heuristic: str = "mf", dtype: int = F64,
-                      rows_per_launch: int = 0, order: Optional[Sequence[int]] = None):
+                      rows_per_launch: int = 0, order: Optional[Sequence[int]] = None, partial=None):
     """Host-only planning of sample_batch (bnpp_plan_sample_batch) -> (stats,
     groups): stats a dict of PLAN_SAMPLE_BATCH_STATS (state_bytes = n_vars *
     rows_per_launch * n_per_row; draw_rows = draw_rows_b + draw_rows_no_b, with
@@ -648,14 +747,17 @@ def plan_sample_batch(model: Model, ev_vars: Sequence[int], n_per_row: int = 1, 
     COND_BATCH_KEY), sum and product buckets, and the draw step last
     (SAMPLE_BATCH_KEY)."""
     ev_vars = [int(v) for v in ev_vars]
-    return _plan_call(_lib.bnpp_plan_sample_batch, "bnpp_plan_sample_batch", PLAN_SAMPLE_BATCH_STATS,
-                      (model.handle, len(ev_vars), _ints(ev_vars), *_order_args(order, heuristic), dtype,
-                       int(rows_per_launch), int(n_per_row)))
+    fn, name, pa = _mv("bnpp_plan_sample_batch", _partial_flags(ev_vars, partial))
+    tail, mask = _mask_tail(pa[0] if pa else None, len(ev_vars))
+    res = _plan_call(fn, name, PLAN_SAMPLE_BATCH_STATS,
+                     (model.handle, len(ev_vars), _ints(ev_vars), *pa, *_order_args(order, heuristic), dtype,
+                      int(rows_per_launch), int(n_per_row)), tail)
+    return res + (mask(),) if pa else res
 
 
 def sample_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, n_per_row: int, seed: int = 0,
                  first_sample: int = 0, row_stride: Optional[int] = None, heuristic: str = "mf", dtype: int = F64,
-                 order: Optional[Sequence[int]] = None, rows_per_launch: int = 0):
+                 order: Optional[Sequence[int]] = None, rows_per_launch: int = 0, partial=None):
     """n_per_row exact joint samples of P(x | evidence row) for every evidence
     row from one plan (bnpp_sample_batch) -> (samples uint8 (n, n_per_row,
     n_vars), log10_z float64[n], n_degenerate int64[n]).  rows: an (n,
@@ -672,9 +774,10 @@ def sample_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, n_per
     lz = np.zeros(max(n, 1))
     deg = np.zeros(max(n, 1), dtype=np.int64)
     up = C.c_double()
-    _check(_lib.bnpp_sample_batch(ctx.handle, model.handle, ne, ev_v, n, ev_x, h, oa, no, dtype, int(rows_per_launch), k,
-                                  int(first_sample), stride, int(seed) & 0xFFFFFFFFFFFFFFFF, _P(out.ctypes.data),
-                                  lz.ctypes.data_as(_DP), deg.ctypes.data_as(_LP), C.byref(up)), "bnpp_sample_batch")
+    fn, name, pa = _mv("bnpp_sample_batch", _partial_flags(ev_vars, partial, keep))
+    _check(fn(_h(ctx), model.handle, ne, ev_v, n, ev_x, *pa, h, oa, no, dtype, int(rows_per_launch), k,
+              int(first_sample), stride, int(seed) & 0xFFFFFFFFFFFFFFFF, _P(out.ctypes.data),
+              lz.ctypes.data_as(_DP), deg.ctypes.data_as(_LP), C.byref(up)), name)
     del keep
     return out[:n, :k, :model.n_vars], lz[:n], deg[:n]
 
@@ -684,7 +787,7 @@ PLAN_COUNTS_STATS = PLAN_BATCH_STATS + ("count_steps", "forward_levels")
 
 
 def plan_counts(model: Model, ev_vars: Sequence[int], heuristic: str = "mf", dtype: int = F64,
-                rows_per_launch: int = 0, order: Optional[Sequence[int]] = None):
+                rows_per_launch: int = 0, order: Optional[Sequence[int]] = None, partial=None):
     """Host-only planning of expected_counts (bnpp_plan_counts) -> (stats,
     groups, beliefs, no_b_elim): stats a dict of PLAN_COUNTS_STATS, groups one
     dict of PLAN_GROUP_FIELDS per launch group (the accumulate steps: key
@@ -701,15 +804,18 @@ def plan_counts(model: Model, ev_vars: Sequence[int], heuristic: str = "mf", dty
         bvs.append((C.c_int * max(nb.value, 1))())
         return off, bvs[-1], nb.value, C.byref(nb), C.byref(flag)
 
-    st, groups = _plan_call(_lib.bnpp_plan_counts, "bnpp_plan_counts", PLAN_COUNTS_STATS,
-                            (model.handle, len(ev_vars), _ints(ev_vars), *_order_args(order, heuristic), dtype,
-                             int(rows_per_launch)), beliefs)
+    fn, name, pa = _mv("bnpp_plan_counts", _partial_flags(ev_vars, partial))
+    tail, mask = _mask_tail(pa[0] if pa else None, len(ev_vars), beliefs)
+    st, groups = _plan_call(fn, name, PLAN_COUNTS_STATS,
+                            (model.handle, len(ev_vars), _ints(ev_vars), *pa, *_order_args(order, heuristic), dtype,
+                             int(rows_per_launch)), tail)
     bv = bvs[-1]
-    return st, groups, [[bv[j] for j in range(off[f], off[f + 1])] for f in range(model.n_factors)], bool(flag.value)
+    res = st, groups, [[bv[j] for j in range(off[f], off[f + 1])] for f in range(model.n_factors)], bool(flag.value)
+    return res + (mask(),) if pa else res
 
 
 def expected_counts(ctx: Context, model: Model, ev_vars: Sequence[int], rows, weights=None, heuristic: str = "mf",
-                    dtype: int = F64, rows_per_launch: int = 0, order: Optional[Sequence[int]] = None):
+                    dtype: int = F64, rows_per_launch: int = 0, order: Optional[Sequence[int]] = None, partial=None):
     """Expected sufficient statistics of the evidence rows (bnpp_expected_counts)
     -> (counts, log10_z, n_impossible): counts one flat float64 array, the
     factors in model order, each N_f(x_S) = sum_b w_b P(x_S | row b) in its
@@ -717,7 +823,8 @@ def expected_counts(ctx: Context, model: Model, ev_vars: Sequence[int], rows, we
     row as partition_batch's; n_impossible the rows with Z = 0, which count
     nowhere.  weights: None (all 1) or one finite weight >= 0 per row.  All
     rows share the evidence variables ev_vars: group rows with different missing
-    patterns by pattern, call once per pattern and add the counts."""
+    patterns by pattern, call once per pattern and add the counts -- or declare
+    the variables that are missing somewhere `partial` and pass MISSING."""
     import numpy as np
     ne, ev_v, n, keep, ev_x = _ev_rows(ev_vars, rows)
     h, oa, no = _order_args(order, heuristic)
@@ -731,10 +838,10 @@ def expected_counts(ctx: Context, model: Model, ev_vars: Sequence[int], rows, we
             raise ValueError("one weight per row is needed")
     ni = C.c_int64()
     up = C.c_double()
-    _check(_lib.bnpp_expected_counts(ctx.handle if ctx is not None else None, model.handle, ne, ev_v, n, ev_x,
-                                     w.ctypes.data_as(_DP) if w is not None else None, h, oa, no, dtype, int(rows_per_launch),
-                                     counts.ctypes.data_as(_DP), lz.ctypes.data_as(_DP), C.byref(ni), C.byref(up)),
-           "bnpp_expected_counts")
+    fn, name, pa = _mv("bnpp_expected_counts", _partial_flags(ev_vars, partial, keep))
+    _check(fn(_h(ctx), model.handle, ne, ev_v, n, ev_x, *pa,
+              w.ctypes.data_as(_DP) if w is not None else None, h, oa, no, dtype, int(rows_per_launch),
+              counts.ctypes.data_as(_DP), lz.ctypes.data_as(_DP), C.byref(ni), C.byref(up)), name)
     del keep
     return counts[:total.value], lz[:n], ni.value
 
@@ -771,7 +878,7 @@ def _targets_arg(model: Model, targets):
 
 def plan_marginals_batch(model: Model, ev_vars: Sequence[int], targets: Optional[Sequence[int]] = None,
                          heuristic: str = "mf", dtype: int = F64, rows_per_launch: int = 0,
-                         order: Optional[Sequence[int]] = None):
+                         order: Optional[Sequence[int]] = None, partial=None):
     """Host-only planning of marginals_batch (bnpp_plan_marginals_batch) ->
     (stats, groups, col_kinds): stats a dict of PLAN_MARGINALS_BATCH_STATS,
     groups one dict of PLAN_GROUP_FIELDS per launch group (the groups up to
@@ -782,15 +889,18 @@ def plan_marginals_batch(model: Model, ev_vars: Sequence[int], targets: Optional
     ev_vars = [int(v) for v in ev_vars]
     ts, nt, ta = _targets_arg(model, targets)
     kinds = (C.c_int * max(len(ts), 1))()
-    st, groups = _plan_call(_lib.bnpp_plan_marginals_batch, "bnpp_plan_marginals_batch", PLAN_MARGINALS_BATCH_STATS,
-                            (model.handle, len(ev_vars), _ints(ev_vars), *_order_args(order, heuristic), nt, ta, dtype,
-                             int(rows_per_launch)), lambda: (kinds,))
-    return st, groups, [COL_KINDS[kinds[j]] for j in range(len(ts))]
+    fn, name, pa = _mv("bnpp_plan_marginals_batch", _partial_flags(ev_vars, partial))
+    tail, mask = _mask_tail(pa[0] if pa else None, len(ev_vars), lambda: (kinds,))
+    st, groups = _plan_call(fn, name, PLAN_MARGINALS_BATCH_STATS,
+                            (model.handle, len(ev_vars), _ints(ev_vars), *pa, *_order_args(order, heuristic), nt, ta, dtype,
+                             int(rows_per_launch)), tail)
+    res = st, groups, [COL_KINDS[kinds[j]] for j in range(len(ts))]
+    return res + (mask(),) if pa else res
 
 
 def marginals_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, targets: Optional[Sequence[int]] = None,
                     heuristic: str = "mf", dtype: int = F64, rows_per_launch: int = 0,
-                    order: Optional[Sequence[int]] = None, out=None):
+                    order: Optional[Sequence[int]] = None, out=None, partial=None):
     """Every posterior marginal P(X_t | evidence row) of every row from one
     plan (bnpp_marginals_batch) -> (out, log10_z): out an (n, W) float64 array,
     row-major, W = sum of the targets' cards, the targets' blocks in the given
@@ -813,9 +923,10 @@ def marginals_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, ta
         raise ValueError("out must be a writeable C-contiguous float64 array of shape (n, W)")
     lz = np.zeros(max(n, 1))
     up = C.c_double()
-    _check(_lib.bnpp_marginals_batch(ctx.handle if ctx is not None else None, model.handle, ne, ev_v, n, ev_x, h, oa, no,
-                                     nt, ta, dtype, int(rows_per_launch), out.ctypes.data_as(_DP), lz.ctypes.data_as(_DP),
-                                     C.byref(up)), "bnpp_marginals_batch")
+    fn, name, pa = _mv("bnpp_marginals_batch", _partial_flags(ev_vars, partial, keep))
+    _check(fn(_h(ctx), model.handle, ne, ev_v, n, ev_x, *pa, h, oa, no,
+              nt, ta, dtype, int(rows_per_launch), out.ctypes.data_as(_DP), lz.ctypes.data_as(_DP),
+              C.byref(up)), name)
     del keep
     return out[:n], lz[:n]
 
@@ -1101,13 +1212,16 @@ def divide(ctx: Context, dtype: int, cards: Sequence[int], a: int, a_scope: Sequ
 
 
 def condition_batch(ctx: Context, dtype: int, cards: Sequence[int], table: int, scope: Sequence[int],
-                    ev_vars: Sequence[int], n_rows: int, ev: int, out: int, stream: Optional[int] = None) -> None:
+                    ev_vars: Sequence[int], n_rows: int, ev: int, out: int, stream: Optional[int] = None,
+                    partial=None) -> None:
     """Batched conditioning on caller-owned device buffers (bnpp_condition_batch):
     out[rest][b] = table conditioned on evidence row b; ev: a device
-    int32[len(ev_vars)][n_rows], variable-major.  Only enqueues on `stream`."""
-    _check(_lib.bnpp_condition_batch(ctx.handle, _P(stream) if stream else None, dtype, len(cards), _ints(cards), _P(table),
-                                     len(scope), _ints(scope), len(ev_vars), _ints(ev_vars), int(n_rows), _P(ev), _P(out)),
-           "bnpp_condition_batch")
+    int32[len(ev_vars)][n_rows], variable-major.  Only enqueues on `stream`.
+    partial: the evidence variables that stay dims of `out` under the row's mask
+    (bnpp_condition_batch_mv): a negative value is missing."""
+    fn, name, pa = _mv("bnpp_condition_batch", _partial_flags(ev_vars, partial))
+    _check(fn(ctx.handle, _P(stream) if stream else None, dtype, len(cards), _ints(cards), _P(table),
+              len(scope), _ints(scope), len(ev_vars), _ints(ev_vars), *pa, int(n_rows), _P(ev), _P(out)), name)
 
 
 def bucket_counts(ctx: Context, dtype: int, cards: Sequence[int], table: int, scope: Sequence[int],

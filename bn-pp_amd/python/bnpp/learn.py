@@ -42,7 +42,7 @@ def m_step(model_dict: dict, counts, prior: float = 0.0) -> dict:
 
 
 def em(ctx: Context, model_dict: dict, ev_vars: Sequence[int], rows, iters: int, weights=None, dtype: int = F64,
-       prior: float = 0.0) -> Tuple[dict, List[float]]:
+       prior: float = 0.0, partial=None) -> Tuple[dict, List[float]]:
     """`iters` EM iterations on the rows -> (the fitted model_dict, the
     weighted log-likelihood in log10 of the model each iteration started from).
 
@@ -50,25 +50,31 @@ def em(ctx: Context, model_dict: dict, ev_vars: Sequence[int], rows, iters: int,
     on the device) and refits the CPTs with m_step.  Impossible rows (Z = 0)
     count nowhere and are left out of the log-likelihood.  All rows share
     ev_vars; group rows with different missing patterns by pattern yourself
-    (see the module docstring).
+    (see the module docstring) -- or pass `partial` (the variables that hold
+    bnpp.MISSING in some row, or "auto"): every row then keeps its own pattern
+    in one plan (expected_counts, missing values).
     """
     w = None if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
     cur, lls = model_dict, []
     for _ in range(int(iters)):
-        counts, lz, _ = expected_counts(ctx, Model.from_dict(cur), ev_vars, rows, weights=w, dtype=dtype)
+        counts, lz, _ = expected_counts(ctx, Model.from_dict(cur), ev_vars, rows, weights=w, dtype=dtype,
+                                        partial=partial)
         ok = np.isfinite(lz)
         lls.append(float(np.sum((lz if w is None else w * np.where(ok, lz, 0.0))[ok])))
         cur = m_step(cur, counts, prior)
     return cur, lls
 
 
-def impute(ctx: Context, model: Model, ev_vars: Sequence[int], rows, k: int = 1, seed: int = 0, dtype: int = F64):
+def impute(ctx: Context, model: Model, ev_vars: Sequence[int], rows, k: int = 1, seed: int = 0, dtype: int = F64,
+           partial=None):
     """k completions of every row, drawn from P(x | the row) (sample_batch with
     disjoint streams) -> uint8 (n, k, n_vars): the observed variables keep
     their values, the others are one exact joint draw.  Multiple imputation,
     the E step of a stochastic EM, posterior-predictive checks.  An impossible
-    row (Z = 0) comes back with its observed values and zeros elsewhere."""
-    return sample_batch(ctx, model, ev_vars, rows, int(k), seed=seed, dtype=dtype)[0]
+    row (Z = 0) comes back with its observed values and zeros elsewhere.
+    partial: the variables that may be bnpp.MISSING in a row (or "auto"); a
+    row's observed entries keep their values, its missing ones are drawn."""
+    return sample_batch(ctx, model, ev_vars, rows, int(k), seed=seed, dtype=dtype, partial=partial)[0]
 
 
 def argmax_marginals(cards: Sequence[int], targets, out) -> np.ndarray:
@@ -81,12 +87,13 @@ def argmax_marginals(cards: Sequence[int], targets, out) -> np.ndarray:
     return np.stack([np.argmax(b, axis=1) for b in blocks], axis=1).astype(np.int64)
 
 
-def classify(ctx: Context, model: Model, ev_vars: Sequence[int], rows, targets, dtype: int = F64):
+def classify(ctx: Context, model: Model, ev_vars: Sequence[int], rows, targets, dtype: int = F64, partial=None):
     """Maximum-posterior-marginal decoding: for every row the most probable
     value of each target on its own, argmax_x P(X_t = x | the row) -> (an
     (n, len(targets)) int array, lowest value on ties; the (n, W) marginals of
     marginals_batch).  Unlike the MPE (mpe_batch) the targets are decoded one by
-    one, which minimises the expected number of wrong labels."""
+    one, which minimises the expected number of wrong labels.  partial: as
+    marginals_batch's (rows with bnpp.MISSING entries)."""
     targets = [int(t) for t in targets]
-    out, _ = marginals_batch(ctx, model, ev_vars, rows, targets=targets, dtype=dtype)
+    out, _ = marginals_batch(ctx, model, ev_vars, rows, targets=targets, dtype=dtype, partial=partial)
     return argmax_marginals(model.cards, targets, out), out

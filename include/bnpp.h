@@ -842,6 +842,107 @@ int bnpp_plan_marginals_batch(const bnpp_model *m, int n_ev, const int *ev_vars,
                               int n_order, int n_targets, const int *targets, int dtype, int64_t rows_per_launch,
                               double *stats, int n_stats, int64_t *rows, int cap_rows, int *n_rows, int *col_kind);
 
+/* ------------------------------------------------ missing values (batched calls)
+ * The batched calls above take ONE evidence variable set per call and no
+ * "missing" value.  The _mv siblings take one more argument, partial[n_ev] (or
+ * NULL): partial[j] != 0 declares ev_vars[j] PARTIAL -- ev_vals may then hold
+ * BNPP_MISSING (-1) for it in any row.  Row b's result is, by definition, the
+ * single call's for evidence equal to the row's observed entries.
+ *
+ * A partial variable is not conditioned away: it stays a model variable, it is
+ * eliminated (the order is computed from the other, "hard", evidence variables
+ * only, and an explicit order covers it where it covers the non-evidence
+ * variables), and exactly ONE factor that holds it is gathered under a per-row
+ * 0/1 mask (masked gather step, launch-group key 2^24 + 32768, level 0):
+ *   out[rest][b] = in[hard offsets(b) + offset(rest)]  if for every partial p of the scope
+ *                                                      ev[p][b] < 0 or ev[p][b] == digit_p(rest)
+ *                  0                                   otherwise
+ * The factor: 1. one that holds a hard evidence variable (it is gathered
+ * anyway); 2. among those, else among all factors that hold the variable, the
+ * fewest entries after conditioning; 3. the lowest factor index.  A partial
+ * variable in no factor carries no mask.  Everything downstream is the code of
+ * the call without the argument, so row b equals that call on the model whose
+ * mask-carrying factors were multiplied by row b's indicator, with the hard
+ * evidence only.  Width, message sizes and cost are those of a call WITHOUT the
+ * partial variables as evidence; a mask on a factor with no hard evidence makes
+ * its gathered table R times the factor.  The shared scale of a launch applies.
+ * partial == NULL (or all zero) is the call without the argument, bit for bit;
+ * the entries without _mv pass NULL, and -1 stays BNPP_ERR_INVALID there.
+ * -1 in a column that is not partial, any value below -1 and any value >= the
+ * card are BNPP_ERR_INVALID naming the row and the variable.  A posterior
+ * target may not be listed as evidence, partial or not.  bnpp_mpe_batch_mv and
+ * bnpp_sample_batch_mv write the observed entries of partial variables from the
+ * row (impossible rows included).  The job cache key includes the flags.
+ * bnpp_plan_*_mv also return mask_factor[n_ev] (may be NULL): the factor that
+ * carries variable j's mask, -1 for a hard variable or one in no factor.
+ * bnpp_condition_batch_mv runs the (masked) gather on caller-owned device
+ * buffers: a partial variable of the scope stays a dim of `out`; a negative
+ * value of it is "missing", a value >= its card matches nothing (zeros, no
+ * read).  bnpp_evidence_load_batch_mv reads an .evid file whose samples observe
+ * differing variable sets: ev_vars is the union, ascending, ev_vals holds -1
+ * where a sample is silent and partial[j] = 1 for a variable some sample lacks
+ * (capacity protocol of bnpp_evidence_load_batch). */
+#define BNPP_MISSING (-1)
+int bnpp_partition_batch_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                            const int *ev_vals, const unsigned char *partial, int heuristic, const int *order,
+                            int n_order, int dtype, int64_t rows_per_launch, double *log10_z, double *z,
+                            double *uptime_ms);
+
+int bnpp_posterior_batch_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                            const int *ev_vals, const unsigned char *partial, int heuristic, int target, int dtype,
+                            int64_t rows_per_launch, double *out, double *uptime_ms);
+
+int bnpp_mpe_batch_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                      const int *ev_vals, const unsigned char *partial, int heuristic, const int *order, int n_order,
+                      int dtype, int64_t rows_per_launch, double *log10_value, int *assignment, double *uptime_ms);
+
+int bnpp_sample_batch_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                         const int *ev_vals, const unsigned char *partial, int heuristic, const int *order,
+                         int n_order, int dtype, int64_t rows_per_launch, int64_t n_per_row, int64_t first_sample,
+                         int64_t row_stride, uint64_t seed, uint8_t *out, double *log10_z, int64_t *n_degenerate,
+                         double *uptime_ms);
+
+int bnpp_expected_counts_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                            const int *ev_vals, const unsigned char *partial, const double *weights, int heuristic,
+                            const int *order, int n_order, int dtype, int64_t rows_per_launch, double *counts,
+                            double *log10_z, int64_t *n_impossible, double *uptime_ms);
+
+int bnpp_marginals_batch_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                            const int *ev_vals, const unsigned char *partial, int heuristic, const int *order,
+                            int n_order, int n_targets, const int *targets, int dtype, int64_t rows_per_launch,
+                            double *out, double *log10_z, double *uptime_ms);
+
+int bnpp_plan_batch_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial, int heuristic,
+                       const int *order, int n_order, int target, int dtype, int64_t rows_per_launch, double *stats,
+                       int n_stats, int64_t *rows, int cap_rows, int *n_rows, int *result_scope, int *n_result_scope,
+                       int *mask_factor);
+
+int bnpp_plan_mpe_batch_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial,
+                           int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch,
+                           double *stats, int n_stats, int64_t *rows, int cap_rows, int *n_rows, int *mask_factor);
+
+int bnpp_plan_sample_batch_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial,
+                              int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch,
+                              int64_t n_per_row, double *stats, int n_stats, int64_t *rows, int cap_rows, int *n_rows,
+                              int *mask_factor);
+
+int bnpp_plan_counts_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial,
+                        int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch,
+                        double *stats, int n_stats, int64_t *rows, int cap_rows, int *n_rows, int *belief_off,
+                        int *belief_vars, int cap_belief, int *n_belief, int *no_b_elim, int *mask_factor);
+
+int bnpp_plan_marginals_batch_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial,
+                                 int heuristic, const int *order, int n_order, int n_targets, const int *targets,
+                                 int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows,
+                                 int cap_rows, int *n_rows, int *col_kind, int *mask_factor);
+
+int bnpp_condition_batch_mv(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, const void *in,
+                            int ndims, const int *vars, int n_ev, const int *ev_vars,
+                            const unsigned char *partial /* [n_ev] or NULL */, int64_t n_rows,
+                            const int32_t *ev /* device, [n_ev][n_rows] */, void *out);
+int bnpp_evidence_load_batch_mv(const char *path, int cap_vars, int64_t cap_rows, int *n_ev, int *ev_vars,
+                                int64_t *n_rows, int *ev_vals, unsigned char *partial /* [cap_vars] */);
+
 /* Host-only planning of one part of bnpp_marginals_tree_part (all variables
  * as targets): owned[v] = 1 when this part computes v's marginal; stats as
  * bnpp_job_stats for this part's plan (may be NULL).  The memory budget is

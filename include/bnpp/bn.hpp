@@ -204,6 +204,33 @@ public:
                                                      std::unordered_map<std::string, bool> &options,
                                                      std::vector<double> *log10_z = nullptr,
                                                      double *uptime = nullptr) const;
+    // EXTENSION: missing values (the bnpp_*_mv entries).  The overloads below take rows of int, in which
+    // BNPP_MISSING (-1) marks a value a row does not observe, and partial[j] != 0 for every ev_vars[j] that may
+    // be missing in a row (empty: none -- the call above).  A row's result is the call's for evidence equal to
+    // its observed entries; mpe_batch and sample_batch keep the observed entries.
+    std::vector<double> partition_batch(const std::vector<unsigned> &ev_vars,
+        const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial,
+        std::unordered_map<std::string, bool> &options, std::vector<double> *z = nullptr,
+        double *uptime = nullptr) const;
+    std::vector<std::vector<unsigned>> mpe_batch(const std::vector<unsigned> &ev_vars,
+        const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial,
+        std::unordered_map<std::string, bool> &options, std::vector<double> *log10_value = nullptr,
+        double *uptime = nullptr) const;
+    std::vector<std::vector<double>> posterior_batch(const std::vector<unsigned> &ev_vars,
+        const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, unsigned target,
+        std::unordered_map<std::string, bool> &options, double *uptime = nullptr) const;
+    std::vector<std::vector<double>> expected_counts(const std::vector<unsigned> &ev_vars,
+        const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial,
+        const std::vector<double> &weights, std::unordered_map<std::string, bool> &options,
+        std::vector<double> *log10_z = nullptr, long long *n_impossible = nullptr, double *uptime = nullptr) const;
+    std::vector<std::vector<double>> marginals_batch(const std::vector<unsigned> &ev_vars,
+        const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial,
+        const std::vector<unsigned> &targets, std::unordered_map<std::string, bool> &options,
+        std::vector<double> *log10_z = nullptr, double *uptime = nullptr) const;
+    std::vector<std::vector<unsigned char>> sample_batch(const std::vector<unsigned> &ev_vars,
+        const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial,
+        std::unordered_map<std::string, bool> &options, size_t k, unsigned long long seed = 0,
+        std::vector<double> *log10_z = nullptr, double *uptime = nullptr) const;
     virtual void write(std::ostream &) const {}
 
 protected:
