@@ -369,6 +369,31 @@ std::ostream &operator<<(std::ostream &os, const Factor &f) {      // factor.cpp
 }
 
 // ------------------------------------------------------------------ models
+// the overloads without soft evidence
+std::vector<double> Model::partition_batch(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, std::unordered_map<std::string, bool> &options, std::vector<double> *z, double *uptime) const {
+    return partition_batch(ev_vars, rows, partial, SoftEvidence(), options, z, uptime);
+}
+
+std::vector<std::vector<unsigned>> Model::mpe_batch(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, std::unordered_map<std::string, bool> &options, std::vector<double> *log10_value, double *uptime) const {
+    return mpe_batch(ev_vars, rows, partial, SoftEvidence(), options, log10_value, uptime);
+}
+
+std::vector<std::vector<double>> Model::posterior_batch(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, unsigned target, std::unordered_map<std::string, bool> &options, double *uptime) const {
+    return posterior_batch(ev_vars, rows, partial, SoftEvidence(), target, options, uptime);
+}
+
+std::vector<std::vector<double>> Model::expected_counts(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, const std::vector<double> &weights, std::unordered_map<std::string, bool> &options, std::vector<double> *log10_z, long long *n_impossible, double *uptime) const {
+    return expected_counts(ev_vars, rows, partial, SoftEvidence(), weights, options, log10_z, n_impossible, uptime);
+}
+
+std::vector<std::vector<double>> Model::marginals_batch(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, const std::vector<unsigned> &targets, std::unordered_map<std::string, bool> &options, std::vector<double> *log10_z, double *uptime) const {
+    return marginals_batch(ev_vars, rows, partial, SoftEvidence(), targets, options, log10_z, uptime);
+}
+
+std::vector<std::vector<unsigned char>> Model::sample_batch(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, std::unordered_map<std::string, bool> &options, size_t k, unsigned long long seed, std::vector<double> *log10_z, double *uptime) const {
+    return sample_batch(ev_vars, rows, partial, SoftEvidence(), options, k, seed, log10_z, uptime);
+}
+
 namespace {
 
 bnpp_model *to_engine(const std::vector<Variable *> &vars, const std::vector<const Factor *> &factors) {
@@ -484,16 +509,44 @@ const unsigned char *partial_arg(const std::vector<unsigned> &ev_vars, const std
     if (partial.size() != ev_vars.size()) throw std::runtime_error("one partial flag per evidence variable is needed");
     return partial.data();
 }
+// soft evidence as the _sv entries take it: the ids, and the rows' likelihoods flattened row-major
+struct SoftArg {
+    std::vector<int> ids;
+    std::vector<double> flat;
+    int n = 0;
+    const int *vars = nullptr;
+    const double *lik = nullptr;
+    SoftArg(const SoftEvidence &soft, size_t n_rows, const std::vector<Variable *> &variables) {
+        if (soft.vars.empty()) return;                      // none: the call without the argument
+        if (soft.lik.size() != n_rows) throw std::runtime_error("one row of likelihoods per evidence row is needed");
+        size_t ws = 0;                                      // the entries read the sum of the soft cards per row
+        for (unsigned v : soft.vars) {
+            if (v >= variables.size()) throw std::runtime_error("soft variable " + std::to_string(v) + " out of range");
+            ws += variables[v]->size();
+        }
+        ids.assign(soft.vars.begin(), soft.vars.end());
+        for (size_t r = 0; r < soft.lik.size(); ++r) {
+            if (soft.lik[r].size() != ws)
+                throw std::runtime_error("row " + std::to_string(r) + " holds " + std::to_string(soft.lik[r].size()) +
+                                         " likelihoods, the soft variables have " + std::to_string(ws) + " values");
+            flat.insert(flat.end(), soft.lik[r].begin(), soft.lik[r].end());
+        }
+        n = (int)ids.size();
+        vars = ids.data();
+        lik = flat.data();
+    }
+};
 }  // namespace
 
-std::vector<double> Model::partition_batch(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, std::unordered_map<std::string, bool> &options, std::vector<double> *z, double *uptime) const {
+std::vector<double> Model::partition_batch(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, const SoftEvidence &soft, std::unordered_map<std::string, bool> &options, std::vector<double> *z, double *uptime) const {
+    const SoftArg sa(soft, rows.size(), _variables);
     auto t0 = std::chrono::steady_clock::now();
     ModelGuard g{to_engine(_variables, std::vector<const Factor *>(_factors.begin(), _factors.end()))};
     const std::vector<int> vars(ev_vars.begin(), ev_vars.end()), flat = flatten_rows(ev_vars, rows);
     std::vector<double> lz(rows.size() ? rows.size() : 1, 0.0), zz(lz.size(), 0.0);
     double up = 0;
     int dt = options["fp32"] ? BNPP_F32 : BNPP_F64;
-    check(bnpp_partition_batch_mv(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(), partial_arg(ev_vars, partial),
+    check(bnpp_partition_batch_sv(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(), partial_arg(ev_vars, partial), sa.n, sa.vars, sa.lik,
                                heuristic_of(options), nullptr, 0, dt, 0, lz.data(), zz.data(), &up),
           "partition_batch");
     lz.resize(rows.size());
@@ -510,7 +563,8 @@ std::vector<double> Model::partition_batch(const std::vector<unsigned> &ev_vars,
     return partition_batch(ev_vars, int_rows(rows), std::vector<unsigned char>(), options, z, uptime);
 }
 
-std::vector<std::vector<unsigned>> Model::mpe_batch(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, std::unordered_map<std::string, bool> &options, std::vector<double> *log10_value, double *uptime) const {
+std::vector<std::vector<unsigned>> Model::mpe_batch(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, const SoftEvidence &soft, std::unordered_map<std::string, bool> &options, std::vector<double> *log10_value, double *uptime) const {
+    const SoftArg sa(soft, rows.size(), _variables);
     auto t0 = std::chrono::steady_clock::now();
     ModelGuard g{to_engine(_variables, std::vector<const Factor *>(_factors.begin(), _factors.end()))};
     const std::vector<int> vars(ev_vars.begin(), ev_vars.end()), flat = flatten_rows(ev_vars, rows);
@@ -519,7 +573,7 @@ std::vector<std::vector<unsigned>> Model::mpe_batch(const std::vector<unsigned> 
     std::vector<int> x(std::max<size_t>(rows.size() * nv, 1), 0);
     double up = 0;
     int dt = options["fp32"] ? BNPP_F32 : BNPP_F64;
-    check(bnpp_mpe_batch_mv(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(), partial_arg(ev_vars, partial),
+    check(bnpp_mpe_batch_sv(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(), partial_arg(ev_vars, partial), sa.n, sa.vars, sa.lik,
                          heuristic_of(options), nullptr, 0, dt, 0, lv.data(), x.data(), &up),
           "mpe_batch");
     lv.resize(rows.size());
@@ -537,7 +591,8 @@ std::vector<std::vector<unsigned>> Model::mpe_batch(const std::vector<unsigned> 
     return mpe_batch(ev_vars, int_rows(rows), std::vector<unsigned char>(), options, log10_value, uptime);
 }
 
-std::vector<std::vector<double>> Model::posterior_batch(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, unsigned target, std::unordered_map<std::string, bool> &options, double *uptime) const {
+std::vector<std::vector<double>> Model::posterior_batch(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, const SoftEvidence &soft, unsigned target, std::unordered_map<std::string, bool> &options, double *uptime) const {
+    const SoftArg sa(soft, rows.size(), _variables);
     auto t0 = std::chrono::steady_clock::now();
     ModelGuard g{to_engine(_variables, std::vector<const Factor *>(_factors.begin(), _factors.end()))};
     const std::vector<int> vars(ev_vars.begin(), ev_vars.end()), flat = flatten_rows(ev_vars, rows);
@@ -546,7 +601,7 @@ std::vector<std::vector<double>> Model::posterior_batch(const std::vector<unsign
     std::vector<double> flat_out(std::max<size_t>(rows.size() * k, 1), 0.0);
     double up = 0;
     int dt = options["fp32"] ? BNPP_F32 : BNPP_F64;
-    check(bnpp_posterior_batch_mv(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(), partial_arg(ev_vars, partial),
+    check(bnpp_posterior_batch_sv(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(), partial_arg(ev_vars, partial), sa.n, sa.vars, sa.lik,
                                heuristic_of(options), (int)target, dt, 0, flat_out.data(), &up),
           "posterior_batch");
     std::vector<std::vector<double>> out(rows.size());
@@ -562,7 +617,8 @@ std::vector<std::vector<double>> Model::posterior_batch(const std::vector<unsign
     return posterior_batch(ev_vars, int_rows(rows), std::vector<unsigned char>(), target, options, uptime);
 }
 
-std::vector<std::vector<double>> Model::expected_counts(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, const std::vector<double> &weights, std::unordered_map<std::string, bool> &options, std::vector<double> *log10_z, long long *n_impossible, double *uptime) const {
+std::vector<std::vector<double>> Model::expected_counts(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, const SoftEvidence &soft, const std::vector<double> &weights, std::unordered_map<std::string, bool> &options, std::vector<double> *log10_z, long long *n_impossible, double *uptime) const {
+    const SoftArg sa(soft, rows.size(), _variables);
     auto t0 = std::chrono::steady_clock::now();
     ModelGuard g{to_engine(_variables, std::vector<const Factor *>(_factors.begin(), _factors.end()))};
     const std::vector<int> vars(ev_vars.begin(), ev_vars.end()), flat = flatten_rows(ev_vars, rows);
@@ -572,7 +628,7 @@ std::vector<std::vector<double>> Model::expected_counts(const std::vector<unsign
     std::vector<double> flat_out((size_t)std::max<int64_t>(total, 1), 0.0), lz(rows.size() ? rows.size() : 1, 0.0);
     double up = 0;
     int dt = options["fp32"] ? BNPP_F32 : BNPP_F64;
-    check(bnpp_expected_counts_mv(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(), partial_arg(ev_vars, partial),
+    check(bnpp_expected_counts_sv(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(), partial_arg(ev_vars, partial), sa.n, sa.vars, sa.lik,
                                weights.empty() ? nullptr : weights.data(), heuristic_of(options), nullptr, 0, dt, 0,
                                flat_out.data(), lz.data(), &n_imp, &up),
           "expected_counts");
@@ -598,7 +654,8 @@ std::vector<std::vector<double>> Model::expected_counts(const std::vector<unsign
     return expected_counts(ev_vars, int_rows(rows), std::vector<unsigned char>(), weights, options, log10_z, n_impossible, uptime);
 }
 
-std::vector<std::vector<double>> Model::marginals_batch(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, const std::vector<unsigned> &targets, std::unordered_map<std::string, bool> &options, std::vector<double> *log10_z, double *uptime) const {
+std::vector<std::vector<double>> Model::marginals_batch(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, const SoftEvidence &soft, const std::vector<unsigned> &targets, std::unordered_map<std::string, bool> &options, std::vector<double> *log10_z, double *uptime) const {
+    const SoftArg sa(soft, rows.size(), _variables);
     auto t0 = std::chrono::steady_clock::now();
     ModelGuard g{to_engine(_variables, std::vector<const Factor *>(_factors.begin(), _factors.end()))};
     const std::vector<int> vars(ev_vars.begin(), ev_vars.end()), flat = flatten_rows(ev_vars, rows);
@@ -613,7 +670,7 @@ std::vector<std::vector<double>> Model::marginals_batch(const std::vector<unsign
     std::vector<double> flat_out(std::max<size_t>(rows.size() * w, 1), 0.0), lz(rows.size() ? rows.size() : 1, 0.0);
     double up = 0;
     int dt = options["fp32"] ? BNPP_F32 : BNPP_F64;
-    check(bnpp_marginals_batch_mv(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(), partial_arg(ev_vars, partial),
+    check(bnpp_marginals_batch_sv(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(), partial_arg(ev_vars, partial), sa.n, sa.vars, sa.lik,
                                heuristic_of(options), nullptr, 0, (int)ts.size(), ts.empty() ? nullptr : ts.data(), dt, 0,
                                flat_out.data(), lz.data(), &up),
           "marginals_batch");
@@ -655,7 +712,8 @@ std::vector<std::vector<unsigned char>> Model::sample(const std::unordered_map<u
     return out;
 }
 
-std::vector<std::vector<unsigned char>> Model::sample_batch(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, std::unordered_map<std::string, bool> &options, size_t k, unsigned long long seed, std::vector<double> *log10_z, double *uptime) const {
+std::vector<std::vector<unsigned char>> Model::sample_batch(const std::vector<unsigned> &ev_vars, const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, const SoftEvidence &soft, std::unordered_map<std::string, bool> &options, size_t k, unsigned long long seed, std::vector<double> *log10_z, double *uptime) const {
+    const SoftArg sa(soft, rows.size(), _variables);
     auto t0 = std::chrono::steady_clock::now();
     ModelGuard g{to_engine(_variables, std::vector<const Factor *>(_factors.begin(), _factors.end()))};
     const std::vector<int> vars(ev_vars.begin(), ev_vars.end()), flat = flatten_rows(ev_vars, rows);
@@ -664,7 +722,7 @@ std::vector<std::vector<unsigned char>> Model::sample_batch(const std::vector<un
     std::vector<unsigned char> x(std::max<size_t>(n * nv, 1), 0);
     double up = 0;
     int dt = options["fp32"] ? BNPP_F32 : BNPP_F64;
-    check(bnpp_sample_batch_mv(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(), partial_arg(ev_vars, partial),
+    check(bnpp_sample_batch_sv(ctx(), g.m, (int)vars.size(), vars.data(), (int64_t)rows.size(), flat.data(), partial_arg(ev_vars, partial), sa.n, sa.vars, sa.lik,
                             heuristic_of(options), nullptr, 0, dt, 0, (int64_t)k, 0, (int64_t)k, seed, x.data(), lz.data(),
                             nullptr, &up),
           "sample_batch");

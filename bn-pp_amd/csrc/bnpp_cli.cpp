@@ -28,6 +28,9 @@
 // -missing beside a batch mode: the samples of the evidence file may observe
 // differing variable sets (bnpp_evidence_load_batch_mv); every variable some
 // sample lacks is declared partial and the _mv entries run.  Outputs as without it.
+// -soft rows.lik beside a batch mode: soft evidence (bnpp_likelihood_load, the
+// _sv entries) -- the file names the soft variables and gives every sample of
+// the evidence file one row of likelihoods.  It combines with -missing.
 // -mar-batch (no reference counterpart): every posterior marginal of every
 // sample of the evidence file (bnpp_marginals_batch), one line per sample; with
 // -uai, <base>.MAR ("MAR", the sample count, then per sample the UAI MAR line
@@ -51,7 +54,7 @@
 int main(int argc, char **argv) {
     std::unordered_map<std::string, bool> options;
     std::vector<std::string> positional;
-    std::string uai_out;
+    std::string uai_out, soft_path;
     unsigned long long n_samples = 0, n_per_row = 0, seed = 0;
     unsigned post_target = 0;
     for (int i = 1; i < argc; ++i) {
@@ -65,6 +68,7 @@ int main(int argc, char **argv) {
         else if (p == "-counts") options["counts"] = true;
         else if (p == "-mar-batch") options["marginals-batch"] = true;
         else if (p == "-missing") options["missing"] = true;
+        else if (p == "-soft" && i + 1 < argc) soft_path = argv[++i];
         else if (p == "-post-batch" && i + 1 < argc) { options["posterior-batch"] = true; post_target = (unsigned)std::strtoul(argv[++i], nullptr, 10); }
         else if (p == "-sample" && i + 1 < argc) { options["sample"] = true; n_samples = std::strtoull(argv[++i], nullptr, 10); }
         else if (p == "-sample-batch" && i + 1 < argc) { options["sample-batch"] = true; n_per_row = std::strtoull(argv[++i], nullptr, 10); }
@@ -81,8 +85,13 @@ int main(int argc, char **argv) {
         else if (p[0] == '-') { std::cerr << "Error: invalid option `" << p << "'." << std::endl; return -1; }
         else positional.push_back(p);
     }
+    if (!soft_path.empty() && !(options["partition-batch"] || options["posterior-batch"] || options["counts"] ||
+                                options["mpe-batch"] || options["sample-batch"] || options["marginals-batch"])) {
+        std::cerr << "Error: -soft needs a batch mode (-pr-batch, -post-batch, -mpe-batch, -sample-batch, -counts, -mar-batch)." << std::endl;
+        return -1;
+    }
     if (positional.empty() || options["help"]) {
-        std::cout << "usage: " << argv[0] << " /path/to/model.uai [/path/to/evidence.uai.evid] -pr|-mar|-mar-tree|-mpe|-sample N [-seed S]|-pr-batch|-post-batch T|-mpe-batch|-sample-batch K [-seed S]|-counts|-mar-batch [-missing] [-sp] [-mf|-wmf|-md] [-f32] [-uai base]" << std::endl;
+        std::cout << "usage: " << argv[0] << " /path/to/model.uai [/path/to/evidence.uai.evid] -pr|-mar|-mar-tree|-mpe|-sample N [-seed S]|-pr-batch|-post-batch T|-mpe-batch|-sample-batch K [-seed S]|-counts|-mar-batch [-missing] [-soft rows.lik] [-sp] [-mf|-wmf|-md] [-f32] [-uai base]" << std::endl;
         return positional.empty() ? 1 : 0;
     }
     bnpp_model *probe = nullptr;
@@ -206,8 +215,36 @@ int main(int argc, char **argv) {
             const std::vector<unsigned> vars(ev_vars.begin(), ev_vars.begin() + n_ev);
             std::vector<std::vector<int>> rows((size_t)n_rows);
             for (int64_t r = 0; r < n_rows; ++r) rows[r].assign(flat.begin() + r * n_ev, flat.begin() + (r + 1) * n_ev);
+            // -soft: the soft variables and one row of likelihoods per sample
+            bn::SoftEvidence soft;
+            if (!soft_path.empty()) {
+                bnpp_model *h = nullptr;
+                if (bnpp_model_load_uai(positional[0].c_str(), &h) != BNPP_OK) throw std::runtime_error(bnpp_last_error());
+                int n_soft = 0, nv = 0;
+                int64_t n_lik = 0;
+                bnpp_model_info(h, nullptr, &nv, nullptr);
+                std::vector<int> cards((size_t)(nv > 0 ? nv : 1)), ids((size_t)(nv > 0 ? nv : 1));
+                bnpp_model_cards(h, cards.data());
+                // the sizes and ids: BNPP_ERR_INVALID ("larger than cap") is the answer expected here
+                if (bnpp_likelihood_load(h, soft_path.c_str(), nv, 0, &n_soft, ids.data(), &n_lik, nullptr) == BNPP_ERR_IO) {
+                    bnpp_model_free(h);
+                    throw std::runtime_error(bnpp_last_error());
+                }
+                int64_t ws = 0;
+                for (int i = 0; i < n_soft && i < nv; ++i) ws += cards[ids[i]];
+                std::vector<double> lik((size_t)(n_lik * ws > 0 ? n_lik * ws : 1));
+                const int rc = bnpp_likelihood_load(h, soft_path.c_str(), nv, n_lik * ws, &n_soft, ids.data(), &n_lik, lik.data());
+                bnpp_model_free(h);
+                if (rc != BNPP_OK) throw std::runtime_error(bnpp_last_error());
+                if (n_lik != n_rows)
+                    throw std::runtime_error("-soft: " + std::to_string(n_lik) + " rows of likelihoods for " +
+                                             std::to_string(n_rows) + " evidence rows");
+                soft.vars.assign(ids.begin(), ids.begin() + n_soft);
+                soft.lik.resize((size_t)n_rows);
+                for (int64_t r = 0; r < n_rows; ++r) soft.lik[r].assign(lik.begin() + r * ws, lik.begin() + (r + 1) * ws);
+            }
             if (options["partition-batch"]) {
-                const std::vector<double> lz = model->partition_batch(vars, rows, partial, options, nullptr, &uptime);
+                const std::vector<double> lz = model->partition_batch(vars, rows, partial, soft, options, nullptr, &uptime);
                 std::cout << ">> log10 Z of " << lz.size() << " evidence rows:";
                 for (size_t r = 0; r < lz.size() && r < 8; ++r) std::cout << " " << lz[r];
                 std::cout << (lz.size() > 8 ? " ..." : "") << std::endl << ">> Executed in " << uptime << "ms." << std::endl << std::endl;
@@ -221,7 +258,7 @@ int main(int argc, char **argv) {
             }
             if (options["mpe-batch"]) {
                 std::vector<double> lv;
-                const std::vector<std::vector<unsigned>> xs = model->mpe_batch(vars, rows, partial, options, &lv, &uptime);
+                const std::vector<std::vector<unsigned>> xs = model->mpe_batch(vars, rows, partial, soft, options, &lv, &uptime);
                 for (size_t r = 0; r < xs.size(); ++r) {
                     std::cout << ">> MPE row " << r << " log10 value = " << lv[r] << " assignment:";
                     for (unsigned v : xs[r]) std::cout << " " << v;
@@ -243,7 +280,7 @@ int main(int argc, char **argv) {
             if (options["sample-batch"]) {
                 std::vector<double> lz;
                 const std::vector<std::vector<unsigned char>> xs =
-                    model->sample_batch(vars, rows, partial, options, n_per_row, seed, &lz, &uptime);
+                    model->sample_batch(vars, rows, partial, soft, options, n_per_row, seed, &lz, &uptime);
                 std::cout << ">> " << n_per_row << " samples for each of " << rows.size() << " evidence rows; log10 Z:";
                 for (size_t r = 0; r < lz.size() && r < 8; ++r) std::cout << " " << lz[r];
                 std::cout << (lz.size() > 8 ? " ..." : "") << std::endl << ">> First sample:";
@@ -265,7 +302,7 @@ int main(int argc, char **argv) {
                 std::vector<double> lz;
                 long long n_impossible = 0;
                 const std::vector<std::vector<double>> counts =
-                    model->expected_counts(vars, rows, partial, {}, options, &lz, &n_impossible, &uptime);
+                    model->expected_counts(vars, rows, partial, soft, {}, options, &lz, &n_impossible, &uptime);
                 double ll = 0;
                 for (double v : lz)
                     if (std::isfinite(v)) ll += v;
@@ -285,7 +322,7 @@ int main(int argc, char **argv) {
             }
             if (options["marginals-batch"]) {
                 std::vector<double> lz;
-                const std::vector<std::vector<double>> marg = model->marginals_batch(vars, rows, partial, {}, options, &lz, &uptime);
+                const std::vector<std::vector<double>> marg = model->marginals_batch(vars, rows, partial, soft, {}, options, &lz, &uptime);
                 const std::vector<bn::Variable *> &mv = model->variables();
                 for (size_t r = 0; r < marg.size(); ++r) {
                     std::cout << ">> MAR row " << r << " log10 Z = " << lz[r] << " marginals:";
@@ -310,7 +347,7 @@ int main(int argc, char **argv) {
                 }
             }
             if (options["posterior-batch"]) {
-                const std::vector<std::vector<double>> post = model->posterior_batch(vars, rows, partial, post_target, options, &uptime);
+                const std::vector<std::vector<double>> post = model->posterior_batch(vars, rows, partial, soft, post_target, options, &uptime);
                 std::cout << ">> P(" << post_target << " | row) of " << post.size() << " evidence rows; row 0:";
                 if (!post.empty())
                     for (double v : post[0]) std::cout << " " << v;

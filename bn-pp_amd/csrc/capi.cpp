@@ -15,6 +15,7 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <fstream>
 #include <string>
 #include <utility>
 #include <thread>
@@ -1156,7 +1157,61 @@ struct BatchCall {
             if (partial[j]) return true;
         return false;
     }
+    // soft evidence: the soft variables, and lik = double[n_rows][Ws], the variables' blocks in the listed order
+    int n_soft = 0;
+    const int *soft_vars = nullptr;
+    const double *lik = nullptr;
 };
+
+// the soft variable set (no values): ids in range, no duplicates, none an evidence variable or the target, each in
+// a factor (its likelihoods need a table to carry them)
+int batch_check_soft_vars(const BatchCall &c, bool posterior) {
+    const ModelData &d = c.m->d;
+    const int nv = (int)d.cards.size();
+    if (c.n_soft < 0 || (c.n_soft > 0 && !c.soft_vars)) return set_err(BNPP_ERR_INVALID, "bad soft evidence arrays");
+    std::vector<char> seen(nv, 0), is_ev(nv, 0);
+    for (int j = 0; j < c.n_ev; ++j) is_ev[c.ev_vars[j]] = 1;
+    for (int i = 0; i < c.n_soft; ++i) {
+        const int v = c.soft_vars[i];
+        if (v < 0 || v >= nv) return set_err(BNPP_ERR_INVALID, "soft variable " + std::to_string(v) + " out of range");
+        if (seen[v]) return set_err(BNPP_ERR_INVALID, "soft variable " + std::to_string(v) + " is listed twice");
+        if (is_ev[v])
+            return set_err(BNPP_ERR_INVALID, "variable " + std::to_string(v) + " is both an evidence and a soft variable");
+        if (posterior && v == c.target)
+            return set_err(BNPP_ERR_INVALID, "the target " + std::to_string(v) + " is a soft variable");
+        seen[v] = 1;
+    }
+    for (int i = 0; i < c.n_soft; ++i) {
+        bool in_factor = false;
+        for (const auto &sc : d.scopes) in_factor = in_factor || std::find(sc.begin(), sc.end(), c.soft_vars[i]) != sc.end();
+        if (!in_factor)
+            return set_err(BNPP_ERR_UNSUPPORTED, "soft variable " + std::to_string(c.soft_vars[i]) +
+                                                     " is in no factor: no table can carry its likelihoods");
+    }
+    return BNPP_OK;
+}
+
+// the likelihoods of a batched call: finite and not negative
+int batch_check_lik(const BatchCall &c) {
+    if (c.n_soft <= 0) return BNPP_OK;
+    if (!c.lik) return set_err(BNPP_ERR_INVALID, "bad soft evidence arrays");
+    const ModelData &d = c.m->d;
+    int64_t ws = 0;
+    for (int i = 0; i < c.n_soft; ++i) ws += d.cards[c.soft_vars[i]];
+    for (int64_t r = 0; r < c.n_rows; ++r) {
+        const double *row = c.lik + r * ws;
+        for (int i = 0; i < c.n_soft; ++i) {
+            const int k = d.cards[c.soft_vars[i]];
+            for (int x = 0; x < k; ++x)
+                if (!(row[x] >= 0) || !std::isfinite(row[x]))
+                    return set_err(BNPP_ERR_INVALID, "evidence row " + std::to_string(r) + ": the likelihood of value " +
+                                                         std::to_string(x) + " of soft variable " +
+                                                         std::to_string(c.soft_vars[i]) + " must be finite and not negative");
+            row += k;
+        }
+    }
+    return BNPP_OK;
+}
 
 // the evidence variable set (no values) and the target: ids in range, no duplicates
 int batch_check_vars(const ModelData &d, int n_ev, const int *ev_vars, int target, bool posterior) {
@@ -1181,6 +1236,8 @@ int batch_check_rows(const BatchCall &c, bool posterior = false) {
     const ModelData &d = c.m->d;
     if (c.n_rows < 1) return set_err(BNPP_ERR_INVALID, "n_rows must be at least 1");
     if (int rc = batch_check_vars(d, c.n_ev, c.ev_vars, c.target, posterior)) return rc;
+    if (c.n_soft != 0)
+        if (int rc = batch_check_soft_vars(c, posterior)) return rc;
     if (c.n_ev > 0 && !c.ev_vals) return set_err(BNPP_ERR_INVALID, "bad evidence arrays");
     for (int64_t r = 0; r < c.n_rows; ++r)
         for (int j = 0; j < c.n_ev; ++j) {
@@ -1191,7 +1248,7 @@ int batch_check_rows(const BatchCall &c, bool posterior = false) {
                                                      " of variable " + std::to_string(c.ev_vars[j]) + " is outside [0, " +
                                                      std::to_string(d.cards[c.ev_vars[j]]) + ")");
         }
-    return BNPP_OK;
+    return batch_check_lik(c);
 }
 
 // a null context.  say_no_device (batched MPE and sampling): no context can exist without a device, so say which it is
@@ -1222,6 +1279,7 @@ int plan_batch_schedule(const BatchCall &c, int64_t budget, int64_t auto_cap, Sc
     std::vector<int> ev(nv, -1), evv(c.ev_vars, c.ev_vars + c.n_ev);
     std::vector<char> part;                                 // empty: no partial variable, the planners' own default
     if (c.any_partial()) part.assign(c.partial, c.partial + c.n_ev);
+    const std::vector<int> soft(c.soft_vars, c.soft_vars + (c.soft_vars ? c.n_soft : 0));   // not evidence: eliminated
     // the order depends on which variables are observed in every row only: a partial variable is eliminated
     for (int j = 0; j < c.n_ev; ++j)
         if (!c.is_partial(j)) ev[evv[j]] = 0;
@@ -1260,11 +1318,11 @@ int plan_batch_schedule(const BatchCall &c, int64_t budget, int64_t auto_cap, Sc
     int64_t need = 0;
     // counts: the batched bucket tree (plan_counts), every forward message resident through the backward pass
     auto make = [&](int64_t rows) {
-        return counts ? plan_counts(d.cards, views, ord, evv, rows, eb, plan, &msg, part)
-               : mpe  ? plan_mpe_batch(d.cards, views, ord, evv, rows, eb, plan, &msg, part)
-               : smp  ? plan_sample_batch(d.cards, views, ord, evv, rows, c.K, eb, plan, &msg, part)
-               : mar  ? plan_marginals_batch(d.cards, views, ord, evv, rows, c.targets, eb, plan, &msg, part)
-                      : plan_batch(d.cards, views, ord, evv, rows, target, eb, plan, &msg, part);
+        return counts ? plan_counts(d.cards, views, ord, evv, rows, eb, plan, &msg, part, soft)
+               : mpe  ? plan_mpe_batch(d.cards, views, ord, evv, rows, eb, plan, &msg, part, soft)
+               : smp  ? plan_sample_batch(d.cards, views, ord, evv, rows, c.K, eb, plan, &msg, part, soft)
+               : mar  ? plan_marginals_batch(d.cards, views, ord, evv, rows, c.targets, eb, plan, &msg, part, soft)
+                      : plan_batch(d.cards, views, ord, evv, rows, target, eb, plan, &msg, part, soft);
     };
     if (c.rows_per_launch > 0) {
         R = c.rows_per_launch;
@@ -1316,7 +1374,7 @@ int plan_batch_schedule(const BatchCall &c, int64_t budget, int64_t auto_cap, Sc
     if (!build_schedule({&plan}, d.cards, src_sizes, eb, max_vec_for(dtype), out, &msg, budget))
         return set_err(out.arena_bytes >= kSatMax ? BNPP_ERR_OOM : BNPP_ERR_INVALID, msg);
     int64_t n_gather = 0;
-    for (const Schedule::Group &g : out.groups) n_gather += g.variant == kCondBatchKey || g.variant == kCondBatchMaskKey;
+    for (const Schedule::Group &g : out.groups) n_gather += g.variant == kCondBatchKey || g.variant == kCondBatchMaskKey || g.variant == kCondBatchSoftKey;
     stats[0] = out.entries;
     stats[1] = (double)out.arena_bytes;
     stats[2] = out.n_levels;
@@ -1361,6 +1419,10 @@ uint64_t batch_call_key(const BatchCall &c, int64_t auto_cap) {
     for (int t : c.targets) mix((uint32_t)t);
     if (c.any_partial())                                    // none: the key of the call without the argument
         for (int i = 0; i < c.n_ev; ++i) mix(0x9e3779b9ull + (c.partial[i] ? 1 : 0));
+    if (c.n_soft > 0) {                                     // the variables, never the values; none: nothing
+        mix(0x51f7ull + (uint64_t)c.n_soft);
+        for (int i = 0; i < c.n_soft; ++i) mix((uint32_t)c.soft_vars[i]);
+    }
     mix_plan_knobs(mix);
     return h ? h : 1;
 }
@@ -1379,6 +1441,14 @@ struct BatchRun {
     int64_t R = 0, n_launch = 0;
     int32_t *d_ev = nullptr;                            // the evidence table of the gather steps
     std::vector<int32_t> hev;
+    // soft evidence: the likelihood table of the weighted gather steps, every launch's block T[Ws][R] (scaled, in the
+    // call's dtype), per row the sum of its blocks' exponents (empty: no soft variable), the time the staging took
+    void *d_lam = nullptr;
+    std::vector<unsigned char> hlam;
+    std::vector<int64_t> e_row;
+    int64_t lam_bytes = 0;
+    double lam_ms = 0;
+    int64_t e_of(int64_t row) const { return e_row.empty() ? 0 : e_row[(size_t)row]; }
     bool has_b = false;                                 // the result table is over B (else: one value for every row)
     BatchRun(bnpp_ctx *x, const BatchCall &call, double start) : ctx(x), c(call), t0(start) {}
 };
@@ -1428,7 +1498,8 @@ void batch_stage(BatchRun &run) {
     const Schedule &sc = ex.sched;
     const int64_t R = run.R = run.job->batch_rows, n_launch = run.n_launch = (c.n_rows + R - 1) / R;
     for (const Schedule::Group &g : sc.groups)
-        if ((g.variant == kCondBatchKey || g.variant == kCondBatchMaskKey) && sc.descs[g.begin].in_table[1] >= 0)
+        if ((g.variant == kCondBatchKey || g.variant == kCondBatchMaskKey || g.variant == kCondBatchSoftKey) &&
+            sc.descs[g.begin].in_table[1] >= 0)
             run.d_ev = static_cast<int32_t *>(ex.h_meta[sc.descs[g.begin].in_table[1]].ptr);
         else if (g.variant == kMargRowsKey && sc.pool[sc.descs[g.begin].dim_off + 3] >= 0)   // an evidence block's, gather step or not
             run.d_ev = static_cast<int32_t *>(ex.h_meta[sc.pool[sc.descs[g.begin].dim_off + 3]].ptr);
@@ -1442,6 +1513,52 @@ void batch_stage(BatchRun &run) {
             for (int j = 0; j < n_ev; ++j)
                 for (int64_t b = 0; b < R; ++b)
                     hev[(size_t)((L * n_ev + j) * R + b)] = ev_vals[std::min(L * R + b, n_rows - 1) * n_ev + j];
+    }
+    for (const Schedule::Group &g : sc.groups)
+        if (g.variant == kCondBatchSoftKey && sc.descs[g.begin].in_table[2] >= 0)
+            run.d_lam = ex.h_meta[sc.descs[g.begin].in_table[2]].ptr;
+    if (run.d_lam && c.n_soft > 0) {
+        // per (row, variable) block an exact power of two brings the largest entry into [0.5, 1): every weight is at
+        // most 1 (a gathered table keeps its source's bound), and rows of any magnitude share a launch's scale.  The
+        // exponents go back to the row's log10 Z and Z.  Then T[Ws][R], padding rows copying the last row
+        const double ts = now_ms();
+        const int n_soft = c.n_soft;
+        const int64_t n_rows = c.n_rows;
+        const double *lik = c.lik;
+        const bool f32 = c.dtype == BNPP_F32;
+        std::vector<int> k(n_soft);
+        int64_t ws = 0;
+        for (int i = 0; i < n_soft; ++i) ws += (k[i] = c.m->d.cards[c.soft_vars[i]]);
+        run.lam_bytes = ws * R * (f32 ? 4 : 8);
+        run.hlam.resize((size_t)(n_launch * run.lam_bytes));
+        run.e_row.assign((size_t)n_rows, 0);
+        float *lf = reinterpret_cast<float *>(run.hlam.data());
+        double *ld = reinterpret_cast<double *>(run.hlam.data());
+        for (int64_t L = 0; L < n_launch; ++L)
+            for (int64_t b = 0; b < R; ++b) {
+                const int64_t row = std::min(L * R + b, n_rows - 1);
+                const double *src = lik + row * ws;
+                int64_t w = 0, e_sum = 0;
+                for (int i = 0; i < n_soft; ++i) {
+                    double top = 0;
+                    for (int x = 0; x < k[i]; ++x) top = std::max(top, src[w + x]);
+                    int e = 0;
+                    if (top > 0) (void)std::frexp(top, &e);
+                    e_sum += e;
+                    for (int x = 0; x < k[i]; ++x) {
+                        const double v = std::ldexp(src[w + x], -e);
+                        const size_t at = (size_t)((L * ws + w + x) * R + b);
+                        if (f32) lf[at] = (float)v;
+                        else ld[at] = v;
+                    }
+                    w += k[i];
+                }
+                if (L * R + b < n_rows) run.e_row[(size_t)row] = e_sum;
+            }
+        run.lam_ms = now_ms() - ts;
+        if (std::getenv("BNPP_TIMING"))
+            std::fprintf(stderr, "[bnpp] soft evidence: staging %.3f ms for %lld rows x %lld likelihoods\n", run.lam_ms,
+                         (long long)n_rows, (long long)ws);
     }
     const std::vector<int> &rv = sc.plan_result_vars[0];
     run.has_b = std::find(rv.begin(), rv.end(), (int)c.m->d.cards.size()) != rv.end();
@@ -1461,7 +1578,12 @@ int batch_launches(BatchRun &run, Before &&before, After &&after) {
     for (int64_t L = 0; L < run.n_launch; ++L) {
         const double ta = now_ms();
         const int64_t rows = std::min(R, run.c.n_rows - L * R);
-        if (run.d_ev) {
+        if (run.d_lam && run.lam_bytes > 0) {
+            e = hipMemcpyAsync(run.d_lam, run.hlam.data() + (size_t)(L * run.lam_bytes), (size_t)run.lam_bytes,
+                               hipMemcpyHostToDevice, ctx->c.stream);
+            if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("hipMemcpyAsync(likelihoods): ") + hipGetErrorString(e));
+        }
+        if (run.d_ev && per > 0) {
             e = hipMemcpyAsync(run.d_ev, run.hev.data() + (size_t)(L * per), (size_t)per * sizeof(int32_t),
                                hipMemcpyHostToDevice, ctx->c.stream);
             if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("hipMemcpyAsync(evidence): ") + hipGetErrorString(e));
@@ -1583,8 +1705,8 @@ int run_batch(bnpp_ctx *ctx, BatchCall &c, bool posterior, double *log10_z, doub
                 if (!posterior) {                           // job_results, kind 0
                     double p = 0;
                     p += r[cb];
-                    log10_z[row] = log10_scaled(p, exp2);
-                    if (z) z[row] = std::ldexp(p, (int)std::max<int64_t>(std::min<int64_t>(exp2, 1 << 20), -(1 << 20)));
+                    log10_z[row] = log10_scaled(p, exp2 + run.e_of(row));
+                    if (z) z[row] = std::ldexp(p, (int)std::max<int64_t>(std::min<int64_t>(exp2 + run.e_of(row), 1 << 20), -(1 << 20)));
                 } else if (has_t && k > 0) {                // Factor::normalize (factor.cpp:244-255), as job_results
                     double part = 0;
                     for (int s = 0; s < k; ++s) part += r[s * nb + cb];
@@ -1654,7 +1776,7 @@ int run_mpe_batch(bnpp_ctx *ctx, const BatchCall &c, double *log10_value, int *a
             const uint8_t *x = raw.data() + pg.res_off[0][1];
             for (int64_t b = 0; b < rows; ++b) {
                 const int64_t row = L * R + b;
-                if (log10_value) log10_value[row] = log10_scaled(raw_elem(vals, has_b ? b : 0, eb), tm.exp2);
+                if (log10_value) log10_value[row] = log10_scaled(raw_elem(vals, has_b ? b : 0, eb), tm.exp2 + run.e_of(row));
                 if (assignment)
                     for (int64_t v = 0; v < nv; ++v)
                         assignment[row * nv + v] = ev_col[(size_t)v] >= 0 && ev_vals[row * n_ev + ev_col[(size_t)v]] >= 0
@@ -1735,7 +1857,7 @@ int run_sample_batch(bnpp_ctx *ctx, const BatchCall &c, int64_t first_sample, in
             for (int64_t b = 0; b < rows; ++b) {
                 const int64_t row = L * R + b;
                 const double p = raw_elem(vals, has_b ? b : 0, eb);
-                if (log10_z) log10_z[row] = log10_scaled(p, tm.exp2);
+                if (log10_z) log10_z[row] = log10_scaled(p, tm.exp2 + run.e_of(row));
                 // an impossible row, as the single call: every draw degenerate, every sampled value 0
                 impossible[(size_t)b] = !(p > 0);
                 if (n_degenerate) {
@@ -1846,7 +1968,7 @@ int run_counts(bnpp_ctx *ctx, const BatchCall &c, const double *weights, double 
             for (int64_t b = 0; b < rows; ++b) {
                 double p = 0;
                 p += r[run.has_b ? b : 0];
-                if (log10_z) log10_z[L * R + b] = log10_scaled(p, exp2);
+                if (log10_z) log10_z[L * R + b] = log10_scaled(p, exp2 + run.e_of(L * R + b));
                 if (n_impossible && !(p > 0)) ++*n_impossible;
             }
             return (int)BNPP_OK;
@@ -1955,7 +2077,7 @@ int run_marginals_batch(bnpp_ctx *ctx, const BatchCall &c, double *out, double *
             for (int64_t b = 0; log10_z && b < rows; ++b) {
                 double p = 0;                                   // as run_batch
                 p += raw_elem(rt >= 0 ? zr.data() : nullptr, has_b ? b : 0, eb);
-                log10_z[L * R + b] = log10_scaled(p, tm.exp2);
+                log10_z[L * R + b] = log10_scaled(p, tm.exp2 + run.e_of(L * R + b));
             }
             copy_ms += now_ms() - tw;
             return (int)BNPP_OK;
@@ -1987,6 +2109,8 @@ int plan_batch_entry(const BatchCall &c, bool posterior, double *stats, int n_st
                      int *n_rows, Schedule &s, VEPlan &plan, double *st) {
     if (!c.m || !n_rows || (cap_rows > 0 && !rows) || (n_stats > 0 && !stats)) return set_err(BNPP_ERR_INVALID, "null argument");
     if (int rc = batch_check_vars(c.m->d, c.n_ev, c.ev_vars, c.target, posterior)) return rc;
+    if (c.n_soft != 0)
+        if (int rc = batch_check_soft_vars(c, posterior)) return rc;
     if (c.K < 1) return set_err(BNPP_ERR_INVALID, "n_per_row must be at least 1");
     int64_t R = 0;
     if (int rc = plan_batch_schedule(c, memory_budget(nullptr), kBatchAutoRows, s, st, R, &plan)) return rc;
@@ -2005,17 +2129,28 @@ int bnpp_counts_size(const bnpp_model *m, int64_t *n) {
     return BNPP_OK;
 }
 
-int bnpp_expected_counts_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
-                            const int *ev_vals, const unsigned char *partial, const double *weights, int heuristic,
+int bnpp_expected_counts_sv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                            const int *ev_vals, const unsigned char *partial, int n_soft, const int *soft_vars,
+        const double *lik, const double *weights, int heuristic,
                             const int *order, int n_order, int dtype, int64_t rows_per_launch, double *counts,
                             double *log10_z, int64_t *n_impossible, double *uptime_ms) {
     BNPP_GUARD_BEGIN
     BatchCall c = batch_call(m, kKindCounts, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
     c.partial = partial;
+    c.n_soft = n_soft;
+    c.soft_vars = soft_vars;
+    c.lik = lik;
     c.n_rows = n_rows;
     c.ev_vals = ev_vals;
     return run_counts(ctx, c, weights, counts, log10_z, n_impossible, uptime_ms);
     BNPP_GUARD_END
+}
+
+int bnpp_expected_counts_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                            const int *ev_vals, const unsigned char *partial, const double *weights, int heuristic,
+                            const int *order, int n_order, int dtype, int64_t rows_per_launch, double *counts,
+                            double *log10_z, int64_t *n_impossible, double *uptime_ms) {
+    return bnpp_expected_counts_sv(ctx, m, n_ev, ev_vars, n_rows, ev_vals, partial, 0, nullptr, nullptr, weights, heuristic, order, n_order, dtype, rows_per_launch, counts, log10_z, n_impossible, uptime_ms);
 }
 
 int bnpp_expected_counts(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
@@ -2026,16 +2161,20 @@ int bnpp_expected_counts(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int
                                    n_order, dtype, rows_per_launch, counts, log10_z, n_impossible, uptime_ms);
 }
 
-int bnpp_plan_counts_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial,
+int bnpp_plan_counts_sv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial, int n_soft, const int *soft_vars,
+        const double *lik,
                         int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch,
                         double *stats, int n_stats, int64_t *rows, int cap_rows, int *n_rows, int *belief_off,
-                        int *belief_vars, int cap_belief, int *n_belief, int *no_b_elim, int *mask_factor) {
+                        int *belief_vars, int cap_belief, int *n_belief, int *no_b_elim, int *mask_factor, int *lam_factor) {
     BNPP_GUARD_BEGIN
     Schedule s;
     VEPlan plan;
     double st[12] = {0};
     BatchCall c = batch_call(m, kKindCounts, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
     c.partial = partial;
+    c.n_soft = n_soft;
+    c.soft_vars = soft_vars;
+    c.lik = lik;
     if (int rc = plan_batch_entry(c, false, stats, n_stats, rows, cap_rows, n_rows, s, plan, st)) return rc;
     for (const Schedule::Group &g : s.groups) st[10] += g.variant == kCountsKey;
     st[11] = plan.counts_fwd_levels;
@@ -2068,8 +2207,17 @@ int bnpp_plan_counts_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const
     }
     for (int j = 0; mask_factor && j < n_ev; ++j)
         mask_factor[j] = j < (int)plan.batch_mask_factor.size() ? plan.batch_mask_factor[j] : -1;
+    for (int j = 0; lam_factor && j < n_soft; ++j)
+        lam_factor[j] = j < (int)plan.batch_lam_factor.size() ? plan.batch_lam_factor[j] : -1;
     return BNPP_OK;
     BNPP_GUARD_END
+}
+
+int bnpp_plan_counts_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial,
+                        int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch,
+                        double *stats, int n_stats, int64_t *rows, int cap_rows, int *n_rows, int *belief_off,
+                        int *belief_vars, int cap_belief, int *n_belief, int *no_b_elim, int *mask_factor) {
+    return bnpp_plan_counts_sv(m, n_ev, ev_vars, partial, 0, nullptr, nullptr, heuristic, order, n_order, dtype, rows_per_launch, stats, n_stats, rows, cap_rows, n_rows, belief_off, belief_vars, cap_belief, n_belief, no_b_elim, mask_factor, nullptr);
 }
 
 int bnpp_plan_counts(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
@@ -2135,19 +2283,30 @@ int bnpp_bucket_counts(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, cons
     BNPP_GUARD_END
 }
 
-int bnpp_marginals_batch_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
-                            const int *ev_vals, const unsigned char *partial, int heuristic, const int *order,
+int bnpp_marginals_batch_sv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                            const int *ev_vals, const unsigned char *partial, int n_soft, const int *soft_vars,
+        const double *lik, int heuristic, const int *order,
                             int n_order, int n_targets, const int *targets, int dtype, int64_t rows_per_launch,
                             double *out, double *log10_z, double *uptime_ms) {
     BNPP_GUARD_BEGIN
     BatchCall c = batch_call(m, kKindMarginalsBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
     c.partial = partial;
+    c.n_soft = n_soft;
+    c.soft_vars = soft_vars;
+    c.lik = lik;
     c.n_rows = n_rows;
     c.ev_vals = ev_vals;
     if (!m) return set_err(BNPP_ERR_INVALID, "null context or model");
     if (int rc = marginals_targets(m->d, n_targets, targets, c.targets)) return rc;
     return run_marginals_batch(ctx, c, out, log10_z, uptime_ms);
     BNPP_GUARD_END
+}
+
+int bnpp_marginals_batch_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                            const int *ev_vals, const unsigned char *partial, int heuristic, const int *order,
+                            int n_order, int n_targets, const int *targets, int dtype, int64_t rows_per_launch,
+                            double *out, double *log10_z, double *uptime_ms) {
+    return bnpp_marginals_batch_sv(ctx, m, n_ev, ev_vars, n_rows, ev_vals, partial, 0, nullptr, nullptr, heuristic, order, n_order, n_targets, targets, dtype, rows_per_launch, out, log10_z, uptime_ms);
 }
 
 int bnpp_marginals_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
@@ -2158,16 +2317,20 @@ int bnpp_marginals_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int
                                    n_targets, targets, dtype, rows_per_launch, out, log10_z, uptime_ms);
 }
 
-int bnpp_plan_marginals_batch_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial,
+int bnpp_plan_marginals_batch_sv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial, int n_soft, const int *soft_vars,
+        const double *lik,
                                  int heuristic, const int *order, int n_order, int n_targets, const int *targets,
                                  int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows,
-                                 int cap_rows, int *n_rows, int *col_kind, int *mask_factor) {
+                                 int cap_rows, int *n_rows, int *col_kind, int *mask_factor, int *lam_factor) {
     BNPP_GUARD_BEGIN
     Schedule s;
     VEPlan plan;
     double st[BNPP_PLAN_MARGINALS_BATCH_STATS] = {0};
     BatchCall c = batch_call(m, kKindMarginalsBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
     c.partial = partial;
+    c.n_soft = n_soft;
+    c.soft_vars = soft_vars;
+    c.lik = lik;
     if (!m) return set_err(BNPP_ERR_INVALID, "null argument");
     if (int rc = marginals_targets(m->d, n_targets, targets, c.targets)) return rc;
     if (int rc = plan_batch_entry(c, false, stats, n_stats, rows, cap_rows, n_rows, s, plan, st)) return rc;
@@ -2186,8 +2349,17 @@ int bnpp_plan_marginals_batch_mv(const bnpp_model *m, int n_ev, const int *ev_va
                 col_kind[j] = b.marg_cols[j].table >= 0 ? (b.marg_cols[j].has_b ? 1 : 0) : b.marg_cols[j].ev_row >= 0 ? -1 : -2;
     for (int j = 0; mask_factor && j < n_ev; ++j)
         mask_factor[j] = j < (int)plan.batch_mask_factor.size() ? plan.batch_mask_factor[j] : -1;
+    for (int j = 0; lam_factor && j < n_soft; ++j)
+        lam_factor[j] = j < (int)plan.batch_lam_factor.size() ? plan.batch_lam_factor[j] : -1;
     return BNPP_OK;
     BNPP_GUARD_END
+}
+
+int bnpp_plan_marginals_batch_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial,
+                                 int heuristic, const int *order, int n_order, int n_targets, const int *targets,
+                                 int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows,
+                                 int cap_rows, int *n_rows, int *col_kind, int *mask_factor) {
+    return bnpp_plan_marginals_batch_sv(m, n_ev, ev_vars, partial, 0, nullptr, nullptr, heuristic, order, n_order, n_targets, targets, dtype, rows_per_launch, stats, n_stats, rows, cap_rows, n_rows, col_kind, mask_factor, nullptr);
 }
 
 int bnpp_plan_marginals_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order,
@@ -2772,11 +2944,23 @@ int bnpp_evidence_load_batch_mv(const char *path, int cap_vars, int64_t cap_rows
     BNPP_GUARD_END
 }
 
-int bnpp_condition_batch_mv(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, const void *in,
+int bnpp_condition_batch_sv(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, const void *in,
                             int ndims, const int *vars, int n_ev, const int *ev_vars, const unsigned char *partial,
-                            int64_t n_rows, const int32_t *ev, void *out) {
+                            int n_soft, const int *soft_vars, const void *lam, int64_t n_rows, const int32_t *ev,
+                            void *out) {
     BNPP_GUARD_BEGIN
     if (!ctx || !cards || !in || !out || (n_ev > 0 && (!ev_vars || !ev))) return set_err(BNPP_ERR_INVALID, "null argument");
+    if (n_soft < 0 || (n_soft > 0 && (!soft_vars || !lam))) return set_err(BNPP_ERR_INVALID, "bad soft evidence arrays");
+    for (int i = 0; i < n_soft; ++i) {
+        if (soft_vars[i] < 0 || soft_vars[i] >= n_cards)
+            return set_err(BNPP_ERR_INVALID, "soft variable " + std::to_string(soft_vars[i]) + " out of range");
+        for (int k = 0; k < i; ++k)
+            if (soft_vars[k] == soft_vars[i])
+                return set_err(BNPP_ERR_INVALID, "soft variable " + std::to_string(soft_vars[i]) + " is listed twice");
+        for (int e = 0; e < n_ev; ++e)
+            if (ev_vars[e] == soft_vars[i])
+                return set_err(BNPP_ERR_INVALID, "variable " + std::to_string(soft_vars[i]) + " is both an evidence and a soft variable");
+    }
     if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "dtype must be BNPP_F64 or BNPP_F32");
     if (n_cards < 0 || !valid_scope(ndims, vars, cards, n_cards)) return set_err(BNPP_ERR_INVALID, "bad input scope");
     if (n_ev < 0 || !valid_scope(n_ev, ev_vars, cards, n_cards)) return set_err(BNPP_ERR_INVALID, "bad evidence variables");
@@ -2787,11 +2971,17 @@ int bnpp_condition_batch_mv(bnpp_ctx *ctx, void *stream, int dtype, int n_cards,
     b.cond_batch = true;
     b.in.push_back(natural_view(0, std::vector<int>(vars, vars + ndims), cv));
     int n_in_scope = 0;
-    bool masked = false;
+    bool masked = false, weighted = false;
     for (int j = 0; j < ndims; ++j) {
-        int row = -1;
+        int row = -1, lrow = -1, lnext = 0;
         for (int e = 0; e < n_ev; ++e)
             if (ev_vars[e] == vars[j]) row = e;
+        for (int i = 0; i < n_soft; ++i) {                  // the variable's first row of lam: the cards of those before it
+            if (soft_vars[i] == vars[j]) lrow = lnext;
+            lnext += cards[soft_vars[i]];
+        }
+        b.soft_rows.push_back(lrow);
+        weighted = weighted || lrow >= 0;
         const bool part = row >= 0 && partial && partial[row];     // kept, under the row's mask
         b.cond_rows.push_back(part ? -1 : row);
         b.mask_rows.push_back(part ? row : -1);
@@ -2800,6 +2990,7 @@ int bnpp_condition_batch_mv(bnpp_ctx *ctx, void *stream, int dtype, int n_cards,
         else ++n_in_scope;
     }
     if (!masked) b.mask_rows.clear();
+    if (!weighted) b.soft_rows.clear();
     if (n_in_scope > kCondMaxEv) return set_err(BNPP_ERR_UNSUPPORTED, "at most 32 evidence variables in the scope of a single-op call");
     b.out_vars.push_back(n_cards);
     b.out_table = 1;
@@ -2808,7 +2999,19 @@ int bnpp_condition_batch_mv(bnpp_ctx *ctx, void *stream, int dtype, int n_cards,
     std::string msg;
     if (!build_desc(b, cv, max_vec_for(dtype), d, pool, &msg)) return set_err(BNPP_ERR_UNSUPPORTED, msg);
     hipError_t e = hipSuccess;
-    if (masked) {
+    if (weighted) {
+        CondBatchSoftArgs a;
+        std::memset(&a, 0, sizeof a);
+        if (pool.size() > sizeof a.pool / sizeof a.pool[0]) return set_err(BNPP_ERR_UNSUPPORTED, "scope too wide for a single-op call");
+        std::copy(pool.begin(), pool.end(), a.pool);
+        a.src = in;
+        a.out = out;
+        a.ev = ev;
+        a.lam = lam;
+        a.n_rows = n_rows;
+        e = hipSetDevice(ctx->c.device);
+        if (e == hipSuccess) e = launch_cond_batch_soft_single(dtype == BNPP_F32, a, ctx->c.max_grid, pick_stream(ctx, stream));
+    } else if (masked) {
         CondBatchMaskedArgs a;
         std::memset(&a, 0, sizeof a);
         if (pool.size() > sizeof a.pool / sizeof a.pool[0]) return set_err(BNPP_ERR_UNSUPPORTED, "scope too wide for a single-op call");
@@ -2832,6 +3035,65 @@ int bnpp_condition_batch_mv(bnpp_ctx *ctx, void *stream, int dtype, int n_cards,
         if (e == hipSuccess) e = launch_cond_batch_single(dtype == BNPP_F32, a, ctx->c.max_grid, pick_stream(ctx, stream));
     }
     if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+int bnpp_condition_batch_mv(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, const void *in,
+                            int ndims, const int *vars, int n_ev, const int *ev_vars, const unsigned char *partial,
+                            int64_t n_rows, const int32_t *ev, void *out) {
+    return bnpp_condition_batch_sv(ctx, stream, dtype, n_cards, cards, in, ndims, vars, n_ev, ev_vars, partial, 0, nullptr,
+                                   nullptr, n_rows, ev, out);
+}
+
+int bnpp_likelihood_load(const bnpp_model *m, const char *path, int cap_vars, int64_t cap_vals, int *n_soft,
+                         int *soft_vars, int64_t *n_rows, double *lik) {
+    BNPP_GUARD_BEGIN
+    if (!m || !path || !n_soft || !n_rows) return set_err(BNPP_ERR_INVALID, "null argument");
+    std::ifstream f(path);
+    if (!f) return set_err(BNPP_ERR_IO, std::string("couldn't read file ") + path);
+    const int nv = (int)m->d.cards.size();
+    long long ns = 0, nr = 0;
+    if (!(f >> ns) || ns < 0 || ns > nv) return set_err(BNPP_ERR_IO, std::string(path) + ": bad soft variable count");
+    std::vector<int> vars((size_t)ns);
+    int64_t ws = 0;
+    for (auto &v : vars) {
+        if (!(f >> v) || v < 0 || v >= nv) return set_err(BNPP_ERR_IO, std::string(path) + ": bad soft variable id");
+        ws += m->d.cards[v];
+    }
+    if (!(f >> nr) || nr < 0) return set_err(BNPP_ERR_IO, std::string(path) + ": bad row count");
+    *n_soft = (int)ns;
+    *n_rows = nr;
+    if (ns > cap_vars) return set_err(BNPP_ERR_INVALID, "likelihoods larger than cap");
+    if (ns > 0 && !soft_vars) return set_err(BNPP_ERR_INVALID, "null argument");
+    std::copy(vars.begin(), vars.end(), soft_vars);
+    if (nr * ws > cap_vals) return set_err(BNPP_ERR_INVALID, "likelihoods larger than cap");
+    if (nr * ws > 0 && !lik) return set_err(BNPP_ERR_INVALID, "null argument");
+    for (int64_t i = 0; i < nr * ws; ++i) {
+        std::string tok;
+        if (!(f >> tok)) return set_err(BNPP_ERR_IO, std::string(path) + ": row " + std::to_string(i / ws) + " is short");
+        char *end = nullptr;
+        lik[i] = std::strtod(tok.c_str(), &end);
+        if (end == tok.c_str() || *end) return set_err(BNPP_ERR_IO, std::string(path) + ": row " + std::to_string(i / ws) + ": bad number " + tok);
+    }
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+// A hook of the test suite, not part of include/bnpp.h: the job cache key of a bnpp_partition_batch call of this
+// shape with the default heuristic and at least 2^16 rows (tests/test_soft_host.py: the key ignores values and is
+// the old one without soft variables)
+extern "C" int bnpp_batch_job_key(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial, int n_soft,
+                                  const int *soft_vars, int dtype, int64_t rows_per_launch, uint64_t *key);
+int bnpp_batch_job_key(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial, int n_soft,
+                       const int *soft_vars, int dtype, int64_t rows_per_launch, uint64_t *key) {
+    BNPP_GUARD_BEGIN
+    if (!m || !key || (n_ev > 0 && !ev_vars) || (n_soft > 0 && !soft_vars)) return set_err(BNPP_ERR_INVALID, "null argument");
+    BatchCall c = batch_call(m, kKindBatch, n_ev, ev_vars, BNPP_MIN_FILL, nullptr, 0, dtype, rows_per_launch);
+    c.partial = partial;
+    c.n_soft = n_soft;
+    c.soft_vars = soft_vars;
+    *key = batch_call_key(c, kBatchAutoRows);
     return BNPP_OK;
     BNPP_GUARD_END
 }
@@ -3274,17 +3536,28 @@ int bnpp_sample(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars
     BNPP_GUARD_END
 }
 
-int bnpp_partition_batch_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
-                            const int *ev_vals, const unsigned char *partial, int heuristic, const int *order,
+int bnpp_partition_batch_sv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                            const int *ev_vals, const unsigned char *partial, int n_soft, const int *soft_vars,
+        const double *lik, int heuristic, const int *order,
                             int n_order, int dtype, int64_t rows_per_launch, double *log10_z, double *z,
                             double *uptime_ms) {
     BNPP_GUARD_BEGIN
     BatchCall c = batch_call(m, kKindBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
     c.partial = partial;
+    c.n_soft = n_soft;
+    c.soft_vars = soft_vars;
+    c.lik = lik;
     c.n_rows = n_rows;
     c.ev_vals = ev_vals;
     return run_batch(ctx, c, false, log10_z, z, nullptr, uptime_ms);
     BNPP_GUARD_END
+}
+
+int bnpp_partition_batch_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                            const int *ev_vals, const unsigned char *partial, int heuristic, const int *order,
+                            int n_order, int dtype, int64_t rows_per_launch, double *log10_z, double *z,
+                            double *uptime_ms) {
+    return bnpp_partition_batch_sv(ctx, m, n_ev, ev_vars, n_rows, ev_vals, partial, 0, nullptr, nullptr, heuristic, order, n_order, dtype, rows_per_launch, log10_z, z, uptime_ms);
 }
 
 int bnpp_partition_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
@@ -3294,17 +3567,27 @@ int bnpp_partition_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int
                                    rows_per_launch, log10_z, z, uptime_ms);
 }
 
-int bnpp_posterior_batch_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
-                            const int *ev_vals, const unsigned char *partial, int heuristic, int target, int dtype,
+int bnpp_posterior_batch_sv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                            const int *ev_vals, const unsigned char *partial, int n_soft, const int *soft_vars,
+        const double *lik, int heuristic, int target, int dtype,
                             int64_t rows_per_launch, double *out, double *uptime_ms) {
     BNPP_GUARD_BEGIN
     BatchCall c = batch_call(m, kKindBatch, n_ev, ev_vars, heuristic, nullptr, 0, dtype, rows_per_launch);
     c.partial = partial;
+    c.n_soft = n_soft;
+    c.soft_vars = soft_vars;
+    c.lik = lik;
     c.target = target;
     c.n_rows = n_rows;
     c.ev_vals = ev_vals;
     return run_batch(ctx, c, true, nullptr, nullptr, out, uptime_ms);
     BNPP_GUARD_END
+}
+
+int bnpp_posterior_batch_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                            const int *ev_vals, const unsigned char *partial, int heuristic, int target, int dtype,
+                            int64_t rows_per_launch, double *out, double *uptime_ms) {
+    return bnpp_posterior_batch_sv(ctx, m, n_ev, ev_vars, n_rows, ev_vals, partial, 0, nullptr, nullptr, heuristic, target, dtype, rows_per_launch, out, uptime_ms);
 }
 
 int bnpp_posterior_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
@@ -3314,16 +3597,26 @@ int bnpp_posterior_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int
                                    rows_per_launch, out, uptime_ms);
 }
 
-int bnpp_mpe_batch_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
-                      const int *ev_vals, const unsigned char *partial, int heuristic, const int *order, int n_order,
+int bnpp_mpe_batch_sv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                      const int *ev_vals, const unsigned char *partial, int n_soft, const int *soft_vars,
+        const double *lik, int heuristic, const int *order, int n_order,
                       int dtype, int64_t rows_per_launch, double *log10_value, int *assignment, double *uptime_ms) {
     BNPP_GUARD_BEGIN
     BatchCall c = batch_call(m, kKindMpeBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
     c.partial = partial;
+    c.n_soft = n_soft;
+    c.soft_vars = soft_vars;
+    c.lik = lik;
     c.n_rows = n_rows;
     c.ev_vals = ev_vals;
     return run_mpe_batch(ctx, c, log10_value, assignment, uptime_ms);
     BNPP_GUARD_END
+}
+
+int bnpp_mpe_batch_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                      const int *ev_vals, const unsigned char *partial, int heuristic, const int *order, int n_order,
+                      int dtype, int64_t rows_per_launch, double *log10_value, int *assignment, double *uptime_ms) {
+    return bnpp_mpe_batch_sv(ctx, m, n_ev, ev_vars, n_rows, ev_vals, partial, 0, nullptr, nullptr, heuristic, order, n_order, dtype, rows_per_launch, log10_value, assignment, uptime_ms);
 }
 
 int bnpp_mpe_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const int *ev_vals,
@@ -3333,15 +3626,19 @@ int bnpp_mpe_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_v
                              rows_per_launch, log10_value, assignment, uptime_ms);
 }
 
-int bnpp_plan_mpe_batch_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial,
+int bnpp_plan_mpe_batch_sv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial, int n_soft, const int *soft_vars,
+        const double *lik,
                            int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch,
-                           double *stats, int n_stats, int64_t *rows, int cap_rows, int *n_rows, int *mask_factor) {
+                           double *stats, int n_stats, int64_t *rows, int cap_rows, int *n_rows, int *mask_factor, int *lam_factor) {
     BNPP_GUARD_BEGIN
     Schedule s;
     VEPlan plan;
     double st[BNPP_PLAN_MPE_BATCH_STATS] = {0};
     BatchCall c = batch_call(m, kKindMpeBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
     c.partial = partial;
+    c.n_soft = n_soft;
+    c.soft_vars = soft_vars;
+    c.lik = lik;
     if (int rc = plan_batch_entry(c, false, stats, n_stats, rows, cap_rows, n_rows, s, plan, st)) return rc;
     st[10] = (double)plan.arg_bytes;
     st[11] = plan.n_max_buckets;
@@ -3352,8 +3649,16 @@ int bnpp_plan_mpe_batch_mv(const bnpp_model *m, int n_ev, const int *ev_vars, co
     for (int i = 0; i < n_stats && i < BNPP_PLAN_MPE_BATCH_STATS; ++i) stats[i] = st[i];
     for (int j = 0; mask_factor && j < n_ev; ++j)
         mask_factor[j] = j < (int)plan.batch_mask_factor.size() ? plan.batch_mask_factor[j] : -1;
+    for (int j = 0; lam_factor && j < n_soft; ++j)
+        lam_factor[j] = j < (int)plan.batch_lam_factor.size() ? plan.batch_lam_factor[j] : -1;
     return BNPP_OK;
     BNPP_GUARD_END
+}
+
+int bnpp_plan_mpe_batch_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial,
+                           int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch,
+                           double *stats, int n_stats, int64_t *rows, int cap_rows, int *n_rows, int *mask_factor) {
+    return bnpp_plan_mpe_batch_sv(m, n_ev, ev_vars, partial, 0, nullptr, nullptr, heuristic, order, n_order, dtype, rows_per_launch, stats, n_stats, rows, cap_rows, n_rows, mask_factor, nullptr);
 }
 
 int bnpp_plan_mpe_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
@@ -3363,19 +3668,31 @@ int bnpp_plan_mpe_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int h
                                   n_stats, rows, cap_rows, n_rows, nullptr);
 }
 
-int bnpp_sample_batch_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
-                         const int *ev_vals, const unsigned char *partial, int heuristic, const int *order,
+int bnpp_sample_batch_sv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                         const int *ev_vals, const unsigned char *partial, int n_soft, const int *soft_vars,
+        const double *lik, int heuristic, const int *order,
                          int n_order, int dtype, int64_t rows_per_launch, int64_t n_per_row, int64_t first_sample,
                          int64_t row_stride, uint64_t seed, uint8_t *out, double *log10_z, int64_t *n_degenerate,
                          double *uptime_ms) {
     BNPP_GUARD_BEGIN
     BatchCall c = batch_call(m, kKindSampleBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
     c.partial = partial;
+    c.n_soft = n_soft;
+    c.soft_vars = soft_vars;
+    c.lik = lik;
     c.K = n_per_row;
     c.n_rows = n_rows;
     c.ev_vals = ev_vals;
     return run_sample_batch(ctx, c, first_sample, row_stride, seed, out, log10_z, n_degenerate, uptime_ms);
     BNPP_GUARD_END
+}
+
+int bnpp_sample_batch_mv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                         const int *ev_vals, const unsigned char *partial, int heuristic, const int *order,
+                         int n_order, int dtype, int64_t rows_per_launch, int64_t n_per_row, int64_t first_sample,
+                         int64_t row_stride, uint64_t seed, uint8_t *out, double *log10_z, int64_t *n_degenerate,
+                         double *uptime_ms) {
+    return bnpp_sample_batch_sv(ctx, m, n_ev, ev_vars, n_rows, ev_vals, partial, 0, nullptr, nullptr, heuristic, order, n_order, dtype, rows_per_launch, n_per_row, first_sample, row_stride, seed, out, log10_z, n_degenerate, uptime_ms);
 }
 
 int bnpp_sample_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const int *ev_vals,
@@ -3387,16 +3704,20 @@ int bnpp_sample_batch(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *e
                                 n_degenerate, uptime_ms);
 }
 
-int bnpp_plan_sample_batch_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial,
+int bnpp_plan_sample_batch_sv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial, int n_soft, const int *soft_vars,
+        const double *lik,
                               int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch,
                               int64_t n_per_row, double *stats, int n_stats, int64_t *rows, int cap_rows, int *n_rows,
-                              int *mask_factor) {
+                              int *mask_factor, int *lam_factor) {
     BNPP_GUARD_BEGIN
     Schedule s;
     VEPlan plan;
     double st[BNPP_PLAN_SAMPLE_BATCH_STATS] = {0};
     BatchCall c = batch_call(m, kKindSampleBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
     c.partial = partial;
+    c.n_soft = n_soft;
+    c.soft_vars = soft_vars;
+    c.lik = lik;
     c.K = n_per_row;
     if (int rc = plan_batch_entry(c, false, stats, n_stats, rows, cap_rows, n_rows, s, plan, st)) return rc;
     st[10] = (double)n_per_row;
@@ -3407,8 +3728,17 @@ int bnpp_plan_sample_batch_mv(const bnpp_model *m, int n_ev, const int *ev_vars,
     for (int i = 0; i < n_stats && i < BNPP_PLAN_SAMPLE_BATCH_STATS; ++i) stats[i] = st[i];
     for (int j = 0; mask_factor && j < n_ev; ++j)
         mask_factor[j] = j < (int)plan.batch_mask_factor.size() ? plan.batch_mask_factor[j] : -1;
+    for (int j = 0; lam_factor && j < n_soft; ++j)
+        lam_factor[j] = j < (int)plan.batch_lam_factor.size() ? plan.batch_lam_factor[j] : -1;
     return BNPP_OK;
     BNPP_GUARD_END
+}
+
+int bnpp_plan_sample_batch_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial,
+                              int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch,
+                              int64_t n_per_row, double *stats, int n_stats, int64_t *rows, int cap_rows, int *n_rows,
+                              int *mask_factor) {
+    return bnpp_plan_sample_batch_sv(m, n_ev, ev_vars, partial, 0, nullptr, nullptr, heuristic, order, n_order, dtype, rows_per_launch, n_per_row, stats, n_stats, rows, cap_rows, n_rows, mask_factor, nullptr);
 }
 
 int bnpp_plan_sample_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,
@@ -3418,10 +3748,11 @@ int bnpp_plan_sample_batch(const bnpp_model *m, int n_ev, const int *ev_vars, in
                                      n_per_row, stats, n_stats, rows, cap_rows, n_rows, nullptr);
 }
 
-int bnpp_plan_batch_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial, int heuristic,
+int bnpp_plan_batch_sv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial, int n_soft, const int *soft_vars,
+        const double *lik, int heuristic,
                        const int *order, int n_order, int target, int dtype, int64_t rows_per_launch, double *stats,
                        int n_stats, int64_t *rows, int cap_rows, int *n_rows, int *result_scope, int *n_result_scope,
-                       int *mask_factor) {
+                       int *mask_factor, int *lam_factor) {
     BNPP_GUARD_BEGIN
     Schedule s;
     VEPlan plan;
@@ -3429,6 +3760,9 @@ int bnpp_plan_batch_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const 
     BatchCall c = batch_call(m, kKindBatch, n_ev, ev_vars, heuristic, target >= 0 ? nullptr : order,
                              target >= 0 ? 0 : n_order, dtype, rows_per_launch);
     c.partial = partial;
+    c.n_soft = n_soft;
+    c.soft_vars = soft_vars;
+    c.lik = lik;
     c.target = target >= 0 ? target : -1;
     if (int rc = plan_batch_entry(c, target >= 0, stats, n_stats, rows, cap_rows, n_rows, s, plan, st)) return rc;
     for (int i = 0; i < n_stats && i < 10; ++i) stats[i] = st[i];
@@ -3438,8 +3772,17 @@ int bnpp_plan_batch_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const 
         for (size_t i = 0; i < rv.size() && i < 2; ++i) result_scope[i] = rv[i];
     for (int j = 0; mask_factor && j < n_ev; ++j)
         mask_factor[j] = j < (int)plan.batch_mask_factor.size() ? plan.batch_mask_factor[j] : -1;
+    for (int j = 0; lam_factor && j < n_soft; ++j)
+        lam_factor[j] = j < (int)plan.batch_lam_factor.size() ? plan.batch_lam_factor[j] : -1;
     return BNPP_OK;
     BNPP_GUARD_END
+}
+
+int bnpp_plan_batch_mv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial, int heuristic,
+                       const int *order, int n_order, int target, int dtype, int64_t rows_per_launch, double *stats,
+                       int n_stats, int64_t *rows, int cap_rows, int *n_rows, int *result_scope, int *n_result_scope,
+                       int *mask_factor) {
+    return bnpp_plan_batch_sv(m, n_ev, ev_vars, partial, 0, nullptr, nullptr, heuristic, order, n_order, target, dtype, rows_per_launch, stats, n_stats, rows, cap_rows, n_rows, result_scope, n_result_scope, mask_factor, nullptr);
 }
 
 int bnpp_plan_batch(const bnpp_model *m, int n_ev, const int *ev_vars, int heuristic, const int *order, int n_order,

@@ -36,6 +36,21 @@
 // lane's value against a scalar per partial dim.  A partial dim is never merged
 // with a neighbour.  The pool continues after the rest words:
 //   n_p, then n_p x (row of ev, index of the rest dim)
+//
+// Weighted form (cond_batch_soft, soft evidence): some rest dims are SOFT
+// variables.  Row b scales an entry by its likelihood of each soft dim's digit,
+// in the order of the source's scope, left to right, each product rounded once:
+//
+//   out[rest][b] = mask_b(rest) ? ((src[...] * lam[row0_d1 + digit_d1][b]) * lam[row0_d2 + digit_d2][b]) ... : 0
+//
+// lam is T[Ws][R], (variable, value)-major, rows fastest: the digits are the
+// (wave-uniform) odometer's, so a wave reads the weights of one rest entry and
+// one soft dim as one contiguous run of 64 * V entries -- a uniform base plus
+// the lane's b -- through the V-wide path of the stores.  A dim's weights are
+// folded into the running product before the next dim's are loaded.  A soft dim
+// is never merged with a neighbour; masks and weights combine.  The pool
+// continues after the masked words (n_p may be 0):
+//   n_s, then n_s x (first row of lam, index of the rest dim)
 #pragma once
 #include "kernels.cuh"
 
@@ -205,6 +220,160 @@ __global__ __launch_bounds__(kBlock) void cond_batch_masked_single_kernel(const 
     cond_batch<T, V, true>(a.pool, static_cast<const T *>(a.src), static_cast<T *>(a.out), a.ev, a.n_rows);
 }
 
+// The weighted gather (soft evidence), masks included: see the head of the file
+template <typename T, int V>
+__device__ __forceinline__ void cond_batch_soft(cst_t<int64_t> *pool, const T *src, T *out, const int32_t *ev, const T *lam,
+                                                int64_t R) {
+    const int n_e = (int)pool[1], n_rest = (int)pool[2];
+    const int64_t n_r = pool[3];
+    cst_t<int64_t> *ew = pool + 4, *rw = ew + 3 * n_e;
+    const int n_p = (int)rw[2 * n_rest];
+    cst_t<int64_t> *pw = rw + 2 * n_rest + 1;
+    const int n_s = (int)pw[2 * n_p];
+    cst_t<int64_t> *sw = pw + 2 * n_p + 1;
+    const int64_t nbb = (R / V + kBlock - 1) / kBlock;
+    const int64_t nrc = (n_r + kCondRestChunk - 1) / kCondRestChunk;
+    for (int64_t vb = blockIdx.x; vb < nbb * nrc; vb += gridDim.x) {
+        const int64_t rc = vb / nbb, bb = vb - rc * nbb;
+        const int64_t b = (bb * kBlock + threadIdx.x) * V;
+        const bool live = b < R;
+        int64_t base[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) base[j] = 0;
+        if (live) {
+            for (int e = 0; e < n_e; ++e) {
+                int32_t x[V];
+                load_n<int32_t, V, false, true>(ev + ew[3 * e] * R + b, x);
+                const int32_t top = (int32_t)ew[3 * e + 2] - 1;
+                const int64_t st = ew[3 * e + 1];
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    const int32_t c = x[j] < 0 ? 0 : x[j] > top ? top : x[j];
+                    base[j] += (int64_t)c * st;
+                }
+            }
+        }
+        // per rest dim, resolved once: a partial dim's values of the lane, a soft dim's first row of lam (uniform)
+        int32_t pv[kCondMaxRest][V];
+        bool pd[kCondMaxRest];
+        int32_t srow[kCondMaxRest];                         // -1: not a soft dim
+#pragma unroll
+        for (int d = 0; d < kCondMaxRest; ++d) {
+            int64_t row = -1, lrow = -1;
+            for (int k = 0; k < n_p; ++k)
+                if (pw[2 * k + 1] == d) row = pw[2 * k];
+            for (int k = 0; k < n_s; ++k)
+                if (sw[2 * k + 1] == d) lrow = sw[2 * k];
+            pd[d] = row >= 0;
+            srow[d] = (int32_t)lrow;
+#pragma unroll
+            for (int j = 0; j < V; ++j) pv[d][j] = -1;
+            if (pd[d] && live) load_n<int32_t, V, false, true>(ev + row * R + b, pv[d]);
+        }
+        const int64_t r0 = rc * kCondRestChunk;
+        const int64_t r1 = r0 + kCondRestChunk < n_r ? r0 + kCondRestChunk : n_r;
+        int64_t dig[kCondMaxRest];
+        int64_t off = 0, q = r0;
+#pragma unroll
+        for (int d = 0; d < kCondMaxRest; ++d) {
+            dig[d] = 0;
+            if (d < n_rest) {
+                const int64_t c = rw[2 * d];
+                dig[d] = q % c;
+                q /= c;
+                off += dig[d] * rw[2 * d + 1];
+            }
+        }
+        for (int64_t r = r0; r < r1; r += kCondBatchU) {
+            int64_t offs[kCondBatchU];
+            int32_t lr[kCondBatchU][kCondMaxRest];          // per entry (uniform): a soft dim's row of lam
+            bool hit[kCondBatchU][V];
+#pragma unroll
+            for (int u = 0; u < kCondBatchU; ++u) {
+                offs[u] = off;
+#pragma unroll
+                for (int j = 0; j < V; ++j) hit[u][j] = true;
+#pragma unroll
+                for (int d = 0; d < kCondMaxRest; ++d) {
+                    lr[u][d] = srow[d] + (int32_t)dig[d];
+                    if (pd[d]) {
+                        const int32_t digit = (int32_t)dig[d];
+#pragma unroll
+                        for (int j = 0; j < V; ++j) hit[u][j] = hit[u][j] && (pv[d][j] < 0 || pv[d][j] == digit);
+                    }
+                }
+                bool carry = true;
+#pragma unroll
+                for (int d = 0; d < kCondMaxRest; ++d) {
+                    if (carry && d < n_rest) {
+                        const int64_t c = rw[2 * d], st = rw[2 * d + 1];
+                        ++dig[d];
+                        off += st;
+                        if (dig[d] == c) {
+                            dig[d] = 0;
+                            off -= c * st;
+                        } else {
+                            carry = false;
+                        }
+                    }
+                }
+            }
+            T x[kCondBatchU][V];
+#pragma unroll
+            for (int u = 0; u < kCondBatchU; ++u)
+                if (live && r + u < r1) {
+#pragma unroll
+                    for (int j = 0; j < V; ++j) x[u][j] = hit[u][j] ? gload(src + base[j] + offs[u]) : T(0);
+                }
+            // the scope's order, left to right: the slowest rest dim first; one dim's weights live at a time
+#pragma unroll
+            for (int d = kCondMaxRest - 1; d >= 0; --d)
+                if (srow[d] >= 0) {
+                    T w[kCondBatchU][V];
+#pragma unroll
+                    for (int u = 0; u < kCondBatchU; ++u)
+                        if (live && r + u < r1) load_n<T, V, false, true>(lam + (int64_t)lr[u][d] * R + b, w[u]);
+#pragma unroll
+                    for (int u = 0; u < kCondBatchU; ++u)
+                        if (live && r + u < r1) {
+#pragma unroll
+                            for (int j = 0; j < V; ++j) x[u][j] = x[u][j] * w[u][j];
+                        }
+                }
+#pragma unroll
+            for (int u = 0; u < kCondBatchU; ++u)
+                if (live && r + u < r1) store_n<T, V, false, true>(out + (r + u) * R + b, x[u]);
+        }
+    }
+}
+
+// The weighted gather step of a batch plan: the weights are at most 1, so the source's exp2 and maxbits stay
+// a valid bound, as for the masked step.  And the weighted single gather (bnpp_condition_batch_sv)
+template <typename T, int V>
+__global__ __launch_bounds__(kBlock) void cond_batch_soft_kernel(const int64_t *pool_, TableMeta *meta, int out_table,
+                                                                 const int32_t *ev, const void *lam, int64_t R) {
+    cst_t<int64_t> *pool = as_const(pool_);
+    const int src_table = (int)pool[0];
+    cst_t<TableMeta> &ms = *as_const(meta + src_table);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        meta[out_table].exp2 = ms.exp2;
+        meta[out_table].maxbits = ms.maxbits;
+    }
+    cond_batch_soft<T, V>(pool, static_cast<const T *>(ms.ptr), static_cast<T *>(as_const(meta + out_table)->ptr), ev,
+                          static_cast<const T *>(lam), R);
+}
+template <typename T, int V>
+__global__ __launch_bounds__(kBlock) void cond_batch_soft_single_kernel(const CondBatchSoftArgs args) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    (void)args;
+    cst_t<CondBatchSoftArgs> &a = *(cst_t<CondBatchSoftArgs> *)__builtin_amdgcn_kernarg_segment_ptr();
+#else
+    cst_t<CondBatchSoftArgs> &a = *(cst_t<CondBatchSoftArgs> *)&args;
+#endif
+    cond_batch_soft<T, V>(a.pool, static_cast<const T *>(a.src), static_cast<T *>(a.out), a.ev,
+                          static_cast<const T *>(a.lam), a.n_rows);
+}
+
 // persistent: the grid capped like the other persistent launches
 template <int V>
 static inline int64_t cond_batch_grid(int64_t rest, int64_t R, int max_grid) {
@@ -263,6 +432,31 @@ static hipError_t go_cond_batch_masked_single(const CondBatchMaskedArgs &a, int 
                            dim3((unsigned)cond_batch_grid<V>(a.pool[3], a.n_rows, max_grid)), dim3(kBlock), 0, stream, a);
     else
         hipLaunchKernelGGL((cond_batch_masked_single_kernel<T, 1>),
+                           dim3((unsigned)cond_batch_grid<1>(a.pool[3], a.n_rows, max_grid)), dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
+
+// the weighted forms: wide accesses need lam 16-byte aligned too
+template <typename T>
+static hipError_t go_cond_batch_soft(const int64_t *pool, int64_t rest, TableMeta *meta, int out_table, const void *out_ptr,
+                                     const int32_t *ev, const void *lam, int64_t R, int max_grid, hipStream_t stream) {
+    constexpr int V = 16 / (int)sizeof(T);
+    if (cond_batch_wide<T>(R, out_ptr, ev) && cond_batch_wide<T>(R, lam, lam))
+        hipLaunchKernelGGL((cond_batch_soft_kernel<T, V>), dim3((unsigned)cond_batch_grid<V>(rest, R, max_grid)), dim3(kBlock),
+                           0, stream, pool, meta, out_table, ev, lam, R);
+    else
+        hipLaunchKernelGGL((cond_batch_soft_kernel<T, 1>), dim3((unsigned)cond_batch_grid<1>(rest, R, max_grid)), dim3(kBlock),
+                           0, stream, pool, meta, out_table, ev, lam, R);
+    return hipGetLastError();
+}
+template <typename T>
+static hipError_t go_cond_batch_soft_single(const CondBatchSoftArgs &a, int max_grid, hipStream_t stream) {
+    constexpr int V = 16 / (int)sizeof(T);
+    if (cond_batch_wide<T>(a.n_rows, a.out, a.ev) && cond_batch_wide<T>(a.n_rows, a.lam, a.lam))
+        hipLaunchKernelGGL((cond_batch_soft_single_kernel<T, V>),
+                           dim3((unsigned)cond_batch_grid<V>(a.pool[3], a.n_rows, max_grid)), dim3(kBlock), 0, stream, a);
+    else
+        hipLaunchKernelGGL((cond_batch_soft_single_kernel<T, 1>),
                            dim3((unsigned)cond_batch_grid<1>(a.pool[3], a.n_rows, max_grid)), dim3(kBlock), 0, stream, a);
     return hipGetLastError();
 }

@@ -57,6 +57,15 @@ hipError_t dispatch_cond_batch_masked_f64(const int64_t *pool, int64_t rest, Tab
 hipError_t dispatch_cond_batch_masked_single_f32(const CondBatchMaskedArgs &a, int max_grid, hipStream_t stream);
 hipError_t dispatch_cond_batch_masked_single_f64(const CondBatchMaskedArgs &a, int max_grid, hipStream_t stream);
 
+hipError_t dispatch_cond_batch_soft_f32(const int64_t *pool, int64_t rest, TableMeta *meta, int out_table,
+                                        const void *out_ptr, const int32_t *ev, const void *lam, int64_t n_rows,
+                                        int max_grid, hipStream_t stream);
+hipError_t dispatch_cond_batch_soft_f64(const int64_t *pool, int64_t rest, TableMeta *meta, int out_table,
+                                        const void *out_ptr, const int32_t *ev, const void *lam, int64_t n_rows,
+                                        int max_grid, hipStream_t stream);
+hipError_t dispatch_cond_batch_soft_single_f32(const CondBatchSoftArgs &a, int max_grid, hipStream_t stream);
+hipError_t dispatch_cond_batch_soft_single_f64(const CondBatchSoftArgs &a, int max_grid, hipStream_t stream);
+
 hipError_t dispatch_counts_f32(const CountsArgs &a, int max_grid, hipStream_t stream);
 hipError_t dispatch_counts_f64(const CountsArgs &a, int max_grid, hipStream_t stream);
 hipError_t dispatch_counts_list_f32(const CountsArgs *list, int n, int64_t rows_max, int64_t rest_max, int max_grid,
@@ -178,6 +187,20 @@ hipError_t launch_cond_batch_masked_single(int is_f32, const CondBatchMaskedArgs
     if (a.n_rows <= 0) return hipSuccess;
     return is_f32 ? dispatch_cond_batch_masked_single_f32(a, max_grid, stream)
                   : dispatch_cond_batch_masked_single_f64(a, max_grid, stream);
+}
+
+hipError_t launch_cond_batch_soft(int is_f32, const int64_t *pool, int64_t rest, TableMeta *meta, int out_table,
+                                  const void *out_ptr, const int32_t *ev, const void *lam, int64_t n_rows, int max_grid,
+                                  hipStream_t stream) {
+    if (n_rows <= 0 || rest <= 0) return hipSuccess;
+    return is_f32 ? dispatch_cond_batch_soft_f32(pool, rest, meta, out_table, out_ptr, ev, lam, n_rows, max_grid, stream)
+                  : dispatch_cond_batch_soft_f64(pool, rest, meta, out_table, out_ptr, ev, lam, n_rows, max_grid, stream);
+}
+
+hipError_t launch_cond_batch_soft_single(int is_f32, const CondBatchSoftArgs &a, int max_grid, hipStream_t stream) {
+    if (a.n_rows <= 0) return hipSuccess;
+    return is_f32 ? dispatch_cond_batch_soft_single_f32(a, max_grid, stream)
+                  : dispatch_cond_batch_soft_single_f64(a, max_grid, stream);
 }
 
 hipError_t launch_counts(int is_f32, const CountsArgs &a, int max_grid, hipStream_t stream) {

@@ -731,22 +731,30 @@ static bool build_condb_desc(const BucketSpec &b, const std::vector<int> &cards,
     std::vector<std::pair<int64_t, int64_t>> rest, evs;     // (card, stride)
     std::vector<int64_t> ev_row;
     std::vector<std::pair<int64_t, int64_t>> masks;         // (row of ev, rest dim): a partial dim is never merged
-    bool masked = false, last_partial = false;
+    std::vector<std::pair<int64_t, int64_t>> softs;         // (first row of lam, rest dim): a soft dim is never merged either
+    bool masked = false, weighted = false, last_partial = false;
     for (int r : b.mask_rows) masked = masked || r >= 0;
+    for (int r : b.soft_rows) weighted = weighted || r >= 0;
     if (masked && b.mask_rows.size() != v.vars.size()) {
         if (msg) *msg = "gather step: one mask row per scope variable is needed";
         return false;
     }
+    if (weighted && b.soft_rows.size() != v.vars.size()) {
+        if (msg) *msg = "gather step: one likelihood row per scope variable is needed";
+        return false;
+    }
     for (int j = (int)v.vars.size() - 1; j >= 0; --j) {
         const int64_t c = cards[v.vars[j]], st = v.strides[j];
-        const bool partial = masked && b.mask_rows[j] >= 0 && b.cond_rows[j] < 0;
+        const bool soft = weighted && b.soft_rows[j] >= 0 && b.cond_rows[j] < 0;
+        const bool partial = soft || (masked && b.mask_rows[j] >= 0 && b.cond_rows[j] < 0);     // kept apart
         if (b.cond_rows[j] >= 0) {
             evs.push_back({c, st});
             ev_row.push_back(b.cond_rows[j]);
         } else if (!partial && !last_partial && !rest.empty() && rest.back().second * rest.back().first == st) {
             rest.back().first *= c;
         } else {
-            if (partial) masks.push_back({b.mask_rows[j], (int64_t)rest.size()});
+            if (soft) softs.push_back({b.soft_rows[j], (int64_t)rest.size()});
+            else if (partial) masks.push_back({b.mask_rows[j], (int64_t)rest.size()});
             rest.push_back({c, st});
             last_partial = partial;
         }
@@ -771,17 +779,25 @@ static bool build_condb_desc(const BucketSpec &b, const std::vector<int> &cards,
         pool.push_back(r.first);
         pool.push_back(r.second);
     }
-    if (masked) {                                           // the masked kernel's words (condbatch.cuh)
+    if (masked || weighted) {                               // the masked kernel's words (condbatch.cuh)
         pool.push_back((int64_t)masks.size());
         for (const auto &m : masks) {
             pool.push_back(m.first);
             pool.push_back(m.second);
         }
     }
+    if (weighted) {                                         // the weighted kernel's words
+        pool.push_back((int64_t)softs.size());
+        for (const auto &m : softs) {
+            pool.push_back(m.first);
+            pool.push_back(m.second);
+        }
+    }
     const int64_t rows = cards[b.out_vars.back()];
-    d.n_in = (int)std::min<size_t>(b.in.size(), 2);
+    d.n_in = (int)std::min<size_t>(b.in.size(), weighted ? 3 : 2);
     d.in_table[0] = v.table;
     d.in_table[1] = b.in.size() > 1 ? b.in[1].table : -1;
+    if (weighted) d.in_table[2] = b.in.size() > 2 ? b.in[2].table : -1;     // the likelihood table (-1: a single-op call)
     d.out_size = sat_mul(n_rest, rows);
     d.k = (int32_t)std::min<int64_t>(n_rest, INT32_MAX);
     d.n_tiles = rows;
@@ -2019,12 +2035,39 @@ std::vector<int> batch_mask_factors(const std::vector<int> &cards, const std::ve
     return mf;
 }
 
+std::vector<int> batch_lam_factors(const std::vector<int> &cards, const std::vector<View> &sources,
+                                   const std::vector<int> &ev_vars, const std::vector<char> &partial,
+                                   const std::vector<int> &soft) {
+    std::vector<int> lf(soft.size(), -1);
+    std::vector<char> hard(cards.size(), 0);
+    for (size_t i = 0; i < ev_vars.size(); ++i) hard[ev_vars[i]] = !(i < partial.size() && partial[i]);
+    for (size_t i = 0; i < soft.size(); ++i) {
+        bool best_hard = false;
+        double best_size = 0;
+        for (size_t f = 0; f < sources.size(); ++f) {
+            if (!contains(sources[f].vars, soft[i])) continue;
+            bool has_hard = false;
+            double size = 1;
+            for (int v : sources[f].vars) {
+                has_hard = has_hard || hard[v];
+                if (!hard[v]) size *= cards[v];
+            }
+            if (lf[i] < 0 || (has_hard && !best_hard) || (has_hard == best_hard && size < best_size)) {
+                lf[i] = (int)f;
+                best_hard = has_hard;
+                best_size = size;
+            }
+        }
+    }
+    return lf;
+}
+
 // level 0 of a batch plan: one gather step per source that mentions a hard
-// evidence variable or carries a partial one's mask (`placed`: per source, the
+// evidence variable or carries a partial one's mask or a soft one's weights (`placed`: per source, the
 // view that takes its place); ce: the model's cards, then the rows
 static bool gather_steps(PlanBuilder &B, VEPlan &p, const std::vector<int> &ce, const std::vector<View> &sources,
-                         const std::vector<int> &ev_vars, const std::vector<char> &partial, int64_t rows, int elem_bytes,
-                         std::vector<View> &placed, std::string *msg) {
+                         const std::vector<int> &ev_vars, const std::vector<char> &partial, const std::vector<int> &soft,
+                         int64_t rows, int elem_bytes, std::vector<View> &placed, std::string *msg) {
     const int nv = (int)ce.size() - 1, Bv = nv;
     std::vector<int> row_of(nv, -1);                        // hard evidence variables only
     bool any_partial = false;
@@ -2035,6 +2078,21 @@ static bool gather_steps(PlanBuilder &B, VEPlan &p, const std::vector<int> &ce, 
     }
     if (any_partial)
         p.batch_mask_factor = batch_mask_factors(std::vector<int>(ce.begin(), ce.begin() + nv), sources, ev_vars, partial);
+    std::vector<int> lam_row(soft.size(), 0);               // per soft variable: its first row of the likelihood table
+    if (!soft.empty()) {
+        p.batch_lam_factor = batch_lam_factors(std::vector<int>(ce.begin(), ce.begin() + nv), sources, ev_vars, partial, soft);
+        int64_t ws = 0;
+        for (size_t i = 0; i < soft.size(); ++i) {
+            if (p.batch_lam_factor[i] < 0) {
+                if (msg) *msg = "soft variable " + std::to_string(soft[i]) + " is in no factor: no table can carry its likelihoods";
+                return false;
+            }
+            lam_row[i] = (int)ws;
+            ws += ce[soft[i]];
+        }
+        p.batch_lam_table = B.new_raw(sat_mul(ws, rows));
+        B.level[p.batch_lam_table] = 0;
+    }
     for (size_t f = 0; f < sources.size(); ++f) {
         const View &s = sources[f];
         bool any = false;
@@ -2047,12 +2105,21 @@ static bool gather_steps(PlanBuilder &B, VEPlan &p, const std::vector<int> &ce, 
                     if (s.vars[j] == ev_vars[i]) mask_rows[j] = (int)i;
                 any = true;
             }
+        std::vector<int> soft_rows;
+        for (size_t i = 0; i < p.batch_lam_factor.size(); ++i)
+            if (p.batch_lam_factor[i] == (int)f) {
+                if (soft_rows.empty()) soft_rows.assign(s.vars.size(), -1);
+                for (size_t j = 0; j < s.vars.size(); ++j)
+                    if (s.vars[j] == soft[i]) soft_rows[j] = lam_row[i];
+                any = true;
+            }
         if (!any) {
             placed.push_back(s);
             continue;
         }
         if (p.batch_ev_table < 0) {
-            const int64_t bytes = sat_mul(sat_mul((int64_t)ev_vars.size(), rows), 4);
+            // (no evidence variable, soft ones only: one row, so that the table exists)
+            const int64_t bytes = sat_mul(sat_mul((int64_t)std::max<size_t>(ev_vars.size(), 1), rows), 4);
             p.batch_ev_table = B.new_raw((bytes + elem_bytes - 1) / elem_bytes);
             B.level[p.batch_ev_table] = 0;
         }
@@ -2063,6 +2130,12 @@ static bool gather_steps(PlanBuilder &B, VEPlan &p, const std::vector<int> &ce, 
         View evt;
         evt.table = p.batch_ev_table;
         g.in.push_back(evt);
+        if (!soft_rows.empty()) {
+            g.soft_rows = soft_rows;
+            View lt;
+            lt.table = p.batch_lam_table;
+            g.in.push_back(lt);
+        }
         for (int v : s.vars) {
             g.cond_rows.push_back(row_of[v]);
             if (row_of[v] < 0) g.out_vars.push_back(v);
@@ -2120,8 +2193,8 @@ struct BatchPlan {
         (bi >= 0 ? buckets[bi] : result).push_back(v);
     }
     bool gather(const std::vector<View> &sources, const std::vector<int> &ev_vars, const std::vector<char> &partial,
-                int elem_bytes, std::string *msg) {
-        if (!gather_steps(B, p, ce, sources, ev_vars, partial, ce.back(), elem_bytes, placed, msg)) return false;
+                int elem_bytes, std::string *msg, const std::vector<int> &soft = std::vector<int>()) {
+        if (!gather_steps(B, p, ce, sources, ev_vars, partial, soft, ce.back(), elem_bytes, placed, msg)) return false;
         for (const View &s : placed) pass(s, 0);
         return true;
     }
@@ -2204,12 +2277,13 @@ struct BucketTree {
 
 bool plan_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                 const std::vector<int> &ev_vars, int64_t rows, int target, int elem_bytes, VEPlan &out,
-                std::string *msg, const std::vector<char> &partial) {
+                std::string *msg, const std::vector<char> &partial,
+                 const std::vector<int> &soft) {
     out = VEPlan{};
     if (!batch_rows_ok(rows, msg)) return false;
     (void)target;                                           // kept: it is not in `order`, canon() lays it before B
     BatchPlan S(cards, sources, order, rows, out);
-    if (!S.gather(sources, ev_vars, partial, elem_bytes, msg)) return false;
+    if (!S.gather(sources, ev_vars, partial, elem_bytes, msg, soft)) return false;
     for (size_t i = 0; i < order.size(); ++i)
         if (!S.buckets[i].empty()) S.emit_bucket((int)i);
     S.emit_result();
@@ -2218,12 +2292,13 @@ bool plan_batch(const std::vector<int> &cards, const std::vector<View> &sources,
 }
 
 bool plan_mpe_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
-                    const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg, const std::vector<char> &partial) {
+                    const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg, const std::vector<char> &partial,
+                 const std::vector<int> &soft) {
     out = VEPlan{};
     VEPlan &p = out;
     if (!batch_rows_ok(rows, msg)) return false;
     BatchPlan S(cards, sources, order, rows, p);
-    if (!S.gather(sources, ev_vars, partial, elem_bytes, msg)) return false;
+    if (!S.gather(sources, ev_vars, partial, elem_bytes, msg, soft)) return false;
     std::vector<BucketSpec::DecodeRow> drows;
     for (int i = 0; i < (int)order.size(); ++i) {
         if (S.buckets[i].empty()) continue;   // a variable in no remaining factor: the assignment keeps 0
@@ -2277,7 +2352,8 @@ bool plan_mpe_batch(const std::vector<int> &cards, const std::vector<View> &sour
 
 bool plan_sample_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                        const std::vector<int> &ev_vars, int64_t rows, int64_t n_per_row, int elem_bytes, VEPlan &out,
-                       std::string *msg, const std::vector<char> &partial) {
+                       std::string *msg, const std::vector<char> &partial,
+                 const std::vector<int> &soft) {
     out = VEPlan{};
     VEPlan &p = out;
     if (!batch_rows_ok(rows, msg)) return false;
@@ -2286,7 +2362,7 @@ bool plan_sample_batch(const std::vector<int> &cards, const std::vector<View> &s
         return false;
     }
     BatchPlan S(cards, sources, order, rows, p);
-    if (!S.gather(sources, ev_vars, partial, elem_bytes, msg)) return false;
+    if (!S.gather(sources, ev_vars, partial, elem_bytes, msg, soft)) return false;
     std::vector<BucketSpec::SampleRow> rws(order.size());
     for (int i = 0; i < (int)order.size(); ++i) {
         if (cards[order[i]] > kMaxOutCard) {
@@ -2353,9 +2429,9 @@ struct BatchBucketTree {
         return S.B.view(S.B.reduce_keep(in, keep));
     }
     bool build(const std::vector<View> &sources, const std::vector<int> &ev_vars, const std::vector<char> &partial,
-               int elem_bytes, std::string *msg) {
+               int elem_bytes, std::string *msg, const std::vector<int> &soft = std::vector<int>()) {
         PlanBuilder &B = S.B;
-        if (!S.gather(sources, ev_vars, partial, elem_bytes, msg)) return false;
+        if (!S.gather(sources, ev_vars, partial, elem_bytes, msg, soft)) return false;
         bucket_of.assign(S.placed.size(), -1);
         for (size_t i = 0; i < ev_vars.size(); ++i)         // a partial variable is no evidence variable to the tree
             if (!(i < partial.size() && partial[i])) row_of[ev_vars[i]] = (int)i;
@@ -2380,12 +2456,13 @@ struct BatchBucketTree {
 }  // namespace
 
 bool plan_counts(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
-                 const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg, const std::vector<char> &partial) {
+                 const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg, const std::vector<char> &partial,
+                 const std::vector<int> &soft) {
     out = VEPlan{};
     VEPlan &p = out;
     if (!batch_rows_ok(rows, msg)) return false;
     BatchBucketTree W(cards, sources, order, rows, p);
-    if (!W.build(sources, ev_vars, partial, elem_bytes, msg)) return false;
+    if (!W.build(sources, ev_vars, partial, elem_bytes, msg, soft)) return false;
     BatchPlan &S = W.S;
     BucketTree &T = W.T;
     PlanBuilder &B = S.B;
@@ -2457,7 +2534,8 @@ bool plan_counts(const std::vector<int> &cards, const std::vector<View> &sources
 
 bool plan_marginals_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                           const std::vector<int> &ev_vars, int64_t rows, const std::vector<int> &targets, int elem_bytes,
-                          VEPlan &out, std::string *msg, const std::vector<char> &partial) {
+                          VEPlan &out, std::string *msg, const std::vector<char> &partial,
+                 const std::vector<int> &soft) {
     out = VEPlan{};
     VEPlan &p = out;
     if (!batch_rows_ok(rows, msg)) return false;
@@ -2472,7 +2550,7 @@ bool plan_marginals_batch(const std::vector<int> &cards, const std::vector<View>
         }
     }
     BatchBucketTree W(cards, sources, order, rows, p);
-    if (!W.build(sources, ev_vars, partial, elem_bytes, msg)) return false;
+    if (!W.build(sources, ev_vars, partial, elem_bytes, msg, soft)) return false;
     BatchPlan &S = W.S;
     BucketTree &T = W.T;
     PlanBuilder &B = S.B;
@@ -3898,6 +3976,8 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
             it.key = kCondBatchKey;
             for (int r : b.mask_rows)
                 if (r >= 0) it.key = kCondBatchMaskKey;
+            for (int r : b.soft_rows)
+                if (r >= 0) it.key = kCondBatchSoftKey;
             return;
         }
         if (b.counts) {                      // an accumulate step of a counts plan: the executor's, its words in the pool
@@ -3976,7 +4056,7 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
         int64_t vb = 0;
         for (; i < ord.size() && items[ord[i]].level == g.level && items[ord[i]].key == g.variant &&
                items[ord[i]].b->lane == g.lane &&
-               !((g.variant == kCondBatchKey || g.variant == kCondBatchMaskKey || g.variant == kCountsKey) && (int)i > g.begin);   // one launch per gather / accumulate step
+               !((g.variant == kCondBatchKey || g.variant == kCondBatchMaskKey || g.variant == kCondBatchSoftKey || g.variant == kCountsKey) && (int)i > g.begin);   // one launch per gather / accumulate step
              ++i) {
             const Item &it = items[ord[i]];
             BucketDesc &d = s.descs[i];

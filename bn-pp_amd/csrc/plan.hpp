@@ -177,6 +177,9 @@ struct BucketSpec {
     // in[0].vars[j] whose mask this step carries (cond_rows[j] is then -1 and the variable stays in out_vars);
     // empty, or all -1: an unmasked step
     std::vector<int> mask_rows;
+    // soft evidence: soft_rows[j] >= 0 names the first row of the likelihood table (in[2]) of a SOFT variable
+    // in[0].vars[j] whose weights this step carries (the variable stays in out_vars); empty, or all -1: none
+    std::vector<int> soft_rows;
     // an accumulate step of a counts plan (plan_counts, counts.cuh): in[0] is
     // the belief of one factor over (its non-evidence variables, B) -- B the
     // fastest dim, absent when no evidence reaches the belief -- and the other
@@ -253,6 +256,8 @@ constexpr int kSampleBatchPoolHead = 4;   // words before the rows of a batched 
 constexpr int kMargRowsKey = kXchgKeyBase + 28672;
 // ... of a masked gather step (BucketSpec::cond_batch with mask_rows: partial evidence variables): the executor's
 constexpr int kCondBatchMaskKey = kXchgKeyBase + 32768;
+// ... of a weighted gather step (BucketSpec::cond_batch with soft_rows: soft variables, masks beside them): the executor's
+constexpr int kCondBatchSoftKey = kXchgKeyBase + 36864;
 constexpr int kMargRowsPoolHead = 4;      // words before the column blocks of an emit step's pool
 constexpr int kMargRowsColWords = 5;      // words per column block
 constexpr int kCountsMaxDims = 32;  // evidence variables, and other variables, in one factor scope of an accumulate step
@@ -316,6 +321,8 @@ struct VEPlan {
     int n_draw_b = 0, n_draw_nob = 0;
     int batch_ev_table = -1;            // plan_batch: the evidence table (-1: no gather step)
     std::vector<int> batch_mask_factor; // per evidence variable: the factor whose gather step carries its mask (-1: none)
+    int batch_lam_table = -1;           // soft evidence: the likelihood table T[Ws][rows] (-1: no soft variable)
+    std::vector<int> batch_lam_factor;  // per soft variable: the factor whose gather step carries its weights
     // plan_counts: the per-launch weights (double[rows]) and the first
     // accumulate step's scratch (3 x 8 bytes per row; one per step), raw tables; per factor the
     // variables of its belief table (B = cards.size() last when carried);
@@ -368,6 +375,14 @@ bool plan_sample(const std::vector<int> &cards, const std::vector<View> &sources
 // gather step that holds it carries its mask (BucketSpec::mask_rows), chosen
 // by batch_mask_factors.  Empty `partial`: none.
 //
+// Soft evidence (all batched planners): `soft` lists the SOFT variables -- row b
+// carries a likelihood per value of each.  A soft variable is no evidence
+// variable: it is an ordinary variable of `order`, and exactly one gather step
+// that holds it multiplies its weights in (BucketSpec::soft_rows), chosen by
+// batch_lam_factors.  The weights of a launch are a raw table T[Ws][rows]
+// (VEPlan::batch_lam_table), variable-major in the order of `soft`, Ws the sum
+// of the soft cards.  Empty `soft`: none, and nothing of the plan changes.
+//
 // Batched evidence: one plan for `rows` evidence assignments over the evidence
 // variables ev_vars.  `sources` are the NATURAL views of the model's factors.
 // A virtual variable B (id cards.size(), card = rows) stands for "which row":
@@ -387,13 +402,18 @@ bool plan_sample(const std::vector<int> &cards, const std::vector<View> &sources
 // than kCondMaxRest runs of non-evidence variables between evidence variables.
 bool plan_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                 const std::vector<int> &ev_vars, int64_t rows, int target, int elem_bytes, VEPlan &out,
-                std::string *msg, const std::vector<char> &partial = std::vector<char>());
+                std::string *msg, const std::vector<char> &partial = std::vector<char>(),
+                const std::vector<int> &soft = std::vector<int>());
 
 // The factor that carries the mask of each evidence variable (-1: hard, or in no factor): 1. a factor that
 // holds a hard evidence variable (it has a gather step anyway); 2. among those, else among all factors that
 // hold it, the fewest entries after conditioning on the hard variables; 3. the lowest factor index
 std::vector<int> batch_mask_factors(const std::vector<int> &cards, const std::vector<View> &sources,
                                     const std::vector<int> &ev_vars, const std::vector<char> &partial);
+// The factor that carries the weights of each soft variable (-1: in no factor), by the same rule
+std::vector<int> batch_lam_factors(const std::vector<int> &cards, const std::vector<View> &sources,
+                                   const std::vector<int> &ev_vars, const std::vector<char> &partial,
+                                   const std::vector<int> &soft);
 
 // Batched MPE: plan_batch's gather steps (level 0), evidence table and cards_ext
 // = cards + {rows}, then plan_mpe's elimination over them: every eliminating
@@ -405,7 +425,8 @@ std::vector<int> batch_mask_factors(const std::vector<int> &cards, const std::ve
 // when no evidence reaches it; x = uint8[n_vars][rows]}.  `order` covers every
 // non-evidence variable.  Returns false (msg) as plan_batch and plan_mpe do.
 bool plan_mpe_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
-                    const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg, const std::vector<char> &partial = std::vector<char>());
+                    const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg, const std::vector<char> &partial = std::vector<char>(),
+                 const std::vector<int> &soft = std::vector<int>());
 
 // Batched sampling: plan_batch's gather steps (level 0), evidence table and
 // cards_ext = cards + {rows}, then plan_sample's loop over the placed views: no
@@ -420,7 +441,8 @@ bool plan_mpe_batch(const std::vector<int> &cards, const std::vector<View> &sour
 // false (msg) as plan_batch and plan_sample do.
 bool plan_sample_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                        const std::vector<int> &ev_vars, int64_t rows, int64_t n_per_row, int elem_bytes, VEPlan &out,
-                       std::string *msg, const std::vector<char> &partial = std::vector<char>());
+                       std::string *msg, const std::vector<char> &partial = std::vector<char>(),
+                 const std::vector<int> &soft = std::vector<int>());
 
 // Expected sufficient statistics: a batched bucket tree.  plan_batch's gather
 // steps (level 0) and forward pass -- the same buckets in the same order, the
@@ -439,7 +461,8 @@ bool plan_sample_batch(const std::vector<int> &cards, const std::vector<View> &s
 // kCountsMaxDims evidence (or other) variables, or when `order` leaves out a
 // non-evidence variable of a factor.
 bool plan_counts(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
-                 const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg, const std::vector<char> &partial = std::vector<char>());
+                 const std::vector<int> &ev_vars, int64_t rows, int elem_bytes, VEPlan &out, std::string *msg, const std::vector<char> &partial = std::vector<char>(),
+                 const std::vector<int> &soft = std::vector<int>());
 
 // Batched marginals: plan_counts's batched bucket tree -- the same gather
 // steps, forward pass (plan_batch's, so the first result is its table over (B))
@@ -457,7 +480,8 @@ bool plan_counts(const std::vector<int> &cards, const std::vector<View> &sources
 // false (msg) as plan_counts does, or on a target out of range or listed twice.
 bool plan_marginals_batch(const std::vector<int> &cards, const std::vector<View> &sources, const std::vector<int> &order,
                           const std::vector<int> &ev_vars, int64_t rows, const std::vector<int> &targets, int elem_bytes,
-                          VEPlan &out, std::string *msg, const std::vector<char> &partial = std::vector<char>());
+                          VEPlan &out, std::string *msg, const std::vector<char> &partial = std::vector<char>(),
+                 const std::vector<int> &soft = std::vector<int>());
 
 // All marginals of `targets` from one two-pass bucket tree over `order`
 // (Shafer-Shenoy on the VE bucket tree; replaces the N independent VEs of

@@ -119,6 +119,20 @@ struct CondBatchMaskedArgs {
     int64_t n_rows;
 };
 hipError_t launch_cond_batch_masked_single(int is_f32, const CondBatchMaskedArgs &a, int max_grid, hipStream_t stream);
+// the weighted forms (soft evidence: soft variables among the rest dims, masks beside them); lam is T[Ws][n_rows]; the
+// pool continues after the masked words with n_s and n_s x (first row of lam, rest dim)
+hipError_t launch_cond_batch_soft(int is_f32, const int64_t *pool, int64_t rest, TableMeta *meta, int out_table,
+                                  const void *out_ptr, const int32_t *ev, const void *lam, int64_t n_rows, int max_grid,
+                                  hipStream_t stream);
+struct CondBatchSoftArgs {
+    int64_t pool[4 + 3 * kCondMaxEv + 2 * kCondMaxRest + 1 + 2 * kCondMaxRest + 1 + 2 * kCondMaxRest];
+    const void *src;
+    void *out;
+    const int32_t *ev;
+    const void *lam;
+    int64_t n_rows;
+};
+hipError_t launch_cond_batch_soft_single(int is_f32, const CondBatchSoftArgs &a, int max_grid, hipStream_t stream);
 // expected counts (counts.cuh): one factor's belief T over (rest, b) folded
 // into its accumulator, normalised row by row (include/bnpp.h,
 // bnpp_bucket_counts, states the arithmetic).  Everything by value in the

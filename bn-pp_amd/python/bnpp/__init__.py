@@ -139,6 +139,32 @@ _SIGS = {
                                           _IP, _IP]),
     "bnpp_condition_batch_mv": (_I, [_P, _P, _I, _I, _IP, _P, _I, _IP, _I, _IP, _UBP, C.c_int64, _P, _P]),
     "bnpp_evidence_load_batch_mv": (_I, [C.c_char_p, _I, C.c_int64, _IP, _IP, _LP, _IP, _UBP]),
+    # soft evidence: the _sv siblings take (n_soft, soft_vars, lik) after partial; the plan entries also return
+    # lam_factor[n_soft] last
+    "bnpp_partition_batch_sv": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _UBP, _I, _IP, _DP, _I, _IP, _I, _I, C.c_int64, _DP,
+                                     _DP, _DP]),
+    "bnpp_posterior_batch_sv": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _UBP, _I, _IP, _DP, _I, _I, _I, C.c_int64, _DP, _DP]),
+    "bnpp_plan_batch_sv": (_I, [_P, _I, _IP, _UBP, _I, _IP, _DP, _I, _IP, _I, _I, _I, C.c_int64, _DP, _I, _LP, _I, _IP, _IP,
+                                _IP, _IP, _IP]),
+    "bnpp_mpe_batch_sv": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _UBP, _I, _IP, _DP, _I, _IP, _I, _I, C.c_int64, _DP, _IP,
+                               _DP]),
+    "bnpp_plan_mpe_batch_sv": (_I, [_P, _I, _IP, _UBP, _I, _IP, _DP, _I, _IP, _I, _I, C.c_int64, _DP, _I, _LP, _I, _IP, _IP,
+                                    _IP]),
+    "bnpp_sample_batch_sv": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _UBP, _I, _IP, _DP, _I, _IP, _I, _I, C.c_int64,
+                                  C.c_int64, C.c_int64, C.c_int64, C.c_uint64, _P, _DP, _LP, _DP]),
+    "bnpp_plan_sample_batch_sv": (_I, [_P, _I, _IP, _UBP, _I, _IP, _DP, _I, _IP, _I, _I, C.c_int64, C.c_int64, _DP, _I, _LP,
+                                       _I, _IP, _IP, _IP]),
+    "bnpp_expected_counts_sv": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _UBP, _I, _IP, _DP, _DP, _I, _IP, _I, _I, C.c_int64,
+                                     _DP, _DP, _LP, _DP]),
+    "bnpp_plan_counts_sv": (_I, [_P, _I, _IP, _UBP, _I, _IP, _DP, _I, _IP, _I, _I, C.c_int64, _DP, _I, _LP, _I, _IP, _IP,
+                                 _IP, _I, _IP, _IP, _IP, _IP]),
+    "bnpp_marginals_batch_sv": (_I, [_P, _P, _I, _IP, C.c_int64, _IP, _UBP, _I, _IP, _DP, _I, _IP, _I, _I, _IP, _I,
+                                     C.c_int64, _DP, _DP, _DP]),
+    "bnpp_plan_marginals_batch_sv": (_I, [_P, _I, _IP, _UBP, _I, _IP, _DP, _I, _IP, _I, _I, _IP, _I, C.c_int64, _DP, _I, _LP,
+                                          _I, _IP, _IP, _IP, _IP]),
+    "bnpp_condition_batch_sv": (_I, [_P, _P, _I, _I, _IP, _P, _I, _IP, _I, _IP, _UBP, _I, _IP, _P, C.c_int64, _P, _P]),
+    "bnpp_likelihood_load": (_I, [_P, C.c_char_p, _I, C.c_int64, _IP, _IP, _LP, _DP]),
+    "bnpp_batch_job_key": (_I, [_P, _I, _IP, _UBP, _I, _IP, _I, C.c_int64, C.POINTER(C.c_uint64)]),
     "bnpp_job_create": (_I, [_P, _P, _I, _I, _IP, _IP, _I, _IP, _I, _I, _IP, _I, C.POINTER(_P)]),
     "bnpp_job_stats": (_I, [_P, _DP, _I]),
     "bnpp_job_launch": (_I, [_P, _P]),
@@ -570,6 +596,66 @@ def _mv(name: str, pf):
     return getattr(_lib, name + "_mv"), name + "_mv", (pf,)
 
 
+COND_BATCH_SOFT_KEY = (1 << 24) + 36864   # the launch-group key of a weighted gather step (plan.hpp kCondBatchSoftKey)
+
+
+def _soft_vars(soft):
+    """The soft variable ids of a `soft` argument: (soft_vars, lik), or for a plan function the ids alone."""
+    if isinstance(soft, (tuple, list)) and len(soft) == 2 and hasattr(soft[0], "__len__"):   # (ids, lik), as the run calls
+        soft = soft[0]
+    return [int(v) for v in soft]
+
+
+def _soft_args(model: "Model", soft, n_rows: int):
+    """soft = (soft_vars, lik) as the _sv run entries take it -> (n_soft, the ids as c ints, the (n, Ws) float64
+    array (keep it alive), its pointer).  lik: an (n, Ws) array, Ws the sum of the soft cards with the variables'
+    blocks in the listed order (what marginals_batch returns), or a list of one (n, card) array per variable."""
+    import numpy as np
+    if not (isinstance(soft, (tuple, list)) and len(soft) == 2):
+        raise ValueError("soft must be (soft_vars, lik)")
+    ids = [int(v) for v in soft[0]]
+    lik = soft[1]
+    cards = [model.cards[v] if 0 <= v < model.n_vars else None for v in ids]
+    if isinstance(lik, (list, tuple)) and len(lik) == len(ids) and all(getattr(a, "ndim", 0) == 2 for a in lik):
+        for v, k, a in zip(ids, cards, lik):
+            if k is not None and a.shape != (n_rows, k):
+                raise ValueError("the likelihoods of soft variable %d must have shape (%d, %d), not %s"
+                                 % (v, n_rows, k, tuple(a.shape)))
+        lik = np.concatenate([np.asarray(a, dtype=np.float64) for a in lik], axis=1) if ids else np.zeros((n_rows, 0))
+    a = np.ascontiguousarray(lik, dtype=np.float64)
+    if None not in cards:
+        ws = sum(cards)
+        if a.ndim != 2 or a.shape != (n_rows, ws):
+            raise ValueError("lik must have shape (%d, %d): one row per evidence row, the sum of the soft cards wide; "
+                             "got %s" % (n_rows, ws, tuple(a.shape)))
+    elif a.ndim != 2 or a.shape[0] != n_rows:      # a bad id: the library names it
+        raise ValueError("lik must have one row per evidence row")
+    return len(ids), _ints(ids) if ids else (C.c_int * 1)(), a, a.ctypes.data_as(_DP)
+
+
+def _sv(name: str, pf, soft, model=None, n_rows=None):
+    """_mv, or with `soft` the _sv entry point -> (fn, name, the arguments to splice in after the evidence, what
+    to keep alive).  n_rows None: a plan entry (ids only, no likelihoods)."""
+    if soft is None:
+        return _mv(name, pf) + (None,)
+    if n_rows is None:
+        ids = _soft_vars(soft)
+        return getattr(_lib, name + "_sv"), name + "_sv", (pf, len(ids), _ints(ids) if ids else (C.c_int * 1)(), None), None
+    ns, sv, keep, lp = _soft_args(model, soft, n_rows)
+    return getattr(_lib, name + "_sv"), name + "_sv", (pf, ns, sv, lp), keep
+
+
+def _plan_tail(pf, n_ev, soft, tail=lambda: ()):
+    """_mask_tail, and with `soft` also lam_factor -> (tail, what to append to the plan function's result)."""
+    if soft is None:
+        t, mask = _mask_tail(pf, n_ev, tail)
+        return t, (lambda: (mask(),) if pf is not None else ())
+    n_soft = len(_soft_vars(soft))
+    mf, lf = (C.c_int * max(n_ev, 1))(), (C.c_int * max(n_soft, 1))()
+    return ((lambda: (*tail(), mf, lf)),
+            (lambda: (([mf[j] for j in range(n_ev)],) if pf is not None else ()) + ([lf[j] for j in range(n_soft)],)))
+
+
 def _mask_tail(pf, n_ev, tail=lambda: ()):
     """The tail of a plan entry with mask_factor appended for the _mv entries; the list that reads it back."""
     mf = (C.c_int * max(n_ev, 1))()
@@ -633,8 +719,40 @@ def load_evidence_batch(path: str, missing: bool = False):
     return [vs[i] for i in range(n_ev.value)], rows
 
 
+def load_likelihoods(model: Model, path: str):
+    """A likelihood file (bnpp_likelihood_load; synth.write_likelihoods writes one): n_soft, the ids, n_rows, then
+    per row the Ws likelihoods -> (soft_vars, lik as an (n_rows, Ws) float64 array): what to pass as `soft`."""
+    import numpy as np
+    ns, nr = C.c_int(), C.c_int64()
+    rc = _lib.bnpp_likelihood_load(model.handle, path.encode(), 0, 0, C.byref(ns), None, C.byref(nr), None)
+    if rc != OK and not (rc == ERR_INVALID and (ns.value > 0 or nr.value > 0)):
+        raise BnppError(rc, "bnpp_likelihood_load")
+    vs = (C.c_int * max(ns.value, 1))()
+    _lib.bnpp_likelihood_load(model.handle, path.encode(), ns.value, 0, C.byref(ns), vs, C.byref(nr), None)
+    ids = [vs[i] for i in range(ns.value)]
+    ws = sum(model.cards[v] for v in ids)
+    lik = np.zeros((nr.value, ws))
+    _check(_lib.bnpp_likelihood_load(model.handle, path.encode(), ns.value, nr.value * ws, C.byref(ns), vs, C.byref(nr),
+                                     lik.ctypes.data_as(_DP)), "bnpp_likelihood_load")
+    return ids, lik
+
+
+def batch_job_key(model: Model, ev_vars: Sequence[int], partial=None, soft=None, dtype: int = F64,
+                  rows_per_launch: int = 0) -> int:
+    """The job cache key of a partition_batch call of this shape (bnpp_batch_job_key): it depends on the variable
+    lists, never on values, and a call without `soft` keeps the key it had before soft evidence existed."""
+    ev_vars = [int(v) for v in ev_vars]
+    ids = _soft_vars(soft) if soft is not None else []
+    key = C.c_uint64()
+    _check(_lib.bnpp_batch_job_key(model.handle, len(ev_vars), _ints(ev_vars) if ev_vars else None,
+                                   _partial_flags(ev_vars, partial), len(ids), _ints(ids) if ids else None, dtype,
+                                   int(rows_per_launch), C.byref(key)), "bnpp_batch_job_key")
+    return key.value
+
+
 def plan_batch(model: Model, ev_vars: Sequence[int], target: Optional[int] = None, heuristic: str = "mf",
-               dtype: int = F64, rows_per_launch: int = 0, order: Optional[Sequence[int]] = None, partial=None):
+               dtype: int = F64, rows_per_launch: int = 0, order: Optional[Sequence[int]] = None, partial=None,
+               soft=None):
     """partial (here and in every batched call and plan function): None, or the
     evidence variables that may be MISSING in a row -- a sequence of ids, or
     "auto" in the run calls for the columns that hold a MISSING (include/bnpp.h,
@@ -650,17 +768,18 @@ def plan_batch(model: Model, ev_vars: Sequence[int], target: Optional[int] = Non
     nrs = C.c_int()
     rs = (C.c_int * 2)()
     t = -1 if target is None else int(target)
-    fn, name, pa = _mv("bnpp_plan_batch", _partial_flags(ev_vars, partial))
-    tail, mask = _mask_tail(pa[0] if pa else None, len(ev_vars), lambda: (rs, C.byref(nrs)))
+    fn, name, pa, _ = _sv("bnpp_plan_batch", _partial_flags(ev_vars, partial), soft)
+    tail, extra = _plan_tail(pa[0] if pa else None, len(ev_vars), soft, lambda: (rs, C.byref(nrs)))
     st, groups = _plan_call(fn, name, PLAN_BATCH_STATS,
                             (model.handle, len(ev_vars), _ints(ev_vars), *pa, *_order_args(order, heuristic), t, dtype,
                              int(rows_per_launch)), tail)
     res = st, groups, [rs[i] for i in range(min(nrs.value, 2))]
-    return res + (mask(),) if pa else res
+    return res + extra()
 
 
 def partition_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, heuristic: str = "mf", dtype: int = F64,
-                    rows_per_launch: int = 0, order: Optional[Sequence[int]] = None, partial=None):
+                    rows_per_launch: int = 0, order: Optional[Sequence[int]] = None, partial=None,
+                    soft=None):
     """log10 Z and Z of every evidence row from one plan (bnpp_partition_batch)
     -> (log10_z, z, uptime_ms), numpy float64 arrays of length n.  rows: an
     (n, len(ev_vars)) integer array, rows[r][j] the value of ev_vars[j]."""
@@ -669,15 +788,15 @@ def partition_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, he
     h, oa, no = _order_args(order, heuristic)
     lz, z = np.zeros(max(n, 1)), np.zeros(max(n, 1))
     up = C.c_double()
-    fn, name, pa = _mv("bnpp_partition_batch", _partial_flags(ev_vars, partial, keep))
+    fn, name, pa, keep_lik = _sv("bnpp_partition_batch", _partial_flags(ev_vars, partial, keep), soft, model, n)
     _check(fn(_h(ctx), model.handle, ne, ev_v, n, ev_x, *pa, h, oa, no, dtype, int(rows_per_launch),
               lz.ctypes.data_as(_DP), z.ctypes.data_as(_DP), C.byref(up)), name)
-    del keep
+    del keep, keep_lik
     return lz[:n], z[:n], up.value
 
 
 def posterior_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, target: int, heuristic: str = "mf",
-                    dtype: int = F64, rows_per_launch: int = 0, partial=None):
+                    dtype: int = F64, rows_per_launch: int = 0, partial=None, soft=None):
     """P(target | evidence row) for every row from one plan (bnpp_posterior_batch)
     -> (an (n, card(target)) numpy float64 array, uptime_ms)."""
     import numpy as np
@@ -686,10 +805,10 @@ def posterior_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, ta
     k = model.cards[t] if 0 <= t < model.n_vars else 1
     out = np.zeros((max(n, 1), max(k, 1)))
     up = C.c_double()
-    fn, name, pa = _mv("bnpp_posterior_batch", _partial_flags(ev_vars, partial, keep))
+    fn, name, pa, keep_lik = _sv("bnpp_posterior_batch", _partial_flags(ev_vars, partial, keep), soft, model, n)
     _check(fn(_h(ctx), model.handle, ne, ev_v, n, ev_x, *pa, HEURISTICS[heuristic], t, dtype,
               int(rows_per_launch), out.ctypes.data_as(_DP), C.byref(up)), name)
-    del keep
+    del keep, keep_lik
     return out[:n, :k], up.value
 
 
@@ -699,23 +818,24 @@ PLAN_MPE_BATCH_STATS = PLAN_BATCH_STATS + ("arg_bytes", "max_buckets", "arg_tabl
 
 
 def plan_mpe_batch(model: Model, ev_vars: Sequence[int], heuristic: str = "mf", dtype: int = F64,
-                   rows_per_launch: int = 0, order: Optional[Sequence[int]] = None, partial=None):
+                   rows_per_launch: int = 0, order: Optional[Sequence[int]] = None, partial=None,
+                   soft=None):
     """Host-only planning of mpe_batch (bnpp_plan_mpe_batch) -> (stats, groups):
     stats a dict of PLAN_MPE_BATCH_STATS (arg_bytes = arg_entries_per_row *
     rows_per_launch + arg_entries_no_b), groups one dict of PLAN_GROUP_FIELDS per
     launch group: the gather steps (level 0, COND_BATCH_KEY), max and product
     buckets, and the traceback step last (MPE_DECODE_BATCH_KEY)."""
     ev_vars = [int(v) for v in ev_vars]
-    fn, name, pa = _mv("bnpp_plan_mpe_batch", _partial_flags(ev_vars, partial))
-    tail, mask = _mask_tail(pa[0] if pa else None, len(ev_vars))
+    fn, name, pa, _ = _sv("bnpp_plan_mpe_batch", _partial_flags(ev_vars, partial), soft)
+    tail, extra = _plan_tail(pa[0] if pa else None, len(ev_vars), soft)
     res = _plan_call(fn, name, PLAN_MPE_BATCH_STATS,
                      (model.handle, len(ev_vars), _ints(ev_vars), *pa, *_order_args(order, heuristic), dtype,
                       int(rows_per_launch)), tail)
-    return res + (mask(),) if pa else res
+    return res + extra()
 
 
 def mpe_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, heuristic: str = "mf", dtype: int = F64,
-              order: Optional[Sequence[int]] = None, rows_per_launch: int = 0, partial=None):
+              order: Optional[Sequence[int]] = None, rows_per_launch: int = 0, partial=None, soft=None):
     """The most probable completion of every evidence row from one plan
     (bnpp_mpe_batch) -> (log10_value float64[n], assignment int32 (n, n_vars),
     uptime_ms).  rows: an (n, len(ev_vars)) integer array, rows[r][j] the value
@@ -726,10 +846,10 @@ def mpe_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, heuristi
     lv = np.zeros(max(n, 1))
     x = np.zeros((max(n, 1), max(model.n_vars, 1)), dtype=np.intc)
     up = C.c_double()
-    fn, name, pa = _mv("bnpp_mpe_batch", _partial_flags(ev_vars, partial, keep))
+    fn, name, pa, keep_lik = _sv("bnpp_mpe_batch", _partial_flags(ev_vars, partial, keep), soft, model, n)
     _check(fn(_h(ctx), model.handle, ne, ev_v, n, ev_x, *pa, h, oa, no, dtype, int(rows_per_launch),
               lv.ctypes.data_as(_DP), x.ctypes.data_as(_IP), C.byref(up)), name)
-    del keep
+    del keep, keep_lik
     return lv[:n], x[:n, :model.n_vars].astype(np.int32, copy=False), up.value
 
 
@@ -738,7 +858,8 @@ PLAN_SAMPLE_BATCH_STATS = PLAN_BATCH_STATS + ("n_per_row", "state_bytes", "draw_
 
 
 def plan_sample_batch(model: Model, ev_vars: Sequence[int], n_per_row: int = 1, heuristic: str = "mf", dtype: int = F64,
-                      rows_per_launch: int = 0, order: Optional[Sequence[int]] = None, partial=None):
+                      rows_per_launch: int = 0, order: Optional[Sequence[int]] = None, partial=None,
+                      soft=None):
     """Host-only planning of sample_batch (bnpp_plan_sample_batch) -> (stats,
     groups): stats a dict of PLAN_SAMPLE_BATCH_STATS (state_bytes = n_vars *
     rows_per_launch * n_per_row; draw_rows = draw_rows_b + draw_rows_no_b, with
@@ -747,17 +868,17 @@ def plan_sample_batch(model: Model, ev_vars: Sequence[int], n_per_row: int = 1, 
     COND_BATCH_KEY), sum and product buckets, and the draw step last
     (SAMPLE_BATCH_KEY)."""
     ev_vars = [int(v) for v in ev_vars]
-    fn, name, pa = _mv("bnpp_plan_sample_batch", _partial_flags(ev_vars, partial))
-    tail, mask = _mask_tail(pa[0] if pa else None, len(ev_vars))
+    fn, name, pa, _ = _sv("bnpp_plan_sample_batch", _partial_flags(ev_vars, partial), soft)
+    tail, extra = _plan_tail(pa[0] if pa else None, len(ev_vars), soft)
     res = _plan_call(fn, name, PLAN_SAMPLE_BATCH_STATS,
                      (model.handle, len(ev_vars), _ints(ev_vars), *pa, *_order_args(order, heuristic), dtype,
                       int(rows_per_launch), int(n_per_row)), tail)
-    return res + (mask(),) if pa else res
+    return res + extra()
 
 
 def sample_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, n_per_row: int, seed: int = 0,
                  first_sample: int = 0, row_stride: Optional[int] = None, heuristic: str = "mf", dtype: int = F64,
-                 order: Optional[Sequence[int]] = None, rows_per_launch: int = 0, partial=None):
+                 order: Optional[Sequence[int]] = None, rows_per_launch: int = 0, partial=None, soft=None):
     """n_per_row exact joint samples of P(x | evidence row) for every evidence
     row from one plan (bnpp_sample_batch) -> (samples uint8 (n, n_per_row,
     n_vars), log10_z float64[n], n_degenerate int64[n]).  rows: an (n,
@@ -774,11 +895,11 @@ def sample_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, n_per
     lz = np.zeros(max(n, 1))
     deg = np.zeros(max(n, 1), dtype=np.int64)
     up = C.c_double()
-    fn, name, pa = _mv("bnpp_sample_batch", _partial_flags(ev_vars, partial, keep))
+    fn, name, pa, keep_lik = _sv("bnpp_sample_batch", _partial_flags(ev_vars, partial, keep), soft, model, n)
     _check(fn(_h(ctx), model.handle, ne, ev_v, n, ev_x, *pa, h, oa, no, dtype, int(rows_per_launch), k,
               int(first_sample), stride, int(seed) & 0xFFFFFFFFFFFFFFFF, _P(out.ctypes.data),
               lz.ctypes.data_as(_DP), deg.ctypes.data_as(_LP), C.byref(up)), name)
-    del keep
+    del keep, keep_lik
     return out[:n, :k, :model.n_vars], lz[:n], deg[:n]
 
 
@@ -787,7 +908,8 @@ PLAN_COUNTS_STATS = PLAN_BATCH_STATS + ("count_steps", "forward_levels")
 
 
 def plan_counts(model: Model, ev_vars: Sequence[int], heuristic: str = "mf", dtype: int = F64,
-                rows_per_launch: int = 0, order: Optional[Sequence[int]] = None, partial=None):
+                rows_per_launch: int = 0, order: Optional[Sequence[int]] = None, partial=None,
+                soft=None):
     """Host-only planning of expected_counts (bnpp_plan_counts) -> (stats,
     groups, beliefs, no_b_elim): stats a dict of PLAN_COUNTS_STATS, groups one
     dict of PLAN_GROUP_FIELDS per launch group (the accumulate steps: key
@@ -804,18 +926,19 @@ def plan_counts(model: Model, ev_vars: Sequence[int], heuristic: str = "mf", dty
         bvs.append((C.c_int * max(nb.value, 1))())
         return off, bvs[-1], nb.value, C.byref(nb), C.byref(flag)
 
-    fn, name, pa = _mv("bnpp_plan_counts", _partial_flags(ev_vars, partial))
-    tail, mask = _mask_tail(pa[0] if pa else None, len(ev_vars), beliefs)
+    fn, name, pa, _ = _sv("bnpp_plan_counts", _partial_flags(ev_vars, partial), soft)
+    tail, extra = _plan_tail(pa[0] if pa else None, len(ev_vars), soft, beliefs)
     st, groups = _plan_call(fn, name, PLAN_COUNTS_STATS,
                             (model.handle, len(ev_vars), _ints(ev_vars), *pa, *_order_args(order, heuristic), dtype,
                              int(rows_per_launch)), tail)
     bv = bvs[-1]
     res = st, groups, [[bv[j] for j in range(off[f], off[f + 1])] for f in range(model.n_factors)], bool(flag.value)
-    return res + (mask(),) if pa else res
+    return res + extra()
 
 
 def expected_counts(ctx: Context, model: Model, ev_vars: Sequence[int], rows, weights=None, heuristic: str = "mf",
-                    dtype: int = F64, rows_per_launch: int = 0, order: Optional[Sequence[int]] = None, partial=None):
+                    dtype: int = F64, rows_per_launch: int = 0, order: Optional[Sequence[int]] = None, partial=None,
+                    soft=None):
     """Expected sufficient statistics of the evidence rows (bnpp_expected_counts)
     -> (counts, log10_z, n_impossible): counts one flat float64 array, the
     factors in model order, each N_f(x_S) = sum_b w_b P(x_S | row b) in its
@@ -838,11 +961,11 @@ def expected_counts(ctx: Context, model: Model, ev_vars: Sequence[int], rows, we
             raise ValueError("one weight per row is needed")
     ni = C.c_int64()
     up = C.c_double()
-    fn, name, pa = _mv("bnpp_expected_counts", _partial_flags(ev_vars, partial, keep))
+    fn, name, pa, keep_lik = _sv("bnpp_expected_counts", _partial_flags(ev_vars, partial, keep), soft, model, n)
     _check(fn(_h(ctx), model.handle, ne, ev_v, n, ev_x, *pa,
               w.ctypes.data_as(_DP) if w is not None else None, h, oa, no, dtype, int(rows_per_launch),
               counts.ctypes.data_as(_DP), lz.ctypes.data_as(_DP), C.byref(ni), C.byref(up)), name)
-    del keep
+    del keep, keep_lik
     return counts[:total.value], lz[:n], ni.value
 
 
@@ -878,7 +1001,8 @@ def _targets_arg(model: Model, targets):
 
 def plan_marginals_batch(model: Model, ev_vars: Sequence[int], targets: Optional[Sequence[int]] = None,
                          heuristic: str = "mf", dtype: int = F64, rows_per_launch: int = 0,
-                         order: Optional[Sequence[int]] = None, partial=None):
+                         order: Optional[Sequence[int]] = None, partial=None,
+                         soft=None):
     """Host-only planning of marginals_batch (bnpp_plan_marginals_batch) ->
     (stats, groups, col_kinds): stats a dict of PLAN_MARGINALS_BATCH_STATS,
     groups one dict of PLAN_GROUP_FIELDS per launch group (the groups up to
@@ -889,18 +1013,18 @@ def plan_marginals_batch(model: Model, ev_vars: Sequence[int], targets: Optional
     ev_vars = [int(v) for v in ev_vars]
     ts, nt, ta = _targets_arg(model, targets)
     kinds = (C.c_int * max(len(ts), 1))()
-    fn, name, pa = _mv("bnpp_plan_marginals_batch", _partial_flags(ev_vars, partial))
-    tail, mask = _mask_tail(pa[0] if pa else None, len(ev_vars), lambda: (kinds,))
+    fn, name, pa, _ = _sv("bnpp_plan_marginals_batch", _partial_flags(ev_vars, partial), soft)
+    tail, extra = _plan_tail(pa[0] if pa else None, len(ev_vars), soft, lambda: (kinds,))
     st, groups = _plan_call(fn, name, PLAN_MARGINALS_BATCH_STATS,
                             (model.handle, len(ev_vars), _ints(ev_vars), *pa, *_order_args(order, heuristic), nt, ta, dtype,
                              int(rows_per_launch)), tail)
     res = st, groups, [COL_KINDS[kinds[j]] for j in range(len(ts))]
-    return res + (mask(),) if pa else res
+    return res + extra()
 
 
 def marginals_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, targets: Optional[Sequence[int]] = None,
                     heuristic: str = "mf", dtype: int = F64, rows_per_launch: int = 0,
-                    order: Optional[Sequence[int]] = None, out=None, partial=None):
+                    order: Optional[Sequence[int]] = None, out=None, partial=None, soft=None):
     """Every posterior marginal P(X_t | evidence row) of every row from one
     plan (bnpp_marginals_batch) -> (out, log10_z): out an (n, W) float64 array,
     row-major, W = sum of the targets' cards, the targets' blocks in the given
@@ -923,11 +1047,11 @@ def marginals_batch(ctx: Context, model: Model, ev_vars: Sequence[int], rows, ta
         raise ValueError("out must be a writeable C-contiguous float64 array of shape (n, W)")
     lz = np.zeros(max(n, 1))
     up = C.c_double()
-    fn, name, pa = _mv("bnpp_marginals_batch", _partial_flags(ev_vars, partial, keep))
+    fn, name, pa, keep_lik = _sv("bnpp_marginals_batch", _partial_flags(ev_vars, partial, keep), soft, model, n)
     _check(fn(_h(ctx), model.handle, ne, ev_v, n, ev_x, *pa, h, oa, no,
               nt, ta, dtype, int(rows_per_launch), out.ctypes.data_as(_DP), lz.ctypes.data_as(_DP),
               C.byref(up)), name)
-    del keep
+    del keep, keep_lik
     return out[:n], lz[:n]
 
 
@@ -1213,13 +1337,20 @@ def divide(ctx: Context, dtype: int, cards: Sequence[int], a: int, a_scope: Sequ
 
 def condition_batch(ctx: Context, dtype: int, cards: Sequence[int], table: int, scope: Sequence[int],
                     ev_vars: Sequence[int], n_rows: int, ev: int, out: int, stream: Optional[int] = None,
-                    partial=None) -> None:
+                    partial=None, soft=None) -> None:
     """Batched conditioning on caller-owned device buffers (bnpp_condition_batch):
     out[rest][b] = table conditioned on evidence row b; ev: a device
     int32[len(ev_vars)][n_rows], variable-major.  Only enqueues on `stream`.
     partial: the evidence variables that stay dims of `out` under the row's mask
-    (bnpp_condition_batch_mv): a negative value is missing."""
+    (bnpp_condition_batch_mv): a negative value is missing.
+    soft: (soft_vars, lam) -- the weighted gather (bnpp_condition_batch_sv): the
+    soft variables of the scope stay dims of `out`, scaled by lam, a device
+    T[Ws][n_rows] in the call's dtype, (variable, value)-major, used as it is."""
     fn, name, pa = _mv("bnpp_condition_batch", _partial_flags(ev_vars, partial))
+    if soft is not None:
+        ids = [int(v) for v in soft[0]]
+        fn, name = _lib.bnpp_condition_batch_sv, "bnpp_condition_batch_sv"
+        pa = (pa[0] if pa else None, len(ids), _ints(ids) if ids else (C.c_int * 1)(), _P(soft[1]) if soft[1] else None)
     _check(fn(ctx.handle, _P(stream) if stream else None, dtype, len(cards), _ints(cards), _P(table),
               len(scope), _ints(scope), len(ev_vars), _ints(ev_vars), *pa, int(n_rows), _P(ev), _P(out)), name)
 

@@ -42,7 +42,7 @@ def m_step(model_dict: dict, counts, prior: float = 0.0) -> dict:
 
 
 def em(ctx: Context, model_dict: dict, ev_vars: Sequence[int], rows, iters: int, weights=None, dtype: int = F64,
-       prior: float = 0.0, partial=None) -> Tuple[dict, List[float]]:
+       prior: float = 0.0, partial=None, soft=None) -> Tuple[dict, List[float]]:
     """`iters` EM iterations on the rows -> (the fitted model_dict, the
     weighted log-likelihood in log10 of the model each iteration started from).
 
@@ -52,13 +52,15 @@ def em(ctx: Context, model_dict: dict, ev_vars: Sequence[int], rows, iters: int,
     ev_vars; group rows with different missing patterns by pattern yourself
     (see the module docstring) -- or pass `partial` (the variables that hold
     bnpp.MISSING in some row, or "auto"): every row then keeps its own pattern
-    in one plan (expected_counts, missing values).
+    in one plan (expected_counts, missing values).  soft: (soft_vars, lik),
+    per-row likelihoods of variables known only as noisy labels or scores
+    (expected_counts, soft evidence); the log-likelihood then includes them.
     """
     w = None if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
     cur, lls = model_dict, []
     for _ in range(int(iters)):
         counts, lz, _ = expected_counts(ctx, Model.from_dict(cur), ev_vars, rows, weights=w, dtype=dtype,
-                                        partial=partial)
+                                        partial=partial, soft=soft)
         ok = np.isfinite(lz)
         lls.append(float(np.sum((lz if w is None else w * np.where(ok, lz, 0.0))[ok])))
         cur = m_step(cur, counts, prior)
@@ -66,15 +68,16 @@ def em(ctx: Context, model_dict: dict, ev_vars: Sequence[int], rows, iters: int,
 
 
 def impute(ctx: Context, model: Model, ev_vars: Sequence[int], rows, k: int = 1, seed: int = 0, dtype: int = F64,
-           partial=None):
+           partial=None, soft=None):
     """k completions of every row, drawn from P(x | the row) (sample_batch with
     disjoint streams) -> uint8 (n, k, n_vars): the observed variables keep
     their values, the others are one exact joint draw.  Multiple imputation,
     the E step of a stochastic EM, posterior-predictive checks.  An impossible
     row (Z = 0) comes back with its observed values and zeros elsewhere.
     partial: the variables that may be bnpp.MISSING in a row (or "auto"); a
-    row's observed entries keep their values, its missing ones are drawn."""
-    return sample_batch(ctx, model, ev_vars, rows, int(k), seed=seed, dtype=dtype, partial=partial)[0]
+    row's observed entries keep their values, its missing ones are drawn.
+    soft: (soft_vars, lik), per-row likelihoods; a soft variable is drawn."""
+    return sample_batch(ctx, model, ev_vars, rows, int(k), seed=seed, dtype=dtype, partial=partial, soft=soft)[0]
 
 
 def argmax_marginals(cards: Sequence[int], targets, out) -> np.ndarray:
@@ -87,13 +90,16 @@ def argmax_marginals(cards: Sequence[int], targets, out) -> np.ndarray:
     return np.stack([np.argmax(b, axis=1) for b in blocks], axis=1).astype(np.int64)
 
 
-def classify(ctx: Context, model: Model, ev_vars: Sequence[int], rows, targets, dtype: int = F64, partial=None):
+def classify(ctx: Context, model: Model, ev_vars: Sequence[int], rows, targets, dtype: int = F64, partial=None,
+             soft=None):
     """Maximum-posterior-marginal decoding: for every row the most probable
     value of each target on its own, argmax_x P(X_t = x | the row) -> (an
     (n, len(targets)) int array, lowest value on ties; the (n, W) marginals of
     marginals_batch).  Unlike the MPE (mpe_batch) the targets are decoded one by
     one, which minimises the expected number of wrong labels.  partial: as
-    marginals_batch's (rows with bnpp.MISSING entries)."""
+    marginals_batch's (rows with bnpp.MISSING entries); soft: (soft_vars, lik),
+    per-row likelihoods (a soft target reads its posterior with them included)."""
     targets = [int(t) for t in targets]
-    out, _ = marginals_batch(ctx, model, ev_vars, rows, targets=targets, dtype=dtype, partial=partial)
+    out, _ = marginals_batch(ctx, model, ev_vars, rows, targets=targets, dtype=dtype, partial=partial,
+                             soft=soft)
     return argmax_marginals(model.cards, targets, out), out

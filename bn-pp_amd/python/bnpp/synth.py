@@ -134,6 +134,16 @@ def write_evidence(ev: dict, path: str) -> None:
         f.write("1\n%d %s\n" % (len(ev), " ".join("%d %d" % (k, v) for k, v in sorted(ev.items()))))
 
 
+def write_likelihoods(soft_vars, lik, path: str) -> None:
+    """A likelihood file as bnpp.load_likelihoods reads it: n_soft, the ids, n_rows, then one line per row with the
+    Ws likelihoods (repr: they read back to the same doubles).  lik: (n_rows, Ws), the variables' blocks in order."""
+    rows = [[float(x) for x in r] for r in lik]
+    with open(path, "w") as f:
+        f.write("%d %s\n%d\n" % (len(soft_vars), " ".join(str(int(v)) for v in soft_vars), len(rows)))
+        for r in rows:
+            f.write(" ".join(repr(x) for x in r) + "\n")
+
+
 def read_uai(path: str) -> dict:
     """UAI reader with the reference's token rules (io.cpp:14-100)."""
     toks = []

@@ -943,6 +943,136 @@ int bnpp_condition_batch_mv(bnpp_ctx *ctx, void *stream, int dtype, int n_cards,
 int bnpp_evidence_load_batch_mv(const char *path, int cap_vars, int64_t cap_rows, int *n_ev, int *ev_vars,
                                 int64_t *n_rows, int *ev_vals, unsigned char *partial /* [cap_vars] */);
 
+/* ------------------------------------------------ soft evidence (batched calls)
+ * A row can say "X = 2" (hard) or "X unknown" (missing).  The _sv siblings let
+ * it say "X is 0/1/2 with likelihoods 0.7/0.2/0.1": beside ev_vars / partial
+ * they name SOFT variables soft_vars[n_soft] and lik, double[n_rows][Ws]
+ * row-major with Ws = sum card(soft_vars[i]); the variables' blocks come in the
+ * listed order (the layout bnpp_marginals_batch returns).  Row b's result is,
+ * by definition, the _mv call's result on the model that has one more unary
+ * factor lik_b,i on each soft_vars[i], with the row's hard and partial evidence.
+ * Hard and missing values are the corners: a one-hot and an all-ones block.
+ *
+ * Values: every likelihood is finite and >= 0, with no upper bound.  A NaN, an
+ * inf or a negative value is BNPP_ERR_INVALID naming the row and the variable,
+ * checked with the rows, before the context is looked at.  A (row, variable)
+ * block of all zeros makes the row impossible: it reads as an impossible row of
+ * the call reads (-inf, NaN or zeros, n_impossible, every draw degenerate); its
+ * neighbours keep their bits.
+ *
+ * Scaling: the runtime multiplies each (row, variable) block by an exact power
+ * of two so that its largest entry lies in [0.5, 1), sums the exponents per row
+ * (e_b) and gives them back: log10_z[b] and log10_value[b] are the logarithm of
+ * p * 2^(exp2 + e_b), z[b] is scaled by 2^e_b.  Posteriors, marginals, counts,
+ * assignments and samples do not see the scale.  Every weight is then at most
+ * 1, so a gathered table keeps its source's bound, and rows of any magnitude
+ * share a launch.  The scaled block is converted to the call's dtype.
+ *
+ * Arguments: a variable in both ev_vars and soft_vars, one listed twice and an
+ * id out of range are BNPP_ERR_INVALID.  A soft variable in no factor is
+ * BNPP_ERR_UNSUPPORTED, naming it: its likelihoods would scale Z with no table
+ * to carry them.  The target of bnpp_posterior_batch_sv may not be soft; a soft
+ * target of bnpp_marginals_batch_sv is a belief column and reads the posterior
+ * with its likelihoods included.  n_ev = 0 with n_soft > 0 is a valid call.
+ * Sampling keeps its limit of 256 values for a sampled variable.  n_soft = 0 is
+ * the _mv call, bit for bit (plans, groups, stats, job keys, results); the _mv
+ * entries pass 0.  partial may be NULL.
+ *
+ * Planning: a soft variable stays a model variable, as a partial one does: the
+ * order comes from the hard evidence variables only; it is eliminated,
+ * maximised, drawn and counted like any other variable (bnpp_mpe_batch_sv and
+ * bnpp_sample_batch_sv write it from the traceback and the draws).  Exactly ONE
+ * factor that holds it carries its likelihoods, by the rule of the masks:
+ * 1. a factor that holds a hard evidence variable; 2. among those, else among
+ * all its factors, the fewest entries after conditioning; 3. the lowest index.
+ * That factor is gathered by the weighted gather step (launch-group key
+ * 2^24 + 36864, level 0, one group per step), masks and weights together:
+ *   out[rest][b] = mask_b(rest) ? ((in[hard offsets(b) + offset(rest)] * lam_d1[digit_d1][b]) * lam_d2[digit_d2][b]) ... : 0
+ * the soft dims d1, d2, ... in the order of the factor's scope, left to right,
+ * each product rounded once in the call's dtype.  A soft dim is never merged
+ * with a neighbour and counts against the 8 rest dims of a gather step
+ * (BNPP_ERR_UNSUPPORTED).  The job cache key includes the soft variable list,
+ * never the values: a call with other likelihoods relaunches the cached job.
+ * bnpp_plan_*_sv ignore lik (it may be NULL) and also return lam_factor[n_soft]
+ * (may be NULL): the factor that carries variable i's likelihoods.
+ *
+ * bnpp_condition_batch_sv runs the weighted gather on caller-owned device
+ * buffers: lam is T[Ws][n_rows] in the call's dtype, (variable, value)-major,
+ * rows fastest, used as it is (no scaling); a soft variable of the scope stays
+ * a dim of `out`, one outside the scope is ignored.
+ * bnpp_likelihood_load reads a text file: n_soft, the ids, n_rows, then Ws
+ * numbers per row.  n_soft and n_rows are always set; soft_vars is filled when
+ * cap_vars >= n_soft, and lik when also cap_vals >= n_rows * Ws (else
+ * BNPP_ERR_INVALID, so a caller may ask for the sizes, then the ids, first). */
+int bnpp_expected_counts_sv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const
+                            int *ev_vals, const unsigned char *partial, int n_soft, const int *soft_vars, const
+                            double *lik, const double *weights, int heuristic, const int *order, int n_order, int
+                            dtype, int64_t rows_per_launch, double *counts, double *log10_z, int64_t *n_impossible,
+                            double *uptime_ms);
+
+int bnpp_plan_counts_sv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial, int n_soft,
+                        const int *soft_vars, const double *lik, int heuristic, const int *order, int n_order, int
+                        dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows, int cap_rows, int
+                        *n_rows, int *belief_off, int *belief_vars, int cap_belief, int *n_belief, int *no_b_elim,
+                        int *mask_factor, int *lam_factor);
+
+int bnpp_marginals_batch_sv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const
+                            int *ev_vals, const unsigned char *partial, int n_soft, const int *soft_vars, const
+                            double *lik, int heuristic, const int *order, int n_order, int n_targets, const int
+                            *targets, int dtype, int64_t rows_per_launch, double *out, double *log10_z, double
+                            *uptime_ms);
+
+int bnpp_plan_marginals_batch_sv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial,
+                                 int n_soft, const int *soft_vars, const double *lik, int heuristic, const int
+                                 *order, int n_order, int n_targets, const int *targets, int dtype, int64_t
+                                 rows_per_launch, double *stats, int n_stats, int64_t *rows, int cap_rows, int
+                                 *n_rows, int *col_kind, int *mask_factor, int *lam_factor);
+
+int bnpp_partition_batch_sv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const
+                            int *ev_vals, const unsigned char *partial, int n_soft, const int *soft_vars, const
+                            double *lik, int heuristic, const int *order, int n_order, int dtype, int64_t
+                            rows_per_launch, double *log10_z, double *z, double *uptime_ms);
+
+int bnpp_posterior_batch_sv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const
+                            int *ev_vals, const unsigned char *partial, int n_soft, const int *soft_vars, const
+                            double *lik, int heuristic, int target, int dtype, int64_t rows_per_launch, double *out,
+                            double *uptime_ms);
+
+int bnpp_mpe_batch_sv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const int
+                      *ev_vals, const unsigned char *partial, int n_soft, const int *soft_vars, const double *lik,
+                      int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch, double
+                      *log10_value, int *assignment, double *uptime_ms);
+
+int bnpp_plan_mpe_batch_sv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial, int
+                           n_soft, const int *soft_vars, const double *lik, int heuristic, const int *order, int
+                           n_order, int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows,
+                           int cap_rows, int *n_rows, int *mask_factor, int *lam_factor);
+
+int bnpp_sample_batch_sv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows, const int
+                         *ev_vals, const unsigned char *partial, int n_soft, const int *soft_vars, const double
+                         *lik, int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch,
+                         int64_t n_per_row, int64_t first_sample, int64_t row_stride, uint64_t seed, uint8_t *out,
+                         double *log10_z, int64_t *n_degenerate, double *uptime_ms);
+
+int bnpp_plan_sample_batch_sv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial, int
+                              n_soft, const int *soft_vars, const double *lik, int heuristic, const int *order, int
+                              n_order, int dtype, int64_t rows_per_launch, int64_t n_per_row, double *stats, int
+                              n_stats, int64_t *rows, int cap_rows, int *n_rows, int *mask_factor, int *lam_factor);
+
+int bnpp_plan_batch_sv(const bnpp_model *m, int n_ev, const int *ev_vars, const unsigned char *partial, int n_soft,
+                       const int *soft_vars, const double *lik, int heuristic, const int *order, int n_order, int
+                       target, int dtype, int64_t rows_per_launch, double *stats, int n_stats, int64_t *rows, int
+                       cap_rows, int *n_rows, int *result_scope, int *n_result_scope, int *mask_factor, int
+                       *lam_factor);
+
+int bnpp_condition_batch_sv(bnpp_ctx *ctx, void *stream, int dtype, int n_cards, const int *cards, const void *in,
+                            int ndims, const int *vars, int n_ev, const int *ev_vars,
+                            const unsigned char *partial /* [n_ev] or NULL */, int n_soft, const int *soft_vars,
+                            const void *lam /* device, T[Ws][n_rows] */, int64_t n_rows,
+                            const int32_t *ev /* device, [n_ev][n_rows] */, void *out);
+int bnpp_likelihood_load(const bnpp_model *m, const char *path, int cap_vars, int64_t cap_vals, int *n_soft,
+                         int *soft_vars, int64_t *n_rows, double *lik);
+
 /* Host-only planning of one part of bnpp_marginals_tree_part (all variables
  * as targets): owned[v] = 1 when this part computes v's marginal; stats as
  * bnpp_job_stats for this part's plan (may be NULL).  The memory budget is

@@ -105,6 +105,13 @@ private:
     mutable std::shared_ptr<const PendingSum> _pending;
 };
 
+// EXTENSION: soft evidence of the batched calls (Model::*_batch, expected_counts): the soft variables and, per
+// evidence row, their likelihoods -- the variables' blocks in the listed order
+struct SoftEvidence {
+    std::vector<unsigned> vars;
+    std::vector<std::vector<double>> lik;
+};
+
 // The GPU engine's precision for Model/BN inference (default fp64, bit-exact
 // with the reference's arithmetic); options["fp32"] selects fp32 storage.
 class Model {                                      // model.hh:11-38
@@ -229,6 +236,34 @@ public:
         std::vector<double> *log10_z = nullptr, double *uptime = nullptr) const;
     std::vector<std::vector<unsigned char>> sample_batch(const std::vector<unsigned> &ev_vars,
         const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial,
+        std::unordered_map<std::string, bool> &options, size_t k, unsigned long long seed = 0,
+        std::vector<double> *log10_z = nullptr, double *uptime = nullptr) const;
+    // EXTENSION: soft evidence (the bnpp_*_sv entries).  Beside the evidence a row carries likelihoods of the
+    // SOFT variables soft.vars: soft.lik[b] holds row b's Ws = sum of their cards numbers, the variables'
+    // blocks in the listed order (the layout marginals_batch returns), finite and >= 0.  A row's result is the
+    // call's on the model with one more unary factor per soft variable; a soft variable is no evidence
+    // variable: it is eliminated, maximised, drawn and counted.  Empty soft.vars: the overload above.
+    std::vector<double> partition_batch(const std::vector<unsigned> &ev_vars,
+        const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, const SoftEvidence &soft,
+        std::unordered_map<std::string, bool> &options, std::vector<double> *z = nullptr,
+        double *uptime = nullptr) const;
+    std::vector<std::vector<unsigned>> mpe_batch(const std::vector<unsigned> &ev_vars,
+        const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, const SoftEvidence &soft,
+        std::unordered_map<std::string, bool> &options, std::vector<double> *log10_value = nullptr,
+        double *uptime = nullptr) const;
+    std::vector<std::vector<double>> posterior_batch(const std::vector<unsigned> &ev_vars,
+        const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, const SoftEvidence &soft,
+        unsigned target, std::unordered_map<std::string, bool> &options, double *uptime = nullptr) const;
+    std::vector<std::vector<double>> expected_counts(const std::vector<unsigned> &ev_vars,
+        const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, const SoftEvidence &soft,
+        const std::vector<double> &weights, std::unordered_map<std::string, bool> &options,
+        std::vector<double> *log10_z = nullptr, long long *n_impossible = nullptr, double *uptime = nullptr) const;
+    std::vector<std::vector<double>> marginals_batch(const std::vector<unsigned> &ev_vars,
+        const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, const SoftEvidence &soft,
+        const std::vector<unsigned> &targets, std::unordered_map<std::string, bool> &options,
+        std::vector<double> *log10_z = nullptr, double *uptime = nullptr) const;
+    std::vector<std::vector<unsigned char>> sample_batch(const std::vector<unsigned> &ev_vars,
+        const std::vector<std::vector<int>> &rows, const std::vector<unsigned char> &partial, const SoftEvidence &soft,
         std::unordered_map<std::string, bool> &options, size_t k, unsigned long long seed = 0,
         std::vector<double> *log10_z = nullptr, double *uptime = nullptr) const;
     virtual void write(std::ostream &) const {}
