@@ -1374,7 +1374,7 @@ int plan_batch_schedule(const BatchCall &c, int64_t budget, int64_t auto_cap, Sc
     if (!build_schedule({&plan}, d.cards, src_sizes, eb, max_vec_for(dtype), out, &msg, budget))
         return set_err(out.arena_bytes >= kSatMax ? BNPP_ERR_OOM : BNPP_ERR_INVALID, msg);
     int64_t n_gather = 0;
-    for (const Schedule::Group &g : out.groups) n_gather += g.variant == kCondBatchKey || g.variant == kCondBatchMaskKey || g.variant == kCondBatchSoftKey;
+    for (const Schedule::Group &g : out.groups) n_gather += cond_form_of_key(g.variant) >= 0;
     stats[0] = out.entries;
     stats[1] = (double)out.arena_bytes;
     stats[2] = out.n_levels;
@@ -1498,8 +1498,7 @@ void batch_stage(BatchRun &run) {
     const Schedule &sc = ex.sched;
     const int64_t R = run.R = run.job->batch_rows, n_launch = run.n_launch = (c.n_rows + R - 1) / R;
     for (const Schedule::Group &g : sc.groups)
-        if ((g.variant == kCondBatchKey || g.variant == kCondBatchMaskKey || g.variant == kCondBatchSoftKey) &&
-            sc.descs[g.begin].in_table[1] >= 0)
+        if (cond_form_of_key(g.variant) >= 0 && sc.descs[g.begin].in_table[1] >= 0)
             run.d_ev = static_cast<int32_t *>(ex.h_meta[sc.descs[g.begin].in_table[1]].ptr);
         else if (g.variant == kMargRowsKey && sc.pool[sc.descs[g.begin].dim_off + 3] >= 0)   // an evidence block's, gather step or not
             run.d_ev = static_cast<int32_t *>(ex.h_meta[sc.pool[sc.descs[g.begin].dim_off + 3]].ptr);
@@ -1515,7 +1514,7 @@ void batch_stage(BatchRun &run) {
                     hev[(size_t)((L * n_ev + j) * R + b)] = ev_vals[std::min(L * R + b, n_rows - 1) * n_ev + j];
     }
     for (const Schedule::Group &g : sc.groups)
-        if (g.variant == kCondBatchSoftKey && sc.descs[g.begin].in_table[2] >= 0)
+        if (cond_form_of_key(g.variant) == kCondWeighted && sc.descs[g.begin].in_table[2] >= 0)
             run.d_lam = ex.h_meta[sc.descs[g.begin].in_table[2]].ptr;
     if (run.d_lam && c.n_soft > 0) {
         // per (row, variable) block an exact power of two brings the largest entry into [0.5, 1): every weight is at
@@ -1658,8 +1657,18 @@ int batch_close(BatchRun &run, int rc, double *uptime_ms) {
     return BNPP_OK;
 }
 
+// what the _mv and _sv plan entries return last: per evidence variable the factor whose gather step carries its mask,
+// per soft variable the one that carries its weights (-1: none); either array may be null
+void report_evidence_factors(const VEPlan &plan, int n_ev, int *mask_factor, int n_soft, int *lam_factor) {
+    for (int j = 0; mask_factor && j < n_ev; ++j)
+        mask_factor[j] = j < (int)plan.batch_mask_factor.size() ? plan.batch_mask_factor[j] : -1;
+    for (int j = 0; lam_factor && j < n_soft; ++j)
+        lam_factor[j] = j < (int)plan.batch_lam_factor.size() ? plan.batch_lam_factor[j] : -1;
+}
+
 BatchCall batch_call(const bnpp_model *m, int kind, int n_ev, const int *ev_vars, int heuristic, const int *order,
-                     int n_order, int dtype, int64_t rows_per_launch) {
+                     int n_order, int dtype, int64_t rows_per_launch, const unsigned char *partial, int n_soft,
+                     const int *soft_vars, const double *lik) {
     BatchCall c{};
     c.m = m;
     c.kind = kind;
@@ -1670,6 +1679,10 @@ BatchCall batch_call(const bnpp_model *m, int kind, int n_ev, const int *ev_vars
     c.n_order = n_order;
     c.dtype = dtype;
     c.rows_per_launch = rows_per_launch;
+    c.partial = partial;
+    c.n_soft = n_soft;
+    c.soft_vars = soft_vars;
+    c.lik = lik;
     return c;
 }
 
@@ -2135,11 +2148,8 @@ int bnpp_expected_counts_sv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const 
                             const int *order, int n_order, int dtype, int64_t rows_per_launch, double *counts,
                             double *log10_z, int64_t *n_impossible, double *uptime_ms) {
     BNPP_GUARD_BEGIN
-    BatchCall c = batch_call(m, kKindCounts, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
-    c.partial = partial;
-    c.n_soft = n_soft;
-    c.soft_vars = soft_vars;
-    c.lik = lik;
+    BatchCall c = batch_call(m, kKindCounts, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch,
+                             partial, n_soft, soft_vars, lik);
     c.n_rows = n_rows;
     c.ev_vals = ev_vals;
     return run_counts(ctx, c, weights, counts, log10_z, n_impossible, uptime_ms);
@@ -2170,11 +2180,8 @@ int bnpp_plan_counts_sv(const bnpp_model *m, int n_ev, const int *ev_vars, const
     Schedule s;
     VEPlan plan;
     double st[12] = {0};
-    BatchCall c = batch_call(m, kKindCounts, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
-    c.partial = partial;
-    c.n_soft = n_soft;
-    c.soft_vars = soft_vars;
-    c.lik = lik;
+    BatchCall c = batch_call(m, kKindCounts, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch,
+                             partial, n_soft, soft_vars, lik);
     if (int rc = plan_batch_entry(c, false, stats, n_stats, rows, cap_rows, n_rows, s, plan, st)) return rc;
     for (const Schedule::Group &g : s.groups) st[10] += g.variant == kCountsKey;
     st[11] = plan.counts_fwd_levels;
@@ -2205,10 +2212,7 @@ int bnpp_plan_counts_sv(const bnpp_model *m, int n_ev, const int *ev_vars, const
                 *no_b_elim = 0;
         }
     }
-    for (int j = 0; mask_factor && j < n_ev; ++j)
-        mask_factor[j] = j < (int)plan.batch_mask_factor.size() ? plan.batch_mask_factor[j] : -1;
-    for (int j = 0; lam_factor && j < n_soft; ++j)
-        lam_factor[j] = j < (int)plan.batch_lam_factor.size() ? plan.batch_lam_factor[j] : -1;
+    report_evidence_factors(plan, n_ev, mask_factor, n_soft, lam_factor);
     return BNPP_OK;
     BNPP_GUARD_END
 }
@@ -2289,11 +2293,8 @@ int bnpp_marginals_batch_sv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const 
                             int n_order, int n_targets, const int *targets, int dtype, int64_t rows_per_launch,
                             double *out, double *log10_z, double *uptime_ms) {
     BNPP_GUARD_BEGIN
-    BatchCall c = batch_call(m, kKindMarginalsBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
-    c.partial = partial;
-    c.n_soft = n_soft;
-    c.soft_vars = soft_vars;
-    c.lik = lik;
+    BatchCall c = batch_call(m, kKindMarginalsBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch,
+                             partial, n_soft, soft_vars, lik);
     c.n_rows = n_rows;
     c.ev_vals = ev_vals;
     if (!m) return set_err(BNPP_ERR_INVALID, "null context or model");
@@ -2326,11 +2327,8 @@ int bnpp_plan_marginals_batch_sv(const bnpp_model *m, int n_ev, const int *ev_va
     Schedule s;
     VEPlan plan;
     double st[BNPP_PLAN_MARGINALS_BATCH_STATS] = {0};
-    BatchCall c = batch_call(m, kKindMarginalsBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
-    c.partial = partial;
-    c.n_soft = n_soft;
-    c.soft_vars = soft_vars;
-    c.lik = lik;
+    BatchCall c = batch_call(m, kKindMarginalsBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch,
+                             partial, n_soft, soft_vars, lik);
     if (!m) return set_err(BNPP_ERR_INVALID, "null argument");
     if (int rc = marginals_targets(m->d, n_targets, targets, c.targets)) return rc;
     if (int rc = plan_batch_entry(c, false, stats, n_stats, rows, cap_rows, n_rows, s, plan, st)) return rc;
@@ -2347,10 +2345,7 @@ int bnpp_plan_marginals_batch_sv(const bnpp_model *m, int n_ev, const int *ev_va
         for (const BucketSpec &b : plan.buckets)
             for (size_t j = 0; b.marg_rows && j < b.marg_cols.size(); ++j)
                 col_kind[j] = b.marg_cols[j].table >= 0 ? (b.marg_cols[j].has_b ? 1 : 0) : b.marg_cols[j].ev_row >= 0 ? -1 : -2;
-    for (int j = 0; mask_factor && j < n_ev; ++j)
-        mask_factor[j] = j < (int)plan.batch_mask_factor.size() ? plan.batch_mask_factor[j] : -1;
-    for (int j = 0; lam_factor && j < n_soft; ++j)
-        lam_factor[j] = j < (int)plan.batch_lam_factor.size() ? plan.batch_lam_factor[j] : -1;
+    report_evidence_factors(plan, n_ev, mask_factor, n_soft, lam_factor);
     return BNPP_OK;
     BNPP_GUARD_END
 }
@@ -2998,42 +2993,18 @@ int bnpp_condition_batch_sv(bnpp_ctx *ctx, void *stream, int dtype, int n_cards,
     std::vector<int64_t> pool;
     std::string msg;
     if (!build_desc(b, cv, max_vec_for(dtype), d, pool, &msg)) return set_err(BNPP_ERR_UNSUPPORTED, msg);
-    hipError_t e = hipSuccess;
-    if (weighted) {
-        CondBatchSoftArgs a;
-        std::memset(&a, 0, sizeof a);
-        if (pool.size() > sizeof a.pool / sizeof a.pool[0]) return set_err(BNPP_ERR_UNSUPPORTED, "scope too wide for a single-op call");
-        std::copy(pool.begin(), pool.end(), a.pool);
-        a.src = in;
-        a.out = out;
-        a.ev = ev;
-        a.lam = lam;
-        a.n_rows = n_rows;
-        e = hipSetDevice(ctx->c.device);
-        if (e == hipSuccess) e = launch_cond_batch_soft_single(dtype == BNPP_F32, a, ctx->c.max_grid, pick_stream(ctx, stream));
-    } else if (masked) {
-        CondBatchMaskedArgs a;
-        std::memset(&a, 0, sizeof a);
-        if (pool.size() > sizeof a.pool / sizeof a.pool[0]) return set_err(BNPP_ERR_UNSUPPORTED, "scope too wide for a single-op call");
-        std::copy(pool.begin(), pool.end(), a.pool);
-        a.src = in;
-        a.out = out;
-        a.ev = ev;
-        a.n_rows = n_rows;
-        e = hipSetDevice(ctx->c.device);
-        if (e == hipSuccess) e = launch_cond_batch_masked_single(dtype == BNPP_F32, a, ctx->c.max_grid, pick_stream(ctx, stream));
-    } else {
-        CondBatchSingleArgs a;
-        std::memset(&a, 0, sizeof a);
-        if (pool.size() > sizeof a.pool / sizeof a.pool[0]) return set_err(BNPP_ERR_UNSUPPORTED, "scope too wide for a single-op call");
-        std::copy(pool.begin(), pool.end(), a.pool);
-        a.src = in;
-        a.out = out;
-        a.ev = ev;
-        a.n_rows = n_rows;
-        e = hipSetDevice(ctx->c.device);
-        if (e == hipSuccess) e = launch_cond_batch_single(dtype == BNPP_F32, a, ctx->c.max_grid, pick_stream(ctx, stream));
-    }
+    const int form = weighted ? kCondWeighted : masked ? kCondMasked : kCondPlain;
+    CondBatchArgs a;
+    std::memset(&a, 0, sizeof a);
+    if ((int64_t)pool.size() > cond_single_pool_words(form)) return set_err(BNPP_ERR_UNSUPPORTED, "scope too wide for a single-op call");
+    std::copy(pool.begin(), pool.end(), a.pool);
+    a.src = in;
+    a.out = out;
+    a.ev = ev;
+    a.lam = weighted ? lam : nullptr;
+    a.n_rows = n_rows;
+    hipError_t e = hipSetDevice(ctx->c.device);
+    if (e == hipSuccess) e = launch_cond_batch_single(dtype == BNPP_F32, form, a, ctx->c.max_grid, pick_stream(ctx, stream));
     if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return BNPP_OK;
     BNPP_GUARD_END
@@ -3089,10 +3060,8 @@ int bnpp_batch_job_key(const bnpp_model *m, int n_ev, const int *ev_vars, const 
                        const int *soft_vars, int dtype, int64_t rows_per_launch, uint64_t *key) {
     BNPP_GUARD_BEGIN
     if (!m || !key || (n_ev > 0 && !ev_vars) || (n_soft > 0 && !soft_vars)) return set_err(BNPP_ERR_INVALID, "null argument");
-    BatchCall c = batch_call(m, kKindBatch, n_ev, ev_vars, BNPP_MIN_FILL, nullptr, 0, dtype, rows_per_launch);
-    c.partial = partial;
-    c.n_soft = n_soft;
-    c.soft_vars = soft_vars;
+    BatchCall c = batch_call(m, kKindBatch, n_ev, ev_vars, BNPP_MIN_FILL, nullptr, 0, dtype, rows_per_launch,
+                             partial, n_soft, soft_vars, nullptr);
     *key = batch_call_key(c, kBatchAutoRows);
     return BNPP_OK;
     BNPP_GUARD_END
@@ -3542,11 +3511,8 @@ int bnpp_partition_batch_sv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const 
                             int n_order, int dtype, int64_t rows_per_launch, double *log10_z, double *z,
                             double *uptime_ms) {
     BNPP_GUARD_BEGIN
-    BatchCall c = batch_call(m, kKindBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
-    c.partial = partial;
-    c.n_soft = n_soft;
-    c.soft_vars = soft_vars;
-    c.lik = lik;
+    BatchCall c = batch_call(m, kKindBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch,
+                             partial, n_soft, soft_vars, lik);
     c.n_rows = n_rows;
     c.ev_vals = ev_vals;
     return run_batch(ctx, c, false, log10_z, z, nullptr, uptime_ms);
@@ -3572,11 +3538,7 @@ int bnpp_posterior_batch_sv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const 
         const double *lik, int heuristic, int target, int dtype,
                             int64_t rows_per_launch, double *out, double *uptime_ms) {
     BNPP_GUARD_BEGIN
-    BatchCall c = batch_call(m, kKindBatch, n_ev, ev_vars, heuristic, nullptr, 0, dtype, rows_per_launch);
-    c.partial = partial;
-    c.n_soft = n_soft;
-    c.soft_vars = soft_vars;
-    c.lik = lik;
+    BatchCall c = batch_call(m, kKindBatch, n_ev, ev_vars, heuristic, nullptr, 0, dtype, rows_per_launch, partial, n_soft, soft_vars, lik);
     c.target = target;
     c.n_rows = n_rows;
     c.ev_vals = ev_vals;
@@ -3602,11 +3564,8 @@ int bnpp_mpe_batch_sv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *e
         const double *lik, int heuristic, const int *order, int n_order,
                       int dtype, int64_t rows_per_launch, double *log10_value, int *assignment, double *uptime_ms) {
     BNPP_GUARD_BEGIN
-    BatchCall c = batch_call(m, kKindMpeBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
-    c.partial = partial;
-    c.n_soft = n_soft;
-    c.soft_vars = soft_vars;
-    c.lik = lik;
+    BatchCall c = batch_call(m, kKindMpeBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch,
+                             partial, n_soft, soft_vars, lik);
     c.n_rows = n_rows;
     c.ev_vals = ev_vals;
     return run_mpe_batch(ctx, c, log10_value, assignment, uptime_ms);
@@ -3634,11 +3593,8 @@ int bnpp_plan_mpe_batch_sv(const bnpp_model *m, int n_ev, const int *ev_vars, co
     Schedule s;
     VEPlan plan;
     double st[BNPP_PLAN_MPE_BATCH_STATS] = {0};
-    BatchCall c = batch_call(m, kKindMpeBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
-    c.partial = partial;
-    c.n_soft = n_soft;
-    c.soft_vars = soft_vars;
-    c.lik = lik;
+    BatchCall c = batch_call(m, kKindMpeBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch,
+                             partial, n_soft, soft_vars, lik);
     if (int rc = plan_batch_entry(c, false, stats, n_stats, rows, cap_rows, n_rows, s, plan, st)) return rc;
     st[10] = (double)plan.arg_bytes;
     st[11] = plan.n_max_buckets;
@@ -3647,10 +3603,7 @@ int bnpp_plan_mpe_batch_sv(const bnpp_model *m, int n_ev, const int *ev_vars, co
     st[14] = (double)plan.arg_b_entries;
     st[15] = (double)plan.arg_nob_entries;
     for (int i = 0; i < n_stats && i < BNPP_PLAN_MPE_BATCH_STATS; ++i) stats[i] = st[i];
-    for (int j = 0; mask_factor && j < n_ev; ++j)
-        mask_factor[j] = j < (int)plan.batch_mask_factor.size() ? plan.batch_mask_factor[j] : -1;
-    for (int j = 0; lam_factor && j < n_soft; ++j)
-        lam_factor[j] = j < (int)plan.batch_lam_factor.size() ? plan.batch_lam_factor[j] : -1;
+    report_evidence_factors(plan, n_ev, mask_factor, n_soft, lam_factor);
     return BNPP_OK;
     BNPP_GUARD_END
 }
@@ -3675,11 +3628,8 @@ int bnpp_sample_batch_sv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int
                          int64_t row_stride, uint64_t seed, uint8_t *out, double *log10_z, int64_t *n_degenerate,
                          double *uptime_ms) {
     BNPP_GUARD_BEGIN
-    BatchCall c = batch_call(m, kKindSampleBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
-    c.partial = partial;
-    c.n_soft = n_soft;
-    c.soft_vars = soft_vars;
-    c.lik = lik;
+    BatchCall c = batch_call(m, kKindSampleBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch,
+                             partial, n_soft, soft_vars, lik);
     c.K = n_per_row;
     c.n_rows = n_rows;
     c.ev_vals = ev_vals;
@@ -3713,11 +3663,8 @@ int bnpp_plan_sample_batch_sv(const bnpp_model *m, int n_ev, const int *ev_vars,
     Schedule s;
     VEPlan plan;
     double st[BNPP_PLAN_SAMPLE_BATCH_STATS] = {0};
-    BatchCall c = batch_call(m, kKindSampleBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch);
-    c.partial = partial;
-    c.n_soft = n_soft;
-    c.soft_vars = soft_vars;
-    c.lik = lik;
+    BatchCall c = batch_call(m, kKindSampleBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch,
+                             partial, n_soft, soft_vars, lik);
     c.K = n_per_row;
     if (int rc = plan_batch_entry(c, false, stats, n_stats, rows, cap_rows, n_rows, s, plan, st)) return rc;
     st[10] = (double)n_per_row;
@@ -3726,10 +3673,7 @@ int bnpp_plan_sample_batch_sv(const bnpp_model *m, int n_ev, const int *ev_vars,
     st[13] = plan.n_draw_b;
     st[14] = plan.n_draw_nob;
     for (int i = 0; i < n_stats && i < BNPP_PLAN_SAMPLE_BATCH_STATS; ++i) stats[i] = st[i];
-    for (int j = 0; mask_factor && j < n_ev; ++j)
-        mask_factor[j] = j < (int)plan.batch_mask_factor.size() ? plan.batch_mask_factor[j] : -1;
-    for (int j = 0; lam_factor && j < n_soft; ++j)
-        lam_factor[j] = j < (int)plan.batch_lam_factor.size() ? plan.batch_lam_factor[j] : -1;
+    report_evidence_factors(plan, n_ev, mask_factor, n_soft, lam_factor);
     return BNPP_OK;
     BNPP_GUARD_END
 }
@@ -3758,11 +3702,7 @@ int bnpp_plan_batch_sv(const bnpp_model *m, int n_ev, const int *ev_vars, const 
     VEPlan plan;
     double st[10] = {0};
     BatchCall c = batch_call(m, kKindBatch, n_ev, ev_vars, heuristic, target >= 0 ? nullptr : order,
-                             target >= 0 ? 0 : n_order, dtype, rows_per_launch);
-    c.partial = partial;
-    c.n_soft = n_soft;
-    c.soft_vars = soft_vars;
-    c.lik = lik;
+                             target >= 0 ? 0 : n_order, dtype, rows_per_launch, partial, n_soft, soft_vars, lik);
     c.target = target >= 0 ? target : -1;
     if (int rc = plan_batch_entry(c, target >= 0, stats, n_stats, rows, cap_rows, n_rows, s, plan, st)) return rc;
     for (int i = 0; i < n_stats && i < 10; ++i) stats[i] = st[i];
@@ -3770,10 +3710,7 @@ int bnpp_plan_batch_sv(const bnpp_model *m, int n_ev, const int *ev_vars, const 
     if (n_result_scope) *n_result_scope = (int)rv.size();
     if (result_scope)
         for (size_t i = 0; i < rv.size() && i < 2; ++i) result_scope[i] = rv[i];
-    for (int j = 0; mask_factor && j < n_ev; ++j)
-        mask_factor[j] = j < (int)plan.batch_mask_factor.size() ? plan.batch_mask_factor[j] : -1;
-    for (int j = 0; lam_factor && j < n_soft; ++j)
-        lam_factor[j] = j < (int)plan.batch_lam_factor.size() ? plan.batch_lam_factor[j] : -1;
+    report_evidence_factors(plan, n_ev, mask_factor, n_soft, lam_factor);
     return BNPP_OK;
     BNPP_GUARD_END
 }

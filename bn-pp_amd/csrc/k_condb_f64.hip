@@ -1,14 +1,10 @@
 // Kernel instantiations compiled as a separate translation unit (parallel build).
-// Batched conditioning kernels (condbatch.cuh).
+// Batched conditioning kernels (condbatch.cuh): the plain gather.
 #include "condbatch.cuh"
 
 namespace bnpp {
 
-hipError_t dispatch_cond_batch_f64(const int64_t *pool, int64_t rest, TableMeta *meta, int out_table, const void *out_ptr,
-                                   const int32_t *ev, int64_t n_rows, int max_grid, hipStream_t stream) {
-    return go_cond_batch<double>(pool, rest, meta, out_table, out_ptr, ev, n_rows, max_grid, stream);
-}
-hipError_t dispatch_cond_batch_single_f64(const CondBatchSingleArgs &a, int max_grid, hipStream_t stream) {
-    return go_cond_batch_single<double>(a, max_grid, stream);
-}
+template hipError_t go_cond_batch<double, kCondPlain>(const int64_t *, int64_t, TableMeta *, int, const void *, const int32_t *,
+                                                     const void *, int64_t, int, hipStream_t);
+template hipError_t go_cond_batch_single<double, kCondPlain>(const CondBatchArgs &, int, hipStream_t);
 }  // namespace bnpp

@@ -1,15 +1,10 @@
 // Kernel instantiations compiled as a separate translation unit (parallel build).
-// Masked batched conditioning kernels (condbatch.cuh, Masked = true): missing values.
+// Masked batched conditioning kernels (condbatch.cuh, kCondMasked): missing values.
 #include "condbatch.cuh"
 
 namespace bnpp {
 
-hipError_t dispatch_cond_batch_masked_f32(const int64_t *pool, int64_t rest, TableMeta *meta, int out_table,
-                                          const void *out_ptr, const int32_t *ev, int64_t n_rows, int max_grid,
-                                          hipStream_t stream) {
-    return go_cond_batch_masked<float>(pool, rest, meta, out_table, out_ptr, ev, n_rows, max_grid, stream);
-}
-hipError_t dispatch_cond_batch_masked_single_f32(const CondBatchMaskedArgs &a, int max_grid, hipStream_t stream) {
-    return go_cond_batch_masked_single<float>(a, max_grid, stream);
-}
+template hipError_t go_cond_batch<float, kCondMasked>(const int64_t *, int64_t, TableMeta *, int, const void *, const int32_t *,
+                                                     const void *, int64_t, int, hipStream_t);
+template hipError_t go_cond_batch_single<float, kCondMasked>(const CondBatchArgs &, int, hipStream_t);
 }  // namespace bnpp

@@ -41,30 +41,12 @@ hipError_t dispatch_sample_rows_batch_f64(const int64_t *pool, const TableMeta *
 hipError_t dispatch_sample_single_f32(const SampleSingleArgs &a, int max_grid, hipStream_t stream);
 hipError_t dispatch_sample_single_f64(const SampleSingleArgs &a, int max_grid, hipStream_t stream);
 
-hipError_t dispatch_cond_batch_f32(const int64_t *pool, int64_t rest, TableMeta *meta, int out_table, const void *out_ptr,
-                                   const int32_t *ev, int64_t n_rows, int max_grid, hipStream_t stream);
-hipError_t dispatch_cond_batch_f64(const int64_t *pool, int64_t rest, TableMeta *meta, int out_table, const void *out_ptr,
-                                   const int32_t *ev, int64_t n_rows, int max_grid, hipStream_t stream);
-hipError_t dispatch_cond_batch_single_f32(const CondBatchSingleArgs &a, int max_grid, hipStream_t stream);
-hipError_t dispatch_cond_batch_single_f64(const CondBatchSingleArgs &a, int max_grid, hipStream_t stream);
-
-hipError_t dispatch_cond_batch_masked_f32(const int64_t *pool, int64_t rest, TableMeta *meta, int out_table,
-                                          const void *out_ptr, const int32_t *ev, int64_t n_rows, int max_grid,
-                                          hipStream_t stream);
-hipError_t dispatch_cond_batch_masked_f64(const int64_t *pool, int64_t rest, TableMeta *meta, int out_table,
-                                          const void *out_ptr, const int32_t *ev, int64_t n_rows, int max_grid,
-                                          hipStream_t stream);
-hipError_t dispatch_cond_batch_masked_single_f32(const CondBatchMaskedArgs &a, int max_grid, hipStream_t stream);
-hipError_t dispatch_cond_batch_masked_single_f64(const CondBatchMaskedArgs &a, int max_grid, hipStream_t stream);
-
-hipError_t dispatch_cond_batch_soft_f32(const int64_t *pool, int64_t rest, TableMeta *meta, int out_table,
-                                        const void *out_ptr, const int32_t *ev, const void *lam, int64_t n_rows,
-                                        int max_grid, hipStream_t stream);
-hipError_t dispatch_cond_batch_soft_f64(const int64_t *pool, int64_t rest, TableMeta *meta, int out_table,
-                                        const void *out_ptr, const int32_t *ev, const void *lam, int64_t n_rows,
-                                        int max_grid, hipStream_t stream);
-hipError_t dispatch_cond_batch_soft_single_f32(const CondBatchSoftArgs &a, int max_grid, hipStream_t stream);
-hipError_t dispatch_cond_batch_soft_single_f64(const CondBatchSoftArgs &a, int max_grid, hipStream_t stream);
+// condbatch.cuh: one form and one type instantiated per unit (k_condb, k_condbm, k_condbs _f32/f64)
+template <typename T, int Form>
+hipError_t go_cond_batch(const int64_t *pool, int64_t rest, TableMeta *meta, int out_table, const void *out_ptr,
+                         const int32_t *ev, const void *lam, int64_t n_rows, int max_grid, hipStream_t stream);
+template <typename T, int Form>
+hipError_t go_cond_batch_single(const CondBatchArgs &a, int max_grid, hipStream_t stream);
 
 hipError_t dispatch_counts_f32(const CountsArgs &a, int max_grid, hipStream_t stream);
 hipError_t dispatch_counts_f64(const CountsArgs &a, int max_grid, hipStream_t stream);
@@ -163,44 +145,39 @@ hipError_t launch_sample_single(int is_f32, const SampleSingleArgs &a, int max_g
     return is_f32 ? dispatch_sample_single_f32(a, max_grid, stream) : dispatch_sample_single_f64(a, max_grid, stream);
 }
 
-hipError_t launch_cond_batch(int is_f32, const int64_t *pool, int64_t rest, TableMeta *meta, int out_table,
-                             const void *out_ptr, const int32_t *ev, int64_t n_rows, int max_grid, hipStream_t stream) {
-    if (n_rows <= 0 || rest <= 0) return hipSuccess;
-    return is_f32 ? dispatch_cond_batch_f32(pool, rest, meta, out_table, out_ptr, ev, n_rows, max_grid, stream)
-                  : dispatch_cond_batch_f64(pool, rest, meta, out_table, out_ptr, ev, n_rows, max_grid, stream);
-}
-
-hipError_t launch_cond_batch_single(int is_f32, const CondBatchSingleArgs &a, int max_grid, hipStream_t stream) {
-    if (a.n_rows <= 0) return hipSuccess;
-    return is_f32 ? dispatch_cond_batch_single_f32(a, max_grid, stream) : dispatch_cond_batch_single_f64(a, max_grid, stream);
-}
-
-hipError_t launch_cond_batch_masked(int is_f32, const int64_t *pool, int64_t rest, TableMeta *meta, int out_table,
-                                    const void *out_ptr, const int32_t *ev, int64_t n_rows, int max_grid,
-                                    hipStream_t stream) {
-    if (n_rows <= 0 || rest <= 0) return hipSuccess;
-    return is_f32 ? dispatch_cond_batch_masked_f32(pool, rest, meta, out_table, out_ptr, ev, n_rows, max_grid, stream)
-                  : dispatch_cond_batch_masked_f64(pool, rest, meta, out_table, out_ptr, ev, n_rows, max_grid, stream);
-}
-
-hipError_t launch_cond_batch_masked_single(int is_f32, const CondBatchMaskedArgs &a, int max_grid, hipStream_t stream) {
-    if (a.n_rows <= 0) return hipSuccess;
-    return is_f32 ? dispatch_cond_batch_masked_single_f32(a, max_grid, stream)
-                  : dispatch_cond_batch_masked_single_f64(a, max_grid, stream);
-}
-
-hipError_t launch_cond_batch_soft(int is_f32, const int64_t *pool, int64_t rest, TableMeta *meta, int out_table,
+template <typename T>
+static hipError_t cond_batch_form(int form, const int64_t *pool, int64_t rest, TableMeta *meta, int out_table,
                                   const void *out_ptr, const int32_t *ev, const void *lam, int64_t n_rows, int max_grid,
                                   hipStream_t stream) {
-    if (n_rows <= 0 || rest <= 0) return hipSuccess;
-    return is_f32 ? dispatch_cond_batch_soft_f32(pool, rest, meta, out_table, out_ptr, ev, lam, n_rows, max_grid, stream)
-                  : dispatch_cond_batch_soft_f64(pool, rest, meta, out_table, out_ptr, ev, lam, n_rows, max_grid, stream);
+    switch (form) {
+    case kCondPlain: return go_cond_batch<T, kCondPlain>(pool, rest, meta, out_table, out_ptr, ev, lam, n_rows, max_grid, stream);
+    case kCondMasked: return go_cond_batch<T, kCondMasked>(pool, rest, meta, out_table, out_ptr, ev, lam, n_rows, max_grid, stream);
+    case kCondWeighted: return go_cond_batch<T, kCondWeighted>(pool, rest, meta, out_table, out_ptr, ev, lam, n_rows, max_grid, stream);
+    }
+    return hipErrorInvalidValue;
+}
+template <typename T>
+static hipError_t cond_batch_single_form(int form, const CondBatchArgs &a, int max_grid, hipStream_t stream) {
+    switch (form) {
+    case kCondPlain: return go_cond_batch_single<T, kCondPlain>(a, max_grid, stream);
+    case kCondMasked: return go_cond_batch_single<T, kCondMasked>(a, max_grid, stream);
+    case kCondWeighted: return go_cond_batch_single<T, kCondWeighted>(a, max_grid, stream);
+    }
+    return hipErrorInvalidValue;
 }
 
-hipError_t launch_cond_batch_soft_single(int is_f32, const CondBatchSoftArgs &a, int max_grid, hipStream_t stream) {
+hipError_t launch_cond_batch(int is_f32, int form, const int64_t *pool, int64_t rest, TableMeta *meta, int out_table,
+                             const void *out_ptr, const int32_t *ev, const void *lam, int64_t n_rows, int max_grid,
+                             hipStream_t stream) {
+    if (n_rows <= 0 || rest <= 0) return hipSuccess;
+    return is_f32 ? cond_batch_form<float>(form, pool, rest, meta, out_table, out_ptr, ev, lam, n_rows, max_grid, stream)
+                  : cond_batch_form<double>(form, pool, rest, meta, out_table, out_ptr, ev, lam, n_rows, max_grid, stream);
+}
+
+hipError_t launch_cond_batch_single(int is_f32, int form, const CondBatchArgs &a, int max_grid, hipStream_t stream) {
     if (a.n_rows <= 0) return hipSuccess;
-    return is_f32 ? dispatch_cond_batch_soft_single_f32(a, max_grid, stream)
-                  : dispatch_cond_batch_soft_single_f64(a, max_grid, stream);
+    return is_f32 ? cond_batch_single_form<float>(form, a, max_grid, stream)
+                  : cond_batch_single_form<double>(form, a, max_grid, stream);
 }
 
 hipError_t launch_counts(int is_f32, const CountsArgs &a, int max_grid, hipStream_t stream) {

@@ -4056,7 +4056,7 @@ bool build_schedule(const std::vector<const VEPlan *> &plans, const std::vector<
         int64_t vb = 0;
         for (; i < ord.size() && items[ord[i]].level == g.level && items[ord[i]].key == g.variant &&
                items[ord[i]].b->lane == g.lane &&
-               !((g.variant == kCondBatchKey || g.variant == kCondBatchMaskKey || g.variant == kCondBatchSoftKey || g.variant == kCountsKey) && (int)i > g.begin);   // one launch per gather / accumulate step
+               !((cond_form_of_key(g.variant) >= 0 || g.variant == kCountsKey) && (int)i > g.begin);   // one launch per gather / accumulate step
              ++i) {
             const Item &it = items[ord[i]];
             BucketDesc &d = s.descs[i];

@@ -258,12 +258,21 @@ constexpr int kMargRowsKey = kXchgKeyBase + 28672;
 constexpr int kCondBatchMaskKey = kXchgKeyBase + 32768;
 // ... of a weighted gather step (BucketSpec::cond_batch with soft_rows: soft variables, masks beside them): the executor's
 constexpr int kCondBatchSoftKey = kXchgKeyBase + 36864;
+// the three forms of a gather step (condbatch.cuh), and the form a launch-group key stands for (-1: no gather key)
+enum CondForm { kCondPlain = 0, kCondMasked = 1, kCondWeighted = 2 };
+constexpr int cond_form_of_key(int key) {
+    return key == kCondBatchKey ? kCondPlain : key == kCondBatchMaskKey ? kCondMasked : key == kCondBatchSoftKey ? kCondWeighted : -1;
+}
 constexpr int kMargRowsPoolHead = 4;      // words before the column blocks of an emit step's pool
 constexpr int kMargRowsColWords = 5;      // words per column block
 constexpr int kCountsMaxDims = 32;  // evidence variables, and other variables, in one factor scope of an accumulate step
 constexpr int kCountsPoolHead = 12; // words before the per-variable rows of an accumulate step's pool
 constexpr int kCondMaxRest = 8;     // rest dims of a gather step after merging adjacent ones
 constexpr int kCondMaxEv = 32;      // evidence variables in one scope of a single-op gather
+// the most pool words of a single-op gather of a form: the head, the evidence and rest words, then a count and
+// kCondMaxRest pairs for the masks and again for the weights
+static_assert(kCondPlain == 0 && kCondMasked == 1 && kCondWeighted == 2, "a form's value counts its blocks after the rest words");
+constexpr int cond_single_pool_words(int form) { return 4 + 3 * kCondMaxEv + 2 * kCondMaxRest + form * (1 + 2 * kCondMaxRest); }
 // byte offset of the degenerate-draw counter in a sampling step's out_table
 inline int64_t sample_counter_offset(int64_t n_vars, int64_t n_samples) { return (n_vars * n_samples + 7) / 8 * 8; }
 

@@ -372,28 +372,16 @@ int launch(Context &ctx, Executable &ex, hipStream_t stream, const XchgHooks *ho
                                    static_cast<double *>(ex.h_meta[d.out_table].ptr),
                                    std::min(ex.marg_rows_live, d.n_tiles), ctx.max_grid, st);
             if (err != hipSuccess) return fail(ctx, err, "launch_marg_rows");
-        } else if (g.variant == kCondBatchKey) {             // a gather step of a batch plan (condbatch.cuh)
+        } else if (const int form = cond_form_of_key(g.variant); form >= 0) {   // a gather step of a batch plan (condbatch.cuh)
             const BucketDesc &d = sc.descs[g.begin];
-            if (d.in_table[1] < 0) return fail(ctx, hipErrorInvalidValue, "gather step without an evidence table");
-            err = launch_cond_batch(ex.dtype == kF32, ex.d_pool + d.dim_off, sc.pool[d.dim_off + 3], ex.d_meta, d.out_table,
+            const bool weighted = form == kCondWeighted;     // the likelihood table is the weighted form's alone
+            if (d.in_table[1] < 0 || (weighted && d.in_table[2] < 0))
+                return fail(ctx, hipErrorInvalidValue, weighted ? "weighted gather step without an evidence or a likelihood table"
+                                                                : "gather step without an evidence table");
+            err = launch_cond_batch(ex.dtype == kF32, form, ex.d_pool + d.dim_off, sc.pool[d.dim_off + 3], ex.d_meta, d.out_table,
                                     ex.h_meta[d.out_table].ptr, static_cast<const int32_t *>(ex.h_meta[d.in_table[1]].ptr),
-                                    d.n_tiles, ctx.max_grid, st);
+                                    weighted ? ex.h_meta[d.in_table[2]].ptr : nullptr, d.n_tiles, ctx.max_grid, st);
             if (err != hipSuccess) return fail(ctx, err, "launch_cond_batch");
-        } else if (g.variant == kCondBatchMaskKey) {         // a masked gather step: partial evidence variables (condbatch.cuh)
-            const BucketDesc &d = sc.descs[g.begin];
-            if (d.in_table[1] < 0) return fail(ctx, hipErrorInvalidValue, "gather step without an evidence table");
-            err = launch_cond_batch_masked(ex.dtype == kF32, ex.d_pool + d.dim_off, sc.pool[d.dim_off + 3], ex.d_meta,
-                                           d.out_table, ex.h_meta[d.out_table].ptr,
-                                           static_cast<const int32_t *>(ex.h_meta[d.in_table[1]].ptr), d.n_tiles, ctx.max_grid, st);
-            if (err != hipSuccess) return fail(ctx, err, "launch_cond_batch_masked");
-        } else if (g.variant == kCondBatchSoftKey) {         // a weighted gather step: soft variables (condbatch.cuh)
-            const BucketDesc &d = sc.descs[g.begin];
-            if (d.in_table[1] < 0 || d.in_table[2] < 0)
-                return fail(ctx, hipErrorInvalidValue, "weighted gather step without an evidence or a likelihood table");
-            err = launch_cond_batch_soft(ex.dtype == kF32, ex.d_pool + d.dim_off, sc.pool[d.dim_off + 3], ex.d_meta, d.out_table,
-                                         ex.h_meta[d.out_table].ptr, static_cast<const int32_t *>(ex.h_meta[d.in_table[1]].ptr),
-                                         ex.h_meta[d.in_table[2]].ptr, d.n_tiles, ctx.max_grid, st);
-            if (err != hipSuccess) return fail(ctx, err, "launch_cond_batch_soft");
         } else if (g.variant == kCountsKey) {                // accumulate steps of a counts plan (counts.cuh)
             // the consecutive accumulate groups (one step each, scratch of their own) run as ONE launch of each pass
             if (!ex.counts_acc || !ex.d_counts_args) return fail(ctx, hipErrorInvalidValue, "accumulate step without accumulators");

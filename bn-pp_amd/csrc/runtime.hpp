@@ -93,46 +93,24 @@ hipError_t launch_sample_rows_batch(int is_f32, const int64_t *pool, const Table
                                     unsigned long long *deg_rows, int64_t lanes, const SampleBatchLaunch &a, int max_grid,
                                     hipStream_t stream);
 // batched conditioning (condbatch.cuh): one gather step of a batch plan (pool:
-// the step's words in the dims pool, rest: its rest entries) into table
-// out_table (at out_ptr) for the n_rows rows of ev = int32[.][n_rows]
-hipError_t launch_cond_batch(int is_f32, const int64_t *pool, int64_t rest, TableMeta *meta, int out_table,
-                             const void *out_ptr, const int32_t *ev, int64_t n_rows, int max_grid, hipStream_t stream);
-// ... and one gather with its metadata in the kernel-argument segment (bnpp_condition_batch)
-struct CondBatchSingleArgs {
-    int64_t pool[4 + 3 * kCondMaxEv + 2 * kCondMaxRest];
-    const void *src;
-    void *out;
-    const int32_t *ev;
-    int64_t n_rows;
-};
-hipError_t launch_cond_batch_single(int is_f32, const CondBatchSingleArgs &a, int max_grid, hipStream_t stream);
-// the masked forms (missing values: partial evidence variables among the rest dims); the pool continues with
-// n_p and n_p x (row of ev, rest dim)
-hipError_t launch_cond_batch_masked(int is_f32, const int64_t *pool, int64_t rest, TableMeta *meta, int out_table,
-                                    const void *out_ptr, const int32_t *ev, int64_t n_rows, int max_grid,
-                                    hipStream_t stream);
-struct CondBatchMaskedArgs {
-    int64_t pool[4 + 3 * kCondMaxEv + 2 * kCondMaxRest + 1 + 2 * kCondMaxRest];
-    const void *src;
-    void *out;
-    const int32_t *ev;
-    int64_t n_rows;
-};
-hipError_t launch_cond_batch_masked_single(int is_f32, const CondBatchMaskedArgs &a, int max_grid, hipStream_t stream);
-// the weighted forms (soft evidence: soft variables among the rest dims, masks beside them); lam is T[Ws][n_rows]; the
-// pool continues after the masked words with n_s and n_s x (first row of lam, rest dim)
-hipError_t launch_cond_batch_soft(int is_f32, const int64_t *pool, int64_t rest, TableMeta *meta, int out_table,
-                                  const void *out_ptr, const int32_t *ev, const void *lam, int64_t n_rows, int max_grid,
-                                  hipStream_t stream);
-struct CondBatchSoftArgs {
-    int64_t pool[4 + 3 * kCondMaxEv + 2 * kCondMaxRest + 1 + 2 * kCondMaxRest + 1 + 2 * kCondMaxRest];
+// the step's words in the dims pool, rest: its rest entries) in one of the
+// three forms (plan.hpp CondForm) into table out_table (at out_ptr) for the
+// n_rows rows of ev = int32[.][n_rows]; lam = T[Ws][n_rows] is the weighted
+// form's alone, null in the others
+hipError_t launch_cond_batch(int is_f32, int form, const int64_t *pool, int64_t rest, TableMeta *meta, int out_table,
+                             const void *out_ptr, const int32_t *ev, const void *lam, int64_t n_rows, int max_grid,
+                             hipStream_t stream);
+// ... and one gather with its metadata in the kernel-argument segment (bnpp_condition_batch, _mv, _sv): a form's
+// pool holds at most cond_single_pool_words(form) words
+struct CondBatchArgs {
+    int64_t pool[cond_single_pool_words(kCondWeighted)];
     const void *src;
     void *out;
     const int32_t *ev;
     const void *lam;
     int64_t n_rows;
 };
-hipError_t launch_cond_batch_soft_single(int is_f32, const CondBatchSoftArgs &a, int max_grid, hipStream_t stream);
+hipError_t launch_cond_batch_single(int is_f32, int form, const CondBatchArgs &a, int max_grid, hipStream_t stream);
 // expected counts (counts.cuh): one factor's belief T over (rest, b) folded
 // into its accumulator, normalised row by row (include/bnpp.h,
 // bnpp_bucket_counts, states the arithmetic).  Everything by value in the

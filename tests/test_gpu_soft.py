@@ -2,7 +2,8 @@
 
   * the weighted gather alone (bnpp_condition_batch_sv) against
     soft_ref.weighted_gather, bit for bit in both dtypes between guard bands:
-    the products come in the scope's order, each rounded once.
+    the products come in the scope's order, each rounded once; and the three
+    forms of the gather against each other on one table.
   * whole runs against a brute-force joint with the likelihoods as unary
     factors, within the project's own tolerances: 1e-12 (fp64) and 1e-5 (fp32)
     relative for Z, posteriors and marginals, n x those for counts.
@@ -49,6 +50,8 @@ OPS = [
     dict(name="partial_soft_hard", cards=[2, 3, 2], scope=[0, 1, 2], ev=[0, 2], partial=[0], soft=[1]),   # rest 6
     dict(name="s_outside_scope", cards=[3, 2, 4], scope=[0, 1], ev=[1], partial=[], soft=[2]),            # the unmasked kernel
 ]
+# one table for the three forms of the gather against each other: R = 5 takes the narrow path, R = 260 the wide one
+THREE_FORMS = dict(name="three_forms", cards=[3, 2, 4], scope=[0, 1, 2], ev=[1], partial=[1], soft=[0])
 ROWS = [1, 63, 64, 65, 257]
 LAMS = ["random", "ones", "onehot", "zeros"]
 
@@ -191,14 +194,16 @@ def test_weighted_gather_under_a_capped_grid(ctx, stream, grid_cap, cap):
 def test_one_hot_and_all_ones_are_the_masked_gather(ctx, stream, dt):
     """A one-hot block gives the bits of the masked gather with that value observed, an all-ones block those of
     the value missing: hard and missing values are the corners of soft evidence."""
-    for i, op in enumerate(OPS[:8]):
-        for R in (64, 65):
+    for i, (op, rows) in enumerate([(op, (64, 65)) for op in OPS[:8]] + [(THREE_FORMS, (5, 260))]):
+        for R in rows:
             rng = np.random.default_rng(700 + i)
             cards, scope = op["cards"], op["scope"]
             src = rng.uniform(0.05, 1.0, int(np.prod([cards[v] for v in scope]))).astype(ND[dt])
             ev = _op_ev(op, R, rng)
             vals = np.stack([rng.integers(0, cards[v], R) for v in op["soft"]]).astype(np.int32)
             vals[:, rng.random(R) < 0.3] = MISSING              # these rows: all ones
+            if op is THREE_FORMS:
+                vals[:, 1:] = MISSING                           # all but the first row: the all-ones corner on its own
             lam = np.zeros((sum(cards[v] for v in op["soft"]), R), dtype=ND[dt])
             at = 0
             for j, v in enumerate(op["soft"]):
@@ -213,6 +218,24 @@ def test_one_hot_and_all_ones_are_the_masked_gather(ctx, stream, dt):
             masked = _gather(ctx, stream, op, dt, R, src, ev2, None, partial=op["partial"] + op["soft"], soft=False,
                              ev_vars=op["ev"] + op["soft"])
             _same(got, masked, (op["name"], dt, R))
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("R", [5, 260])
+def test_masked_with_nothing_missing_is_the_plain_gather(ctx, stream, dt, R):
+    """One source over cards (3, 2, 4): the masked form with no value missing is the plain gather at the observed digit
+    and +0 at the other.  (The weighted form against the masked one on this table: the test above.)"""
+    op = THREE_FORMS
+    rng = np.random.default_rng(900 + R)
+    src = rng.uniform(0.05, 1.0, 24).astype(ND[dt])
+    ev = rng.integers(0, 2, (1, R)).astype(np.int32)
+    plain = _gather(ctx, stream, op, dt, R, src, ev, None, partial=[], soft=False).reshape(3, 4, R)
+    masked = _gather(ctx, stream, op, dt, R, src, ev, None, soft=False)
+    want = np.zeros((3, 2, 4, R), dtype=ND[dt])
+    for b in range(R):
+        want[:, ev[0, b], :, b] = plain[:, :, b]
+    assert np.array_equal(plain, src.reshape(3, 2, 4)[:, ev[0], :].transpose(0, 2, 1)), "the plain gather itself"
+    _same(masked, want.reshape(-1), ("masked against plain", dt, R))
 
 
 def test_nine_rest_dims_are_unsupported(ctx, stream):
