@@ -45,6 +45,57 @@ second padded.
         must hold only keys of LEVEL_KEYS["f32"]: the control of the GPU
         comparison is then made of kernels the suite already holds to bits.
 
+Calls.  Beside bnpp.plan_batch the sweep plans the same models, evidence sets,
+R, dtypes and offset widths through bnpp.plan_counts, plan_marginals_batch (all
+variables as targets), plan_sample_batch (SAMPLE_K = 2 draws) and
+plan_mpe_batch (its product groups only: the max keys have their own census,
+mpe_level_catalogue.py).  Their forward sweeps are plan_batch's; the backward
+pass of the bucket tree (counts, marginals) lays B-carrying buckets out anew.
+An entry of those calls has "call" (an entry without it means "batch"),
+"partial" and "soft" (both null: see Forms).  A key plan_batch supplies keeps
+its plan_batch entry, chosen as before; the other calls add entries only for
+the keys plan_batch does not reach, by the same rule (smallest arena; ties:
+smaller R, model, evidence set, then the order of CALLS).  Conditions of such
+an entry, in both dtypes: the fp32 row condition above (fp32), and the R = 1
+plan of the same call holds only keys of LEVEL_KEYS[dtype] and of plan_batch's
+entries, which test_gpu_batch_variants.py holds to bits against the single
+calls -- the GPU comparison of the entry's R with R = 1 then has a known side.
+Found: keys 82 and 1106 (both dtypes), 100 (fp32), 6434 (both), 6466 and 7201
+(fp64), 6948, 6980 and 17428 (fp32), all through counts or marginals; the
+sample and mpe plans hold no key the others do not.  Not catalogued because no
+case passes the R = 1 control (every plan of Water that holds them has an
+R = 1 plan with a key outside the held set): fp64 stream 5924 and fp32 stream
+5956; they stay "no plan found" in test_variant_census.UNREACHED_LEVEL.
+
+Forms.  Every call is swept with plain evidence (no partial and no soft
+variable); plan_batch and plan_sample_batch also with the last evidence
+variable partial ("last") and with every one partial ("all"): FORMS.  All five
+forms of all five calls take more than ten minutes on 8 cores (a keys-only
+probe of the four other forms alone took 588 s), so the forms whose families
+hold no key beyond the others' are left out -- by that probe: one soft variable
+for plan_batch, plan_sample_batch and plan_mpe_batch; all partial + soft for
+every call; every partial or soft form of plan_mpe_batch; all partial for
+plan_counts and plan_marginals_batch.  Also left out, though the probe saw a
+key there: last-partial and soft evidence for plan_counts and
+plan_marginals_batch, whose only keys beyond the catalogue are fp64 5924 and
+fp32 5956, held at R = 1 itself by plans of Water (so no R = 1 control can be
+made of held kernels, as with plain evidence).
+
+An entry with partial variables has "call", "partial" (the variable ids) and
+"miss_seed": its rows are the distinct assignments with each cell of a partial
+variable MISSING with probability MISSING_FRAC, drawn by punch() from
+random.Random(miss_seed), duplicates dropped; a case needs a missing and an
+observed partial cell.  The oracle Z of such a row is that of its observed
+entries, and the fp32 row condition and "mixed_launch" use it.  The entries
+found: fp64 6436 and 6466 (insurance, both of [0, 8] partial, posterior of 1,
+R = 2 and 4; 6466 replaces the larger marginals entry), fp64 20513 (Water, [5]
+partial, R = 2), fp32 6436 and 6468 (insurance, as fp64), fp32 20770 (Water,
+[4, 31] partial, R = 2) and fp32 4648 (Water, [11] partial, R = 2: with plain
+evidence no case of this key passed the fp32 row condition; a missing cell
+sums the variable out, and its rows pass).  plan_sample_batch's partial plans
+hold 4648 and 20770 too, in larger arenas, so every entry is plan_batch's and
+no entry has "call": "sample".  No key the partial sweep found is left out.
+
 batch_catalogue_data.json holds the entries, per dtype every sum-kernel key
 any plan of the sweep held ("swept": test_batch_census.py checks them against
 the dispatch switches), and per (dtype, family) the index of the entry whose
@@ -100,14 +151,38 @@ class no_o32:
             os.environ["BNPP_NO_O32"] = self.old
 
 
+CALLS = ("batch", "counts", "marginals", "sample", "mpe")
+SAMPLE_K = 2                   # draws per row of the "sample" entries
+MAX_KEY_BASE = 65536           # the max family's keys start here (plan_mpe_batch: product groups only are recorded)
+
+
+def call_of(e):
+    return e.get("call", "batch")
+
+
 def plan(bnpp, e, model=None, R=None):
-    """bnpp.plan_batch of a catalogue entry (at another R if given) -> (stats, groups)."""
+    """The plan function of a catalogue entry's call (at another R if given) -> (stats, groups):
+    bnpp.plan_batch (an entry without "call"), plan_counts, plan_marginals_batch (all variables),
+    plan_sample_batch (SAMPLE_K draws) or plan_mpe_batch, whose max groups are left out."""
     from conftest import model_path
     m = model or bnpp.Model.load(model_path(e["model"] + ".uai"))
+    kw = dict(dtype=bnpp.F32 if e["dtype"] == "f32" else bnpp.F64, rows_per_launch=e["R"] if R is None else R,
+              partial=e.get("partial"), soft=e.get("soft"))
+    call = call_of(e)
     with no_o32(e["no_o32"]):
-        st, groups, _ = bnpp.plan_batch(m, e["ev_vars"], target=e["target"], dtype=bnpp.F32 if e["dtype"] == "f32" else bnpp.F64,
-                                        rows_per_launch=e["R"] if R is None else R)
-    return st, groups
+        if call == "batch":
+            res = bnpp.plan_batch(m, e["ev_vars"], target=e["target"], **kw)
+        elif call == "counts":
+            res = bnpp.plan_counts(m, e["ev_vars"], **kw)
+        elif call == "marginals":
+            res = bnpp.plan_marginals_batch(m, e["ev_vars"], **kw)
+        elif call == "sample":
+            res = bnpp.plan_sample_batch(m, e["ev_vars"], SAMPLE_K, **kw)
+        else:
+            assert call == "mpe", call
+            res = bnpp.plan_mpe_batch(m, e["ev_vars"], **kw)
+    groups = res[1] if call != "mpe" else [g for g in res[1] if not MAX_KEY_BASE <= g["key"] < (1 << 24)]
+    return res[0], groups
 
 
 def rows_of(e):
@@ -158,9 +233,19 @@ def ev_sets(name, d):
     return out
 
 
-def scan_model(name):
-    """Every plan of one model: ({(dtype, key): [(cost, case)]}, the same for the cases over
-    a zero entry's scope alone, {dtype: keys held by any plan})."""
+# the evidence forms swept per call (Forms in the module docstring): "last" the last evidence variable
+# partial, "all" every one
+FORMS = {"batch": ("plain", "last", "all"), "counts": ("plain",), "marginals": ("plain",),
+         "sample": ("plain", "last", "all"), "mpe": ("plain",)}
+MISSING = -1                   # bnpp.MISSING (BNPP_MISSING)
+MISSING_FRAC = 0.25
+
+
+def scan_model(task):
+    """Every plan of one model, call and evidence form: ({(dtype, key): [(cost, case)]}, the same
+    for the cases over a zero entry's scope alone, {dtype: keys held by any plan})."""
+    name, call, form = task
+    plain = call == "batch" and form == "plain"          # the sweep as it was before the other calls and forms
     import bnpp
     from bnpp import synth
     from conftest import model_path
@@ -172,18 +257,23 @@ def scan_model(name):
     zscope = zero_scope(d) if d["type"] == "BAYES" else None
     for ev in ev_sets(name, d):
         free = [v for v in range(m.n_vars) if v not in ev]
-        for target in (None, free[0]):
+        for target in ((None, free[0]) if call == "batch" else (None,)):
             for dt in ("f64", "f32"):
                 for o32off in (False, True):
-                    control = None               # fp32: does the R = 1 plan hold LEVEL_KEYS keys only?
+                    control = None               # batch, fp32: does the R = 1 plan hold LEVEL_KEYS keys only?
+                    r1 = None                    # the other calls: the R = 1 plan's keys (regenerate() judges them)
                     for R in R_LIST:
                         e = {"dtype": dt, "model": name, "ev_vars": ev, "target": target, "R": R, "no_o32": o32off}
+                        if not plain:
+                            e.update(call=call, partial=None if form == "plain" else ev[-1:] if form == "last" else ev,
+                                     soft=None)
                         try:
                             st, groups = plan(bnpp, e, model=m)
                         except bnpp.BnppError:
                             continue
                         if R == 1:
-                            control = set(sum_keys(groups)) <= known["f32"]
+                            control = not plain or set(sum_keys(groups)) <= known["f32"]
+                            r1 = sum_keys(groups)
                         for key in sum_keys(groups):
                             fam = family_of(key)
                             if o32off and fam != "generic":
@@ -191,10 +281,15 @@ def scan_model(name):
                             swept[dt].add(key)
                             if key in known[dt] or st["arena_bytes"] > MAX_ARENA or (dt == "f32" and not control):
                                 continue
+                            if not plain and r1 is None:
+                                continue
                             vb = max(g["vblocks"] for g in groups if g["key"] == key)
-                            cost = (int(st["arena_bytes"]), R, name, ev, target is not None, o32off)
+                            cost = (not plain, int(st["arena_bytes"]), R, name, ev, target is not None, o32off,
+                                    CALLS.index(call), FORMS[call].index(form))
                             case = dict(e, key=key, family=fam, arena_bytes=int(st["arena_bytes"]), vblocks=int(vb))
-                            if ev == zscope:
+                            if not plain:
+                                case["r1_keys"] = r1
+                            if ev == zscope and plain:
                                 zero.setdefault((dt, key), []).append((cost, case))
                             lst = cand.setdefault((dt, key), [])
                             lst.append((cost, case))
@@ -208,7 +303,7 @@ def search(procs=None):
     import multiprocessing as mp
     cand, zero, swept = {}, {}, {"f64": set(), "f32": set()}
     with mp.Pool(procs or min(16, os.cpu_count() or 4)) as pool:
-        for c, z, s in pool.imap_unordered(scan_model, models()):
+        for c, z, s in pool.imap_unordered(scan_model, [(n, c, f) for c in CALLS for f in FORMS[c] for n in models()]):
             for dt in s:
                 swept[dt] |= s[dt]
             for k, lst in c.items():
@@ -257,12 +352,33 @@ class Oracle:
         return self.z[k]
 
 
+def punch(rows, cols, seed):
+    """The rows with about MISSING_FRAC of the cells of `cols` MISSING (random.Random(seed), row by row, column
+    by column), duplicates dropped; None unless some cell of `cols` is missing and some is observed."""
+    rng = random.Random(seed)
+    out = []
+    for r in rows:
+        r = list(r)
+        for j in cols:
+            if rng.random() < MISSING_FRAC:
+                r[j] = MISSING
+        if r not in out:
+            out.append(r)
+    cells = [r[j] for r in out for j in cols]
+    return out if MISSING in cells and any(x != MISSING for x in cells) else None
+
+
 def choose_rows(case, cards, oracle):
     """(the distinct assignments an entry runs, their oracle Z) or None when the
     fp32 row condition leaves too few."""
     ev = case["ev_vars"]
     allrows = assignments(cards, ev, zlib.crc32(repr((case["model"], ev)).encode()))
-    z = [oracle.partition(case["model"], ev, a) for a in allrows]
+    if case.get("partial"):
+        allrows = punch(allrows, [ev.index(v) for v in case["partial"]], case["miss_seed"])
+        if allrows is None:
+            return None
+    z = [oracle.partition(case["model"], [v for v, x in zip(ev, a) if x != MISSING], [x for x in a if x != MISSING])
+         for a in allrows]
     if case["dtype"] == "f64":
         return allrows, z
     top = max(z)
@@ -290,28 +406,42 @@ def control_ok(bnpp, case, model):
 
 
 def regenerate(path=DATA):
-    """Rebuild the frozen table (needs the built library and the oracle; minutes)."""
+    """Rebuild the frozen table (needs the built library and the oracle; 206 s on 8 cores)."""
     import bnpp
     from bnpp import synth
     from conftest import model_path
+    from test_variant_census import LEVEL_KEYS
     cand, zero, swept = search()
     oracle = Oracle()
     loaded = {}
     entries, dropped = [], []
-    for (dt, key) in sorted(cand):
+    # plan_batch's keys first: a key plan_batch supplies keeps its plan_batch entry, and those keys, with
+    # LEVEL_KEYS, are the kernels the R = 1 control of another call's entry may hold
+    order = sorted(cand, key=lambda k: (cand[k][0][0][0], k))
+    held = {dt: set(LEVEL_KEYS[dt]) for dt in LEVEL_KEYS}
+    for (dt, key) in order:
         chosen = None
-        for _, case in cand[(dt, key)]:
+        for cost, case in cand[(dt, key)]:
+            if cost[0]:                          # a call other than plan_batch
+                held_now = held[dt] | {e["key"] for e in entries if e["dtype"] == dt and "call" not in e}
+                case = dict(case)
+                if not set(case.pop("r1_keys")) <= held_now:
+                    dropped.append((dt, key, case["model"], case["ev_vars"], case["R"],
+                                    "%s %s R = 1 control" % (case["call"], case["partial"])))
+                    continue
             name = case["model"]
             if name not in loaded:
                 p = model_path(name + ".uai")
                 loaded[name] = (bnpp.Model.load(p), synth.read_uai(p))
             m, d = loaded[name]
-            if dt == "f32" and not control_ok(bnpp, case, m):
+            if dt == "f32" and "call" not in case and not control_ok(bnpp, case, m):
                 dropped.append((dt, key, name, case["ev_vars"], case["R"], "R = 1 control"))
                 continue
+            if case.get("partial"):
+                case = dict(case, miss_seed=zlib.crc32(repr((name, case["ev_vars"], case["partial"])).encode()))
             got = choose_rows(case, d["cards"], oracle)
             if got is None:
-                dropped.append((dt, key, name, case["ev_vars"], case["R"], "fp32 rows"))
+                dropped.append((dt, key, name, case["ev_vars"], case["R"], "rows"))
                 continue
             rows, z = got
             chosen = finish(case, rows, z)
@@ -324,10 +454,11 @@ def regenerate(path=DATA):
         # a partition and a posterior with an impossible row (-inf / 0, a NaN row): where no smallest case
         # holds one, one more fp64 entry, the smallest case over a zero entry's scope whose launch mixes
         # an impossible row with possible ones
-        if any(e["mixed_launch"] and (e["target"] is not None) == posterior for e in entries if e["dtype"] == "f64"):
+        if any(e["mixed_launch"] and (e["target"] is not None) == posterior for e in entries
+               if e["dtype"] == "f64" and "call" not in e):
             continue
         for _, case in sorted((c for k, lst in zero.items() if k[0] == "f64" for c in lst), key=lambda c: c[0]):
-            if (case["target"] is not None) != posterior:
+            if (case["target"] is not None) != posterior or "call" in case:
                 continue
             d = synth.read_uai(model_path(case["model"] + ".uai"))
             e = finish(case, *choose_rows(case, d["cards"], oracle))
@@ -335,7 +466,8 @@ def regenerate(path=DATA):
                 entries.append(dict(e, extra="impossible row"))
                 break
     for posterior in (False, True):
-        assert any(e["mixed_launch"] and (e["target"] is not None) == posterior for e in entries if e["dtype"] == "f64"), \
+        assert any(e["mixed_launch"] and (e["target"] is not None) == posterior for e in entries
+                   if e["dtype"] == "f64" and "call" not in e), \
             "no fp64 entry mixes an impossible row with possible ones"
     entries.sort(key=lambda e: (e["dtype"], e["key"], "extra" in e))
     capped = {}

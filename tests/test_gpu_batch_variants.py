@@ -20,6 +20,23 @@ Per catalogue entry (n_rows = R + 3 or R + 1: two launches, the second padded):
     (asserted first; the catalogue's rows span less than 2^30 by the oracle).
     log10_z within 1e-6 relative of the fp64 batch, posteriors within 1e-5
     absolute: the project's fp32 tolerances.
+  * entries of the other batched calls ("call": counts, marginals; plain
+    evidence), with their own plan function as the instrument: every
+    output has the bits of the same call at rows_per_launch = 1 (fp32 after the
+    span assertion), a plan of kernels already held to bits
+    (test_batch_census.py).  counts, fp64: log10_z with partition_batch's
+    bits, counts within n x 1e-12 of counts_ref's brute force where the joint
+    has at most 2^16 states, else every factor's counts sum to the possible
+    rows within n x 1e-12.  marginals, fp64: log10_z with partition_batch's
+    bits, every distinct row within 1e-12 of bnpp.marginals, evidence
+    variables one-hot, impossible rows NaN.  fp32: marginals within 1e-5,
+    counts within n x 1e-5, log10_z within 1e-6 relative of the fp64 call.
+  * entries with partial evidence variables (plan_batch; the stored rows hold MISSING in about a quarter of the partial cells): the
+    bits of rows_per_launch = 1 as above, and against the single calls on the
+    per-row masked model of missing_ref.py with the row's hard entries as
+    evidence -- fp64 partitions: z with bnpp.partition's bits, log10_z within
+    4 ulp; fp64 posteriors within 1e-12 of bnpp.marginals; fp32
+    within 1e-6 relative (log10_z) / 1e-5 (posteriors) of the fp64 call.
   * the entry of each (dtype, family) whose key has the most virtual blocks
     runs again on a context capped at 1, 2 and 3 workgroups with the same bits
     (generic and stream; the slab grid is flat and is not capped).
@@ -93,7 +110,187 @@ def _same_bits(a, b):
     return all(x.shape == y.shape and np.array_equal(_bits(x), _bits(y)) for x, y in zip(a, b))
 
 
+def _same(a, b):
+    """Two calls' outputs: same shapes, NaN in the same places, the same bits elsewhere (floats) or equal (integers)."""
+    for x, y in zip(a, b):
+        if x.shape != y.shape:
+            return False
+        if x.dtype.kind != "f":
+            if not np.array_equal(x, y):
+                return False
+            continue
+        nan = np.isnan(x)
+        if not np.array_equal(nan, np.isnan(y)) or not np.array_equal(_bits(x)[~nan], _bits(y)[~nan]):
+            return False
+    return True
+
+
+def _run_call(ctx, e, rows, dtype, R):
+    """Every output of an entry's batched call, as a tuple of arrays."""
+    m, _ = _model(e["model"])
+    call, ev = bc.call_of(e), e["ev_vars"]
+    if call == "batch":
+        if e["target"] is None:
+            lz, z, _ = bnpp.partition_batch(ctx, m, ev, rows, dtype=dtype, rows_per_launch=R, partial=e.get("partial"))
+            return lz, z
+        return (bnpp.posterior_batch(ctx, m, ev, rows, e["target"], dtype=dtype, rows_per_launch=R,
+                                     partial=e.get("partial"))[0],)
+    assert e.get("partial") is None, "counts and marginals are swept with plain evidence"
+    if call == "counts":
+        counts, lz, n_imp = bnpp.expected_counts(ctx, m, ev, rows, dtype=dtype, rows_per_launch=R)
+        return counts, lz, np.array([n_imp])
+    assert call == "marginals", call                     # no sample or mpe plan supplies an entry: their keys, where
+    return bnpp.marginals_batch(ctx, m, ev, rows, dtype=dtype, rows_per_launch=R)   # any, have a plan_batch entry
+
+
+def _check_call_entry(ctx, e, capped, grid_cap):
+    """An entry of plan_counts / plan_marginals_batch (module docstring)."""
+    from bnpp import synth
+    import counts_ref
+    m, _ = _model(e["model"])
+    call, ev, R, n = bc.call_of(e), e["ev_vars"], e["R"], e["n_rows"]
+    assert call in ("counts", "marginals") and e["partial"] is None and e["soft"] is None
+    rows = np.array(bc.rows_of(e), dtype=np.int64)
+    idx = np.arange(n) % len(e["rows"])
+    tag = (e["dtype"], e["key"], call, e["model"], ev, R)
+    dtype = DT[e["dtype"]]
+    _, groups = bc.plan(bnpp, e, model=m)
+    assert e["key"] in {g["key"] for g in groups}, (tag, bc.sum_keys(groups))
+    got = _run_call(ctx, e, rows, dtype, R)
+    assert len(got[1]) == n
+    distinct = np.array(e["rows"], dtype=np.int64)
+    if e["dtype"] == "f32":
+        _, zc, _ = bnpp.partition_batch(ctx, m, ev, distinct, dtype=bnpp.F32, rows_per_launch=1)
+        assert (zc > 0).all() and zc.max() / zc.min() < 2.0 ** 40, (tag, zc.min(), zc.max())
+    one = _run_call(ctx, e, rows, dtype, 1)
+    assert _same(got, one), (tag, "differs from rows_per_launch = 1")
+    b64 = got if e["dtype"] == "f64" else _run_call(ctx, e, rows, bnpp.F64, R)
+    free = [v for v in range(m.n_vars) if v not in ev]
+    if call in ("counts", "marginals"):
+        lz = got[1]
+        if e["dtype"] == "f64":
+            lzb, zb, _ = bnpp.partition_batch(ctx, m, ev, rows, dtype=bnpp.F64, rows_per_launch=R)
+            assert np.array_equal(_bits(lz), _bits(lzb)), (tag, "log10_z is not partition_batch's")
+            ok = zb > 0
+        else:
+            fin = np.isfinite(b64[1])
+            assert np.array_equal(np.isfinite(lz), fin) and fin.all(), tag
+            assert (np.abs(lz - b64[1]) <= 1e-6 * np.maximum(1.0, np.abs(b64[1]))).all(), (tag, lz, b64[1])
+            ok = fin
+    if call == "counts":
+        d = synth.read_uai(model_path(e["model"] + ".uai"))
+        per = bnpp.split_counts(d, got[0])
+        assert int(got[2][0]) == int((~ok).sum()), tag
+        if e["dtype"] == "f64":
+            if np.prod([float(c) for c in d["cards"]]) <= 2 ** 16:
+                want, z = counts_ref.brute_counts(d, ev, rows)
+                assert np.array_equal(z > 0, ok), tag
+                worst = max(float(np.abs(g - w).max()) for g, w in zip(per, want))
+                print(tag, "worst |count - brute|", worst, "bound", n * 1e-12)
+                assert worst <= n * 1e-12, (tag, worst)
+            else:
+                for sc, N in zip(d["scopes"], per):
+                    assert abs(N.sum() - ok.sum()) <= n * 1e-12, (tag, sc, N.sum(), int(ok.sum()))
+        else:
+            worst = float(np.abs(got[0] - b64[0]).max())
+            print(tag, "worst |fp32 count - fp64 count|", worst, "bound", n * 1e-5)
+            assert worst <= n * 1e-5, (tag, worst)
+    elif call == "marginals":
+        blocks = bnpp.split_marginals(m.cards, None, got[0])
+        if e["dtype"] == "f64":
+            for j, a in enumerate(e["rows"]):
+                sel = np.flatnonzero(idx == j)
+                for v, x in zip(ev, a):                  # an evidence variable reads one-hot
+                    assert np.array_equal(blocks[v][sel], np.tile(np.eye(m.cards[v])[x], (len(sel), 1))), (tag, j, v)
+                if not ok[sel[0]]:                       # an impossible row reads NaN elsewhere
+                    assert all(np.isnan(blocks[v][sel]).all() for v in free), (tag, j)
+                    continue
+                single = bnpp.marginals(ctx, m, dict(zip(ev, a)), "mf", bnpp.F64, targets=free)[0]
+                for v in free:
+                    err = np.abs(blocks[v][sel] - np.array(single[v])).max()
+                    assert err <= 1e-12, (tag, j, v, err)
+        else:
+            err = np.abs(got[0] - b64[0]).max()
+            assert err <= 1e-5, (tag, err)
+    if capped and e["family"] != "slab":
+        for cap in (1, 2, 3):
+            grid_cap(cap)
+            again = _run_call(ctx, e, rows, dtype, R)
+            grid_cap(0)
+            assert _same(got, again), (tag, cap)
+
+
+def _check_partial_entry(ctx, e, capped, grid_cap):
+    """An entry of plan_batch with partial evidence variables: against the single calls on
+    the per-row masked model (missing_ref.masked_model: the mask-carrying factors times the row's indicator of
+    its observed partial entries), with the row's hard entries as evidence (module docstring)."""
+    from bnpp import synth
+    import missing_ref
+    m, _ = _model(e["model"])
+    d = synth.read_uai(model_path(e["model"] + ".uai"))
+    call, ev, part, R, n = bc.call_of(e), e["ev_vars"], e["partial"], e["R"], e["n_rows"]
+    assert call == "batch" and part and e["soft"] is None
+    hard = [v for v in ev if v not in part]
+    rows = np.array(bc.rows_of(e), dtype=np.int64)
+    idx = np.arange(n) % len(e["rows"])
+    cols = [ev.index(v) for v in part]
+    assert (rows[:, cols] == bnpp.MISSING).any() and (rows[:, cols] != bnpp.MISSING).any()
+    tag = (e["dtype"], e["key"], call, e["model"], ev, part, e["target"], R)
+    dtype = DT[e["dtype"]]
+    _, groups = bc.plan(bnpp, e, model=m)
+    assert e["key"] in {g["key"] for g in groups}, (tag, bc.sum_keys(groups))
+    mf = bnpp.plan_batch(m, ev, partial=part)[-1]
+    assert mf == missing_ref.mask_factors(d, ev, part), tag
+    masked = [(bnpp.Model.from_dict(missing_ref.masked_model(d, ev, mf, a)), {v: int(a[ev.index(v)]) for v in hard})
+              for a in e["rows"]]
+    got = _run_call(ctx, e, rows, dtype, R)
+    assert len(got[0]) == n
+    distinct = np.array(e["rows"], dtype=np.int64)
+    if e["dtype"] == "f32":
+        _, zc, _ = bnpp.partition_batch(ctx, m, ev, distinct, dtype=bnpp.F32, rows_per_launch=1, partial=part)
+        assert (zc > 0).all() and zc.max() / zc.min() < 2.0 ** 40, (tag, zc.min(), zc.max())
+    one = _run_call(ctx, e, rows, dtype, 1)
+    assert _same(got, one), (tag, "differs from rows_per_launch = 1")
+    if e["dtype"] == "f64":
+        for j, (mm, hev) in enumerate(masked):
+            sel = np.flatnonzero(idx == j)
+            if not len(sel):                             # n_rows = R + 3 may not reach every distinct row
+                continue
+            if e["target"] is None:
+                lz1, z1, _ = bnpp.partition(ctx, mm, hev, "mf", bnpp.F64)
+                assert (_bits(got[1][sel]) == _bits(np.array([z1]))[0]).all(), (tag, j, got[1][sel], z1)
+                if z1 == 0:
+                    assert (got[0][sel] == -np.inf).all() and lz1 == -np.inf, (tag, j)
+                else:
+                    bound = 4 * np.spacing(max(1.0, abs(lz1)))
+                    assert (np.abs(got[0][sel] - lz1) <= bound).all(), (tag, j, got[0][sel], lz1, bound)
+            else:
+                z1 = bnpp.partition(ctx, mm, hev, "mf", bnpp.F64)[1]
+                if z1 == 0:
+                    assert np.isnan(got[0][sel]).all(), (tag, j)
+                    continue
+                want = np.array(bnpp.marginals(ctx, mm, hev, "mf", bnpp.F64, targets=[e["target"]])[0][e["target"]])
+                err = np.abs(got[0][sel] - want).max()
+                assert err <= 1e-12, (tag, j, err)
+    else:
+        b64 = _run_call(ctx, e, rows, bnpp.F64, R)
+        if e["target"] is None:
+            assert (np.abs(got[0] - b64[0]) <= 1e-6 * np.maximum(1.0, np.abs(b64[0]))).all(), (tag, got[0], b64[0])
+        else:
+            assert np.abs(got[0] - b64[0]).max() <= 1e-5, (tag, np.abs(got[0] - b64[0]).max())
+    if capped and e["family"] != "slab":
+        for cap in (1, 2, 3):
+            grid_cap(cap)
+            again = _run_call(ctx, e, rows, dtype, R)
+            grid_cap(0)
+            assert _same(got, again), (tag, cap)
+
+
 def _check_entry(ctx, e, capped, grid_cap):
+    if e.get("partial"):
+        return _check_partial_entry(ctx, e, capped, grid_cap)
+    if bc.call_of(e) != "batch":
+        return _check_call_entry(ctx, e, capped, grid_cap)
     m, _ = _model(e["model"])
     rows = np.array(bc.rows_of(e), dtype=np.int64)
     idx = np.arange(e["n_rows"]) % len(e["rows"])

@@ -1,6 +1,8 @@
 """CPU tests of MPE's host side: the numpy reference against itself, the
 MPE plan (bnpp_plan_mpe_groups: max buckets, one traceback step; arena),
-the census of the max kernel family (max_catalogue.py) and the card limit."""
+the census of the max kernel family (max_catalogue.py: single ops;
+mpe_level_catalogue.py: the same keys as level launches of whole plans, in
+both offset widths) and the card limit."""
 import json
 import math
 import os
@@ -9,6 +11,7 @@ import pytest
 
 import bnpp
 import max_catalogue as mc
+import mpe_level_catalogue as ml
 import mpe_ref
 from bnpp import synth
 from conftest import GOLDEN, evidence_of, model_path
@@ -137,6 +140,57 @@ def test_census_of_the_max_family(dt, monkeypatch):
     # the catalogue's own generator gives the recorded entries
     monkeypatch.delenv("BNPP_NO_O32", raising=False)
     assert [e for e in mc.entries_for(bnpp) if e["dtype"] == dt] == ents
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+def test_census_of_the_max_level_kernels(dt):
+    """Every max key as the first launch group of a whole MPE plan
+    (mpe_level_catalogue.py: the level dispatch, which shares its key list with
+    the single-op one, asserted above): the entry's model, eliminated `elim`
+    first, plans onto the entry's key under the entry's BNPP_NO_O32, with the
+    recorded virtual blocks; the entries hold all 24 keys, 12 with the
+    32-bit-offset bit and 12 without, each under one wave ("a") and over
+    several workgroups ("b"); under the other switch the same model plans onto
+    the key's twin.  Brute force finds one maximiser per entry, at a log gap
+    above the catalogue's MIN_GAP, and max-sum in the entry's order agrees."""
+    ents = ml.load()                                     # one list: the entries serve both dtypes
+    level = set(bnpp.kernel_keys(DT[dt], 4, level=True))
+    for e in ents:
+        assert max(e["cards"]) <= 256 and all(e["elim"] in s for s in e["scopes"])
+        g = ml.first_max_group(bnpp, e, DT[dt])
+        assert (g["key"], g["vblocks"], g["level"]) == (e["key"], e["vblocks"], 1), (e["name"], g)
+        assert bool(e["key"] & mc.O32) == (not e["no_o32"])
+        twin = ml.first_max_group(bnpp, e, DT[dt], no_o32=not e["no_o32"])
+        assert twin["key"] == e["key"] ^ mc.O32 and twin["vblocks"] == e["vblocks"]
+        d = ml.model_dict(e)
+        top, x, gap = mpe_ref.brute_force(d)
+        assert gap > ml.MIN_GAP, (e["name"], gap)
+        s, xs = mpe_ref.max_sum(d, order=ml.order_of(e))
+        assert xs == x and abs(s - top) <= 1e-12 * max(1.0, abs(top))
+    held = {e["key"] for e in ents}
+    assert held == level and len(held) == 24
+    assert len([k for k in held if k & mc.O32]) == len([k for k in held if not k & mc.O32]) == 12
+    for key in held:
+        vb = sorted(e["vblocks"] for e in ents if e["key"] == key)
+        assert len(vb) == 2 and vb[0] == 1 and vb[1] > 3, (key, vb)
+    # the catalogue's own generator gives the recorded entries
+    if dt == "f64":
+        assert ml.entries_for(bnpp) == ents
+    assert {e["from"] for e in ents} == {"max_catalogue", "search"}
+
+
+def test_job_cache_keys_on_the_offset_switch(monkeypatch):
+    """A cached job is keyed on BNPP_NO_O32: the key of the same call differs
+    between the two widths (bnpp_batch_job_key mixes the same plan switches in
+    as the single calls' key does), so a context's cached 32-bit job cannot
+    answer for a 64-bit run.  test_gpu_mpe_level.py checks bnpp.mpe itself: a
+    switched call plans anew, a repeat does not."""
+    mm = bnpp.Model.load(model_path("asia.uai"))
+    keys = []
+    for flag in ("0", "1", "0"):
+        monkeypatch.setenv("BNPP_NO_O32", flag)
+        keys.append(bnpp.batch_job_key(mm, [0, 3], rows_per_launch=4))
+    assert keys[0] == keys[2] != keys[1]
 
 
 def test_catalogue_holds_the_named_shapes():

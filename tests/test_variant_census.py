@@ -273,8 +273,10 @@ LEVEL_KEYS = {
 # instantiated level keys of the three families that no plan above reaches:
 # "condition" ones for the reasons of UNREACHED (the level launches plan with
 # the same build_desc), "batched plans only" ones are held by the batched plans
-# of batch_catalogue.py (the row variable B as the fastest dimension: the keys
-# of test_batch_census.BATCH_ONLY_KEYS), "no plan found" ones are reachable in
+# of batch_catalogue.py (the row variable B as the fastest dimension, in the
+# forward sweep of plan_batch or the backward pass of plan_counts and
+# plan_marginals_batch: the keys of test_batch_census.BATCH_ONLY_KEYS), "no plan
+# found" ones are reachable in
 # principle -- the planner owns message layouts, so no caller can ask for them
 # directly
 UNREACHED_LEVEL = {
@@ -282,50 +284,47 @@ UNREACHED_LEVEL = {
         "condition": [
             113, 177, 305, 561, 1137, 1201, 1329, 1585],
         "batched plans only": [
-            137, 146, 185, 546, 1209, 1570],
-        "no plan found": [
-            82, 1106]},
+            82, 137, 146, 185, 546, 1106, 1209, 1570],
+        "no plan found": []},
     ("f64", "stream"): {
         "condition": [
             4369, 4625, 4641, 4673, 4881, 4897, 4929, 5700, 5762, 5956, 6018, 6417, 6673, 6689, 6721, 6929,
             6945, 6977],
         "batched plans only": [
-            4388, 4418, 4644, 5441, 5442, 6433, 7441, 7457, 7489],
+            4388, 4418, 4644, 5441, 5442, 6433, 6434, 6436, 6466, 7201, 7441, 7457, 7489],
         "no plan found": [
-            4386, 5668, 5697, 5698, 5921, 5922, 5924, 5953, 5954, 6434, 6436, 6466, 6946, 7201, 7458, 7460,
-            7490]},
+            4386, 5668, 5697, 5698, 5921, 5922, 5924, 5953, 5954, 6946, 7458, 7460, 7490]},
     ("f64", "slab"): {
         "condition": [
             17442, 17450, 17473, 18466, 18474, 18497, 19490, 19498, 19521, 20514, 20522, 20545, 25873, 25889,
             25929, 26129, 26145, 26185, 26897, 26913, 26953, 27153, 27169, 27209, 27921, 27937, 27977, 28177,
             28193, 28233, 28945, 28961, 29001, 29201, 29217, 29257],
         "batched plans only": [
-            19474, 19489, 19529, 20498, 26641, 27665, 28689],
+            19474, 19489, 19529, 20498, 20513, 26641, 27665, 28689],
         "no plan found": [
-            18465, 20513, 25633, 25673, 26657, 26697, 27681, 27721, 28705, 28745]},
+            18465, 25633, 25673, 26657, 26697, 27681, 27721, 28705, 28745]},
     ("f32", "generic"): {
         "condition": [
             113, 177, 305, 561, 1137, 1201, 1329, 1585],
         "batched plans only": [
-            137, 148, 185, 536, 546, 1209, 1570],
-        "no plan found": [
-            82, 100, 1106]},
+            82, 100, 137, 148, 185, 536, 546, 1106, 1209, 1570],
+        "no plan found": []},
     ("f32", "stream"): {
         "condition": [
             4369, 4625, 4641, 4673, 4881, 4897, 4929, 6417, 6673, 6689, 6721, 6929, 6945, 6977],
         "batched plans only": [
-            4388, 4420, 6466, 6978, 7441, 7457, 7489],
+            4388, 4420, 4648, 6434, 6436, 6466, 6468, 6948, 6978, 6980, 7441, 7457, 7489],
         "no plan found": [
-            4386, 4392, 4418, 4648, 5416, 5668, 5697, 5698, 5700, 5762, 5921, 5922, 5924, 5953, 5954, 5956,
-            6018, 6434, 6436, 6468, 6692, 6722, 6724, 6946, 6948, 6980, 7234, 7236, 7458, 7460, 7490, 7492]},
+            4386, 4392, 4418, 5416, 5668, 5697, 5698, 5700, 5762, 5921, 5922, 5924, 5953, 5954, 5956,
+            6018, 6692, 6722, 6724, 6946, 7234, 7236, 7458, 7460, 7490, 7492]},
     ("f32", "slab"): {
         "condition": [
             17474, 17482, 18498, 18506, 19522, 19530, 20546, 20554],
         "batched plans only": [
-            19476, 19521, 19746, 20500, 25617, 25873, 26641, 26897, 27153, 27665, 27921, 28177, 28689, 28945,
-            29201],
+            17428, 19476, 19521, 19746, 20500, 20770, 25617, 25873, 26641, 26897, 27153, 27665, 27921, 28177, 28689,
+            28945, 29201],
         "no plan found": [
-            17428, 17442, 17698, 18465, 18466, 18497, 18722, 19489, 19490, 20513, 20514, 20770, 25633, 25665,
+            17442, 17698, 18465, 18466, 18497, 18722, 19489, 19490, 20513, 20514, 25633, 25665,
             25889, 25921, 26145, 26177, 26657, 26689, 26913, 26945, 27169, 27201, 27681, 27713, 27937, 27969,
             28193, 28225, 28705, 28737, 28961, 28993, 29217, 29249]},
 }
