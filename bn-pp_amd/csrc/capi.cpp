@@ -1490,18 +1490,32 @@ int batch_open(BatchRun &run) {
     return rc;
 }
 
-// every launch's rows, variable-major, the last launch padded with its last row; kept to the end of
-// the call (the copies are enqueued).  No evidence table: no factor mentions an evidence variable
-void batch_stage(BatchRun &run) {
+// the job's R and launches, the tables its launches read their rows from (the evidence table, the likelihood
+// table; none: no step reads one) and whether its result table is over B
+void batch_bind(BatchRun &run) {
     const BatchCall &c = run.c;
     Executable &ex = run.job->pg.parts[0];
     const Schedule &sc = ex.sched;
-    const int64_t R = run.R = run.job->batch_rows, n_launch = run.n_launch = (c.n_rows + R - 1) / R;
+    const int64_t R = run.R = run.job->batch_rows;
+    run.n_launch = (c.n_rows + R - 1) / R;
     for (const Schedule::Group &g : sc.groups)
         if (cond_form_of_key(g.variant) >= 0 && sc.descs[g.begin].in_table[1] >= 0)
             run.d_ev = static_cast<int32_t *>(ex.h_meta[sc.descs[g.begin].in_table[1]].ptr);
         else if (g.variant == kMargRowsKey && sc.pool[sc.descs[g.begin].dim_off + 3] >= 0)   // an evidence block's, gather step or not
             run.d_ev = static_cast<int32_t *>(ex.h_meta[sc.pool[sc.descs[g.begin].dim_off + 3]].ptr);
+    for (const Schedule::Group &g : sc.groups)
+        if (cond_form_of_key(g.variant) == kCondWeighted && sc.descs[g.begin].in_table[2] >= 0)
+            run.d_lam = ex.h_meta[sc.descs[g.begin].in_table[2]].ptr;
+    const std::vector<int> &rv = sc.plan_result_vars[0];
+    run.has_b = std::find(rv.begin(), rv.end(), (int)c.m->d.cards.size()) != rv.end();
+}
+
+// every launch's rows, variable-major, the last launch padded with its last row; kept to the end of
+// the call (the copies are enqueued).  No evidence table: no factor mentions an evidence variable
+void batch_stage(BatchRun &run) {
+    const BatchCall &c = run.c;
+    batch_bind(run);
+    const int64_t R = run.R, n_launch = run.n_launch;
     if (run.d_ev) {
         const int n_ev = c.n_ev;                        // locals: the stores below could alias the call's fields
         const int64_t n_rows = c.n_rows;
@@ -1513,9 +1527,6 @@ void batch_stage(BatchRun &run) {
                 for (int64_t b = 0; b < R; ++b)
                     hev[(size_t)((L * n_ev + j) * R + b)] = ev_vals[std::min(L * R + b, n_rows - 1) * n_ev + j];
     }
-    for (const Schedule::Group &g : sc.groups)
-        if (cond_form_of_key(g.variant) == kCondWeighted && sc.descs[g.begin].in_table[2] >= 0)
-            run.d_lam = ex.h_meta[sc.descs[g.begin].in_table[2]].ptr;
     if (run.d_lam && c.n_soft > 0) {
         // per (row, variable) block an exact power of two brings the largest entry into [0.5, 1): every weight is at
         // most 1 (a gathered table keeps its source's bound), and rows of any magnitude share a launch's scale.  The
@@ -1559,8 +1570,6 @@ void batch_stage(BatchRun &run) {
             std::fprintf(stderr, "[bnpp] soft evidence: staging %.3f ms for %lld rows x %lld likelihoods\n", run.lam_ms,
                          (long long)n_rows, (long long)ws);
     }
-    const std::vector<int> &rv = sc.plan_result_vars[0];
-    run.has_b = std::find(rv.begin(), rv.end(), (int)c.m->d.cards.size()) != rv.end();
 }
 
 int no_hook(int64_t, int64_t) { return BNPP_OK; }
@@ -2104,6 +2113,240 @@ int run_marginals_batch(bnpp_ctx *ctx, const BatchCall &c, double *out, double *
     return rc;
 }
 
+// ---- device-resident batched calls (_dv): rows and likelihoods from device memory, results to device memory ----
+
+enum DvCall { kDvPartition, kDvMarginals, kDvMpe, kDvSample };
+const char *const kDvName[] = {"partition_batch_dv", "marginals_batch_dv", "mpe_batch_dv", "sample_batch_dv"};
+
+// the caller's device arrays of a _dv call, and the launch data of a sampling call
+struct DvIo {
+    int lik_dtype = BNPP_F64;
+    double *log10_z = nullptr, *z = nullptr, *out = nullptr;
+    int32_t *assignment = nullptr;
+    uint8_t *samples = nullptr;
+    int64_t *n_degenerate = nullptr;
+    int64_t first_sample = 0, row_stride = 0;
+    uint64_t seed = 0;
+};
+
+// batch_check_rows without the values (they are on the device: the staging steps check them)
+int batch_check_rows_dv(const BatchCall &c, int lik_dtype) {
+    if (c.n_rows < 1) return set_err(BNPP_ERR_INVALID, "n_rows must be at least 1");
+    if (int rc = batch_check_vars(c.m->d, c.n_ev, c.ev_vars, c.target, false)) return rc;
+    if (c.n_soft != 0)
+        if (int rc = batch_check_soft_vars(c, false)) return rc;
+    if (c.n_ev > 0 && !c.ev_vals) return set_err(BNPP_ERR_INVALID, "bad evidence arrays");
+    if (c.n_soft > 0 && !c.lik) return set_err(BNPP_ERR_INVALID, "bad soft evidence arrays");
+    if (c.n_soft > 0 && lik_dtype != BNPP_F32 && lik_dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad lik_dtype");
+    return BNPP_OK;
+}
+
+// the sibling's message for the first invalid cell the staging steps found (st: the status block), or BNPP_OK
+int dv_status_error(const BatchCall &c, const int64_t st[2]) {
+    const ModelData &d = c.m->d;
+    if (st[0] != INT64_MAX) {
+        int32_t x = 0;
+        hipError_t e = hipMemcpy(&x, c.ev_vals + st[0], sizeof x, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("hipMemcpy(evidence cell): ") + hipGetErrorString(e));
+        const int64_t r = st[0] / c.n_ev;
+        const int v = c.ev_vars[st[0] % c.n_ev];
+        return set_err(BNPP_ERR_INVALID, "evidence row " + std::to_string(r) + ": value " + std::to_string(x) +
+                                             " of variable " + std::to_string(v) + " is outside [0, " +
+                                             std::to_string(d.cards[v]) + ")");
+    }
+    if (st[1] != INT64_MAX) {
+        int64_t ws = 0;
+        for (int i = 0; i < c.n_soft; ++i) ws += d.cards[c.soft_vars[i]];
+        const int64_t r = st[1] / ws;
+        int64_t x = st[1] % ws;
+        int i = 0;
+        while (i + 1 < c.n_soft && x >= d.cards[c.soft_vars[i]]) x -= d.cards[c.soft_vars[i++]];
+        return set_err(BNPP_ERR_INVALID, "evidence row " + std::to_string(r) + ": the likelihood of value " +
+                                             std::to_string(x) + " of soft variable " + std::to_string(c.soft_vars[i]) +
+                                             " must be finite and not negative");
+    }
+    return BNPP_OK;
+}
+
+// One _dv call.  Per launch: the two staging steps from the caller's arrays at row0, the program, the emit steps
+// into the caller's arrays at row0; everything on the context's stream, in order, with no host wait between
+// launches.  One wait at the end, then the status block
+int run_batch_dv(bnpp_ctx *ctx, int call, BatchCall &c, const DvIo &io, double *uptime_ms) {
+    const double t0 = now_ms();
+    if (!c.m) return set_err(BNPP_ERR_INVALID, "null context or model");
+    const ModelData &d = c.m->d;
+    // the sibling's checks, in the sibling's order, the values left out
+    if (call == kDvPartition || call == kDvMarginals) {
+        if (c.n_rows < 1) return set_err(BNPP_ERR_INVALID, "n_rows must be at least 1");
+        if (call == kDvPartition ? !io.log10_z : !io.out) return set_err(BNPP_ERR_INVALID, "null output");
+    }
+    if (int rc = batch_check_rows_dv(c, io.lik_dtype)) return rc;
+    if (call == kDvMarginals)
+        if (int rc = marginals_order_covers(c)) return rc;
+    if (call == kDvMpe && !io.log10_z && !io.assignment) return set_err(BNPP_ERR_INVALID, "null output");
+    if (call == kDvSample) {
+        if (c.K < 1) return set_err(BNPP_ERR_INVALID, "n_per_row must be at least 1");
+        if (io.row_stride < 0 || io.first_sample < 0)
+            return set_err(BNPP_ERR_INVALID, "row_stride and first_sample must be at least 0");
+        int64_t g = 0;                                     // one past the last global sample index
+        if (__builtin_mul_overflow(c.n_rows - 1, io.row_stride, &g) || __builtin_add_overflow(g, io.first_sample, &g) ||
+            __builtin_add_overflow(g, c.K, &g))
+            return set_err(BNPP_ERR_INVALID, "first_sample + (n_rows - 1) * row_stride + n_per_row overflows int64");
+    }
+    if (c.dtype != BNPP_F32 && c.dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
+    if (!ctx) return batch_null_ctx(call == kDvMpe || call == kDvSample);
+    const int64_t nv = (int64_t)d.cards.size(), K = c.K;
+    BatchRun run(ctx, c, t0);
+    int rc = batch_open(run);
+    const BucketDesc *last = nullptr;                      // the traceback, the draw step or the marginals' emit step
+    if (rc == BNPP_OK && call == kDvPartition && (run.job->pg.parts.size() != 1 || run.job->batch_rows < 1))
+        rc = set_err(BNPP_ERR_INVALID, "batch job without a plan");
+    if (rc == BNPP_OK && call == kDvMpe && !(last = batch_last_step(run.job, kMpeDecodeBatchKey)))
+        rc = set_err(BNPP_ERR_INVALID, "batched MPE job without a traceback step");
+    if (rc == BNPP_OK && call == kDvSample && !(last = batch_last_step(run.job, kSampleBatchKey)))
+        rc = set_err(BNPP_ERR_INVALID, "batched sampling job without a draw step");
+    if (rc == BNPP_OK && call == kDvMarginals && !(last = batch_last_step(run.job, kMargRowsKey)))
+        rc = set_err(BNPP_ERR_INVALID, "batched marginals job without an emit step");
+    double stage_ms = 0, wait_ms = 0;
+    void *scratch = nullptr;
+    size_t scratch_cap = 0;
+    if (rc == BNPP_OK) {
+        const double ts = now_ms();
+        batch_bind(run);
+        const Program &pg = run.job->pg;
+        Executable &ex = run.job->pg.parts[0];
+        const Schedule &sc = ex.sched;
+        const int64_t R = run.R, eb = c.dtype == BNPP_F32 ? 4 : 8, n_ev = c.n_ev, n_soft = c.n_soft;
+        const int rt = sc.plan_result_table[0];
+        const bool has_b = run.has_b;
+        if ((rt < 0 ? 1 : pg.res_size[0][0]) != (has_b ? R : 1))
+            rc = set_err(BNPP_ERR_INVALID, "batch result table of an unexpected size");
+        int64_t W = 0;
+        if (rc == BNPP_OK && call == kDvMarginals) {
+            W = last->out_size;
+            int64_t w_call = 0;
+            for (int t : c.targets) w_call += d.cards[t];
+            if (sc.pool[last->dim_off + 1] != R || W != w_call || pg.res_size[0][1] * eb < R * W * 8)
+                rc = set_err(BNPP_ERR_INVALID, "batched marginals job of another shape");
+        }
+        if (rc == BNPP_OK && call == kDvSample && (sc.pool[last->dim_off + 2] != R || sc.pool[last->dim_off + 3] != K))
+            rc = set_err(BNPP_ERR_INVALID, "batched sampling job of another shape");
+        // the host block: the status words, then the three steps' descriptor words
+        int64_t ws = 0;
+        std::vector<int64_t> host(2, INT64_MAX);
+        for (int j = 0; j < n_ev; ++j) host.push_back((int64_t)d.cards[c.ev_vars[j]] | ((int64_t)(c.is_partial(j) ? 1 : 0) << 32));
+        for (int i = 0; i < n_soft; ++i) {
+            host.push_back((int64_t)d.cards[c.soft_vars[i]] | (ws << 32));
+            ws += d.cards[c.soft_vars[i]];
+        }
+        if (call == kDvMpe || call == kDvSample) {
+            std::vector<int> ev_col((size_t)nv, -1);
+            for (int j = 0; j < n_ev; ++j) ev_col[(size_t)c.ev_vars[j]] = j;
+            // the variables the last step writes: the traceback's rows; every variable the draws can reach
+            std::vector<char> written((size_t)nv, 0);
+            if (call == kDvMpe) {
+                const int64_t *w = sc.pool.data() + last->dim_off;
+                const int64_t *row = w + kDecodeBatchPoolHead;
+                for (int64_t r = 0; r < w[1]; ++r) {
+                    written[(size_t)row[1]] = 1;
+                    row += 4 + 2 * row[3];
+                }
+            } else {
+                for (int64_t v = 0; v < nv; ++v) written[(size_t)v] = ev_col[(size_t)v] < 0 || c.is_partial(ev_col[(size_t)v]);
+            }
+            for (int64_t v = 0; v < nv; ++v)
+                host.push_back((int64_t)(uint32_t)ev_col[(size_t)v] |
+                               ((int64_t)(ev_col[(size_t)v] >= 0 && c.is_partial(ev_col[(size_t)v]) ? 1 : 0) << 32) |
+                               ((int64_t)written[(size_t)v] << 33));
+        }
+        // the device block: the host block, e_row, and a table of its own where the plan reads none (the values
+        // are still checked, and the emit steps read the evidence)
+        auto up = [](int64_t x) { return (x + 255) / 256 * 256; };
+        const int64_t host_bytes = (int64_t)host.size() * 8, o_erow = up(host_bytes), o_ev = o_erow + up(R * 8);
+        const int64_t o_lam = o_ev + (run.d_ev ? 0 : up(n_ev * R * 4)), total = o_lam + (run.d_lam ? 0 : up(ws * R * eb));
+        hipError_t e = hipSetDevice(ctx->c.device);
+        if (rc == BNPP_OK && e == hipSuccess) e = get_buffer(ctx->c, (size_t)total, &scratch, &scratch_cap);
+        if (rc == BNPP_OK && e == hipSuccess)
+            e = hipMemcpyAsync(scratch, host.data(), (size_t)host_bytes, hipMemcpyHostToDevice, ctx->c.stream);
+        if (rc == BNPP_OK && e != hipSuccess)
+            rc = set_err(e == hipErrorOutOfMemory ? BNPP_ERR_OOM : BNPP_ERR_HIP, std::string("row staging buffer: ") + hipGetErrorString(e));
+        char *base = static_cast<char *>(scratch);
+        int64_t *d_status = reinterpret_cast<int64_t *>(base), *d_words = d_status + 2;
+        int64_t *d_erow = reinterpret_cast<int64_t *>(base + o_erow);
+        int32_t *d_ev = run.d_ev ? run.d_ev : n_ev > 0 ? reinterpret_cast<int32_t *>(base + o_ev) : nullptr;
+        void *d_lam = run.d_lam ? run.d_lam : static_cast<void *>(base + o_lam);
+        const bool scaled = run.d_lam && n_soft > 0;       // the rows' exponents go back to their results (batch_stage)
+        const unsigned char *res = static_cast<const unsigned char *>(pg.results);
+        const void *table = rt >= 0 ? res + pg.res_off[0][0] : nullptr;
+        const TableMeta *tmeta = rt >= 0 ? ex.d_meta + rt : nullptr;
+        if (call == kDvSample) {
+            ex.sample_seed = io.seed;
+            ex.sample_first = io.first_sample;
+            ex.sample_row_stride = io.row_stride;
+        }
+        stage_ms = now_ms() - ts;
+        for (int64_t L = 0; rc == BNPP_OK && L < run.n_launch; ++L) {
+            const double ta = now_ms();
+            const int64_t row0 = L * R, rows = std::min(R, c.n_rows - row0);
+            if (n_ev > 0) {
+                RowioSingle<StageRowsArgs> a;
+                a.a = StageRowsArgs{d_words, c.ev_vals, d_ev, d_status, c.n_rows, row0, R, n_ev};
+                e = launch_stage_rows(a, ctx->c.max_grid, ctx->c.stream);
+            }
+            if (e == hipSuccess && n_soft > 0) {
+                RowioSingle<StageLikArgs> a;
+                a.a = StageLikArgs{d_words + n_ev, c.lik, d_lam, d_erow, d_status, c.n_rows, row0, R, ws, n_soft,
+                                   io.lik_dtype == BNPP_F32, c.dtype == BNPP_F32};
+                e = launch_stage_lik(a, ctx->c.max_grid, ctx->c.stream);
+            }
+            if (e != hipSuccess) {
+                rc = set_err(BNPP_ERR_HIP, std::string("row staging: ") + hipGetErrorString(e));
+                break;
+            }
+            ex.sample_row0 = row0;
+            ex.sample_n_valid = rows;
+            ex.marg_rows_live = rows;
+            rc = from_ctx(ctx, launch_program(ctx->c, run.job->pg, ctx->c.stream));
+            if (rc) break;
+            if (io.log10_z) {
+                const EmitScalarsArgs a{table, tmeta, scaled ? d_erow : nullptr, io.log10_z, io.z, row0, rows,
+                                        c.dtype == BNPP_F32, has_b};
+                e = launch_emit_scalars(a, ctx->c.max_grid, ctx->c.stream);
+            }
+            if (e == hipSuccess && (call == kDvMpe ? io.assignment != nullptr : call == kDvSample)) {
+                const uint8_t *x = res + pg.res_off[0][1];
+                RowioSingle<EmitStatesArgs> a;
+                a.a = EmitStatesArgs{d_words + n_ev + n_soft, x, d_ev, table,
+                                     reinterpret_cast<const unsigned long long *>(x + sample_counter_offset(nv, R * K)),
+                                     call == kDvMpe ? static_cast<void *>(io.assignment) : static_cast<void *>(io.samples),
+                                     io.n_degenerate, nv, call == kDvMpe ? 1 : K, R, row0, rows, (int64_t)last->k,
+                                     call == kDvSample, c.dtype == BNPP_F32, has_b, 0};
+                e = launch_emit_states(a, ctx->c.max_grid, ctx->c.stream);
+            }
+            if (e == hipSuccess && call == kDvMarginals)   // the launch's rows are contiguous in the caller's array
+                e = hipMemcpyAsync(io.out + row0 * W, res + pg.res_off[0][1], (size_t)(rows * W * 8), hipMemcpyDeviceToDevice,
+                                   ctx->c.stream);
+            if (e != hipSuccess) rc = set_err(BNPP_ERR_HIP, std::string("row emit: ") + hipGetErrorString(e));
+            run.launch_ms += now_ms() - ta;
+        }
+        // the call's one wait, then the status block
+        const double tw = now_ms();
+        e = hipStreamSynchronize(ctx->c.stream);
+        wait_ms = now_ms() - tw;
+        int64_t st[2] = {INT64_MAX, INT64_MAX};
+        if (e == hipSuccess && scratch) e = hipMemcpy(st, d_status, sizeof st, hipMemcpyDeviceToHost);
+        if (rc == BNPP_OK && e != hipSuccess) rc = set_err(BNPP_ERR_HIP, std::string(kDvName[call]) + ": " + hipGetErrorString(e));
+        if (rc == BNPP_OK) rc = dv_status_error(c, st);
+        run.fetch_ms = now_ms() - tw;
+    }
+    if (scratch) put_buffer(ctx->c, scratch, scratch_cap);
+    const double launch_ms = run.launch_ms;
+    rc = batch_close(run, rc, uptime_ms);
+    if (rc == BNPP_OK && std::getenv("BNPP_TIMING"))
+        std::fprintf(stderr, "[bnpp] %s: stage %.3f ms, enqueue %.3f ms, wait %.3f ms\n", kDvName[call], stage_ms, launch_ms, wait_ms);
+    return rc;
+}
+
 // the launch groups of schedule `batch`, from row n of the caller's rows on: the rows after them
 int64_t copy_group_rows(const Schedule &s, int64_t batch, int64_t *rows, int64_t cap_rows, int64_t n) {
     for (const Schedule::Group &g : s.groups) {
@@ -2406,6 +2649,191 @@ int bnpp_bucket_marginal_rows(bnpp_ctx *ctx, void *stream, int dtype, int n_targ
     a.rows_live = rows_live;
     hipError_t e = hipSetDevice(ctx->c.device);
     if (e == hipSuccess) e = launch_marg_rows_single(dtype == BNPP_F32, a, ctx->c.max_grid, pick_stream(ctx, stream));
+    if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+int bnpp_partition_batch_dv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                            const int32_t *ev_vals, const unsigned char *partial, int n_soft, const int *soft_vars,
+                            const void *lik, int lik_dtype, int heuristic, const int *order, int n_order, int dtype,
+                            int64_t rows_per_launch, double *log10_z, double *z, double *uptime_ms) {
+    BNPP_GUARD_BEGIN
+    BatchCall c = batch_call(m, kKindBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch, partial,
+                             n_soft, soft_vars, static_cast<const double *>(lik));
+    c.n_rows = n_rows;
+    c.ev_vals = ev_vals;
+    c.target = -1;
+    DvIo io;
+    io.lik_dtype = lik_dtype;
+    io.log10_z = log10_z;
+    io.z = z;
+    return run_batch_dv(ctx, kDvPartition, c, io, uptime_ms);
+    BNPP_GUARD_END
+}
+
+int bnpp_marginals_batch_dv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                            const int32_t *ev_vals, const unsigned char *partial, int n_soft, const int *soft_vars,
+                            const void *lik, int lik_dtype, int heuristic, const int *order, int n_order,
+                            int n_targets, const int *targets, int dtype, int64_t rows_per_launch, double *out,
+                            double *log10_z, double *uptime_ms) {
+    BNPP_GUARD_BEGIN
+    BatchCall c = batch_call(m, kKindMarginalsBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch,
+                             partial, n_soft, soft_vars, static_cast<const double *>(lik));
+    c.n_rows = n_rows;
+    c.ev_vals = ev_vals;
+    if (!m) return set_err(BNPP_ERR_INVALID, "null context or model");
+    if (int rc = marginals_targets(m->d, n_targets, targets, c.targets)) return rc;
+    DvIo io;
+    io.lik_dtype = lik_dtype;
+    io.out = out;
+    io.log10_z = log10_z;
+    return run_batch_dv(ctx, kDvMarginals, c, io, uptime_ms);
+    BNPP_GUARD_END
+}
+
+int bnpp_mpe_batch_dv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                      const int32_t *ev_vals, const unsigned char *partial, int n_soft, const int *soft_vars,
+                      const void *lik, int lik_dtype, int heuristic, const int *order, int n_order, int dtype,
+                      int64_t rows_per_launch, double *log10_value, int32_t *assignment, double *uptime_ms) {
+    BNPP_GUARD_BEGIN
+    BatchCall c = batch_call(m, kKindMpeBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch, partial,
+                             n_soft, soft_vars, static_cast<const double *>(lik));
+    c.n_rows = n_rows;
+    c.ev_vals = ev_vals;
+    DvIo io;
+    io.lik_dtype = lik_dtype;
+    io.log10_z = log10_value;
+    io.assignment = assignment;
+    return run_batch_dv(ctx, kDvMpe, c, io, uptime_ms);
+    BNPP_GUARD_END
+}
+
+int bnpp_sample_batch_dv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                         const int32_t *ev_vals, const unsigned char *partial, int n_soft, const int *soft_vars,
+                         const void *lik, int lik_dtype, int heuristic, const int *order, int n_order, int dtype,
+                         int64_t rows_per_launch, int64_t n_per_row, int64_t first_sample, int64_t row_stride,
+                         uint64_t seed, uint8_t *out, double *log10_z, int64_t *n_degenerate, double *uptime_ms) {
+    BNPP_GUARD_BEGIN
+    BatchCall c = batch_call(m, kKindSampleBatch, n_ev, ev_vars, heuristic, order, n_order, dtype, rows_per_launch,
+                             partial, n_soft, soft_vars, static_cast<const double *>(lik));
+    c.K = n_per_row;
+    c.n_rows = n_rows;
+    c.ev_vals = ev_vals;
+    DvIo io;
+    io.lik_dtype = lik_dtype;
+    io.samples = out;
+    io.log10_z = log10_z;
+    io.n_degenerate = n_degenerate;
+    io.first_sample = first_sample;
+    io.row_stride = row_stride;
+    io.seed = seed;
+    return run_batch_dv(ctx, kDvSample, c, io, uptime_ms);
+    BNPP_GUARD_END
+}
+
+// the launch window of a single-step call: checked before the context is looked at
+static int rowio_check_window(int64_t n_rows, int64_t row0, int64_t R) {
+    if (n_rows < 1) return set_err(BNPP_ERR_INVALID, "n_rows must be at least 1");
+    if (R < 1 || R > (int64_t)INT32_MAX) return set_err(BNPP_ERR_INVALID, "R must be in [1, 2^31)");
+    if (row0 < 0 || row0 >= n_rows) return set_err(BNPP_ERR_INVALID, "row0 must be in [0, n_rows)");
+    return BNPP_OK;
+}
+
+int bnpp_stage_evidence_rows(bnpp_ctx *ctx, void *stream, int n_ev, const int *cards, const unsigned char *partial,
+                             int64_t n_rows, int64_t row0, int64_t R, const int32_t *ev, int32_t *out,
+                             int64_t *status) {
+    BNPP_GUARD_BEGIN
+    if (n_ev < 0 || (n_ev > 0 && (!cards || !ev || !out)) || !status) return set_err(BNPP_ERR_INVALID, "null argument");
+    if (int rc = rowio_check_window(n_rows, row0, R)) return rc;
+    for (int j = 0; j < n_ev; ++j)
+        if (cards[j] < 1) return set_err(BNPP_ERR_INVALID, "column " + std::to_string(j) + ": the card must be at least 1");
+    if (n_ev > kRowioSingleMax)
+        return set_err(BNPP_ERR_UNSUPPORTED, "at most " + std::to_string(kRowioSingleMax) + " columns per call");
+    if (!ctx) return set_err(BNPP_ERR_INVALID, "null context");
+    RowioSingle<StageRowsArgs> a;
+    std::memset(&a, 0, sizeof a);
+    for (int j = 0; j < n_ev; ++j) a.single[j] = (int64_t)cards[j] | ((int64_t)(partial && partial[j] ? 1 : 0) << 32);
+    a.a = StageRowsArgs{nullptr, ev, out, status, n_rows, row0, R, n_ev};
+    hipError_t e = hipSetDevice(ctx->c.device);
+    if (e == hipSuccess) e = launch_stage_rows(a, ctx->c.max_grid, pick_stream(ctx, stream));
+    if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+int bnpp_stage_likelihoods(bnpp_ctx *ctx, void *stream, int dtype, int lik_dtype, int n_soft, const int *cards,
+                           int64_t n_rows, int64_t row0, int64_t R, const void *lik, void *out, int64_t *e_row,
+                           int64_t *status) {
+    BNPP_GUARD_BEGIN
+    if (n_soft < 0 || (n_soft > 0 && (!cards || !lik || !out)) || !e_row || !status)
+        return set_err(BNPP_ERR_INVALID, "null argument");
+    if ((dtype != BNPP_F32 && dtype != BNPP_F64) || (lik_dtype != BNPP_F32 && lik_dtype != BNPP_F64))
+        return set_err(BNPP_ERR_INVALID, "dtype and lik_dtype must be BNPP_F64 or BNPP_F32");
+    if (int rc = rowio_check_window(n_rows, row0, R)) return rc;
+    for (int i = 0; i < n_soft; ++i)
+        if (cards[i] < 1) return set_err(BNPP_ERR_INVALID, "variable " + std::to_string(i) + ": the card must be at least 1");
+    if (n_soft > kRowioSingleMax)
+        return set_err(BNPP_ERR_UNSUPPORTED, "at most " + std::to_string(kRowioSingleMax) + " variables per call");
+    if (!ctx) return set_err(BNPP_ERR_INVALID, "null context");
+    RowioSingle<StageLikArgs> a;
+    std::memset(&a, 0, sizeof a);
+    int64_t ws = 0;
+    for (int i = 0; i < n_soft; ++i) {
+        a.single[i] = (int64_t)cards[i] | (ws << 32);
+        ws += cards[i];
+    }
+    a.a = StageLikArgs{nullptr, lik, out, e_row, status, n_rows, row0, R, ws, n_soft, lik_dtype == BNPP_F32, dtype == BNPP_F32};
+    hipError_t e = hipSetDevice(ctx->c.device);
+    if (e == hipSuccess) e = launch_stage_lik(a, ctx->c.max_grid, pick_stream(ctx, stream));
+    if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+int bnpp_emit_row_scalars(bnpp_ctx *ctx, void *stream, int dtype, const void *table, int has_b, const void *meta,
+                          const int64_t *e_row, int64_t row0, int64_t rows_live, double *log10_z, double *z) {
+    BNPP_GUARD_BEGIN
+    if (!log10_z) return set_err(BNPP_ERR_INVALID, "null output");
+    if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "dtype must be BNPP_F64 or BNPP_F32");
+    if (row0 < 0 || rows_live < 0) return set_err(BNPP_ERR_INVALID, "row0 and rows_live must be at least 0");
+    if (!ctx) return set_err(BNPP_ERR_INVALID, "null context");
+    const EmitScalarsArgs a{table, static_cast<const TableMeta *>(meta), e_row, log10_z, z, row0, rows_live,
+                            dtype == BNPP_F32, table && has_b};
+    hipError_t e = hipSetDevice(ctx->c.device);
+    if (e == hipSuccess) e = launch_emit_scalars(a, ctx->c.max_grid, pick_stream(ctx, stream));
+    if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+int bnpp_emit_row_states(bnpp_ctx *ctx, void *stream, int sampling, int n_vars, const int *ev_col,
+                         const unsigned char *written, int64_t K, int64_t R, int64_t row0, int64_t rows_live,
+                         const uint8_t *x, const int32_t *ev, int dtype, const void *table, int has_b,
+                         const uint64_t *deg, int64_t n_drawn, void *out, int64_t *n_degenerate) {
+    BNPP_GUARD_BEGIN
+    if (!ev_col || !written || !x) return set_err(BNPP_ERR_INVALID, "null argument");
+    if (!out && !(sampling && n_degenerate)) return set_err(BNPP_ERR_INVALID, "null output");
+    if (n_vars < 1) return set_err(BNPP_ERR_INVALID, "n_vars must be at least 1");
+    if (sampling ? K < 1 : K != 1) return set_err(BNPP_ERR_INVALID, sampling ? "K must be at least 1" : "K must be 1 without sampling");
+    if (R < 1 || R > (int64_t)INT32_MAX) return set_err(BNPP_ERR_INVALID, "R must be in [1, 2^31)");
+    if (row0 < 0 || rows_live < 0 || rows_live > R) return set_err(BNPP_ERR_INVALID, "row0 must be at least 0 and rows_live in [0, R]");
+    if (sampling && dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "dtype must be BNPP_F64 or BNPP_F32");
+    if (sampling && n_degenerate && !deg) return set_err(BNPP_ERR_INVALID, "n_degenerate without the draw step's counters");
+    for (int v = 0; v < n_vars; ++v)
+        if (ev_col[v] >= 0 && !ev) return set_err(BNPP_ERR_INVALID, "variable " + std::to_string(v) + ": an evidence column without the evidence table");
+    if (n_vars > kRowioSingleMax)
+        return set_err(BNPP_ERR_UNSUPPORTED, "at most " + std::to_string(kRowioSingleMax) + " variables per call");
+    if (!ctx) return set_err(BNPP_ERR_INVALID, "null context");
+    RowioSingle<EmitStatesArgs> a;
+    std::memset(&a, 0, sizeof a);
+    for (int v = 0; v < n_vars; ++v)
+        a.single[v] = (int64_t)(uint32_t)(ev_col[v] >= 0 ? ev_col[v] : -1) | ((int64_t)(written[v] ? 1 : 0) << 33);
+    a.a = EmitStatesArgs{nullptr, x, ev, sampling ? table : nullptr, reinterpret_cast<const unsigned long long *>(deg), out,
+                         sampling ? n_degenerate : nullptr, n_vars, K, R, row0, rows_live, n_drawn, sampling != 0,
+                         dtype == BNPP_F32, table && has_b, 0};
+    hipError_t e = hipSetDevice(ctx->c.device);
+    if (e == hipSuccess) e = launch_emit_states(a, ctx->c.max_grid, pick_stream(ctx, stream));
     if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return BNPP_OK;
     BNPP_GUARD_END

@@ -152,6 +152,54 @@ struct MargRowsSingleArgs {
     int64_t rows_live;
 };
 hipError_t launch_marg_rows_single(int is_f32, const MargRowsSingleArgs &a, int max_grid, hipStream_t stream);
+// device-resident row input and output (rowio.cuh; include/bnpp.h states each step with its single-step entry).
+// A step's descriptor is one int64 word per column, read through the scalar cache: `words` in device memory
+// (the _dv calls), or null: the `single` words behind the arguments in the kernel-argument segment
+constexpr int kRowioSingleMax = 320;    // descriptor words of a single-step call
+struct StageRowsArgs {                  // word j: card | partial << 32
+    const int64_t *words;
+    const int32_t *ev;                  // int32[n_rows][n_ev], row-major
+    int32_t *out;                       // int32[n_ev][R]
+    int64_t *status;                    // int64[2]; word 0: the first invalid cell
+    int64_t n_rows, row0, R, n_ev;
+};
+struct StageLikArgs {                   // word i: card | first column << 32
+    const int64_t *words;
+    const void *lik;                    // [n_rows][Ws], doubles or (lik_f32) floats
+    void *out;                          // T[Ws][R], floats (out_f32) or doubles
+    int64_t *e_row;                     // int64[R]
+    int64_t *status;                    // int64[2]; word 1: the first invalid cell
+    int64_t n_rows, row0, R, Ws, n_soft;
+    int32_t lik_f32, out_f32;
+};
+struct EmitScalarsArgs {
+    const void *table;                  // T[R] (has_b) or T[1]; null: the constant 1
+    const TableMeta *meta;              // the table's metadata (its exp2); null: 0
+    const int64_t *e_row;               // int64[R] or null
+    double *log10_z, *z;                // the caller's arrays (z may be null); entry row0 + b
+    int64_t row0, rows_live;
+    int32_t is_f32, has_b;
+};
+struct EmitStatesArgs {                 // word v: (uint32) evidence column (-1: none) | partial << 32 | written << 33
+    const int64_t *words;
+    const uint8_t *x;                   // uint8[n_vars][K][R]
+    const int32_t *ev;                  // the staged evidence table int32[n_ev][R] (null: no column)
+    const void *table;                  // sampling: the result table, as EmitScalarsArgs (null: 1)
+    const unsigned long long *deg;      // sampling: the draw step's counters, [R]
+    void *out;                          // MPE: int32[n_rows][n_vars]; sampling: uint8[n_rows][K][n_vars]; may be null
+    int64_t *n_degenerate;              // sampling: int64[n_rows], or null
+    int64_t n_vars, K, R, row0, rows_live, n_drawn;
+    int32_t sampling, is_f32, has_b, pad;
+};
+template <typename A>
+struct RowioSingle {
+    A a;
+    int64_t single[kRowioSingleMax];
+};
+hipError_t launch_stage_rows(const RowioSingle<StageRowsArgs> &a, int max_grid, hipStream_t stream);
+hipError_t launch_stage_lik(const RowioSingle<StageLikArgs> &a, int max_grid, hipStream_t stream);
+hipError_t launch_emit_scalars(const EmitScalarsArgs &a, int max_grid, hipStream_t stream);
+hipError_t launch_emit_states(const RowioSingle<EmitStatesArgs> &a, int max_grid, hipStream_t stream);
 // the keys a family's dispatch switch holds (single-op or level launches),
 // appended to `keys`: generated from the X-macro lists of the switches
 // themselves (kernels.cuh, slab.cuh, chain.cuh, chainsplit.cuh), so the two

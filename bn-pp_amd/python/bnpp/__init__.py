@@ -164,6 +164,21 @@ _SIGS = {
                                           _I, _IP, _IP, _IP, _IP]),
     "bnpp_condition_batch_sv": (_I, [_P, _P, _I, _I, _IP, _P, _I, _IP, _I, _IP, _UBP, _I, _IP, _P, C.c_int64, _P, _P]),
     "bnpp_likelihood_load": (_I, [_P, C.c_char_p, _I, C.c_int64, _IP, _IP, _LP, _DP]),
+    # device-resident batched calls: the _dv siblings take ev_vals and lik as device pointers, lik_dtype after lik,
+    # and write device arrays (bnpp.tensor wraps them); then their four steps on caller-owned device buffers
+    "bnpp_partition_batch_dv": (_I, [_P, _P, _I, _IP, C.c_int64, _P, _UBP, _I, _IP, _P, _I, _I, _IP, _I, _I, C.c_int64, _P,
+                                     _P, _DP]),
+    "bnpp_marginals_batch_dv": (_I, [_P, _P, _I, _IP, C.c_int64, _P, _UBP, _I, _IP, _P, _I, _I, _IP, _I, _I, _IP, _I,
+                                     C.c_int64, _P, _P, _DP]),
+    "bnpp_mpe_batch_dv": (_I, [_P, _P, _I, _IP, C.c_int64, _P, _UBP, _I, _IP, _P, _I, _I, _IP, _I, _I, C.c_int64, _P, _P,
+                               _DP]),
+    "bnpp_sample_batch_dv": (_I, [_P, _P, _I, _IP, C.c_int64, _P, _UBP, _I, _IP, _P, _I, _I, _IP, _I, _I, C.c_int64,
+                                  C.c_int64, C.c_int64, C.c_int64, C.c_uint64, _P, _P, _P, _DP]),
+    "bnpp_stage_evidence_rows": (_I, [_P, _P, _I, _IP, _UBP, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
+    "bnpp_stage_likelihoods": (_I, [_P, _P, _I, _I, _I, _IP, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P]),
+    "bnpp_emit_row_scalars": (_I, [_P, _P, _I, _P, _I, _P, _P, C.c_int64, C.c_int64, _P, _P]),
+    "bnpp_emit_row_states": (_I, [_P, _P, _I, _I, _IP, _UBP, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, _P, _I, _P,
+                                  _I, _P, C.c_int64, _P, _P]),
     "bnpp_batch_job_key": (_I, [_P, _I, _IP, _UBP, _I, _IP, _I, C.c_int64, C.POINTER(C.c_uint64)]),
     "bnpp_job_create": (_I, [_P, _P, _I, _I, _IP, _IP, _I, _IP, _I, _I, _IP, _I, C.POINTER(_P)]),
     "bnpp_job_stats": (_I, [_P, _DP, _I]),

@@ -1073,6 +1073,107 @@ int bnpp_condition_batch_sv(bnpp_ctx *ctx, void *stream, int dtype, int n_cards,
 int bnpp_likelihood_load(const bnpp_model *m, const char *path, int cap_vars, int64_t cap_vals, int *n_soft,
                          int *soft_vars, int64_t *n_rows, double *lik);
 
+/* ------------------------------- device-resident batched calls (_dv) */
+/* The _sv calls with every row array in device memory: ev_vals
+ * (int32[n_rows][n_ev]) and lik ([n_rows][Ws], doubles or floats: lik_dtype is
+ * BNPP_F64 or BNPP_F32, floats are widened exactly) are read from the
+ * context's device, and log10_z, z, out, log10_value, assignment, samples and
+ * n_degenerate are written there.  The variable lists, partial, order and
+ * targets stay host arrays.  Row b's results are, by definition, the _sv
+ * sibling's for the same arguments: z, the marginals, the assignments, the
+ * samples and n_degenerate bit for bit, log10_z and log10_value within 4 ulp of
+ * max(|value|, 1) (the device's log10 of the mantissa is the one operation
+ * that is not the host's).  The plan, R and the job cache key are the
+ * sibling's, so the two forms share a cached job.
+ * Everything is enqueued on the context's stream in order: per launch the two
+ * staging steps below, the plan's kernels and the emit steps, with no host wait
+ * between launches; the call waits for the stream once, at its end, so the
+ * outputs are complete when it returns.  Work on another stream that produces
+ * the inputs must have been ordered before the context's stream by the caller.
+ * The variable sets, partial, soft_vars, targets, order, dtype, lik_dtype,
+ * rows_per_launch, n_per_row, first_sample, row_stride and the null checks are
+ * validated on the host as by the sibling (and fail the same without a
+ * device); the values are validated on the device: the first bad evidence
+ * cell in row-major order, else the first bad likelihood, returns
+ * BNPP_ERR_INVALID with the sibling's message.  After an error the outputs
+ * are unspecified.  BNPP_TIMING prints the call's stage / enqueue / wait. */
+int bnpp_partition_batch_dv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                            const int32_t *ev_vals /* device */, const unsigned char *partial, int n_soft,
+                            const int *soft_vars, const void *lik /* device */, int lik_dtype, int heuristic,
+                            const int *order, int n_order, int dtype, int64_t rows_per_launch,
+                            double *log10_z /* device, [n_rows] */, double *z /* device, [n_rows] or NULL */,
+                            double *uptime_ms);
+int bnpp_marginals_batch_dv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                            const int32_t *ev_vals /* device */, const unsigned char *partial, int n_soft,
+                            const int *soft_vars, const void *lik /* device */, int lik_dtype, int heuristic,
+                            const int *order, int n_order, int n_targets, const int *targets, int dtype,
+                            int64_t rows_per_launch, double *out /* device, [n_rows][W] */,
+                            double *log10_z /* device, [n_rows] or NULL */, double *uptime_ms);
+int bnpp_mpe_batch_dv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                      const int32_t *ev_vals /* device */, const unsigned char *partial, int n_soft,
+                      const int *soft_vars, const void *lik /* device */, int lik_dtype, int heuristic,
+                      const int *order, int n_order, int dtype, int64_t rows_per_launch,
+                      double *log10_value /* device, [n_rows] or NULL */,
+                      int32_t *assignment /* device, [n_rows][n_vars] or NULL */, double *uptime_ms);
+int bnpp_sample_batch_dv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                         const int32_t *ev_vals /* device */, const unsigned char *partial, int n_soft,
+                         const int *soft_vars, const void *lik /* device */, int lik_dtype, int heuristic,
+                         const int *order, int n_order, int dtype, int64_t rows_per_launch, int64_t n_per_row,
+                         int64_t first_sample, int64_t row_stride, uint64_t seed,
+                         uint8_t *out /* device, [n_rows][n_per_row][n_vars] or NULL */,
+                         double *log10_z /* device, [n_rows] or NULL */,
+                         int64_t *n_degenerate /* device, [n_rows] or NULL */, double *uptime_ms);
+
+/* The four steps of the _dv calls on caller-owned device buffers (rowio.cuh).
+ * A launch of R rows starts at row row0 of the call's n_rows; its entry b is
+ * row min(row0 + b, n_rows - 1) (the last launch is padded with the last row);
+ * rows_live of its entries are the call's.  status is int64[2] on the device,
+ * set to INT64_MAX by the caller beforehand; only an invalid cell touches it,
+ * by an atomic minimum, so afterwards a word that is not INT64_MAX names the
+ * first invalid cell in row-major order.  Results do not depend on the grid.
+ *
+ * bnpp_stage_evidence_rows: ev = int32[n_rows][n_ev] to out = int32[n_ev][R],
+ *   out[j][b] = ev[min(row0 + b, n_rows - 1)][j].  A value x is valid when
+ *   0 <= x < cards[j], or x == -1 and partial[j] (partial may be NULL); an
+ *   invalid value is stored as 0 and its cell index row * n_ev + j folded into
+ *   status[0].  At most 320 columns.
+ * bnpp_stage_likelihoods: lik = [n_rows][Ws] (lik_dtype) to out = T[Ws][R]
+ *   (dtype) and e_row = int64[R]; Ws = sum of cards, at most 320 variables.
+ *   Per (row, variable) block: top = its largest entry, e = frexp's exponent of
+ *   top (0 when top == 0), every entry ldexp(v, -e) rounded once to T (to the
+ *   nearest even, subnormal floats included); e_row[b] = the sum of the row's
+ *   e.  An entry that is NaN, infinite or negative counts as 0 and its cell
+ *   index row * Ws + w is folded into status[1].
+ * bnpp_emit_row_scalars: p = (double)table[has_b ? b : 0] (table NULL: 1),
+ *   ex = meta->exp2 (meta: a device int64[4] whose third word is the scale;
+ *   NULL: 0) + e_row[b] (NULL: 0);
+ *   log10_z[row0 + b] = p > 0 ? log10(frexp mantissa of p) + (double)(ex +
+ *   frexp exponent of p) * log10(2) : -inf, every operation in fp64 and rounded
+ *   once; z[row0 + b] = ldexp(p, clamp(ex, -2^20, 2^20)) (z may be NULL); for
+ *   b < rows_live.
+ * bnpp_emit_row_states: x = uint8[n_vars][K][R], ev = the staged int32[n_ev][R].
+ *   Per variable v: ev_col[v] (-1: none) and written[v] (a step wrote x's row
+ *   of v).  Cell (row0 + b, s, v), b < rows_live, is ev[ev_col[v]][b] when that
+ *   is >= 0 (observed), else x[v][s][b] when written[v], else 0.
+ *   sampling == 0: K = 1, out = int32[n_rows][n_vars]; table, deg and
+ *   n_degenerate are ignored.  sampling != 0: out = uint8[n_rows][K][n_vars];
+ *   a row whose p (as above) is not > 0 reads 0 in every cell that is not
+ *   observed and n_degenerate[row0 + b] = K * n_drawn, every other row
+ *   n_degenerate[row0 + b] = deg[b] (n_degenerate may be NULL).  At most 320
+ *   variables. */
+int bnpp_stage_evidence_rows(bnpp_ctx *ctx, void *stream, int n_ev, const int *cards, const unsigned char *partial,
+                             int64_t n_rows, int64_t row0, int64_t R, const int32_t *ev, int32_t *out,
+                             int64_t *status);
+int bnpp_stage_likelihoods(bnpp_ctx *ctx, void *stream, int dtype, int lik_dtype, int n_soft, const int *cards,
+                           int64_t n_rows, int64_t row0, int64_t R, const void *lik, void *out, int64_t *e_row,
+                           int64_t *status);
+int bnpp_emit_row_scalars(bnpp_ctx *ctx, void *stream, int dtype, const void *table, int has_b, const void *meta,
+                          const int64_t *e_row, int64_t row0, int64_t rows_live, double *log10_z, double *z);
+int bnpp_emit_row_states(bnpp_ctx *ctx, void *stream, int sampling, int n_vars, const int *ev_col,
+                         const unsigned char *written, int64_t K, int64_t R, int64_t row0, int64_t rows_live,
+                         const uint8_t *x, const int32_t *ev, int dtype, const void *table, int has_b,
+                         const uint64_t *deg, int64_t n_drawn, void *out, int64_t *n_degenerate);
+
 /* Host-only planning of one part of bnpp_marginals_tree_part (all variables
  * as targets): owned[v] = 1 when this part computes v's marginal; stats as
  * bnpp_job_stats for this part's plan (may be NULL).  The memory budget is
