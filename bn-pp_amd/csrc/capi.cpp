@@ -2121,7 +2121,8 @@ const char *const kDvName[] = {"partition_batch_dv", "marginals_batch_dv", "mpe_
 // the caller's device arrays of a _dv call, and the launch data of a sampling call
 struct DvIo {
     int lik_dtype = BNPP_F64;
-    double *log10_z = nullptr, *z = nullptr, *out = nullptr;
+    bool log_only = false;                                 // bnpp_log_partition_dv: lik_dtype must be a log form
+    double *log10_z = nullptr, *z = nullptr, *out = nullptr, *ln_z = nullptr;
     int32_t *assignment = nullptr;
     uint8_t *samples = nullptr;
     int64_t *n_degenerate = nullptr;
@@ -2130,19 +2131,21 @@ struct DvIo {
 };
 
 // batch_check_rows without the values (they are on the device: the staging steps check them)
-int batch_check_rows_dv(const BatchCall &c, int lik_dtype) {
+int batch_check_rows_dv(const BatchCall &c, int lik_dtype, bool log_only = false) {
     if (c.n_rows < 1) return set_err(BNPP_ERR_INVALID, "n_rows must be at least 1");
     if (int rc = batch_check_vars(c.m->d, c.n_ev, c.ev_vars, c.target, false)) return rc;
     if (c.n_soft != 0)
         if (int rc = batch_check_soft_vars(c, false)) return rc;
     if (c.n_ev > 0 && !c.ev_vals) return set_err(BNPP_ERR_INVALID, "bad evidence arrays");
     if (c.n_soft > 0 && !c.lik) return set_err(BNPP_ERR_INVALID, "bad soft evidence arrays");
-    if (c.n_soft > 0 && lik_dtype != BNPP_F32 && lik_dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad lik_dtype");
+    if (c.n_soft > 0 && (lik_dtype < 0 || lik_dtype > (BNPP_F32 | BNPP_LIK_LOG))) return set_err(BNPP_ERR_INVALID, "bad lik_dtype");
+    if (log_only && lik_dtype != (BNPP_F64 | BNPP_LIK_LOG) && lik_dtype != (BNPP_F32 | BNPP_LIK_LOG))
+        return set_err(BNPP_ERR_INVALID, "bad lik_dtype: log likelihoods (BNPP_LIK_LOG) are required");
     return BNPP_OK;
 }
 
 // the sibling's message for the first invalid cell the staging steps found (st: the status block), or BNPP_OK
-int dv_status_error(const BatchCall &c, const int64_t st[2]) {
+int dv_status_error(const BatchCall &c, const int64_t st[2], bool log_form) {
     const ModelData &d = c.m->d;
     if (st[0] != INT64_MAX) {
         int32_t x = 0;
@@ -2163,14 +2166,15 @@ int dv_status_error(const BatchCall &c, const int64_t st[2]) {
         while (i + 1 < c.n_soft && x >= d.cards[c.soft_vars[i]]) x -= d.cards[c.soft_vars[i++]];
         return set_err(BNPP_ERR_INVALID, "evidence row " + std::to_string(r) + ": the likelihood of value " +
                                              std::to_string(x) + " of soft variable " + std::to_string(c.soft_vars[i]) +
-                                             " must be finite and not negative");
+                                             (log_form ? " must not be NaN or +inf" : " must be finite and not negative"));
     }
     return BNPP_OK;
 }
 
 // One _dv call.  Per launch: the two staging steps from the caller's arrays at row0, the program, the emit steps
 // into the caller's arrays at row0; everything on the context's stream, in order, with no host wait between
-// launches.  One wait at the end, then the status block
+// launches.  One wait at the end, then the status block.  A log lik_dtype: stage_loglik for stage_lik, the blocks'
+// tops in the scratch block, and the log emit form, which restores the rows' shifts (also taken for ln_z alone)
 int run_batch_dv(bnpp_ctx *ctx, int call, BatchCall &c, const DvIo &io, double *uptime_ms) {
     const double t0 = now_ms();
     if (!c.m) return set_err(BNPP_ERR_INVALID, "null context or model");
@@ -2178,9 +2182,9 @@ int run_batch_dv(bnpp_ctx *ctx, int call, BatchCall &c, const DvIo &io, double *
     // the sibling's checks, in the sibling's order, the values left out
     if (call == kDvPartition || call == kDvMarginals) {
         if (c.n_rows < 1) return set_err(BNPP_ERR_INVALID, "n_rows must be at least 1");
-        if (call == kDvPartition ? !io.log10_z : !io.out) return set_err(BNPP_ERR_INVALID, "null output");
+        if (call == kDvPartition ? !io.log10_z && !io.ln_z : !io.out) return set_err(BNPP_ERR_INVALID, "null output");
     }
-    if (int rc = batch_check_rows_dv(c, io.lik_dtype)) return rc;
+    if (int rc = batch_check_rows_dv(c, io.lik_dtype, io.log_only)) return rc;
     if (call == kDvMarginals)
         if (int rc = marginals_order_covers(c)) return rc;
     if (call == kDvMpe && !io.log10_z && !io.assignment) return set_err(BNPP_ERR_INVALID, "null output");
@@ -2263,7 +2267,9 @@ int run_batch_dv(bnpp_ctx *ctx, int call, BatchCall &c, const DvIo &io, double *
         // are still checked, and the emit steps read the evidence)
         auto up = [](int64_t x) { return (x + 255) / 256 * 256; };
         const int64_t host_bytes = (int64_t)host.size() * 8, o_erow = up(host_bytes), o_ev = o_erow + up(R * 8);
-        const int64_t o_lam = o_ev + (run.d_ev ? 0 : up(n_ev * R * 4)), total = o_lam + (run.d_lam ? 0 : up(ws * R * eb));
+        const bool log_form = n_soft > 0 && (io.lik_dtype & BNPP_LIK_LOG);
+        const int64_t o_lam = o_ev + (run.d_ev ? 0 : up(n_ev * R * 4)), o_top = o_lam + (run.d_lam ? 0 : up(ws * R * eb));
+        const int64_t total = o_top + (log_form ? up(n_soft * R * 8) : 0);
         hipError_t e = hipSetDevice(ctx->c.device);
         if (rc == BNPP_OK && e == hipSuccess) e = get_buffer(ctx->c, (size_t)total, &scratch, &scratch_cap);
         if (rc == BNPP_OK && e == hipSuccess)
@@ -2275,6 +2281,7 @@ int run_batch_dv(bnpp_ctx *ctx, int call, BatchCall &c, const DvIo &io, double *
         int64_t *d_erow = reinterpret_cast<int64_t *>(base + o_erow);
         int32_t *d_ev = run.d_ev ? run.d_ev : n_ev > 0 ? reinterpret_cast<int32_t *>(base + o_ev) : nullptr;
         void *d_lam = run.d_lam ? run.d_lam : static_cast<void *>(base + o_lam);
+        double *d_top = log_form ? reinterpret_cast<double *>(base + o_top) : nullptr;
         const bool scaled = run.d_lam && n_soft > 0;       // the rows' exponents go back to their results (batch_stage)
         const unsigned char *res = static_cast<const unsigned char *>(pg.results);
         const void *table = rt >= 0 ? res + pg.res_off[0][0] : nullptr;
@@ -2296,8 +2303,9 @@ int run_batch_dv(bnpp_ctx *ctx, int call, BatchCall &c, const DvIo &io, double *
             if (e == hipSuccess && n_soft > 0) {
                 RowioSingle<StageLikArgs> a;
                 a.a = StageLikArgs{d_words + n_ev, c.lik, d_lam, d_erow, d_status, c.n_rows, row0, R, ws, n_soft,
-                                   io.lik_dtype == BNPP_F32, c.dtype == BNPP_F32};
-                e = launch_stage_lik(a, ctx->c.max_grid, ctx->c.stream);
+                                   (io.lik_dtype & BNPP_F32) != 0, c.dtype == BNPP_F32, d_top};
+                e = log_form ? launch_stage_loglik(a, ctx->c.max_grid, ctx->c.stream)
+                             : launch_stage_lik(a, ctx->c.max_grid, ctx->c.stream);
             }
             if (e != hipSuccess) {
                 rc = set_err(BNPP_ERR_HIP, std::string("row staging: ") + hipGetErrorString(e));
@@ -2308,10 +2316,19 @@ int run_batch_dv(bnpp_ctx *ctx, int call, BatchCall &c, const DvIo &io, double *
             ex.marg_rows_live = rows;
             rc = from_ctx(ctx, launch_program(ctx->c, run.job->pg, ctx->c.stream));
             if (rc) break;
-            if (io.log10_z) {
+            {
+                // the shifts go back with the exponents: both belong to the table the plan reads (`scaled`).  A soft
+                // variable is in some factor's scope and that factor's gather is weighted, so n_soft > 0 implies
+                // run.d_lam; were there a plan without one, it would ignore the likelihoods in either form
+                const bool shifted = scaled && log_form;
                 const EmitScalarsArgs a{table, tmeta, scaled ? d_erow : nullptr, io.log10_z, io.z, row0, rows,
-                                        c.dtype == BNPP_F32, has_b};
-                e = launch_emit_scalars(a, ctx->c.max_grid, ctx->c.stream);
+                                        c.dtype == BNPP_F32, has_b, shifted ? d_top : nullptr, io.ln_z,
+                                        shifted ? n_soft : 0, R};
+                if (log_form || io.ln_z) {
+                    if (io.log10_z || io.ln_z || io.z) e = launch_emit_logs(a, ctx->c.max_grid, ctx->c.stream);
+                } else if (io.log10_z) {
+                    e = launch_emit_scalars(a, ctx->c.max_grid, ctx->c.stream);
+                }
             }
             if (e == hipSuccess && (call == kDvMpe ? io.assignment != nullptr : call == kDvSample)) {
                 const uint8_t *x = res + pg.res_off[0][1];
@@ -2336,7 +2353,7 @@ int run_batch_dv(bnpp_ctx *ctx, int call, BatchCall &c, const DvIo &io, double *
         int64_t st[2] = {INT64_MAX, INT64_MAX};
         if (e == hipSuccess && scratch) e = hipMemcpy(st, d_status, sizeof st, hipMemcpyDeviceToHost);
         if (rc == BNPP_OK && e != hipSuccess) rc = set_err(BNPP_ERR_HIP, std::string(kDvName[call]) + ": " + hipGetErrorString(e));
-        if (rc == BNPP_OK) rc = dv_status_error(c, st);
+        if (rc == BNPP_OK) rc = dv_status_error(c, st, n_soft > 0 && (io.lik_dtype & BNPP_LIK_LOG));
         run.fetch_ms = now_ms() - tw;
     }
     if (scratch) put_buffer(ctx->c, scratch, scratch_cap);
@@ -2732,6 +2749,35 @@ int bnpp_sample_batch_dv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int
     BNPP_GUARD_END
 }
 
+int bnpp_log_partition_dv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                          const int32_t *ev_vals, const unsigned char *partial, int n_soft, const int *soft_vars,
+                          const void *loglik, int lik_dtype, int heuristic, const int *order, int n_order, int dtype,
+                          int64_t rows_per_launch, double *ln_z, double *post, double *uptime_ms) {
+    BNPP_GUARD_BEGIN
+    // post: the batched-marginals plan with the soft variables as targets (marginals_batch's job on them), ln_z
+    // from its result table; no post, or nothing soft: the batch plan (partition_batch's job)
+    const bool with_post = post && n_soft > 0;
+    BatchCall c = batch_call(m, with_post ? kKindMarginalsBatch : kKindBatch, n_ev, ev_vars, heuristic, order, n_order,
+                             dtype, rows_per_launch, partial, n_soft, soft_vars, static_cast<const double *>(loglik));
+    c.n_rows = n_rows;
+    c.ev_vals = ev_vals;
+    if (!with_post) c.target = -1;
+    DvIo io;
+    io.lik_dtype = lik_dtype;
+    io.log_only = true;
+    io.ln_z = ln_z;
+    if (!m) return set_err(BNPP_ERR_INVALID, "null context or model");
+    if (n_rows < 1) return set_err(BNPP_ERR_INVALID, "n_rows must be at least 1");
+    if (!ln_z) return set_err(BNPP_ERR_INVALID, "null output");
+    if (with_post) {
+        if (int rc = batch_check_rows_dv(c, lik_dtype, true)) return rc;   // the soft variables, before they are targets
+        if (int rc = marginals_targets(m->d, n_soft, soft_vars, c.targets)) return rc;
+        io.out = post;
+    }
+    return run_batch_dv(ctx, with_post ? kDvMarginals : kDvPartition, c, io, uptime_ms);
+    BNPP_GUARD_END
+}
+
 // the launch window of a single-step call: checked before the context is looked at
 static int rowio_check_window(int64_t n_rows, int64_t row0, int64_t R) {
     if (n_rows < 1) return set_err(BNPP_ERR_INVALID, "n_rows must be at least 1");
@@ -2783,9 +2829,41 @@ int bnpp_stage_likelihoods(bnpp_ctx *ctx, void *stream, int dtype, int lik_dtype
         a.single[i] = (int64_t)cards[i] | (ws << 32);
         ws += cards[i];
     }
-    a.a = StageLikArgs{nullptr, lik, out, e_row, status, n_rows, row0, R, ws, n_soft, lik_dtype == BNPP_F32, dtype == BNPP_F32};
+    a.a = StageLikArgs{nullptr, lik, out, e_row, status, n_rows, row0, R, ws, n_soft, lik_dtype == BNPP_F32, dtype == BNPP_F32,
+                       nullptr};
     hipError_t e = hipSetDevice(ctx->c.device);
     if (e == hipSuccess) e = launch_stage_lik(a, ctx->c.max_grid, pick_stream(ctx, stream));
+    if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+int bnpp_stage_loglikelihoods(bnpp_ctx *ctx, void *stream, int dtype, int lik_dtype, int n_soft, const int *cards,
+                              int64_t n_rows, int64_t row0, int64_t R, const void *loglik, void *out, int64_t *e_row,
+                              double *top, int64_t *status) {
+    BNPP_GUARD_BEGIN
+    if (n_soft < 0 || (n_soft > 0 && (!cards || !loglik || !out || !top)) || !e_row || !status)
+        return set_err(BNPP_ERR_INVALID, "null argument");
+    if ((dtype != BNPP_F32 && dtype != BNPP_F64) ||
+        (lik_dtype != (BNPP_F32 | BNPP_LIK_LOG) && lik_dtype != (BNPP_F64 | BNPP_LIK_LOG)))
+        return set_err(BNPP_ERR_INVALID, "dtype must be BNPP_F64 or BNPP_F32, lik_dtype one of them with BNPP_LIK_LOG");
+    if (int rc = rowio_check_window(n_rows, row0, R)) return rc;
+    for (int i = 0; i < n_soft; ++i)
+        if (cards[i] < 1) return set_err(BNPP_ERR_INVALID, "variable " + std::to_string(i) + ": the card must be at least 1");
+    if (n_soft > kRowioSingleMax)
+        return set_err(BNPP_ERR_UNSUPPORTED, "at most " + std::to_string(kRowioSingleMax) + " variables per call");
+    if (!ctx) return set_err(BNPP_ERR_INVALID, "null context");
+    RowioSingle<StageLikArgs> a;
+    std::memset(&a, 0, sizeof a);
+    int64_t ws = 0;
+    for (int i = 0; i < n_soft; ++i) {
+        a.single[i] = (int64_t)cards[i] | (ws << 32);
+        ws += cards[i];
+    }
+    a.a = StageLikArgs{nullptr, loglik, out, e_row, status, n_rows, row0, R, ws, n_soft, (lik_dtype & BNPP_F32) != 0,
+                       dtype == BNPP_F32, top};
+    hipError_t e = hipSetDevice(ctx->c.device);
+    if (e == hipSuccess) e = launch_stage_loglik(a, ctx->c.max_grid, pick_stream(ctx, stream));
     if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return BNPP_OK;
     BNPP_GUARD_END
@@ -2799,9 +2877,28 @@ int bnpp_emit_row_scalars(bnpp_ctx *ctx, void *stream, int dtype, const void *ta
     if (row0 < 0 || rows_live < 0) return set_err(BNPP_ERR_INVALID, "row0 and rows_live must be at least 0");
     if (!ctx) return set_err(BNPP_ERR_INVALID, "null context");
     const EmitScalarsArgs a{table, static_cast<const TableMeta *>(meta), e_row, log10_z, z, row0, rows_live,
-                            dtype == BNPP_F32, table && has_b};
+                            dtype == BNPP_F32, table && has_b, nullptr, nullptr, 0, 0};
     hipError_t e = hipSetDevice(ctx->c.device);
     if (e == hipSuccess) e = launch_emit_scalars(a, ctx->c.max_grid, pick_stream(ctx, stream));
+    if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+int bnpp_emit_row_logs(bnpp_ctx *ctx, void *stream, int dtype, const void *table, int has_b, const void *meta,
+                       const int64_t *e_row, int n_soft, const double *top, int64_t R, int64_t row0, int64_t rows_live,
+                       double *ln_z, double *log10_z, double *z) {
+    BNPP_GUARD_BEGIN
+    if (!ln_z && !log10_z && !z) return set_err(BNPP_ERR_INVALID, "null output");
+    if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "dtype must be BNPP_F64 or BNPP_F32");
+    if (n_soft < 0 || (n_soft > 0 && !top)) return set_err(BNPP_ERR_INVALID, "null argument");
+    if (R < 1 || R > (int64_t)INT32_MAX) return set_err(BNPP_ERR_INVALID, "R must be in [1, 2^31)");
+    if (row0 < 0 || rows_live < 0 || rows_live > R) return set_err(BNPP_ERR_INVALID, "row0 must be at least 0 and rows_live in [0, R]");
+    if (!ctx) return set_err(BNPP_ERR_INVALID, "null context");
+    const EmitScalarsArgs a{table, static_cast<const TableMeta *>(meta), e_row, log10_z, z, row0, rows_live,
+                            dtype == BNPP_F32, table && has_b, top, ln_z, n_soft, R};
+    hipError_t e = hipSetDevice(ctx->c.device);
+    if (e == hipSuccess) e = launch_emit_logs(a, ctx->c.max_grid, pick_stream(ctx, stream));
     if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return BNPP_OK;
     BNPP_GUARD_END

@@ -16,9 +16,21 @@ hipError_t launch_stage_lik(const RowioSingle<StageLikArgs> &a, int max_grid, hi
     return hipGetLastError();
 }
 
+hipError_t launch_stage_loglik(const RowioSingle<StageLikArgs> &a, int max_grid, hipStream_t stream) {
+    if (a.a.R <= 0 || a.a.n_soft <= 0) return hipSuccess;
+    hipLaunchKernelGGL(stage_loglik_kernel, dim3(rowio_grid(a.a.R, 64, max_grid)), dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_emit_scalars(const EmitScalarsArgs &a, int max_grid, hipStream_t stream) {
     if (a.rows_live <= 0) return hipSuccess;
     hipLaunchKernelGGL(emit_scalars_kernel, dim3(rowio_grid(a.rows_live, 64, max_grid)), dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_emit_logs(const EmitScalarsArgs &a, int max_grid, hipStream_t stream) {
+    if (a.rows_live <= 0) return hipSuccess;
+    hipLaunchKernelGGL(emit_logs_kernel, dim3(rowio_grid(a.rows_live, 64, max_grid)), dim3(64), 0, stream, a);
     return hipGetLastError();
 }
 

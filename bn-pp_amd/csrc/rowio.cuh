@@ -4,14 +4,17 @@
 //
 //   stage_rows         ev  = int32[n_rows][n_ev]  ->  the launch's evidence table int32[n_ev][R]
 //   stage_lik          lik = [n_rows][Ws]         ->  T[Ws][R] scaled per (row, variable) block, e_row[R]
+//   stage_loglik       loglik = [n_rows][Ws]      ->  T[Ws][R] = exp(l - top) / 2, e_row[R], top[n_soft][R]
 //   emit_row_scalars   the result table T[R]      ->  log10_z[row0 + b], z[row0 + b]
+//   emit_row_logs      the result table T[R], top ->  ln_z, log10_z, z with the rows' shifts restored
 //   emit_row_states    x = uint8[n_vars][K][R]    ->  int32[n_rows][n_vars] / uint8[n_rows][K][n_vars]
 //
 // row0 is the launch's first row, entry b of a launch is row min(row0 + b,
 // n_rows - 1) (the last launch is padded with the call's last row), rows_live
 // the launch's rows that are the call's.  include/bnpp.h states each step's
 // arithmetic with its single-step entry (bnpp_stage_evidence_rows,
-// bnpp_stage_likelihoods, bnpp_emit_row_scalars, bnpp_emit_row_states).
+// bnpp_stage_likelihoods, bnpp_emit_row_scalars, bnpp_emit_row_states; the log
+// forms: bnpp_stage_loglikelihoods, bnpp_emit_row_logs).
 //
 // A workgroup owns a tile of 64 rows and a persistent grid walks the tiles.
 // Wherever rows are the fastest dimension (the evidence table, T, x, the
@@ -166,14 +169,39 @@ __device__ __forceinline__ void lik_store(cst_t<StageLikArgs> &a, int64_t at, do
     else *((gbl_t<double> *)a.out + at) = v;
 }
 
+// The two forms of a likelihood block.  Linear: the entries are likelihoods, the block is scaled by the power of two
+// that brings its top into [0.5, 1).  Log: the entries are natural logs (-inf: the likelihood 0; NaN and +inf are
+// invalid and count as -inf), the block is E = exp(l - top) scaled by 2^-1, which is what the linear form makes of
+// E (its top is 1.0 = 0.5 * 2^1); a block of nothing but -inf is all zero and adds no exponent
+template <bool kLog>
+__device__ __forceinline__ bool lik_invalid(double v) {
+    if (kLog) return v != v || v == __builtin_inf();
+    return lik_bad(v);
+}
+template <bool kLog>
+__device__ __forceinline__ int lik_exponent(double top) {
+    if (kLog) return top == -__builtin_inf() ? 0 : 1;
+    int e = 0;
+    if (top > 0) (void)frexp(top, &e);
+    return e;
+}
+template <bool kLog>
+__device__ __forceinline__ double lik_scaled(double v, double top, int e) {
+    if (kLog) return lik_invalid<true>(v) || top == -__builtin_inf() ? 0.0 : ldexp(exp(__dsub_rn(v, top)), -1);
+    return ldexp(lik_bad(v) ? 0.0 : v, -e);
+}
+
 // The waves split the soft variables into contiguous runs.  A wave takes as many whole blocks as fit the 16
 // columns of its tile at once; a block wider than the tile passes through it in chunks twice, its maximum
-// taken first.  A lane owns a row: its block's top, exponent and scaled entries, stored along b.
-__global__ __launch_bounds__(kBlock) void stage_lik_kernel(const RowioSingle<StageLikArgs> args) {
+// taken first.  A lane owns a row: its block's top, exponent and scaled entries, stored along b.  The log form
+// also stores the block's top, per variable: the emit step sums a row's tops in soft_vars order, so the sum does
+// not depend on how the waves split the variables
+template <bool kLog>
+__device__ __forceinline__ void stage_lik_body(cst_t<RowioSingle<StageLikArgs>> &s) {
     __shared__ double tiles[kRowioWaves][64 * kRowioP64];
     __shared__ int64_t esum[kRowioWaves][64];
-    cst_t<RowioSingle<StageLikArgs>> &s = rowio_args(args);
     cst_t<StageLikArgs> &a = s.a;
+    constexpr double kFloor = kLog ? -__builtin_inf() : 0.0;
     cst_t<int64_t> *w = a.words ? as_const(a.words) : s.single;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     double *tile = tiles[wv];
@@ -188,29 +216,29 @@ __global__ __launch_bounds__(kBlock) void stage_lik_kernel(const RowioSingle<Sta
         for (int64_t i = i0; i < i1;) {
             const int64_t k = w[i] & 0xffffffff, col = w[i] >> 32;
             if (k > kRowioC64) {
-                double top = 0;
+                double top = kFloor;
                 for (int64_t c0 = 0; c0 < k; c0 += kRowioC64) {
                     const int n = k - c0 < kRowioC64 ? (int)(k - c0) : kRowioC64;
                     lik_fill(tile, a, b0, col + c0, n, lane);
                     for (int x = 0; live && x < n; ++x) {
                         double v = tile[lane * kRowioP64 + x];
-                        if (lik_bad(v)) {
+                        if (lik_invalid<kLog>(v)) {
                             rowio_flag(a.status, 1, row * a.Ws + col + c0 + x);
-                            v = 0;
+                            v = kFloor;
                         }
                         top = v > top ? v : top;
                     }
                     rowio_wave_sync();
                 }
-                int e = 0;
-                if (top > 0) (void)frexp(top, &e);
+                const int e = lik_exponent<kLog>(top);
                 e_sum += e;
+                if (kLog && live) *((gbl_t<double> *)a.top + i * R + b) = top;
                 for (int64_t c0 = 0; c0 < k; c0 += kRowioC64) {
                     const int n = k - c0 < kRowioC64 ? (int)(k - c0) : kRowioC64;
                     lik_fill(tile, a, b0, col + c0, n, lane);
                     for (int x = 0; live && x < n; ++x) {
                         const double v = tile[lane * kRowioP64 + x];
-                        lik_store(a, (col + c0 + x) * R + b, ldexp(lik_bad(v) ? 0.0 : v, -e));
+                        lik_store(a, (col + c0 + x) * R + b, lik_scaled<kLog>(v, top, e));
                     }
                     rowio_wave_sync();
                 }
@@ -223,21 +251,21 @@ __global__ __launch_bounds__(kBlock) void stage_lik_kernel(const RowioSingle<Sta
                 int x0 = 0;
                 for (; i < i2; ++i) {
                     const int kk = (int)(w[i] & 0xffffffff);
-                    double top = 0;
+                    double top = kFloor;
                     for (int x = 0; live && x < kk; ++x) {
                         double v = tile[lane * kRowioP64 + x0 + x];
-                        if (lik_bad(v)) {
+                        if (lik_invalid<kLog>(v)) {
                             rowio_flag(a.status, 1, row * a.Ws + col + x0 + x);
-                            v = 0;
+                            v = kFloor;
                         }
                         top = v > top ? v : top;
                     }
-                    int e = 0;
-                    if (top > 0) (void)frexp(top, &e);
+                    const int e = lik_exponent<kLog>(top);
                     e_sum += e;
+                    if (kLog && live) *((gbl_t<double> *)a.top + i * R + b) = top;
                     for (int x = 0; live && x < kk; ++x) {
                         const double v = tile[lane * kRowioP64 + x0 + x];
-                        lik_store(a, (col + x0 + x) * R + b, ldexp(lik_bad(v) ? 0.0 : v, -e));
+                        lik_store(a, (col + x0 + x) * R + b, lik_scaled<kLog>(v, top, e));
                     }
                     x0 += kk;
                 }
@@ -253,6 +281,13 @@ __global__ __launch_bounds__(kBlock) void stage_lik_kernel(const RowioSingle<Sta
         }
         __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(kBlock) void stage_lik_kernel(const RowioSingle<StageLikArgs> args) {
+    stage_lik_body<false>(rowio_args(args));
+}
+__global__ __launch_bounds__(kBlock) void stage_loglik_kernel(const RowioSingle<StageLikArgs> args) {
+    stage_lik_body<true>(rowio_args(args));
 }
 
 // ---- emit_row_scalars ----------------------------------------------------------------------------------------
@@ -276,6 +311,29 @@ __global__ __launch_bounds__(64) void emit_scalars_kernel(const EmitScalarsArgs 
             const int64_t c = ex > (1 << 20) ? (1 << 20) : ex < -(1 << 20) ? -(1 << 20) : ex;
             *((gbl_t<double> *)a.z + a.row0 + b) = ldexp(p, (int)c);
         }
+    }
+}
+
+// The log form: the row's shift is the sum of its blocks' tops, taken from 0.0 in soft_vars order, and goes back
+// to the natural and the decimal log; 0x1.62e42fefa39efp-1 is ln 2, 0x1.bcb7b1526e50ep-2 log10(e).  z = exp(ln_z)
+// may overflow.  Each output may be null
+__global__ __launch_bounds__(64) void emit_logs_kernel(const EmitScalarsArgs a) {
+    for (int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x; b < a.rows_live; b += (int64_t)gridDim.x * 64) {
+        double p = 0;
+        p = __dadd_rn(p, rowio_elem(a.table, a.is_f32, a.has_b ? b : 0));
+        int64_t ex = a.meta ? as_const(a.meta)->exp2 : 0;
+        if (a.e_row) ex += gload(a.e_row + b);
+        double shift = 0.0;
+        for (int64_t i = 0; i < a.n_soft; ++i) shift = __dadd_rn(shift, gload(a.top + i * a.R + b));
+        int pe = 0;
+        const double pm = frexp(p, &pe), pw = (double)(ex + pe), ninf = -__builtin_inf();
+        const double ln_z = p > 0 ? __dadd_rn(__dadd_rn(log(pm), __dmul_rn(pw, 0x1.62e42fefa39efp-1)), shift) : ninf;
+        if (a.ln_z) *((gbl_t<double> *)a.ln_z + a.row0 + b) = ln_z;
+        if (a.log10_z)
+            *((gbl_t<double> *)a.log10_z + a.row0 + b) =
+                p > 0 ? __dadd_rn(__dadd_rn(log10(pm), __dmul_rn(pw, 0x1.34413509f79ffp-2)), __dmul_rn(shift, 0x1.bcb7b1526e50ep-2))
+                      : ninf;
+        if (a.z) *((gbl_t<double> *)a.z + a.row0 + b) = exp(ln_z);
     }
 }
 

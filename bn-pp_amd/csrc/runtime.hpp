@@ -171,6 +171,7 @@ struct StageLikArgs {                   // word i: card | first column << 32
     int64_t *status;                    // int64[2]; word 1: the first invalid cell
     int64_t n_rows, row0, R, Ws, n_soft;
     int32_t lik_f32, out_f32;
+    double *top;                        // the log form: double[n_soft][R], each block's largest entry
 };
 struct EmitScalarsArgs {
     const void *table;                  // T[R] (has_b) or T[1]; null: the constant 1
@@ -179,6 +180,9 @@ struct EmitScalarsArgs {
     double *log10_z, *z;                // the caller's arrays (z may be null); entry row0 + b
     int64_t row0, rows_live;
     int32_t is_f32, has_b;
+    const double *top;                  // the log form: double[n_soft][R] (n_soft 0: no shift), and its natural log
+    double *ln_z;
+    int64_t n_soft, R;
 };
 struct EmitStatesArgs {                 // word v: (uint32) evidence column (-1: none) | partial << 32 | written << 33
     const int64_t *words;
@@ -198,7 +202,9 @@ struct RowioSingle {
 };
 hipError_t launch_stage_rows(const RowioSingle<StageRowsArgs> &a, int max_grid, hipStream_t stream);
 hipError_t launch_stage_lik(const RowioSingle<StageLikArgs> &a, int max_grid, hipStream_t stream);
+hipError_t launch_stage_loglik(const RowioSingle<StageLikArgs> &a, int max_grid, hipStream_t stream);
 hipError_t launch_emit_scalars(const EmitScalarsArgs &a, int max_grid, hipStream_t stream);
+hipError_t launch_emit_logs(const EmitScalarsArgs &a, int max_grid, hipStream_t stream);
 hipError_t launch_emit_states(const RowioSingle<EmitStatesArgs> &a, int max_grid, hipStream_t stream);
 // the keys a family's dispatch switch holds (single-op or level launches),
 // appended to `keys`: generated from the X-macro lists of the switches

@@ -34,6 +34,7 @@ _lib = C.CDLL(LIB_PATH)
 
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_OOM, ERR_HIP, ERR_IO, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5, -6
 F64, F32 = 0, 1
+LIK_LOG = 2                             # OR-ed into a _dv call's lik_dtype: natural logs (BNPP_LIK_LOG)
 ORDER_GIVEN, MIN_FILL, WEIGHTED_MIN_FILL, MIN_DEGREE = 0, 1, 2, 3
 HEURISTICS = {"given": ORDER_GIVEN, "mf": MIN_FILL, "wmf": WEIGHTED_MIN_FILL, "md": MIN_DEGREE}
 
@@ -179,6 +180,12 @@ _SIGS = {
     "bnpp_emit_row_scalars": (_I, [_P, _P, _I, _P, _I, _P, _P, C.c_int64, C.c_int64, _P, _P]),
     "bnpp_emit_row_states": (_I, [_P, _P, _I, _I, _IP, _UBP, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, _P, _I, _P,
                                   _I, _P, C.c_int64, _P, _P]),
+    # log-space soft evidence: lik_dtype | LIK_LOG in the _dv calls, the two steps of the log form (top after e_row;
+    # n_soft, top, R after e_row and ln_z first of the outputs) and ln Z with the soft posteriors (ln_z, post)
+    "bnpp_stage_loglikelihoods": (_I, [_P, _P, _I, _I, _I, _IP, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
+    "bnpp_emit_row_logs": (_I, [_P, _P, _I, _P, _I, _P, _P, _I, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
+    "bnpp_log_partition_dv": (_I, [_P, _P, _I, _IP, C.c_int64, _P, _UBP, _I, _IP, _P, _I, _I, _IP, _I, _I, C.c_int64, _P,
+                                   _P, _DP]),
     "bnpp_batch_job_key": (_I, [_P, _I, _IP, _UBP, _I, _IP, _I, C.c_int64, C.POINTER(C.c_uint64)]),
     "bnpp_job_create": (_I, [_P, _P, _I, _I, _IP, _IP, _I, _IP, _I, _I, _IP, _I, C.POINTER(_P)]),
     "bnpp_job_stats": (_I, [_P, _DP, _I]),

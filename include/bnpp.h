@@ -60,6 +60,8 @@ enum bnpp_status {
 };
 
 enum bnpp_dtype { BNPP_F64 = 0, BNPP_F32 = 1 };
+/* OR-ed into the lik_dtype of a _dv call: the likelihood array holds natural logs (the log form, below) */
+#define BNPP_LIK_LOG 2
 
 /* elimination-order heuristics: bn flags -mf / -wmf / -md (bn.cpp:183-191) */
 enum bnpp_heuristic { BNPP_ORDER_GIVEN = 0, BNPP_MIN_FILL = 1, BNPP_WEIGHTED_MIN_FILL = 2, BNPP_MIN_DEGREE = 3 };
@@ -1076,7 +1078,8 @@ int bnpp_likelihood_load(const bnpp_model *m, const char *path, int cap_vars, in
 /* ------------------------------- device-resident batched calls (_dv) */
 /* The _sv calls with every row array in device memory: ev_vals
  * (int32[n_rows][n_ev]) and lik ([n_rows][Ws], doubles or floats: lik_dtype is
- * BNPP_F64 or BNPP_F32, floats are widened exactly) are read from the
+ * BNPP_F64 or BNPP_F32, floats are widened exactly; with BNPP_LIK_LOG: natural
+ * logs, see "the log form" below) are read from the
  * context's device, and log10_z, z, out, log10_value, assignment, samples and
  * n_degenerate are written there.  The variable lists, partial, order and
  * targets stay host arrays.  Row b's results are, by definition, the _sv
@@ -1173,6 +1176,60 @@ int bnpp_emit_row_states(bnpp_ctx *ctx, void *stream, int sampling, int n_vars, 
                          const unsigned char *written, int64_t K, int64_t R, int64_t row0, int64_t rows_live,
                          const uint8_t *x, const int32_t *ev, int dtype, const void *table, int has_b,
                          const uint64_t *deg, int64_t n_drawn, void *out, int64_t *n_degenerate);
+
+/* ------------------------------------ log-space soft evidence (the log form) */
+/* lik_dtype BNPP_F64 | BNPP_LIK_LOG (2) or BNPP_F32 | BNPP_LIK_LOG (3): the
+ * likelihood array of a _dv call holds natural logs l[b][v][x], doubles or
+ * floats (widened exactly).  An entry is valid when it is finite or -inf (the
+ * likelihood 0); NaN and +inf count as -inf and are named by the error
+ * "evidence row R: the likelihood of value X of soft variable V must not be
+ * NaN or +inf".  Row b's results are the linear call's for lik = E, where
+ * E[b][v][x] = exp(l[b][v][x] - top[b][v]) and top is the block's largest entry
+ * (a block of nothing but -inf: E = 0 throughout, an impossible row):
+ * marginals, assignments, samples and n_degenerate bit for bit, log10_z and
+ * log10_value with shift_b * log10(e) added, shift_b being the fp64 sum of the
+ * row's tops taken from 0.0 in soft_vars order; z = exp of the row's natural
+ * log, which may overflow to inf and carries no bit contract.  The plans and job
+ * keys are the linear calls'.  The host-array calls have no log form.
+ *
+ * bnpp_stage_loglikelihoods: bnpp_stage_likelihoods for the log form, with
+ *   top = double[n_soft][R].  Per (row, variable) block: top = its largest
+ *   entry after invalid ones are replaced by -inf.  top == -inf: every entry is
+ *   stored as 0 and the block adds 0 to e_row.  Else every entry is
+ *   ldexp(exp(v - top), -1) (the difference rounded once), rounded once to T,
+ *   and the block adds 1 to e_row: what bnpp_stage_likelihoods makes of E,
+ *   whose largest entry is 1.0 = 0.5 * 2^1.  The cell index of an invalid entry
+ *   is folded into status[1].
+ * bnpp_emit_row_logs: p, ex as bnpp_emit_row_scalars, pm and pe the frexp
+ *   mantissa and exponent of p, shift = the sum of top[i][b], i = 0 .. n_soft-1
+ *   in order from 0.0 (n_soft 0: 0.0);
+ *   ln_z[row0 + b] = p > 0 ? (ln(pm) + (double)(ex + pe) * 0x1.62e42fefa39efp-1) + shift : -inf,
+ *   log10_z[row0 + b] = p > 0 ? (log10(pm) + (double)(ex + pe) * 0x1.34413509f79ffp-2)
+ *                               + shift * 0x1.bcb7b1526e50ep-2 : -inf,
+ *   z[row0 + b] = exp(ln_z); every operation in fp64 and rounded once.  Each of
+ *   the three outputs may be NULL (not all).
+ * bnpp_log_partition_dv: ln Z of every row, and with post != NULL (and
+ *   n_soft > 0) the posterior of every soft variable, post[b][w] over the Ws
+ *   columns of loglik: d ln Z_b / d l[b][v][x] = P(X_v = x | row b), the
+ *   likelihoods included, so post is the gradient of ln_z.  post == NULL: the
+ *   batch plan (the job and key of bnpp_partition_batch_dv); else the batched
+ *   marginals plan with targets = soft_vars (the job of
+ *   bnpp_marginals_batch_dv on those targets), ln_z from its result table and
+ *   post written as that call writes out (an impossible row: NaN).  n_soft == 0
+ *   is valid: ln_z of the hard evidence, post untouched.  lik_dtype must be 2 or
+ *   3.  The host-side checks are the siblings'. */
+int bnpp_stage_loglikelihoods(bnpp_ctx *ctx, void *stream, int dtype, int lik_dtype, int n_soft, const int *cards,
+                              int64_t n_rows, int64_t row0, int64_t R, const void *loglik, void *out, int64_t *e_row,
+                              double *top, int64_t *status);
+int bnpp_emit_row_logs(bnpp_ctx *ctx, void *stream, int dtype, const void *table, int has_b, const void *meta,
+                       const int64_t *e_row, int n_soft, const double *top, int64_t R, int64_t row0, int64_t rows_live,
+                       double *ln_z, double *log10_z, double *z);
+int bnpp_log_partition_dv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const int *ev_vars, int64_t n_rows,
+                          const int32_t *ev_vals /* device */, const unsigned char *partial, int n_soft,
+                          const int *soft_vars, const void *loglik /* device */, int lik_dtype /* 2 or 3 */,
+                          int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch,
+                          double *ln_z /* device, [n_rows] */, double *post /* device, [n_rows][Ws], or NULL */,
+                          double *uptime_ms);
 
 /* Host-only planning of one part of bnpp_marginals_tree_part (all variables
  * as targets): owned[v] = 1 when this part computes v's marginal; stats as
