@@ -53,10 +53,22 @@ struct bnpp_ctx {
     bnpp_job *job_cached = nullptr;
     uint64_t job_key = 0;
     int64_t job_budget = 0;             // the memory budget the cached job was planned under
+    // bnpp_mstep_dv: the per-factor words of the last model it refitted, on the device
+    std::mutex mstep_mu;
+    void *mstep_words = nullptr;
+    size_t mstep_cap = 0;
+    uint64_t mstep_uid = 0;
+    int64_t mstep_cfg = 0;              // its parent configurations in all
+    hipStream_t mstep_stream = nullptr; // the stream of the last M step (it may still read the words)
+    bool mstep_launched = false;
 };
 // live contexts: bnpp_model_free releases what they cache for the model
 std::mutex g_ctxs_mu;
 std::vector<bnpp_ctx *> g_ctxs;
+// live table sets: bnpp_ctx_destroy releases those of its context, which then only remain to be freed
+struct bnpp_tables;
+std::mutex g_tables_mu;
+std::vector<bnpp_tables *> g_tables;
 
 struct bnpp_model {
     ModelData d;
@@ -78,6 +90,24 @@ struct bnpp_job {
     int n_slices = 1, slice_rank = 0;  // message-sliced bucket tree (bnpp_marginals_tree_sliced)
     double stats[10] = {0};            // bnpp_job_stats [0..8), then n_xchg, exchange bytes sent
     int64_t batch_rows = 0;            // batched evidence (kind 6): rows per launch
+    uint64_t tables_uid = 0;           // the table set it reads instead of the model's own (bnpp_tables_free evicts it)
+};
+// The tables of one model on one context in one dtype, rewritten in place on the device (bnpp_tables_set_dv).
+// One block holds the factors' device TableMeta, the shift and the tops, stage_tables' descriptor words and
+// its status word; src is the layout upload_sources makes, whose buffer never moves
+struct bnpp_tables {
+    bnpp_ctx *ctx = nullptr;
+    uint64_t uid = bnpp_model::next_uid(), model_uid = 0;
+    int dtype = BNPP_F64;
+    bool log_form = false;
+    std::shared_ptr<DeviceSources> src;
+    std::vector<int64_t> sizes;                         // per factor, and the flat array's length
+    int64_t total = 0;
+    void *block = nullptr;
+    size_t block_cap = 0;
+    TableMeta *d_meta = nullptr;
+    double *d_shift = nullptr;                          // [1 + n_factors]: the shift, the factors' tops
+    int64_t *d_words = nullptr, *d_status = nullptr;
 };
 
 namespace {
@@ -1161,6 +1191,7 @@ struct BatchCall {
     int n_soft = 0;
     const int *soft_vars = nullptr;
     const double *lik = nullptr;
+    const bnpp_tables *tables = nullptr;                // the table set the plan reads (null: the model's own)
 };
 
 // the soft variable set (no values): ids in range, no duplicates, none an evidence variable or the target, each in
@@ -1404,7 +1435,7 @@ uint64_t batch_call_key(const BatchCall &c, int64_t auto_cap) {
     if (std::getenv("BNPP_NO_JOB_CACHE")) return 0;
     uint64_t h = 1469598103934665603ull;
     auto mix = [&](uint64_t x) { h = (h ^ x) * 1099511628211ull; };
-    mix(c.m->uid);
+    mix(c.tables ? c.tables->uid : c.m->uid);           // a table set has a job of its own: the model's is untouched
     mix((uint64_t)c.kind);
     mix((uint64_t)c.n_ev);
     for (int i = 0; i < c.n_ev; ++i) mix((uint32_t)c.ev_vars[i]);
@@ -1467,6 +1498,7 @@ int batch_open(BatchRun &run) {
         j->ctx = ctx;
         j->kind = c.kind;
         j->model_uid = c.m->uid;
+        j->tables_uid = c.tables ? c.tables->uid : 0;
         j->cards = c.m->d.cards;
         if (cache_ok) evict_cached_job(ctx);       // it runs in the arena this job may replace
         const double tp = now_ms();
@@ -1474,7 +1506,8 @@ int batch_open(BatchRun &run) {
         int rc2 = plan_batch_schedule(c, budget, auto_cap, batches[0], j->stats, j->batch_rows, nullptr);
         if (rc2) return rc2;
         const double ta = now_ms();
-        rc2 = cached_sources(ctx, c.m, c.dtype, j->src);
+        if (c.tables) j->src = c.tables->src;       // the planner reads scopes and cards only: one plan for every set
+        else rc2 = cached_sources(ctx, c.m, c.dtype, j->src);
         if (rc2) return rc2;
         const double tb = now_ms();
         rc2 = from_ctx(ctx, make_program(ctx->c, *j->src, std::move(batches), j->pg, cache_ok));
@@ -2115,8 +2148,9 @@ int run_marginals_batch(bnpp_ctx *ctx, const BatchCall &c, double *out, double *
 
 // ---- device-resident batched calls (_dv): rows and likelihoods from device memory, results to device memory ----
 
-enum DvCall { kDvPartition, kDvMarginals, kDvMpe, kDvSample };
-const char *const kDvName[] = {"partition_batch_dv", "marginals_batch_dv", "mpe_batch_dv", "sample_batch_dv"};
+enum DvCall { kDvPartition, kDvMarginals, kDvMpe, kDvSample, kDvCounts };
+const char *const kDvName[] = {"partition_batch_dv", "marginals_batch_dv", "mpe_batch_dv", "sample_batch_dv",
+                               "expected_counts_dv"};
 
 // the caller's device arrays of a _dv call, and the launch data of a sampling call
 struct DvIo {
@@ -2128,6 +2162,12 @@ struct DvIo {
     int64_t *n_degenerate = nullptr;
     int64_t first_sample = 0, row_stride = 0;
     uint64_t seed = 0;
+    // bnpp_expected_counts_dv: the rows' weights (null: 1), the accumulators (kDvCounts), whether the fold goes on
+    // from their values, and the counter of impossible rows (also with the batch plan, counts == NULL)
+    const double *weights = nullptr;
+    double *counts = nullptr;
+    bool accumulate = false;
+    int64_t *n_impossible = nullptr;
 };
 
 // batch_check_rows without the values (they are on the device: the staging steps check them)
@@ -2145,7 +2185,7 @@ int batch_check_rows_dv(const BatchCall &c, int lik_dtype, bool log_only = false
 }
 
 // the sibling's message for the first invalid cell the staging steps found (st: the status block), or BNPP_OK
-int dv_status_error(const BatchCall &c, const int64_t st[2], bool log_form) {
+int dv_status_error(const BatchCall &c, const int64_t st[3], bool log_form) {
     const ModelData &d = c.m->d;
     if (st[0] != INT64_MAX) {
         int32_t x = 0;
@@ -2168,6 +2208,8 @@ int dv_status_error(const BatchCall &c, const int64_t st[2], bool log_form) {
                                              std::to_string(x) + " of soft variable " + std::to_string(c.soft_vars[i]) +
                                              (log_form ? " must not be NaN or +inf" : " must be finite and not negative"));
     }
+    if (st[2] != INT64_MAX)
+        return set_err(BNPP_ERR_INVALID, "evidence row " + std::to_string(st[2]) + ": the weight must be finite and not negative");
     return BNPP_OK;
 }
 
@@ -2184,6 +2226,11 @@ int run_batch_dv(bnpp_ctx *ctx, int call, BatchCall &c, const DvIo &io, double *
         if (c.n_rows < 1) return set_err(BNPP_ERR_INVALID, "n_rows must be at least 1");
         if (call == kDvPartition ? !io.log10_z && !io.ln_z : !io.out) return set_err(BNPP_ERR_INVALID, "null output");
     }
+    if (call == kDvCounts && !io.counts) return set_err(BNPP_ERR_INVALID, "null output");
+    // a table set belongs to one model and one dtype (and, once there is a context to compare, to it)
+    if (c.tables && (c.tables->model_uid != c.m->uid || c.tables->dtype != c.dtype))
+        return set_err(BNPP_ERR_INVALID, c.tables->model_uid != c.m->uid ? "the tables are those of another model"
+                                                                         : "the tables are of another dtype than the call");
     if (int rc = batch_check_rows_dv(c, io.lik_dtype, io.log_only)) return rc;
     if (call == kDvMarginals)
         if (int rc = marginals_order_covers(c)) return rc;
@@ -2199,12 +2246,14 @@ int run_batch_dv(bnpp_ctx *ctx, int call, BatchCall &c, const DvIo &io, double *
     }
     if (c.dtype != BNPP_F32 && c.dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
     if (!ctx) return batch_null_ctx(call == kDvMpe || call == kDvSample);
+    if (c.tables && c.tables->ctx != ctx) return set_err(BNPP_ERR_INVALID, "the tables are those of another context");
     const int64_t nv = (int64_t)d.cards.size(), K = c.K;
     BatchRun run(ctx, c, t0);
     int rc = batch_open(run);
     const BucketDesc *last = nullptr;                      // the traceback, the draw step or the marginals' emit step
-    if (rc == BNPP_OK && call == kDvPartition && (run.job->pg.parts.size() != 1 || run.job->batch_rows < 1))
-        rc = set_err(BNPP_ERR_INVALID, "batch job without a plan");
+    if (rc == BNPP_OK && (call == kDvPartition || call == kDvCounts) &&
+        (run.job->pg.parts.size() != 1 || run.job->batch_rows < 1))
+        rc = set_err(BNPP_ERR_INVALID, call == kDvCounts ? "counts job without a plan" : "batch job without a plan");
     if (rc == BNPP_OK && call == kDvMpe && !(last = batch_last_step(run.job, kMpeDecodeBatchKey)))
         rc = set_err(BNPP_ERR_INVALID, "batched MPE job without a traceback step");
     if (rc == BNPP_OK && call == kDvSample && !(last = batch_last_step(run.job, kSampleBatchKey)))
@@ -2237,7 +2286,8 @@ int run_batch_dv(bnpp_ctx *ctx, int call, BatchCall &c, const DvIo &io, double *
             rc = set_err(BNPP_ERR_INVALID, "batched sampling job of another shape");
         // the host block: the status words, then the three steps' descriptor words
         int64_t ws = 0;
-        std::vector<int64_t> host(2, INT64_MAX);
+        constexpr int kStatusWords = 3;                    // the first invalid evidence cell, likelihood, weight
+        std::vector<int64_t> host(kStatusWords, INT64_MAX);
         for (int j = 0; j < n_ev; ++j) host.push_back((int64_t)d.cards[c.ev_vars[j]] | ((int64_t)(c.is_partial(j) ? 1 : 0) << 32));
         for (int i = 0; i < n_soft; ++i) {
             host.push_back((int64_t)d.cards[c.soft_vars[i]] | (ws << 32));
@@ -2277,7 +2327,7 @@ int run_batch_dv(bnpp_ctx *ctx, int call, BatchCall &c, const DvIo &io, double *
         if (rc == BNPP_OK && e != hipSuccess)
             rc = set_err(e == hipErrorOutOfMemory ? BNPP_ERR_OOM : BNPP_ERR_HIP, std::string("row staging buffer: ") + hipGetErrorString(e));
         char *base = static_cast<char *>(scratch);
-        int64_t *d_status = reinterpret_cast<int64_t *>(base), *d_words = d_status + 2;
+        int64_t *d_status = reinterpret_cast<int64_t *>(base), *d_words = d_status + kStatusWords;
         int64_t *d_erow = reinterpret_cast<int64_t *>(base + o_erow);
         int32_t *d_ev = run.d_ev ? run.d_ev : n_ev > 0 ? reinterpret_cast<int32_t *>(base + o_ev) : nullptr;
         void *d_lam = run.d_lam ? run.d_lam : static_cast<void *>(base + o_lam);
@@ -2291,6 +2341,27 @@ int run_batch_dv(bnpp_ctx *ctx, int call, BatchCall &c, const DvIo &io, double *
             ex.sample_first = io.first_sample;
             ex.sample_row_stride = io.row_stride;
         }
+        // expected counts: the weights table of the accumulate steps; the caller's array is the accumulator buffer,
+        // zeroed on the stream unless the fold goes on from its values
+        double *d_w = nullptr;
+        if (rc == BNPP_OK && call == kDvCounts) {
+            for (const Schedule::Group &g : sc.groups)
+                if (g.variant == kCountsKey && sc.pool[sc.descs[g.begin].dim_off + 8] >= 0)
+                    d_w = static_cast<double *>(ex.h_meta[sc.pool[sc.descs[g.begin].dim_off + 8]].ptr);
+            int64_t total = 0;
+            for (const auto &v : d.values) total += (int64_t)v.size();
+            if (!io.accumulate && total > 0) e = hipMemsetAsync(io.counts, 0, (size_t)total * sizeof(double), ctx->c.stream);
+            ex.counts_acc = io.counts;
+        }
+        if (rc == BNPP_OK && e == hipSuccess && io.n_impossible)
+            e = hipMemsetAsync(io.n_impossible, 0, sizeof(int64_t), ctx->c.stream);
+        // a table set: its factors' metadata as they are now, into the pristine copy every launch restores.  The
+        // source pointers were baked in when the job was made and never move; no exponent reaches the host
+        if (rc == BNPP_OK && e == hipSuccess && c.tables && sc.n_src > 0)
+            e = hipMemcpyAsync(ex.d_meta0, c.tables->d_meta, (size_t)sc.n_src * sizeof(TableMeta), hipMemcpyDeviceToDevice,
+                               ctx->c.stream);
+        if (rc == BNPP_OK && e != hipSuccess) rc = set_err(BNPP_ERR_HIP, std::string("call setup: ") + hipGetErrorString(e));
+        const double *tshift = c.tables && c.tables->log_form ? c.tables->d_shift : nullptr;
         stage_ms = now_ms() - ts;
         for (int64_t L = 0; rc == BNPP_OK && L < run.n_launch; ++L) {
             const double ta = now_ms();
@@ -2307,10 +2378,15 @@ int run_batch_dv(bnpp_ctx *ctx, int call, BatchCall &c, const DvIo &io, double *
                 e = log_form ? launch_stage_loglik(a, ctx->c.max_grid, ctx->c.stream)
                              : launch_stage_lik(a, ctx->c.max_grid, ctx->c.stream);
             }
+            if (e == hipSuccess && d_w) {
+                const StageWeightsArgs a{io.weights, d_w, d_status, c.n_rows, row0, R};
+                e = launch_stage_weights(a, ctx->c.max_grid, ctx->c.stream);
+            }
             if (e != hipSuccess) {
                 rc = set_err(BNPP_ERR_HIP, std::string("row staging: ") + hipGetErrorString(e));
                 break;
             }
+            ex.counts_rows = rows;
             ex.sample_row0 = row0;
             ex.sample_n_valid = rows;
             ex.marg_rows_live = rows;
@@ -2323,10 +2399,10 @@ int run_batch_dv(bnpp_ctx *ctx, int call, BatchCall &c, const DvIo &io, double *
                 const bool shifted = scaled && log_form;
                 const EmitScalarsArgs a{table, tmeta, scaled ? d_erow : nullptr, io.log10_z, io.z, row0, rows,
                                         c.dtype == BNPP_F32, has_b, shifted ? d_top : nullptr, io.ln_z,
-                                        shifted ? n_soft : 0, R};
-                if (log_form || io.ln_z) {
-                    if (io.log10_z || io.ln_z || io.z) e = launch_emit_logs(a, ctx->c.max_grid, ctx->c.stream);
-                } else if (io.log10_z) {
+                                        shifted ? n_soft : 0, R, tshift, io.n_impossible};
+                if (log_form || io.ln_z || tshift) {           // log-form tables: the shift goes back in the log emit
+                    if (io.log10_z || io.ln_z || io.z || io.n_impossible) e = launch_emit_logs(a, ctx->c.max_grid, ctx->c.stream);
+                } else if (io.log10_z || io.n_impossible) {
                     e = launch_emit_scalars(a, ctx->c.max_grid, ctx->c.stream);
                 }
             }
@@ -2350,7 +2426,8 @@ int run_batch_dv(bnpp_ctx *ctx, int call, BatchCall &c, const DvIo &io, double *
         const double tw = now_ms();
         e = hipStreamSynchronize(ctx->c.stream);
         wait_ms = now_ms() - tw;
-        int64_t st[2] = {INT64_MAX, INT64_MAX};
+        ex.counts_acc = nullptr;
+        int64_t st[kStatusWords] = {INT64_MAX, INT64_MAX, INT64_MAX};
         if (e == hipSuccess && scratch) e = hipMemcpy(st, d_status, sizeof st, hipMemcpyDeviceToHost);
         if (rc == BNPP_OK && e != hipSuccess) rc = set_err(BNPP_ERR_HIP, std::string(kDvName[call]) + ": " + hipGetErrorString(e));
         if (rc == BNPP_OK) rc = dv_status_error(c, st, n_soft > 0 && (io.lik_dtype & BNPP_LIK_LOG));
@@ -2778,6 +2855,240 @@ int bnpp_log_partition_dv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const in
     BNPP_GUARD_END
 }
 
+// ---- device-resident model tables: bnpp_tables, bnpp_expected_counts_dv, bnpp_mstep_dv (tables.cuh) ----
+
+static int tables_check_dtypes(int dtype, int values_dtype) {
+    if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "dtype must be BNPP_F64 or BNPP_F32");
+    if (values_dtype < 0 || values_dtype > (BNPP_F32 | BNPP_LIK_LOG))
+        return set_err(BNPP_ERR_INVALID, "values_dtype must be BNPP_F64 or BNPP_F32, alone or with BNPP_LIK_LOG");
+    return BNPP_OK;
+}
+
+int bnpp_tables_create(bnpp_ctx *ctx, const bnpp_model *m, int dtype, bnpp_tables **out) {
+    BNPP_GUARD_BEGIN
+    if (!out) return set_err(BNPP_ERR_INVALID, "null output");
+    *out = nullptr;
+    if (!m) return set_err(BNPP_ERR_INVALID, "null model");
+    if (dtype != BNPP_F32 && dtype != BNPP_F64) return set_err(BNPP_ERR_INVALID, "bad dtype");
+    if (!ctx) return set_err(BNPP_ERR_INVALID, "null context");
+    std::unique_ptr<bnpp_tables> t(new bnpp_tables);
+    t->ctx = ctx;
+    t->model_uid = m->uid;
+    t->dtype = dtype;
+    Context *c = &ctx->c;
+    t->src = std::shared_ptr<DeviceSources>(new DeviceSources, [c](DeviceSources *p) {
+        free_sources(*c, *p);
+        delete p;
+    });
+    // the layout, and the model's own values in it, are upload_sources'
+    if (int rc = upload_sources(ctx->c, m->d.values, dtype == BNPP_F32 ? kF32 : kF64, *t->src)) return from_ctx(ctx, rc);
+    const size_t n = m->d.values.size();
+    std::vector<int64_t> words(3 * n + 1, 0);
+    for (size_t f = 0; f < n; ++f) {
+        words[3 * f] = t->total;
+        words[3 * f + 1] = (int64_t)m->d.values[f].size();
+        words[3 * f + 2] = static_cast<unsigned char *>(t->src->meta[f].ptr) - static_cast<unsigned char *>(t->src->buf);
+        t->sizes.push_back((int64_t)m->d.values[f].size());
+        t->total += (int64_t)m->d.values[f].size();
+    }
+    const size_t meta_b = n * sizeof(TableMeta), shift_b = (1 + n) * sizeof(double), words_b = words.size() * sizeof(int64_t);
+    hipError_t e = get_buffer(ctx->c, meta_b + shift_b + words_b + sizeof(int64_t), &t->block, &t->block_cap);
+    if (e != hipSuccess)
+        return set_err(e == hipErrorOutOfMemory ? BNPP_ERR_OOM : BNPP_ERR_HIP, std::string("tables: ") + hipGetErrorString(e));
+    char *base = static_cast<char *>(t->block);
+    t->d_meta = reinterpret_cast<TableMeta *>(base);
+    t->d_shift = reinterpret_cast<double *>(base + meta_b);
+    t->d_words = reinterpret_cast<int64_t *>(base + meta_b + shift_b);
+    t->d_status = reinterpret_cast<int64_t *>(base + meta_b + shift_b + words_b);
+    if (meta_b) e = hipMemcpy(t->d_meta, t->src->meta.data(), meta_b, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(t->d_shift, 0, shift_b);
+    if (e == hipSuccess) e = hipMemcpy(t->d_words, words.data(), words_b, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        put_buffer(ctx->c, t->block, t->block_cap);
+        return set_err(BNPP_ERR_HIP, std::string("tables: ") + hipGetErrorString(e));
+    }
+    {
+        std::lock_guard<std::mutex> g(g_tables_mu);
+        g_tables.push_back(t.get());
+    }
+    *out = t.release();
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+// what a table set holds of its context goes back to it (the caller holds g_tables_mu and has set the device)
+static void tables_release(bnpp_tables *t) {
+    put_buffer(t->ctx->c, t->block, t->block_cap);
+    t->block = nullptr;
+    t->src.reset();                                         // its deleter hands the buffer to the context
+    t->ctx = nullptr;
+}
+
+int bnpp_tables_free(bnpp_tables *t) {
+    if (!t) return BNPP_OK;
+    std::lock_guard<std::mutex> g(g_tables_mu);             // against the context's destruction on another thread
+    g_tables.erase(std::remove(g_tables.begin(), g_tables.end(), t), g_tables.end());
+    bnpp_ctx *ctx = t->ctx;
+    if (!ctx) {                                             // its context is gone, and took the buffers with it
+        delete t;
+        return BNPP_OK;
+    }
+    int dev = -1;
+    const bool had = hipGetDevice(&dev) == hipSuccess;
+    (void)hipSetDevice(ctx->c.device);
+    {
+        // a cached job planned for these tables reads their buffer: it goes first (as bnpp_model_free's)
+        std::lock_guard<std::mutex> lk(ctx->cache_mu);
+        if (ctx->job_cached && ctx->job_cached->tables_uid == t->uid) evict_cached_job(ctx);
+    }
+    (void)hipStreamSynchronize(ctx->c.stream);              // a staging step may still write the block
+    tables_release(t);
+    if (had) (void)hipSetDevice(dev);
+    delete t;
+    return BNPP_OK;
+}
+
+int bnpp_tables_set_dv(bnpp_tables *t, const void *values, int values_dtype) {
+    BNPP_GUARD_BEGIN
+    if (!t) return set_err(BNPP_ERR_INVALID, "null tables");
+    if (!values && t->total > 0) return set_err(BNPP_ERR_INVALID, "null values");
+    if (int rc = tables_check_dtypes(t->dtype, values_dtype)) return rc;
+    bnpp_ctx *ctx = t->ctx;
+    if (!ctx) return set_err(BNPP_ERR_INVALID, "the tables' context has been destroyed");
+    const bool log_form = (values_dtype & BNPP_LIK_LOG) != 0;
+    static const int64_t kClear = INT64_MAX;
+    StageTablesSingle a;
+    std::memset(&a, 0, sizeof a);
+    a.a = StageTablesArgs{t->d_words, values, t->src->buf, t->d_meta, t->d_shift, t->d_status, (int64_t)t->sizes.size(),
+                          (values_dtype & BNPP_F32) != 0, t->dtype == BNPP_F32};
+    hipError_t e = hipSetDevice(ctx->c.device);
+    if (e == hipSuccess) e = hipMemcpyAsync(t->d_status, &kClear, sizeof kClear, hipMemcpyHostToDevice, ctx->c.stream);
+    if (e == hipSuccess) e = launch_stage_tables(a, log_form, ctx->c.max_grid, ctx->c.stream);
+    if (e == hipSuccess) t->log_form = log_form;           // the buffer holds that form from here on, invalid entries as 0
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->c.stream);
+    int64_t st = INT64_MAX;
+    if (e == hipSuccess) e = hipMemcpy(&st, t->d_status, sizeof st, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("bnpp_tables_set_dv: ") + hipGetErrorString(e));
+    if (st != INT64_MAX) {
+        size_t f = 0;
+        while (f + 1 < t->sizes.size() && st >= t->sizes[f]) st -= t->sizes[f++];
+        return set_err(BNPP_ERR_INVALID, "factor " + std::to_string(f) + ": entry " + std::to_string(st) +
+                                             (log_form ? " must not be NaN or +inf" : " must be finite and not negative"));
+    }
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+int bnpp_stage_tables(bnpp_ctx *ctx, void *stream, int dtype, int values_dtype, int n_factors, const int64_t *sizes,
+                      const void *values, void *out_buf, void *out_meta, double *out_shift, int64_t *status) {
+    BNPP_GUARD_BEGIN
+    if (n_factors < 0 || (n_factors > 0 && (!sizes || !values || !out_buf || !out_meta)) || !out_shift || !status)
+        return set_err(BNPP_ERR_INVALID, "null argument");
+    if (int rc = tables_check_dtypes(dtype, values_dtype)) return rc;
+    for (int f = 0; f < n_factors; ++f)
+        if (sizes[f] < 1) return set_err(BNPP_ERR_INVALID, "factor " + std::to_string(f) + ": the size must be at least 1");
+    if (n_factors > kTablesSingleMax)
+        return set_err(BNPP_ERR_UNSUPPORTED, "at most " + std::to_string(kTablesSingleMax) + " factors per call");
+    if (!ctx) return set_err(BNPP_ERR_INVALID, "null context");
+    StageTablesSingle a;
+    std::memset(&a, 0, sizeof a);
+    const int64_t eb = dtype == BNPP_F32 ? 4 : 8;
+    int64_t in0 = 0, out_off = 0;
+    for (int f = 0; f < n_factors; ++f) {                   // upload_sources' offsets: every factor on a 256-byte line
+        a.single[3 * f] = in0;
+        a.single[3 * f + 1] = sizes[f];
+        a.single[3 * f + 2] = out_off;
+        in0 += sizes[f];
+        out_off += (sizes[f] * eb + 255) / 256 * 256;
+    }
+    a.a = StageTablesArgs{nullptr, values, out_buf, static_cast<TableMeta *>(out_meta), out_shift, status, n_factors,
+                          (values_dtype & BNPP_F32) != 0, dtype == BNPP_F32};
+    hipError_t e = hipSetDevice(ctx->c.device);
+    if (e == hipSuccess)
+        e = launch_stage_tables(a, (values_dtype & BNPP_LIK_LOG) != 0, ctx->c.max_grid, pick_stream(ctx, stream));
+    if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
+int bnpp_expected_counts_dv(bnpp_ctx *ctx, const bnpp_model *m, const bnpp_tables *tables, int n_ev, const int *ev_vars,
+                            int64_t n_rows, const int32_t *ev_vals, const unsigned char *partial, int n_soft,
+                            const int *soft_vars, const void *lik, int lik_dtype, const double *weights, int flags,
+                            int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch,
+                            double *counts, double *log10_z, double *ln_z, int64_t *n_impossible, double *uptime_ms) {
+    BNPP_GUARD_BEGIN
+    // counts: the counts plan (the job and key of bnpp_expected_counts_sv); none: the batch plan (those of
+    // bnpp_partition_batch_dv), the likelihood of the rows under the tables without the backward pass
+    BatchCall c = batch_call(m, counts ? kKindCounts : kKindBatch, n_ev, ev_vars, heuristic, order, n_order, dtype,
+                             rows_per_launch, partial, n_soft, soft_vars, static_cast<const double *>(lik));
+    c.n_rows = n_rows;
+    c.ev_vals = ev_vals;
+    c.tables = tables;
+    if (!counts) c.target = -1;
+    DvIo io;
+    io.lik_dtype = lik_dtype;
+    io.log10_z = log10_z;
+    io.ln_z = ln_z;
+    io.weights = weights;
+    io.counts = counts;
+    io.accumulate = (flags & BNPP_COUNTS_ACCUMULATE) != 0;
+    io.n_impossible = n_impossible;
+    if (!m) return set_err(BNPP_ERR_INVALID, "null context or model");
+    if (n_rows < 1) return set_err(BNPP_ERR_INVALID, "n_rows must be at least 1");
+    if (flags & ~BNPP_COUNTS_ACCUMULATE) return set_err(BNPP_ERR_INVALID, "bad flags");
+    return run_batch_dv(ctx, counts ? kDvCounts : kDvPartition, c, io, uptime_ms);
+    BNPP_GUARD_END
+}
+
+int bnpp_mstep_dv(bnpp_ctx *ctx, void *stream, const bnpp_model *m, const double *counts, double prior,
+                  const double *old_values, double *new_values) {
+    BNPP_GUARD_BEGIN
+    if (!m) return set_err(BNPP_ERR_INVALID, "null model");
+    if (!counts || !old_values || !new_values) return set_err(BNPP_ERR_INVALID, "null argument");
+    if (!(prior >= 0) || !std::isfinite(prior)) return set_err(BNPP_ERR_INVALID, "the prior must be finite and not negative");
+    if (!m->d.is_bayes)
+        return set_err(BNPP_ERR_UNSUPPORTED, "the M step fits the CPTs of a BAYES model; Markov networks need iterative fitting");
+    if (!ctx) return set_err(BNPP_ERR_INVALID, "null context");
+    const ModelData &d = m->d;
+    const int64_t n = (int64_t)d.values.size();
+    hipError_t e = hipSetDevice(ctx->c.device);
+    std::lock_guard<std::mutex> g(ctx->mstep_mu);
+    if (e == hipSuccess && ctx->mstep_uid != m->uid) {
+        // per factor its first entry, k and first parent configuration: kept for the model (read-only, its uid never
+        // reused), so a training loop uploads them once.  An earlier M step may still read the old words
+        std::vector<int64_t> words((size_t)(3 * n + 1), 0);
+        int64_t at = 0, cfg = 0;
+        for (int64_t f = 0; f < n; ++f) {
+            const int64_t k = d.scopes[(size_t)f].empty() ? 1 : d.cards[d.scopes[(size_t)f].back()];
+            words[(size_t)(3 * f)] = at;
+            words[(size_t)(3 * f + 1)] = k;
+            words[(size_t)(3 * f + 2)] = cfg;
+            at += (int64_t)d.values[(size_t)f].size();
+            cfg += (int64_t)d.values[(size_t)f].size() / k;
+        }
+        words[(size_t)(3 * n)] = cfg;
+        if (ctx->mstep_launched) e = hipStreamSynchronize(ctx->mstep_stream);
+        if (e == hipSuccess && ctx->mstep_cap < words.size() * sizeof(int64_t)) {
+            put_buffer(ctx->c, ctx->mstep_words, ctx->mstep_cap);
+            ctx->mstep_words = nullptr;
+            ctx->mstep_cap = 0;
+            e = get_buffer(ctx->c, words.size() * sizeof(int64_t), &ctx->mstep_words, &ctx->mstep_cap);
+        }
+        if (e == hipSuccess) e = hipMemcpy(ctx->mstep_words, words.data(), words.size() * sizeof(int64_t), hipMemcpyHostToDevice);
+        ctx->mstep_uid = e == hipSuccess ? m->uid : 0;
+        ctx->mstep_cfg = cfg;
+    }
+    if (e == hipSuccess) {
+        const MstepArgs a{static_cast<const int64_t *>(ctx->mstep_words), counts, old_values, new_values, prior, n};
+        e = launch_mstep(a, ctx->mstep_cfg, ctx->c.max_grid, pick_stream(ctx, stream));
+        ctx->mstep_stream = pick_stream(ctx, stream);
+        ctx->mstep_launched = true;
+    }
+    if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("bnpp_mstep_dv: ") + hipGetErrorString(e));
+    return BNPP_OK;
+    BNPP_GUARD_END
+}
+
 // the launch window of a single-step call: checked before the context is looked at
 static int rowio_check_window(int64_t n_rows, int64_t row0, int64_t R) {
     if (n_rows < 1) return set_err(BNPP_ERR_INVALID, "n_rows must be at least 1");
@@ -2877,7 +3188,7 @@ int bnpp_emit_row_scalars(bnpp_ctx *ctx, void *stream, int dtype, const void *ta
     if (row0 < 0 || rows_live < 0) return set_err(BNPP_ERR_INVALID, "row0 and rows_live must be at least 0");
     if (!ctx) return set_err(BNPP_ERR_INVALID, "null context");
     const EmitScalarsArgs a{table, static_cast<const TableMeta *>(meta), e_row, log10_z, z, row0, rows_live,
-                            dtype == BNPP_F32, table && has_b, nullptr, nullptr, 0, 0};
+                            dtype == BNPP_F32, table && has_b, nullptr, nullptr, 0, 0, nullptr, nullptr};
     hipError_t e = hipSetDevice(ctx->c.device);
     if (e == hipSuccess) e = launch_emit_scalars(a, ctx->c.max_grid, pick_stream(ctx, stream));
     if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
@@ -2896,7 +3207,7 @@ int bnpp_emit_row_logs(bnpp_ctx *ctx, void *stream, int dtype, const void *table
     if (row0 < 0 || rows_live < 0 || rows_live > R) return set_err(BNPP_ERR_INVALID, "row0 must be at least 0 and rows_live in [0, R]");
     if (!ctx) return set_err(BNPP_ERR_INVALID, "null context");
     const EmitScalarsArgs a{table, static_cast<const TableMeta *>(meta), e_row, log10_z, z, row0, rows_live,
-                            dtype == BNPP_F32, table && has_b, top, ln_z, n_soft, R};
+                            dtype == BNPP_F32, table && has_b, top, ln_z, n_soft, R, nullptr, nullptr};
     hipError_t e = hipSetDevice(ctx->c.device);
     if (e == hipSuccess) e = launch_emit_logs(a, ctx->c.max_grid, pick_stream(ctx, stream));
     if (e != hipSuccess) return set_err(BNPP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
@@ -3010,9 +3321,17 @@ int bnpp_ctx_destroy(bnpp_ctx *ctx) {
         std::lock_guard<std::mutex> lk(ctx->cache_mu);
         evict_cached_job(ctx);
     }
+    {
+        // table sets that outlive the context keep nothing of it: they can still be freed, and nothing else
+        std::lock_guard<std::mutex> g(g_tables_mu);
+        (void)hipStreamSynchronize(ctx->c.stream);
+        for (bnpp_tables *t : g_tables)
+            if (t->ctx == ctx) tables_release(t);
+    }
     if (ctx->c.stream) (void)hipStreamDestroy(ctx->c.stream);
     if (ctx->c.lane_stream) (void)hipStreamDestroy(ctx->c.lane_stream);
     if (ctx->c.counts_scratch) (void)hipFree(ctx->c.counts_scratch);
+    put_buffer(ctx->c, ctx->mstep_words, ctx->mstep_cap);
     ctx->srcs.clear();
     drop_arena_cache(ctx->c);
     drop_buffer_cache(ctx->c);
@@ -3403,6 +3722,12 @@ int bnpp_model_info(const bnpp_model *m, int *is_bayes, int *n_vars, int *n_fact
 int bnpp_model_cards(const bnpp_model *m, int *cards) {
     if (!m || !cards) return set_err(BNPP_ERR_INVALID, "null argument");
     std::copy(m->d.cards.begin(), m->d.cards.end(), cards);
+    return BNPP_OK;
+}
+
+int bnpp_model_values(const bnpp_model *m, double *values) {
+    if (!m || !values) return set_err(BNPP_ERR_INVALID, "null argument");
+    for (const auto &v : m->d.values) values = std::copy(v.begin(), v.end(), values);
     return BNPP_OK;
 }
 

@@ -22,6 +22,12 @@ hipError_t launch_stage_loglik(const RowioSingle<StageLikArgs> &a, int max_grid,
     return hipGetLastError();
 }
 
+hipError_t launch_stage_weights(const StageWeightsArgs &a, int max_grid, hipStream_t stream) {
+    if (a.R <= 0) return hipSuccess;
+    hipLaunchKernelGGL(stage_weights_kernel, dim3(rowio_grid(a.R, 64, max_grid)), dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_emit_scalars(const EmitScalarsArgs &a, int max_grid, hipStream_t stream) {
     if (a.rows_live <= 0) return hipSuccess;
     hipLaunchKernelGGL(emit_scalars_kernel, dim3(rowio_grid(a.rows_live, 64, max_grid)), dim3(64), 0, stream, a);

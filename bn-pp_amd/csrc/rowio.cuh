@@ -5,6 +5,7 @@
 //   stage_rows         ev  = int32[n_rows][n_ev]  ->  the launch's evidence table int32[n_ev][R]
 //   stage_lik          lik = [n_rows][Ws]         ->  T[Ws][R] scaled per (row, variable) block, e_row[R]
 //   stage_loglik       loglik = [n_rows][Ws]      ->  T[Ws][R] = exp(l - top) / 2, e_row[R], top[n_soft][R]
+//   stage_weights      weights = double[n_rows]   ->  the launch's weights table double[R] (expected counts)
 //   emit_row_scalars   the result table T[R]      ->  log10_z[row0 + b], z[row0 + b]
 //   emit_row_logs      the result table T[R], top ->  ln_z, log10_z, z with the rows' shifts restored
 //   emit_row_states    x = uint8[n_vars][K][R]    ->  int32[n_rows][n_vars] / uint8[n_rows][K][n_vars]
@@ -46,7 +47,7 @@
 // Every tile is private to its wave (the waves split the columns), so a wave
 // synchronises with itself only; stage_lik alone meets at a workgroup barrier,
 // to add the waves' exponent sums of a row.  The only values shared between
-// workgroups are the two status words, folded by a 64-bit atomic minimum that
+// workgroups are the status words, folded by a 64-bit atomic minimum that
 // only an invalid cell touches: results do not depend on the grid.  Plain C++
 // and vector memory operations throughout.
 //
@@ -54,7 +55,7 @@
 // scalar cache: from device memory (the _dv calls), or from the
 // kernel-argument segment behind the arguments (the single-step entries).
 #pragma once
-#include "kernels.cuh"
+#include "rowio_dev.cuh"
 
 namespace bnpp {
 
@@ -63,32 +64,17 @@ constexpr int kRowioC32 = 32, kRowioP32 = 33;       // int32 tiles: columns, pit
 constexpr int kRowioC8 = 64, kRowioP8 = 68;         // byte tile: columns, pitch in bytes
 constexpr int kRowioC64 = 16, kRowioP64 = 17;       // fp64 tile: columns, pitch in doubles
 
+// the step's arguments and its descriptor words, both in the kernel-argument segment unless a.words says otherwise
+template <typename A>
+__device__ __forceinline__ cst_t<RowioSingle<A>> &rowio_args(const RowioSingle<A> &args) {
+    return kernarg_of(args);
+}
+
 // the wave's LDS stores are visible to its own later loads (and the other way round)
 __device__ __forceinline__ void rowio_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// the step's arguments and its descriptor words, both in the kernel-argument segment unless a.words says otherwise
-template <typename A>
-__device__ __forceinline__ cst_t<RowioSingle<A>> &rowio_args(const RowioSingle<A> &args) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    (void)args;
-    return *(cst_t<RowioSingle<A>> *)__builtin_amdgcn_kernarg_segment_ptr();
-#else
-    return *(cst_t<RowioSingle<A>> *)&args;
-#endif
-}
-
-__device__ __forceinline__ void rowio_flag(int64_t *status, int word, int64_t cell) {
-    __hip_atomic_fetch_min(status + word, cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the value a table of floats or doubles holds at entry i, as a double; no table: the empty product
-__device__ __forceinline__ double rowio_elem(const void *table, int is_f32, int64_t i) {
-    if (!table) return 1.0;
-    return is_f32 ? (double)gload(static_cast<const float *>(table) + i) : gload(static_cast<const double *>(table) + i);
 }
 
 // ---- stage_rows ----------------------------------------------------------------------------------------------
@@ -152,43 +138,9 @@ __device__ __forceinline__ void lik_fill(double *tile, cst_t<StageLikArgs> &a, i
     rowio_wave_sync();
 }
 
-// an entry that is NaN, infinite or negative counts as 0
-__device__ __forceinline__ bool lik_bad(double v) { return !(v >= 0) || v == __builtin_inf(); }
-
-// (float)v, rounded once to nearest even, subnormal results included without relying on the conversion
-// instruction's denormal mode: below 2^-126 the sum with 2^-97 (whose ulp is 2^-149, the subnormal floats'
-// spacing) rounds v to a multiple of 2^-149, and that multiple is the float's bit pattern
-__device__ __forceinline__ float lik_to_float(double v) {
-    if (v >= 0x1p-126) return (float)v;
-    const double m = __dsub_rn(__dadd_rn(v, 0x1p-97), 0x1p-97);
-    return __uint_as_float((unsigned)__dmul_rn(m, 0x1p149));
-}
-
 __device__ __forceinline__ void lik_store(cst_t<StageLikArgs> &a, int64_t at, double v) {
     if (a.out_f32) *((gbl_t<float> *)a.out + at) = lik_to_float(v);
     else *((gbl_t<double> *)a.out + at) = v;
-}
-
-// The two forms of a likelihood block.  Linear: the entries are likelihoods, the block is scaled by the power of two
-// that brings its top into [0.5, 1).  Log: the entries are natural logs (-inf: the likelihood 0; NaN and +inf are
-// invalid and count as -inf), the block is E = exp(l - top) scaled by 2^-1, which is what the linear form makes of
-// E (its top is 1.0 = 0.5 * 2^1); a block of nothing but -inf is all zero and adds no exponent
-template <bool kLog>
-__device__ __forceinline__ bool lik_invalid(double v) {
-    if (kLog) return v != v || v == __builtin_inf();
-    return lik_bad(v);
-}
-template <bool kLog>
-__device__ __forceinline__ int lik_exponent(double top) {
-    if (kLog) return top == -__builtin_inf() ? 0 : 1;
-    int e = 0;
-    if (top > 0) (void)frexp(top, &e);
-    return e;
-}
-template <bool kLog>
-__device__ __forceinline__ double lik_scaled(double v, double top, int e) {
-    if (kLog) return lik_invalid<true>(v) || top == -__builtin_inf() ? 0.0 : ldexp(exp(__dsub_rn(v, top)), -1);
-    return ldexp(lik_bad(v) ? 0.0 : v, -e);
 }
 
 // The waves split the soft variables into contiguous runs.  A wave takes as many whole blocks as fit the 16
@@ -299,14 +251,38 @@ __device__ __forceinline__ double rowio_log10_scaled(double p, int64_t ex) {
     return p > 0 ? __dadd_rn(log10(pm), __dmul_rn((double)(ex + pe), 0x1.34413509f79ffp-2)) : -__builtin_inf();
 }
 
+// a row with p <= 0 is impossible: counted with an integer atomic add, whose result no order changes
+__device__ __forceinline__ void rowio_count_impossible(int64_t *counter, double p) {
+    if (counter && !(p > 0)) atomicAdd(reinterpret_cast<unsigned long long *>(counter), 1ull);
+}
+
+// ---- stage_weights -------------------------------------------------------------------------------------------
+// a lane owns a row: the launch's weights, padding rows 0, no weights 1; a weight that is not finite or is
+// negative is flagged in status word 2 and stored as 0
+__global__ __launch_bounds__(64) void stage_weights_kernel(const StageWeightsArgs a) {
+    for (int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x; b < a.R; b += (int64_t)gridDim.x * 64) {
+        const int64_t row = a.row0 + b;
+        double w = 0.0;
+        if (row < a.n_rows) {
+            w = a.weights ? gload(a.weights + row) : 1.0;
+            if (!(w >= 0) || w == __builtin_inf()) {
+                rowio_flag(a.status, 2, row);
+                w = 0.0;
+            }
+        }
+        *((gbl_t<double> *)a.out + b) = w;
+    }
+}
+
 // a lane owns a row: nothing to turn, so a workgroup is the one wave of its tile
 __global__ __launch_bounds__(64) void emit_scalars_kernel(const EmitScalarsArgs a) {
     for (int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x; b < a.rows_live; b += (int64_t)gridDim.x * 64) {
         double p = 0;
         p = __dadd_rn(p, rowio_elem(a.table, a.is_f32, a.has_b ? b : 0));
+        rowio_count_impossible(a.n_impossible, p);
         int64_t ex = a.meta ? as_const(a.meta)->exp2 : 0;
         if (a.e_row) ex += gload(a.e_row + b);
-        *((gbl_t<double> *)a.log10_z + a.row0 + b) = rowio_log10_scaled(p, ex);
+        if (a.log10_z) *((gbl_t<double> *)a.log10_z + a.row0 + b) = rowio_log10_scaled(p, ex);
         if (a.z) {
             const int64_t c = ex > (1 << 20) ? (1 << 20) : ex < -(1 << 20) ? -(1 << 20) : ex;
             *((gbl_t<double> *)a.z + a.row0 + b) = ldexp(p, (int)c);
@@ -325,6 +301,8 @@ __global__ __launch_bounds__(64) void emit_logs_kernel(const EmitScalarsArgs a) 
         if (a.e_row) ex += gload(a.e_row + b);
         double shift = 0.0;
         for (int64_t i = 0; i < a.n_soft; ++i) shift = __dadd_rn(shift, gload(a.top + i * a.R + b));
+        if (a.table_shift) shift = __dadd_rn(shift, gload(a.table_shift));
+        rowio_count_impossible(a.n_impossible, p);
         int pe = 0;
         const double pm = frexp(p, &pe), pw = (double)(ex + pe), ninf = -__builtin_inf();
         const double ln_z = p > 0 ? __dadd_rn(__dadd_rn(log(pm), __dmul_rn(pw, 0x1.62e42fefa39efp-1)), shift) : ninf;
@@ -389,12 +367,6 @@ __global__ __launch_bounds__(kBlock) void emit_states_mpe_kernel(const RowioSing
 }
 __global__ __launch_bounds__(kBlock) void emit_states_sample_kernel(const RowioSingle<EmitStatesArgs> args) {
     emit_states<uint8_t, kRowioC8, kRowioP8>(rowio_args(args));
-}
-
-// persistent: a workgroup per tile of 64 rows, capped like the other persistent launches
-inline unsigned rowio_grid(int64_t rows, int64_t per, int max_grid) {
-    const int64_t g = (rows + per - 1) / per;
-    return (unsigned)(g < 1 ? 1 : g < max_grid ? g : max_grid);
 }
 
 }  // namespace bnpp

@@ -183,7 +183,42 @@ struct EmitScalarsArgs {
     const double *top;                  // the log form: double[n_soft][R] (n_soft 0: no shift), and its natural log
     double *ln_z;
     int64_t n_soft, R;
+    const double *table_shift;          // the log form: one double added to every row's shift (log-form tables), or null
+    int64_t *n_impossible;              // a counter the rows with p <= 0 are added to, or null
 };
+struct StageWeightsArgs {
+    const double *weights;              // double[n_rows], or null: every row weighs 1
+    double *out;                        // double[R]: the launch's weights, padding rows 0
+    int64_t *status;                    // word 2: the first row whose weight is not finite or is negative
+    int64_t n_rows, row0, R;
+};
+// device-resident model tables (tables.cuh).  words, per factor: its first entry in values, its size, its byte
+// offset in out_buf; in device memory, or null: the `single` words behind the arguments
+constexpr int kTablesSingleMax = 96;    // factors of a single-step call
+struct StageTablesArgs {
+    const int64_t *words;
+    const void *values;                 // flat, doubles or (values_f32) floats
+    void *out_buf;                      // the tables, floats (out_f32) or doubles
+    TableMeta *out_meta;                // [n_factors]
+    double *out_shift;                  // [1 + n_factors]: the shift, then every factor's top
+    int64_t *status;                    // word 0: the first invalid entry (its flat index)
+    int64_t n_factors;
+    int32_t values_f32, out_f32;
+};
+struct StageTablesSingle {
+    StageTablesArgs a;
+    int64_t single[3 * kTablesSingleMax];
+};
+struct MstepArgs {
+    const int64_t *words;               // per factor: first entry, k, first configuration; then the configurations in all
+    const double *counts, *old_values;
+    double *new_values;
+    double prior;
+    int64_t n_factors;
+};
+hipError_t launch_stage_tables(const StageTablesSingle &a, bool log_form, int max_grid, hipStream_t stream);
+hipError_t launch_mstep(const MstepArgs &a, int64_t n_cfg, int max_grid, hipStream_t stream);
+hipError_t launch_stage_weights(const StageWeightsArgs &a, int max_grid, hipStream_t stream);
 struct EmitStatesArgs {                 // word v: (uint32) evidence column (-1: none) | partial << 32 | written << 33
     const int64_t *words;
     const uint8_t *x;                   // uint8[n_vars][K][R]

@@ -186,6 +186,17 @@ _SIGS = {
     "bnpp_emit_row_logs": (_I, [_P, _P, _I, _P, _I, _P, _P, _I, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
     "bnpp_log_partition_dv": (_I, [_P, _P, _I, _IP, C.c_int64, _P, _UBP, _I, _IP, _P, _I, _I, _IP, _I, _I, C.c_int64, _P,
                                    _P, _DP]),
+    # device-resident model tables (bnpp.tensor.Tables): the table set, its staging step on caller-owned buffers,
+    # expected counts on device arrays (tables after the model, weights and flags after lik_dtype, ln_z after
+    # log10_z) and the M step
+    "bnpp_model_values": (_I, [_P, _DP]),
+    "bnpp_tables_create": (_I, [_P, _P, _I, C.POINTER(_P)]),
+    "bnpp_tables_free": (_I, [_P]),
+    "bnpp_tables_set_dv": (_I, [_P, _P, _I]),
+    "bnpp_stage_tables": (_I, [_P, _P, _I, _I, _I, _LP, _P, _P, _P, _P, _P]),
+    "bnpp_expected_counts_dv": (_I, [_P, _P, _P, _I, _IP, C.c_int64, _P, _UBP, _I, _IP, _P, _I, _P, _I, _I, _IP, _I, _I,
+                                     C.c_int64, _P, _P, _P, _P, _DP]),
+    "bnpp_mstep_dv": (_I, [_P, _P, _P, _P, C.c_double, _P, _P]),
     "bnpp_batch_job_key": (_I, [_P, _I, _IP, _UBP, _I, _IP, _I, C.c_int64, C.POINTER(C.c_uint64)]),
     "bnpp_job_create": (_I, [_P, _P, _I, _I, _IP, _IP, _I, _IP, _I, _I, _IP, _I, C.POINTER(_P)]),
     "bnpp_job_stats": (_I, [_P, _DP, _I]),

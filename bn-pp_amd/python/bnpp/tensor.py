@@ -14,6 +14,13 @@ likelihoods (a network's logits or log-probabilities; -inf is the likelihood 0),
 staged on the device without an exp in torch.  log_partition is ln Z of every
 row as a torch.autograd.Function: its gradient with respect to loglik is the
 posterior of the soft variables, which the same bucket-tree pass returns.
+
+Tables is the tables of one model rewritten in place on the device, so that a
+training loop plans once: expected_counts(tables=...) takes the rows' expected
+sufficient statistics under them, m_step refits CPTs from the counts, em is
+learn.em's loop made of the two, and log_likelihood is the rows' weighted
+log-likelihood as a torch.autograd.Function whose gradient with respect to the
+log tables is those counts.
 """
 from __future__ import annotations
 
@@ -249,3 +256,230 @@ def log_partition(ctx: Context, model: Model, ev_vars: Sequence[int], rows, log_
     need = loglik is not None and isinstance(loglik, torch.Tensor) and loglik.requires_grad and torch.is_grad_enabled()
     return _LogPartition.apply(loglik, need, ctx, model, ev_vars, rows, soft_vars, partial, heuristic, dtype,
                                int(rows_per_launch), order)
+
+
+# ---- device-resident model tables: parameter learning without a trip through the host ----
+
+def _leave(ctx: Context) -> None:
+    """torch's current stream waits for what the context's stream has been given (a step that is not waited for)."""
+    torch.cuda.current_stream(ctx.device).wait_stream(torch.cuda.ExternalStream(ctx.stream(), device=ctx.device))
+
+
+def _counts_size(model: Model) -> int:
+    total = C.c_int64()
+    _check(_lib.bnpp_counts_size(model.handle, C.byref(total)), "bnpp_counts_size")
+    return total.value
+
+
+def _flat(ctx: Context, t, n: int, what: str, dtypes=(torch.float64, torch.float32)):
+    """t as a contiguous flat tensor of n entries on the context's device (the same data where it already is one)."""
+    t = _on_device(ctx, t, what)
+    if t.dtype not in dtypes:
+        raise ValueError("%s must be a %s tensor" % (what, " or ".join(str(d).replace("torch.", "") for d in dtypes)))
+    if t.numel() != n:
+        raise ValueError("%s must have %d entries (the model's tables, flat), not %d" % (what, n, t.numel()))
+    return t.detach().contiguous().reshape(-1)
+
+
+class Tables:
+    """The tables of one model on one context in one dtype, rewritten in place on the device (bnpp_tables): the
+    calls that take tables= read them instead of the model's own values, from one plan and one job however often
+    they are set.  They start as the model's own values.  Keeps its context and its model alive."""
+
+    def __init__(self, ctx: Context, model: Model, dtype: int = F64):
+        self._h = _P()
+        self.ctx, self.model, self.dtype = ctx, model, dtype
+        self.size = _counts_size(model)
+        _check(_lib.bnpp_tables_create(_h(ctx), model.handle, dtype, C.byref(self._h)), "bnpp_tables_create")
+        own = (C.c_double * max(self.size, 1))()
+        _check(_lib.bnpp_model_values(model.handle, own), "bnpp_model_values")
+        self.values = torch.tensor(list(own[: self.size]), dtype=torch.float64, device="cuda:%d" % ctx.device)
+        self.log = False
+
+    @property
+    def handle(self):
+        return self._h
+
+    def set(self, values, log: bool = False) -> "Tables":
+        """New values for every factor: one flat float64 or float32 tensor of the device in the layout of counts;
+        log=True: natural logs (-inf is the value 0).  The first invalid entry raises, naming its factor."""
+        v = _flat(self.ctx, values, self.size, "values")
+        _enter(self.ctx)
+        _check(_lib.bnpp_tables_set_dv(self._h, _ptr(v), (F32 if v.dtype == torch.float32 else F64) | (LIK_LOG if log else 0)),
+               "bnpp_tables_set_dv")
+        self.values, self.log = values, bool(log)
+        return self
+
+    def to_model_dict(self, model_dict: dict) -> dict:
+        """model_dict (type, cards, scopes) with the values last set (their exp, for a log form), by one
+        device-to-host copy: what Model.from_dict takes, for the calls that take no tables."""
+        v = self.values.detach().reshape(-1).double()
+        flat = (torch.exp(v) if self.log else v).cpu().tolist()
+        out, at = dict(model_dict), 0
+        out["values"] = []
+        for s in model_dict["scopes"]:
+            size = 1
+            for x in s:
+                size *= model_dict["cards"][x]
+            out["values"].append(flat[at:at + size])
+            at += size
+        if at != len(flat):
+            raise ValueError("model_dict does not match the tables' model")
+        return out
+
+    def close(self) -> None:
+        if self._h:
+            _lib.bnpp_tables_free(self._h)
+            self._h = _P()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _counts_call(ctx, model, ev_vars, rows, weights, tables, partial, soft, log_soft, accumulate, out, heuristic, dtype,
+                 rows_per_launch, order, with_counts: bool, with_ln: bool):
+    """bnpp_expected_counts_dv -> (counts or None, log10_z, ln_z or None, n_impossible)."""
+    ne, ev_v, n, r32 = _rows(ctx, ev_vars, rows)
+    ns, sv, lik, lp, ld = _soft(ctx, model, soft, n, log_soft)
+    h, oa, no = _order_args(order, heuristic)
+    if tables is not None and not isinstance(tables, Tables):
+        raise ValueError("tables must be a bnpp.tensor.Tables")
+    if dtype is None:
+        dtype = tables.dtype if tables is not None else F64
+    w = None if weights is None else _flat(ctx, weights, n, "weights", (torch.float64,))
+    total = _counts_size(model)
+    counts = None
+    if with_counts:
+        if accumulate and out is None:
+            raise ValueError("accumulate=True adds to out: pass the counts tensor of the earlier call")
+        counts = _out(ctx, out, (max(total, 1),), torch.float64, "out")
+    lz = _out(ctx, None, (n,), torch.float64, "log10_z")
+    ln = _out(ctx, None, (n,), torch.float64, "ln_z") if with_ln else None
+    ni = _out(ctx, None, (), torch.int64, "n_impossible")
+    up = C.c_double()
+    _enter(ctx)
+    _check(_lib.bnpp_expected_counts_dv(_h(ctx), model.handle, tables.handle if tables is not None else None, ne, ev_v, n,
+                                        _ptr(r32), _partial(ev_vars, partial, r32), ns, sv, lp, ld,
+                                        _ptr(w) if w is not None else None, 1 if accumulate else 0, h, oa, no, dtype,
+                                        int(rows_per_launch), _ptr(counts) if with_counts else None, _ptr(lz),
+                                        _ptr(ln) if with_ln else None, _ptr(ni), C.byref(up)), "bnpp_expected_counts_dv")
+    del r32, lik, w
+    return (counts[:total] if with_counts else None), lz, ln, ni
+
+
+def expected_counts(ctx: Context, model: Model, ev_vars: Sequence[int], rows, weights=None, tables: Optional[Tables] = None,
+                    partial=None, soft=None, log_soft=None, accumulate: bool = False, out=None, heuristic: str = "mf",
+                    dtype: Optional[int] = None, rows_per_launch: int = 0, order: Optional[Sequence[int]] = None):
+    """bnpp.expected_counts on device tensors -> (counts float64[counts_size], log10_z float64[n], n_impossible, a
+    0-dim int64 tensor), all on the device.  tables: a Tables of this model to read instead of its own values
+    (dtype then defaults to theirs).  weights: a float64 tensor of n entries.  accumulate=True adds to `out`,
+    the counts of an earlier call, continuing its fold; else out (if given) is overwritten."""
+    c, lz, _, ni = _counts_call(ctx, model, ev_vars, rows, weights, tables, partial, soft, log_soft, accumulate, out,
+                                heuristic, dtype, rows_per_launch, order, True, False)
+    return c, lz, ni
+
+
+def m_step(ctx: Context, model: Model, counts, old_values, prior: float = 0.0, out=None):
+    """The M step of a BAYES model on device tensors (bnpp_mstep_dv; learn.m_step with a fixed summation order):
+    new = (counts + prior) / its sum over the child, a parent configuration whose sum is 0 keeping its old row.
+    counts, old_values: flat float64 tensors; out: the tensor to write (it may be old_values), else a new one."""
+    n = _counts_size(model)
+    c = _flat(ctx, counts, n, "counts", (torch.float64,))
+    old = _flat(ctx, old_values, n, "old_values", (torch.float64,))
+    new = _out(ctx, out, (n,), torch.float64, "out")
+    _enter(ctx)
+    _check(_lib.bnpp_mstep_dv(_h(ctx), None, model.handle, _ptr(c), float(prior), _ptr(old), _ptr(new)), "bnpp_mstep_dv")
+    _leave(ctx)
+    return new
+
+
+def em(ctx: Context, model: Model, ev_vars: Sequence[int], rows, iters: int, weights=None, prior: float = 0.0,
+       tables: Optional[Tables] = None, partial=None, soft=None, dtype: int = F64):
+    """learn.em's loop on the device -> (tables, lls): every iteration is expected_counts(tables=...), m_step and
+    tables.set, with no new Model, no plan after the first and no copy to the host; lls[i] is the weighted
+    log-likelihood in log10 of the tables iteration i started from, impossible rows left out.  tables: the set to
+    start from and to refit (linear form), else a new one holding the model's own values."""
+    t = tables if tables is not None else Tables(ctx, model, dtype)
+    if t.log:
+        raise ValueError("em refits linear tables; these were last set in log form")
+    w = None if weights is None else _flat(ctx, weights, rows.shape[0], "weights", (torch.float64,))
+    lls = []
+    for _ in range(int(iters)):
+        counts, lz, _ = expected_counts(ctx, model, ev_vars, rows, weights=w, tables=t, partial=partial, soft=soft)
+        ok = torch.isfinite(lz)
+        lls.append(torch.sum((lz if w is None else w * torch.where(ok, lz, torch.zeros_like(lz)))[ok]))
+        t.set(m_step(ctx, model, counts, t.values.detach().reshape(-1).double(), prior))
+    return t, (torch.stack(lls).tolist() if lls else [])
+
+
+class _LogLikelihood(torch.autograd.Function):
+    """ll = sum_b w_b ln Z_b under the tables exp(log_tables); d ll / d log theta_f(x) = N_f(x), the expected counts
+    the same bucket-tree pass accumulates (bnpp_expected_counts_dv on log-form tables)."""
+
+    _tables = {}                                            # (context, model, dtype) -> Tables, the few last used
+
+    @classmethod
+    def tables_for(cls, ctx: Context, model: Model, dtype: int) -> Tables:
+        key = (id(ctx), id(model), dtype)
+        t = cls._tables.pop(key, None)                      # a Tables keeps both alive, so the ids stay theirs
+        if t is None:
+            t = Tables(ctx, model, dtype)
+        cls._tables[key] = t
+        while len(cls._tables) > 4:
+            cls._tables.pop(next(iter(cls._tables)))
+        return t
+
+    @staticmethod
+    def forward(fctx, log_tables, need, ctx, model, ev_vars, rows, weights, tables, partial, log_soft, heuristic,
+                rows_per_launch, order):
+        tables.set(log_tables.detach(), log=True)
+        counts, _, ln_z, ni = _counts_call(ctx, model, ev_vars, rows, weights, tables, partial, None, log_soft, False, None,
+                                           heuristic, None, rows_per_launch, order, need, True)
+        ok = torch.isfinite(ln_z)
+        terms = ln_z if weights is None else weights.detach().reshape(-1).double() * ln_z
+        ll = torch.sum(torch.where(ok, terms, torch.zeros_like(ln_z)))
+        if need:
+            fctx.save_for_backward(counts)
+        fctx.shape, fctx.dtype = tuple(log_tables.shape), log_tables.dtype
+        fctx.mark_non_differentiable(ln_z, ni)
+        return ll, ln_z, ni
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, g_ll, g_ln, g_ni):
+        (counts,) = fctx.saved_tensors
+        return ((g_ll.double() * counts).to(fctx.dtype).reshape(fctx.shape),) + (None,) * 12
+
+
+def log_likelihood(ctx: Context, model: Model, ev_vars: Sequence[int], rows, log_tables, weights=None,
+                   tables: Optional[Tables] = None, partial=None, log_soft=None, heuristic: str = "mf",
+                   dtype: Optional[int] = None, rows_per_launch: int = 0, order: Optional[Sequence[int]] = None):
+    """The weighted log-likelihood of the rows under the tables exp(log_tables) -> (ll, ln_z, n_impossible):
+    ll = sum_b w_b ln Z_b over the rows with a finite ln Z_b, a 0-dim float64 tensor differentiable with respect
+    to log_tables (one flat tensor of natural logs in the layout of counts); its gradient is the expected counts
+    of the rows, which the same pass returns.  ln_z float64[n] and n_impossible are not differentiable.  Where
+    log_tables requires no gradient (or grad mode is off) the call runs the batch plan, without the backward
+    pass.  tables: the Tables to stage log_tables in (else one kept per context, model and dtype); dtype then
+    defaults to theirs, and another one is a ValueError.  weights are not differentiated (that gradient is ln_z
+    itself): weights that require grad are a ValueError.  The tables are not normalised: for CPTs, pass log_softmax over the child.  No double backward."""
+    if log_soft is not None and isinstance(log_soft, (tuple, list)) and len(log_soft) == 2 and \
+            isinstance(log_soft[1], torch.Tensor) and log_soft[1].requires_grad and torch.is_grad_enabled():
+        raise ValueError("log_likelihood has no gradient with respect to log_soft (the counts job does not produce the "
+                         "rows' posteriors): use log_partition for the soft evidence's gradient")
+    if isinstance(weights, torch.Tensor) and weights.requires_grad and torch.is_grad_enabled():
+        raise ValueError("log_likelihood has no gradient with respect to weights: it is ln_z, which the call returns "
+                         "(detach the weights, or weigh ln_z in torch)")
+    if not isinstance(log_tables, torch.Tensor):
+        raise ValueError("log_tables must be a torch tensor on the context's device")
+    if tables is None:
+        tables = _LogLikelihood.tables_for(ctx, model, F64 if dtype is None else dtype)
+    elif not isinstance(tables, Tables):
+        raise ValueError("tables must be a bnpp.tensor.Tables")
+    elif dtype is not None and tables.dtype != dtype:
+        raise ValueError("tables are of dtype %d, the call asks for %d" % (tables.dtype, dtype))
+    need = log_tables.requires_grad and torch.is_grad_enabled()
+    return _LogLikelihood.apply(log_tables, need, ctx, model, ev_vars, rows, weights, tables, partial, log_soft, heuristic,
+                                int(rows_per_launch), order)

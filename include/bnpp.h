@@ -250,6 +250,9 @@ int bnpp_model_from_arrays(int is_bayes, int n_vars, const int *cards, int n_fac
 int bnpp_model_free(bnpp_model *m);
 int bnpp_model_info(const bnpp_model *m, int *is_bayes, int *n_vars, int *n_factors);
 int bnpp_model_cards(const bnpp_model *m, int *cards);
+/* the model's values as one flat array in the layout of counts (bnpp_counts_size entries): what a
+ * bnpp_tables of the model starts from */
+int bnpp_model_values(const bnpp_model *m, double *values);
 /* read_uai_evidence (io.cpp:157-180): *n pairs (0 unless the first integer is 1) */
 int bnpp_evidence_load(const char *path, int cap, int *n, int *vars, int *vals);
 /* An .evid file of any number of samples: the sample count, then per sample
@@ -1230,6 +1233,94 @@ int bnpp_log_partition_dv(bnpp_ctx *ctx, const bnpp_model *m, int n_ev, const in
                           int heuristic, const int *order, int n_order, int dtype, int64_t rows_per_launch,
                           double *ln_z /* device, [n_rows] */, double *post /* device, [n_rows][Ws], or NULL */,
                           double *uptime_ms);
+
+/* ------------------------------------------ device-resident model tables
+ * A model is read-only after creation, and the planner reads only its scopes
+ * and cards.  A bnpp_tables is the tables of one model on one context in one
+ * dtype, rewritten in place on the device: one plan, one job and one program
+ * serve every iteration of a training loop.  Symbols added to version 205.
+ *
+ * bnpp_tables_create: the set starts as the model's own values.  It owns the
+ *   layout the engine uploads a model in (every factor pre-scaled by a power of
+ *   two, on a 256-byte line), the factors' metadata on the device, one device
+ *   double `shift` and a uid of its own from the counter of the models' uids.
+ *   The buffer's address never changes; only its bytes and the factors'
+ *   maxbits / exp2 words do.  The set keeps what it needs of the model (the
+ *   sizes), so bnpp_model_free leaves it valid but useless: a call takes the
+ *   set together with the model it was created for.  bnpp_ctx_destroy takes
+ *   back the buffers of its context's sets: such a set can still be freed, and
+ *   every other use of it is BNPP_ERR_INVALID.  A set is not synchronised
+ *   against calls of other threads.
+ * bnpp_tables_free: a cached job planned for the set is evicted first.
+ * bnpp_tables_set_dv: values is one flat device array in the layout of counts
+ *   (bnpp_counts_size entries: the factors in model order, each in its natural
+ *   layout), doubles or floats (widened exactly).  One step on the context's
+ *   stream (bnpp_stage_tables states it), then the call waits and reports the
+ *   first invalid entry as BNPP_ERR_INVALID, naming the factor and the entry's
+ *   index in it; the set then holds the valid entries and 0 for the others.
+ * bnpp_stage_tables: the step on caller-owned buffers.  Factor f has sizes[f]
+ *   entries, starts at the sum of the earlier sizes in values and at the sum of
+ *   the earlier factors' bytes, each rounded up to 256, in out_buf.  out_meta
+ *   is n_factors records {void *ptr; uint64 maxbits; int64 exp2; int64 size},
+ *   out_shift is double[1 + n_factors] (the shift, then every factor's top),
+ *   status one int64 the caller sets to INT64_MAX: it receives the smallest
+ *   flat index of an invalid entry.  At most 96 factors.  Per factor,
+ *   linear form (values_dtype 0 or 1): an entry that is NaN, infinite or
+ *     negative is invalid and counts as 0; top = the largest entry; e = the
+ *     exponent frexp gives top (0 for top = 0); stored entry = ldexp(v, -e),
+ *     converted once to dtype; maxbits = the bits of the largest stored entry,
+ *     exp2 = e; shift = 0.  This is what the engine makes of a model's values.
+ *   log form (values_dtype | BNPP_LIK_LOG): the entries are natural logs, -inf
+ *     the value 0; NaN and +inf are invalid and count as -inf; top = the largest
+ *     entry; stored entry = exp(l - top) / 2, exp2 = 1, maxbits = the bits of
+ *     0.5; a factor of nothing but -inf is stored as zeros with exp2 = 0 and
+ *     maxbits = 0.  shift = the sum of the tops in factor order from 0.0, in
+ *     fp64, every add rounded once, the factors of nothing but -inf left out.
+ *   Nothing depends on the grid (bnpp_ctx_set_max_grid).
+ * bnpp_expected_counts_dv: bnpp_expected_counts_sv with every per-row array
+ *   (ev_vals, lik, weights) and every output in device memory.  tables == NULL:
+ *   the model's own values, and without a flag counts are the host-array
+ *   call's bit for bit, log10_z as the other _dv calls' (the device's log10),
+ *   n_impossible equal; the plan, R and the cached job are that call's.  With
+ *   tables (of this model, this dtype and this context, else
+ *   BNPP_ERR_INVALID) the call reads them instead, under a job key of their
+ *   own; after a linear set of v the results are those of tables == NULL on a
+ *   model made of v, bit for bit.  After a log set ln_z and log10_z include
+ *   the set's shift (ln Z of the tables exp(l)); counts are those of exp(l).
+ *   flags: BNPP_COUNTS_ACCUMULATE adds to what counts holds, continuing the
+ *   fold between launches across calls; else counts is zeroed first.  weights:
+ *   device, or NULL for 1; the first weight that is not finite or is negative
+ *   is reported with the sibling's message.  log10_z, ln_z and n_impossible
+ *   (one int64, the rows with Z = 0) may each be NULL.  counts == NULL: the
+ *   batch plan (the job of bnpp_partition_batch_dv) under the tables -- the
+ *   rows' likelihood without the backward pass; weights are then not read,
+ *   and one of log10_z and ln_z is needed.
+ * bnpp_mstep_dv: the M step of a BAYES model (else BNPP_ERR_UNSUPPORTED), all
+ *   factors in one launch on `stream` (NULL: the context's), not waited for.
+ *   A factor's child is the last variable of its scope (k values), so a parent
+ *   configuration is k contiguous entries: num_i = counts_i + prior,
+ *   tot = ((0.0 + num_0) + num_1) + ..., new_i = tot > 0 ? num_i / tot : old_i,
+ *   in fp64, every operation rounded once.  new_values may be old_values; it
+ *   must not overlap counts.  prior must be finite and not negative.  The
+ *   context keeps the per-factor words of the last model on the device; when
+ *   the model changes, the call waits for the stream of the last M step (not
+ *   for the device) before it uploads the new ones. */
+#define BNPP_COUNTS_ACCUMULATE 1
+typedef struct bnpp_tables bnpp_tables;
+int bnpp_tables_create(bnpp_ctx *ctx, const bnpp_model *m, int dtype, bnpp_tables **out);
+int bnpp_tables_free(bnpp_tables *t);
+int bnpp_tables_set_dv(bnpp_tables *t, const void *values /* device, flat */, int values_dtype);
+int bnpp_stage_tables(bnpp_ctx *ctx, void *stream, int dtype, int values_dtype, int n_factors, const int64_t *sizes,
+                      const void *values, void *out_buf, void *out_meta, double *out_shift, int64_t *status);
+int bnpp_expected_counts_dv(bnpp_ctx *ctx, const bnpp_model *m, const bnpp_tables *tables /* NULL: the model's own */,
+                            int n_ev, const int *ev_vars, int64_t n_rows, const int32_t *ev_vals /* device */,
+                            const unsigned char *partial, int n_soft, const int *soft_vars, const void *lik /* device */,
+                            int lik_dtype, const double *weights /* device or NULL */, int flags, int heuristic,
+                            const int *order, int n_order, int dtype, int64_t rows_per_launch,
+                            double *counts /* device, or NULL */, double *log10_z, double *ln_z,
+                            int64_t *n_impossible /* device or NULL */, double *uptime_ms);
+int bnpp_mstep_dv(bnpp_ctx *ctx, void *stream, const bnpp_model *m, const double *counts, double prior,
+                  const double *old_values, double *new_values /* may alias old_values */);
 
 /* Host-only planning of one part of bnpp_marginals_tree_part (all variables
  * as targets): owned[v] = 1 when this part computes v's marginal; stats as
